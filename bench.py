@@ -84,6 +84,9 @@ def parse():
                    help="timed regions of --steps steps run back to back; the first is the line's value, all are in ms_per_step_runs")
     p.add_argument("--in-flight", type=int, default=1,
                    help="independent sequence batches in flight (each on its own stream and model state); 1 = the quoted number")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0): the "
+                        "metrics test_step returns and the depth map of the sequence's last frame (dump_outputs)")
     return p.parse_args()
 
 
@@ -438,6 +441,47 @@ def check_world(args, environ, device_count):
     return "run"
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs writes at most this much (64 MB)
+DUMP_SAMPLE_SEED = 20251015
+
+
+def step_outputs(model, depth):
+    """The arrays one timed step computed, as host float32: the 7 metrics ``test_step`` / ``graphed_test_step`` hand their
+    caller (m4depth_network.py:473-474, Keras-Mean values over the timed steps so far) and ``depth``, the forward's output
+    for the last frame of the sequence (batch, H, W, 1)."""
+    import torch
+    out = {f"metric_{k}": torch.as_tensor(v).detach().float().cpu().numpy().reshape(1) for k, v in model._metric_results().items()}
+    out["depth"] = depth.detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=DUMP_SAMPLE_SEED):
+    """Writes ``arrays`` ({name: float32 / float64 ndarray}) as ``out_dir/<name>.npy``.  When all of them together exceed
+    ``limit`` bytes, each array larger than its share of what the small ones leave is replaced by a fixed seeded sample of its
+    elements: ``<name>_sample.npy`` (the values, flattened, C order) + ``<name>_sample_index.npy`` (their flat indices, float64,
+    ascending) -- the same elements on every run of the same shape.  Returns {file name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)) for k, v in arrays.items()}
+    files = {}
+    big = []
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        header = 128 * 2 * len(arrays)                                              # .npy headers, generously
+        small = sum(a.nbytes for a in arrays.values() if a.nbytes <= limit // (2 * len(arrays)))
+        big = [k for k, a in arrays.items() if a.nbytes > limit // (2 * len(arrays))]
+        share = (limit - small - header) // max(len(big), 1)
+    for name, a in arrays.items():
+        if name in big:
+            n = min(a.size, share // (a.itemsize + 8))                              # value + float64 index per element
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, n, replace=False))
+            for fname, v in ((f"{name}_sample", a.reshape(-1)[idx]), (f"{name}_sample_index", idx.astype(np.float64))):
+                np.save(os.path.join(out_dir, fname + ".npy"), v)
+                files[fname] = list(v.shape)
+        else:
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            files[name] = list(a.shape)
+    return files
+
+
 def timed_region(step, steps, D, dev, sync):
     """EXACTLY ``steps`` calls of ``step`` bracketed by a barrier + device synchronisation on both sides.  Returns
     (max-over-ranks wall time of the region including the closing barrier, the per-rank wall times without it)."""
@@ -618,6 +662,21 @@ def main():
             m.reset_state()
     stag = getattr(runner, "stagger_us", None) if runner is not None else None
     dt, per_rank_s, ms_runs, per_rank_stagger = timed_job(step, args, D, dev, torch.cuda.synchronize, stag)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the LAST timed step computed, read before anything else runs on the model (the replicas' metric accumulators
+        # are folded below, the kernel timing runs more eager steps)
+        if runner is None:                                                    # --eager: test_step's own forward
+            from m4depth_amd import network_ops as nops
+            last = model
+            depth = nops.resize_nearest(model.last_estimates[-1][0]["depth"], args.height, args.width)
+        elif args.in_flight > 1:
+            i = (counter[0] - 1) % args.in_flight
+            last, depth = replicas[i], runners[i].depth
+        else:
+            last, depth = model, runner.depth
+        torch.cuda.synchronize()
+        dumped = dump_outputs(args.dump_outputs, step_outputs(last, depth))
     for mr in replicas[1:]:                                                   # fold the replicas' Keras-Mean accumulators together
         for m, m2 in zip(model.compiled_metrics, mr.compiled_metrics):
             if m2.total is not None:
@@ -680,6 +739,8 @@ def main():
                                                   "levels on one HIP stream per frame (M4D_LEVEL_PIPELINE)"),
     })
     out["ms_per_step_runs"] = run_spread(ms_runs)
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     out["per_rank_winograd_stagger_us"] = [int(v) for v in per_rank_stagger]
     tuned = getattr(runner, "stagger_autotune_ms", None) if not args.eager else None
     probe = box_kind_probe(tuned, getattr(runner, "stagger_us", None))

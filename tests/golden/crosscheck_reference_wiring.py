@@ -1,4 +1,4 @@
-"""Cross-check of the oracle's WIRING against the reference's own Python source, in the build container only.
+"""Cross-check of the oracle's WIRING against the reference's own Python source.
 
 What this is.  The reference is Python on TensorFlow 2.7, which is not installed here, so nothing of it can run as shipped and
 the parity grade stays "unpinned".  But `/root/reference/utils/depth_operations.py` and `utils/dense_image_warp.py` are plain
@@ -26,10 +26,14 @@ conv2d_same, so the convolution ARITHMETIC is shared and what is compared is eve
 a 3-level model steps through a reset frame and two full frames with the oracle's weights, every level's depth / parallax /
 other of every frame, the final depth and the seven metrics compared with oracle.M4Depth / oracle.metrics_batch.
 
-Nothing of this travels: the script reads /root/reference (absent on the GPU box), is not imported by any `-m gpu` test, by
-smoke() or by bench.py; `tests/test_oracle.py::test_reference_wiring_crosscheck` runs it when /root/reference exists and
-skips otherwise.  Run by hand:  python tests/golden/crosscheck_reference_wiring.py  -> prints the report (also kept as
-tests/golden/crosscheck_reference_wiring.txt)."""
+Record and replay.  A live run needs the reference's source (REF, overridable with M4D_REFERENCE_ROOT); what the reference's
+functions returned is recorded in tests/golden/crosscheck_reference_wiring.npz (data only: the arrays of its side of the 73
+comparisons, none of its text), and `tests/test_oracle.py::test_reference_wiring_crosscheck` replays the comparisons from that
+file -- the oracle's side recomputed from the same seeded and golden inputs -- so the check runs from the repository alone.
+Nothing here is imported by any `-m gpu` test, by smoke() or by bench.py.  Run by hand:
+    python tests/golden/crosscheck_reference_wiring.py           live run -> the report (kept as crosscheck_reference_wiring.txt)
+    python tests/golden/crosscheck_reference_wiring.py --record  live run, then rewrite the recording
+    python tests/golden/crosscheck_reference_wiring.py --replay  the test's comparisons, from the recording"""
 import contextlib
 import importlib.util
 import os
@@ -40,6 +44,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 REF = os.environ.get("M4D_REFERENCE_ROOT", "/root/reference")
+RECORDED = os.path.join(ROOT, "tests", "golden", "crosscheck_reference_wiring.npz")     # the reference's side of a live run
 F = np.float32
 
 
@@ -538,17 +543,58 @@ def _cmp(name, got, want, rows, tol=0.0):
     rows.append((name, mx <= tol, f"max rel. difference {mx:.3e} over {int((err > 0).sum())} of {err.size} elements (tolerance {tol:g})"))
 
 
-def run_network(rows):
-    """m4depth_network.py + metrics.py of the reference under the stand-in against oracle.M4Depth / oracle.metrics_batch: a
-    3-level model, batch 2, one reset frame + two full frames, the oracle's He-normal weights."""
-    sys.path.insert(0, ROOT)
-    from oracle import m4depth_oracle as O
-    from m4depth_amd import synthetic as S
+class ReferenceSide:
+    """The reference's side of every comparison.  Live (``recorded`` None): each value is computed by the reference's own
+    functions under the stand-in and also kept in ``self.values``; replay: each value is read back from a live run's recording
+    (RECORDED, written by ``--record``), so the comparison runs wherever the reference's source is absent.  A result that is a
+    (nested) tuple is kept flattened under ``key#0``, ``key#1``, ..."""
+
+    def __init__(self, recorded=None):
+        self.recorded = recorded
+        self.values = {}
+
+    def __call__(self, key, thunk):
+        if self.recorded is not None:
+            if key in self.recorded:
+                return self.recorded[key]
+            n = sum(1 for k in self.recorded if k.startswith(key + "#"))
+            if n == 0:
+                raise KeyError(f"{key!r} is not in the recording {RECORDED}: re-record it with --record")
+            return tuple(self.recorded[f"{key}#{i}"] for i in range(n))
+        v = thunk()
+        if isinstance(v, (tuple, list)):
+            flat = tuple(_flatten(v))
+            for i, x in enumerate(flat):
+                self.values[f"{key}#{i}"] = x
+            return flat
+        self.values[key] = _arr(v)
+        return self.values[key]
+
+
+def _arr(v):
+    return np.array(v.a if isinstance(v, T) else v)
+
+
+def _flatten(v):
+    for x in v:
+        if isinstance(x, (tuple, list)):
+            yield from _flatten(x)
+        else:
+            yield _arr(x)
+
+
+def load_recorded(path=None):
+    """{key: array} of the recording a live run wrote (``--record``)."""
+    with np.load(path or RECORDED, allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _reference_network(Wts, samples, cam, L, Tn, gt, est):
+    """The reference's m4depth_network.py + metrics.py under the stand-in (see run_network), flattened: the feature pyramid of
+    frame 1 (L maps), every level's depth / parallax / other of every frame (Tn x L x 3), M4Depth.call's depth, the names of the
+    seven metrics, their values on (gt, est)."""
     with contextlib.redirect_stdout(open(os.devnull, "w")):              # (the reference prints "Seq sample ..." while tracing)
         _, _, N, MT = load_reference(network=True)
-        L, b, Tn, H, Wd = 3, 2, 3, 32, 48
-        Wts = S.init_weights(L, seed=77)
-        samples, cam = S.make_sequence(b, Tn, H, Wd, seed=78)
         model = N.M4Depth(nbre_levels=L)
         enc = model.encoder
         for i in range(L):
@@ -579,34 +625,55 @@ def run_network(rows):
         model2.encoder.dn_layers[0].bias.assign(Wts["enc.dn.0.bias"].reshape(1, 1, 1, -1))
         pyrs = [model2.encoder(s["RGB_im"]) for s in tsamples]
         ref_seq = model2.d_estimator(pyrs, tsamples, tcam, False)
-        o_out, o_seq = O.M4Depth(Wts, L)(samples, cam)
-        opyr = O.feature_pyramid(samples[1]["RGB_im"], Wts, L)
-    for l in range(L):
-        _cmp(f"FeaturePyramid level {l + 1} (incl. DomainNormalization at level 0)", pyrs[1][l], opyr[l], rows)
-    for t in range(Tn):
-        for l in range(L):
-            for key in ("depth", "parallax", "other"):
-                _cmp(f"DepthEstimatorPyramid frame {t} level {l + 1} {key}", ref_seq[t][l][key], o_seq[t][l][key], rows)
-    _cmp("M4Depth.call depth (nearest x2 of the finest level)", ref_out["depth"], o_out["depth"], rows)
     # metrics.py through the clipping of test_step (m4depth_network.py:462-470)
-    gt = np.clip(samples[-1]["depth"], 0.0, 80.0).astype(F)
-    est = np.clip(o_out["depth"], 0.001, 80.0).astype(F)
     mets = [MT.AbsRelError(), MT.SqRelError(), MT.RootMeanSquaredError(), MT.RootMeanSquaredLogError(),
             MT.ThresholdRelError(1), MT.ThresholdRelError(2), MT.ThresholdRelError(3)]
     for m in mets:
         m.update_state(T(gt), T(est))
-    want = O.metrics_batch(samples[-1]["depth"], o_out["depth"])
-    for m, w_ in zip(mets, want):
-        _cmp(f"metrics.py {m.name}", np.asarray(m.result().a, F).reshape(1), np.asarray(w_, F).reshape(1), rows, tol=2e-6)
+    return ([pyrs[1][l] for l in range(L)]
+            + [ref_seq[t][l][key] for t in range(Tn) for l in range(L) for key in ("depth", "parallax", "other")]
+            + [ref_out["depth"], np.array([m.name for m in mets])]
+            + [np.asarray(m.result().a, F).reshape(1) for m in mets])
 
 
-def run(verbose=True):
+def run_network(rows, ref):
+    """m4depth_network.py + metrics.py of the reference under the stand-in against oracle.M4Depth / oracle.metrics_batch: a
+    3-level model, batch 2, one reset frame + two full frames, the oracle's He-normal weights."""
     sys.path.insert(0, ROOT)
     from oracle import m4depth_oracle as O
-    R, W = load_reference()
+    from m4depth_amd import synthetic as S
+    L, b, Tn, H, Wd = 3, 2, 3, 32, 48
+    Wts = S.init_weights(L, seed=77)
+    samples, cam = S.make_sequence(b, Tn, H, Wd, seed=78)
+    o_out, o_seq = O.M4Depth(Wts, L)(samples, cam)
+    opyr = O.feature_pyramid(samples[1]["RGB_im"], Wts, L)
+    gt = np.clip(samples[-1]["depth"], 0.0, 80.0).astype(F)
+    est = np.clip(o_out["depth"], 0.001, 80.0).astype(F)
+    got = iter(ref("M4Depth network", lambda: _reference_network(Wts, samples, cam, L, Tn, gt, est)))
+    for l in range(L):
+        _cmp(f"FeaturePyramid level {l + 1} (incl. DomainNormalization at level 0)", next(got), opyr[l], rows)
+    for t in range(Tn):
+        for l in range(L):
+            for key in ("depth", "parallax", "other"):
+                _cmp(f"DepthEstimatorPyramid frame {t} level {l + 1} {key}", next(got), o_seq[t][l][key], rows)
+    _cmp("M4Depth.call depth (nearest x2 of the finest level)", next(got), o_out["depth"], rows)
+    names = next(got)
+    want = O.metrics_batch(samples[-1]["depth"], o_out["depth"])
+    for name, w_ in zip(names, want):
+        _cmp(f"metrics.py {name}", next(got), np.asarray(w_, F).reshape(1), rows, tol=2e-6)
+
+
+def run(verbose=True, recorded=None):
+    """Every comparison, as [(name, ok, message)].  ``recorded`` None: the reference's functions run live (needs REF);
+    otherwise the reference's side comes from that recording (load_recorded()).  Returns (rows, the reference's side)."""
+    sys.path.insert(0, ROOT)
+    from oracle import m4depth_oracle as O
+    ref = ReferenceSide(recorded)
+    R = W = None
+    if recorded is None:
+        R, W = load_reference()
     rows = []
     g = dict(np.load(os.path.join(ROOT, "tests", "golden", "ops.npz")))
-    cvg = dict(np.load(os.path.join(ROOT, "tests", "golden", "cost_volumes.npz")))
 
     def cam_t(cam):
         return {k: T(v) for k, v in cam.items()}
@@ -626,7 +693,7 @@ def run(verbose=True):
         return {"f": np.tile(np.array([[0.5 * w, 0.55 * h]], F), [b, 1]), "c": np.tile(np.array([[0.48 * w, 0.52 * h]], F), [b, 1])}
 
     # ---- dense_image_warp (the python path: backproject.so is absent, dense_image_warp.py:44-61) on the golden vectors
-    out = W.dense_image_warp(T(g["warp_img"]), T(g["warp_flow"]))
+    out = ref("dense_image_warp(golden ops.npz)", lambda: W.dense_image_warp(T(g["warp_img"]), T(g["warp_flow"])))
     _cmp("dense_image_warp(golden ops.npz) vs golden output", out, g["warp_out"], rows)
     _cmp("dense_image_warp vs oracle.dense_image_warp", out, O.dense_image_warp(g["warp_img"], g["warp_flow"]), rows)
 
@@ -635,26 +702,31 @@ def run(verbose=True):
         b, h, w = 2, 7, 9
         rot, trans = motion(b, quat)
         cam = camera(b, h, w)
-        _cmp(f"get_rot_mat [{tag}]", R.get_rot_mat(T(rot)), O.get_rot_mat(rot), rows)
+        _cmp(f"get_rot_mat [{tag}]", ref(f"get_rot_mat [{tag}]", lambda: R.get_rot_mat(T(rot))), O.get_rot_mat(rot), rows)
         m = rng.standard_normal([b, h, w, 3]).astype(F)
-        co, me = R.get_coords_2d(T(m), cam_t(cam))
+        co, me = ref(f"get_coords_2d [{tag}]", lambda: R.get_coords_2d(T(m), cam_t(cam)))
         oc, om = O.get_coords_2d(b, h, w, cam)
-        _cmp(f"get_coords_2d coords [{tag}]", co[..., 0] if co.a.ndim == 5 else co, oc.reshape(np.asarray(co.a[..., 0] if co.a.ndim == 5 else co.a).shape), rows)
-        _cmp(f"get_coords_2d mesh [{tag}]", me, np.broadcast_to(om, me.a.shape), rows)
+        co = co[..., 0] if co.ndim == 5 else co
+        _cmp(f"get_coords_2d coords [{tag}]", co, oc.reshape(co.shape), rows)
+        _cmp(f"get_coords_2d mesh [{tag}]", me, np.broadcast_to(om, me.shape), rows)
         depth = (2.0 + 30.0 * rng.random([b, h, w, 1])).astype(F)
         para = (0.3 + 5.0 * rng.random([b, h, w, 1])).astype(F)
-        _cmp(f"parallax2depth [{tag}]", R.parallax2depth(T(para), T(rot), T(trans), cam_t(cam)), O.parallax2depth(para, rot, trans, cam), rows)
-        _cmp(f"depth2parallax [{tag}]", R.depth2parallax(T(depth), T(rot), T(trans), cam_t(cam)), O.depth2parallax(depth, rot, trans, cam), rows)
-        _cmp(f"prev_d2para [{tag}]", R.prev_d2para(T(depth), T(rot), T(trans), cam_t(cam)), O.prev_d2para(depth, rot, trans, cam), rows)
-        rw, (ra, rb) = R.reproject(T(m), T(depth), T(rot), T(trans), cam_t(cam))
+        _cmp(f"parallax2depth [{tag}]", ref(f"parallax2depth [{tag}]", lambda: R.parallax2depth(T(para), T(rot), T(trans), cam_t(cam))),
+             O.parallax2depth(para, rot, trans, cam), rows)
+        _cmp(f"depth2parallax [{tag}]", ref(f"depth2parallax [{tag}]", lambda: R.depth2parallax(T(depth), T(rot), T(trans), cam_t(cam))),
+             O.depth2parallax(depth, rot, trans, cam), rows)
+        _cmp(f"prev_d2para [{tag}]", ref(f"prev_d2para [{tag}]", lambda: R.prev_d2para(T(depth), T(rot), T(trans), cam_t(cam))),
+             O.prev_d2para(depth, rot, trans, cam), rows)
+        rw, ra, rb = ref(f"reproject [{tag}]", lambda: R.reproject(T(m), T(depth), T(rot), T(trans), cam_t(cam)))
         ow, (oa, ob) = O.reproject(m, depth, rot, trans, cam)
         _cmp(f"reproject warped map [{tag}]", rw, ow, rows, tol=0.0)
         _cmp(f"reproject aux 0 (proj - rot coords) [{tag}]", ra, oa, rows)
         _cmp(f"reproject aux 1 (rot coords) [{tag}]", rb, ob, rows)
-        _cmp(f"recompute_depth [{tag}]", R.recompute_depth(T(depth), T(rot), T(trans), cam_t(cam)), O.recompute_depth(depth, rot, trans, cam), rows)
-    _cmp("tile_in_batch", R.tile_in_batch(T(g["warp_img"]), 5), O.tile_in_batch(g["warp_img"], 5), rows)
+        _cmp(f"recompute_depth [{tag}]", ref(f"recompute_depth [{tag}]", lambda: R.recompute_depth(T(depth), T(rot), T(trans), cam_t(cam))),
+             O.recompute_depth(depth, rot, trans, cam), rows)
+    _cmp("tile_in_batch", ref("tile_in_batch", lambda: R.tile_in_batch(T(g["warp_img"]), 5)), O.tile_in_batch(g["warp_img"], 5), rows)
 
-    # ---- the two cost volumes: golden inputs where the file has them, + seeded geometries (1 / 2 / 4 cuts, ranges 4 and 2)
+    # ---- the two cost volumes: seeded geometries (1 / 2 / 4 cuts, ranges 4 and 2)
     for (b, h, w, C, k, r, quat) in ((1, 6, 7, 16, 1, 4, True), (2, 5, 8, 32, 2, 4, False), (1, 6, 6, 96, 4, 2, True)):
         rot, trans = motion(b, quat)
         cam = camera(b, h, w)
@@ -662,20 +734,31 @@ def run(verbose=True):
         c2 = O.normalize_cuts(rng.standard_normal([b, h, w, C]).astype(F), k)
         disp = (0.2 + 6.0 * rng.random([b, h, w, 1])).astype(F)
         dpt = (0.2 + 6.0 * rng.random([b, h, w, 1])).astype(F)
-        rcv, rpd = R.get_parallax_sweeping_cv(T(c1), T(c2), T(dpt), T(disp), T(rot), T(trans), cam_t(cam), r, k)
+        rcv, rpd = ref(f"get_parallax_sweeping_cv C={C} cuts={k} range={r}",
+                       lambda: R.get_parallax_sweeping_cv(T(c1), T(c2), T(dpt), T(disp), T(rot), T(trans), cam_t(cam), r, k))
         ocv, opd = O.get_parallax_sweeping_cv(c1, c2, dpt, disp, rot, trans, cam, r, k)
         _cmp(f"DSCV cost volume  C={C} cuts={k} range={r}", rcv, ocv, rows)
         _cmp(f"DSCV warped previous parallax  C={C} cuts={k} range={r}", rpd, opd, rows)
         for dil in (1, 2):
             _cmp(f"SNCV cost_volume  C={C} cuts={k} range=3 dilation={dil}",
-                 R.cost_volume(T(c1), T(c2), 3, dilation_rate=dil, nbre_cuts=k), O.cost_volume(c1, c2, 3, dilation_rate=dil, nbre_cuts=k), rows)
-    run_network(rows)
+                 ref(f"cost_volume C={C} cuts={k} range=3 dilation={dil}",
+                     lambda: R.cost_volume(T(c1), T(c2), 3, dilation_rate=dil, nbre_cuts=k)),
+                 O.cost_volume(c1, c2, 3, dilation_rate=dil, nbre_cuts=k), rows)
+    run_network(rows, ref)
     if verbose:
         for name, ok, msg in rows:
             print(f"{'ok  ' if ok else 'FAIL'}  {name:70s} {msg}")
         print(f"{sum(ok for _, ok, _ in rows)} of {len(rows)} comparisons agree")
-    return rows
+    return rows, ref.values
 
 
 if __name__ == "__main__":
-    sys.exit(0 if all(ok for _, ok, _ in run()) else 1)
+    # (no argument) live run against REF; --record: live run, then write what the reference returned to RECORDED;
+    # --replay: the same comparisons with the reference's side read from RECORDED (what the test suite runs)
+    replay = "--replay" in sys.argv[1:]
+    rows, values = run(recorded=load_recorded() if replay else None)
+    ok = all(ok for _, ok, _ in rows)
+    if "--record" in sys.argv[1:] and not replay and ok:
+        np.savez_compressed(RECORDED, **values)
+        print(f"recorded {len(values)} arrays of the reference's side to {os.path.relpath(RECORDED, ROOT)}")
+    sys.exit(0 if ok else 1)

@@ -95,3 +95,23 @@ def test_run_spread_and_box_kind_probe():
     assert slow["kind"].startswith("lock-step-slow") and slow["lock_step_over_staggered"] == round(2.498 / 2.408, 4) and slow["chosen_stagger_us"] == 9
     fast = bench.box_kind_probe({9: [2.40, 2.41], 0: [2.33, 2.34]}, 0)
     assert fast["kind"].startswith("lock-step-fast") and fast["lock_step_over_staggered"] < 1.0
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: arrays that fit are written whole as float32 / float64 .npy; past 64 MB in all the large ones become the
+    same seeded sample of their elements on every run (values + float64 flat indices), and the files stay within the limit."""
+    import numpy as np
+    small = {"metric_AbsRel": np.array([0.25], np.float32), "depth": np.random.default_rng(0).random([1, 6, 8, 1], dtype=np.float32)}
+    files = bench.dump_outputs(str(tmp_path / "a"), small)
+    assert files == {"metric_AbsRel": [1], "depth": [1, 6, 8, 1]}
+    assert np.array_equal(np.load(tmp_path / "a" / "depth.npy"), small["depth"])
+    big = {"metric_AbsRel": np.array([0.25], np.float32), "depth": np.arange(36 * 384 * 1280, dtype=np.float32).reshape(36, 384, 1280, 1)}
+    for run in ("b", "c"):
+        files = bench.dump_outputs(str(tmp_path / run), big)
+        assert set(files) == {"metric_AbsRel", "depth_sample", "depth_sample_index"}
+        names = os.listdir(tmp_path / run)
+        assert sum(os.path.getsize(tmp_path / run / n) for n in names) <= bench.DUMP_LIMIT_BYTES
+        assert all(np.load(tmp_path / run / n).dtype in (np.float32, np.float64) for n in names)
+    idx = np.load(tmp_path / "b" / "depth_sample_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "depth_sample_index.npy")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "depth_sample.npy"), idx.astype(np.float32))

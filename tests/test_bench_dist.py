@@ -52,6 +52,9 @@ def _worker(rank, world, port, q):
     from m4depth_amd import metrics as MT
     args = _args(gpus=world)
     assert B.check_world(args, os.environ, 0) == "run"
+    # the ranks of this leg are GPU-less on every machine: on a GPU box init_from_env would otherwise bind rank r to cuda:r,
+    # which a one-GPU box does not have
+    torch.cuda.is_available = lambda: False
     r, w, _, dev = D.init_from_env(backend="gloo")
     args.batch = 1 if w == 1 else 32                       # bench.main's default: configs[3]'s 32 sequences per rank
     args.batch = 4                                         # (kept small here: the batch is real data)

@@ -17,6 +17,7 @@ def _worker(rank, world, port, q):
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from m4depth_amd import dist as D
     from m4depth_amd import metrics as MT
+    torch.cuda.is_available = lambda: False                # CPU ranks on every machine (a GPU box would bind rank r to cuda:r)
     r, w, _, dev = D.init_from_env(backend="gloo")
     rng = np.random.default_rng(0)
     gt = torch.from_numpy((1 + 70 * rng.random([8, 2, 8, 8, 1])).astype(np.float32))      # 8 batches of 2
@@ -70,6 +71,7 @@ def _grad_worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from m4depth_amd import dist as D
+    torch.cuda.is_available = lambda: False                # CPU ranks on every machine (a GPU box would bind rank r to cuda:r)
     r, w, _, dev = D.init_from_env(backend="gloo")
     params = [torch.nn.Parameter(torch.zeros(3, 4)), torch.nn.Parameter(torch.zeros(5)), torch.nn.Parameter(torch.zeros(2))]
     params[0].grad = torch.full((3, 4), float(r + 1))

@@ -257,10 +257,10 @@ def test_oracle_matches_golden_well_conditioned(golden):
 
 
 def test_reference_wiring_crosscheck():
-    """the reference's OWN utils/depth_operations.py and utils/dense_image_warp.py, imported unmodified from
-    /root/reference under a minimal numpy-backed module named ``tensorflow`` (tests/golden/crosscheck_reference_wiring.py: ~60
-    array ops, each one numpy call), return what oracle/m4depth_oracle.py returns on the golden inputs and on seeded inputs --
-    warp, get_rot_mat, get_coords_2d, the converters, prev_d2para, reproject (both aux outputs), recompute_depth, tile_in_batch,
+    """the reference's OWN utils/depth_operations.py and utils/dense_image_warp.py, imported unmodified
+    under a minimal numpy-backed module named ``tensorflow`` (tests/golden/crosscheck_reference_wiring.py: ~60 array ops, each
+    one numpy call), return what oracle/m4depth_oracle.py returns on the golden inputs and on seeded inputs -- warp,
+    get_rot_mat, get_coords_2d, the converters, prev_d2para, reproject (both aux outputs), recompute_depth, tile_in_batch,
     the DSCV (1 / 2 / 4 cuts, ranges 4 and 2) and the SNCV (dilation 1 and 2) -- bit for bit; and the reference's
     m4depth_network.py (FeaturePyramid with DomainNormalization, DispRefiner, DepthEstimatorLevel.call with its temporal memory,
     DepthEstimatorPyramid.call, M4Depth.call) stepped through a reset frame and two full frames of a 3-level model with the
@@ -268,17 +268,17 @@ def test_reference_wiring_crosscheck():
     bit (the convolution arithmetic is shared: the stand-in's Conv2D calls the oracle's conv2d_same), its metrics.py the seven
     metrics of oracle.metrics_batch to float32 rounding.  It checks the restatement's
     WIRING (reshapes, axes, channel order, operand order) against the reference's text; it does not pin TensorFlow's internal
-    arithmetic (the stand-in takes the oracle's documented [UNPINNED] choices), so the parity grade stays "unpinned".  Build
-    container only: skipped where /root/reference does not exist (the GPU box)."""
+    arithmetic (the stand-in takes the oracle's documented [UNPINNED] choices), so the parity grade stays "unpinned".
+    The reference's side of every comparison is the recording of a live run (tests/golden/crosscheck_reference_wiring.npz,
+    written by ``python tests/golden/crosscheck_reference_wiring.py --record`` where the reference's source is at hand): the
+    oracle's side is recomputed here from the same inputs and compared with it."""
     import importlib.util
     import os
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crosscheck_reference_wiring.py")
     spec = importlib.util.spec_from_file_location("crosscheck_reference_wiring", here)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    if not os.path.isfile(os.path.join(mod.REF, "utils", "depth_operations.py")):
-        pytest.skip("no /root/reference here (the GPU box): the cross-check is a build-container tool")
-    rows = mod.run(verbose=False)
+    rows, _ = mod.run(verbose=False, recorded=mod.load_recorded())
     bad = [(n, m) for n, ok, m in rows if not ok]
     assert len(rows) >= 73 and not bad, bad
     import sys

@@ -73,7 +73,7 @@ def test_latest_checkpoint_state_file(tmp_path):
 
 # ------------------------------------------------------------------ files written by TensorFlow itself
 # tests/golden/tf_legacy/: the index files of the bundles the reference ships for its legacy model
-# (/root/reference/.legacy/trained_weights/M4Depth-d6: M4Depth/features, its optimizers, M4Depth/upscaler, pipeline)
+# (the reference's .legacy/trained_weights/M4Depth-d6: M4Depth/features, its optimizers, M4Depth/upscaler, pipeline)
 # and the first 66624 bytes (8 tensors) of the features data file.  Every block trailer and every tensor entry holds a
 # masked crc32c computed by TensorFlow: they pin the table, BundleEntryProto and tensor-data layers of the reader.
 _LEGACY = os.path.join(os.path.dirname(__file__), "golden", "tf_legacy")
@@ -108,6 +108,9 @@ def test_index_known_answers():
     assert up["RIDEN_0/depth_estimator/conv_0/kernel"]["shape"] == [3, 3, 107, 128]
     pipe = TC.CheckpointReader(os.path.join(_LEGACY, "pipeline")).entries
     assert pipe["Pipeline_Global_Step/global_step"]["dtype"] == 9 and pipe["Pipeline_Global_Step/global_step"]["shape"] == []
+    sizes = sorted((v["offset"], v["size"]) for v in pipe.values())
+    assert sizes[0][0] == 0 and all(a[0] + a[1] == b[0] for a, b in zip(sizes, sizes[1:]))
+    assert sizes[-1][0] + sizes[-1][1] == 3907680                         # = the size of the pipeline data file in the reference
 
 
 def _legacy_reader(tmp_path=None, corrupt_at=None):
@@ -153,20 +156,3 @@ def test_checksum_functions():
     assert TC.crc32c(b"123456789") == 0xE3069283
     assert TC.crc32c(b"\x00" * 32) == 0x8A9136AA and TC.crc32c(b"\xff" * 32) == 0x62A8AB43       # RFC 3720 B.4
     assert TC.masked_crc32c(b"abc") == W.masked_crc(b"abc")
-
-
-_REFERENCE_LEGACY = "/root/reference/.legacy/trained_weights/M4Depth-d6"
-
-
-@pytest.mark.skipif(not os.path.isdir(_REFERENCE_LEGACY), reason="the reference tree is not on this machine")
-@pytest.mark.parametrize("prefix", ["M4Depth/features/checkpoint-200000", "pipeline/checkpoint-200000"])
-def test_complete_bundles_of_the_reference(prefix):
-    """Every tensor of the two bundles whose data files the reference ships (8 MB), crc-verified."""
-    assert TC.latest_checkpoint(os.path.join(_REFERENCE_LEGACY, os.path.dirname(prefix))) == os.path.join(_REFERENCE_LEGACY, prefix)
-    reader = TC.CheckpointReader(os.path.join(_REFERENCE_LEGACY, prefix))
-    total = 0
-    for k in reader.keys():
-        t = reader.tensor(k)
-        assert list(t.shape) == reader.entries[k]["shape"]
-        total += t.nbytes
-    assert total == os.path.getsize(os.path.join(_REFERENCE_LEGACY, prefix) + ".data-00000-of-00001")
