@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define M4D_ABI_VERSION 6   /* 6 (round 6): + m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
+#define M4D_ABI_VERSION 6   /* 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
 
 /* Library / device introspection (no GPU work). */
 int m4d_abi_version(void);
@@ -223,6 +223,32 @@ int m4d_refiner_tail6(const float* x32, const void* w6f, const float* b6, const 
                       const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
                       int b, int h, int w, float scale, float* parallax, float* depth, float* other,
                       float* depth_state, void* stream);
+
+/* ---- streaming inference: B independent streams in one batch, per-sample trajectory resets on the device ---------------------
+ * The masked level close: m4d_refiner_tail6 / m4d_refiner_tail / m4d_level_post with reset [b] (uint8, nonzero = the sample's
+ * trajectory starts at this frame).  A masked sample gets the reset constants m4d_pyramid_reset writes (m4depth_network.py:198-214):
+ * parallax = reset_parallax (the caller passes 2^(number of coarser levels)), depth = 1000, other = 0, depth_state = 1000 -- the
+ * refiner's values are neither computed nor written for it; an unmasked sample gets exactly the bits of the unmasked entry point
+ * (:216-260).  depth_state and reset are required here.  No sample's result depends on another sample's inputs. */
+int m4d_refiner_tail6_m(const float* x32, const void* w6f, const float* b6, const void* w7f, const float* b7,
+                        const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
+                        int b, int h, int w, float scale, float* parallax, float* depth, float* other,
+                        float* depth_state, const unsigned char* reset, float reset_parallax, void* stream);
+int m4d_refiner_tail_m(const float* x32, const float* w6p, const float* b6, const float* w7p, const float* b7,
+                       const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
+                       int b, int h, int w, float scale, float* parallax, float* depth, float* other,
+                       float* depth_state, const unsigned char* reset, float reset_parallax, void* stream);
+int m4d_level_post_m(const float* refiner_out, const float* rot, int rot_c, const float* trans,
+                     const float* cam_f, const float* cam_c, int b, int h, int w, float scale,
+                     float* parallax, float* depth, float* other, float* depth_state,
+                     const unsigned char* reset, float reset_parallax, void* stream);
+/* One launch per streamed frame (the reference's per-frame loop, main.py:150-172, with the batch-level rule of
+ * m4depth_network.py:206-208 made per sample): reset[s] = force_all || new_traj[s] (new_traj [b] bool / uint8); rot_out [b,rot_c] /
+ * trans_out [b,3] = the pose copy the level fronts read, in which a reset sample carries identity rotation ((0,0,0) small angle,
+ * (1,0,0,0) quaternion) and translation (0,0,1) instead of its own (its outputs are the reset constants; its pose only keeps the
+ * discarded arithmetic finite).  Continuing samples: their pose, unchanged. */
+int m4d_stream_prepare(const unsigned char* new_traj, int force_all, const float* rot, int rot_c, const float* trans,
+                       int b, unsigned char* reset, float* rot_out, float* trans_out, void* stream);
 
 /* ---- gradients of the cost volumes (train_step, m4depth_network.py:371-399) ------ */
 

@@ -137,6 +137,13 @@ _SIGNATURES = {
     "m4d_camera_pyramid": [_c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp],
     "m4d_level_post": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
                        _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
+    "m4d_refiner_tail_m": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
+                           _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp],
+    "m4d_refiner_tail6_m": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
+                            _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp],
+    "m4d_level_post_m": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
+                         _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp],
+    "m4d_stream_prepare": [_c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp],
 }
 
 # include/m4depth_hip_experiments.h: present only in a `make EXPERIMENTS=1` build of the library (the launch tape and the

@@ -230,15 +230,28 @@ extern "C" int m4d_pyramid_reset(const m4d_reset_level* levels, int n_levels, in
 }
 
 // ---- fused "depth_estimator" tail (:247-260) --------------------------------------
+// MASK (streaming, m4d_level_post_m): the workgroup's image is blockIdx.y -- a reset sample is a workgroup-uniform branch that
+// writes the reset constants (:198-214, what m4d_pyramid_reset writes) instead of the computed values.
+template <bool MASK>
 __global__ void __launch_bounds__(256)
 level_post_kernel(const float* __restrict__ ro, const float* __restrict__ rot, int rot_c,
                   const float* __restrict__ trans, const float* __restrict__ cam_f,
                   const float* __restrict__ cam_c, int h, int w, float scale,
                   float* __restrict__ parallax, float* __restrict__ depth, float* __restrict__ other,
-                  float* __restrict__ depth_state) {
+                  float* __restrict__ depth_state, const unsigned char* __restrict__ reset, float reset_parallax) {
   const int bi = blockIdx.y;
-  const M4dMotion m = m4d_load_motion(rot, rot_c, trans, cam_f, cam_c, bi);
   const int hw = h * w;
+  if (MASK && reset[bi]) {
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += gridDim.x * blockDim.x) {
+      const long long gp = (long long)bi * hw + p;
+      parallax[gp] = reset_parallax;
+      depth[gp] = 1000.0f;
+      depth_state[gp] = 1000.0f;
+      *reinterpret_cast<float4*>(other + gp * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
+  const M4dMotion m = m4d_load_motion(rot, rot_c, trans, cam_f, cam_c, bi);
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += gridDim.x * blockDim.x) {
     const int i = p % w, j = p / w;
     const long long gp = (long long)bi * hw + p;
@@ -251,6 +264,22 @@ level_post_kernel(const float* __restrict__ ro, const float* __restrict__ rot, i
     if (depth_state) depth_state[gp] = d;
     *reinterpret_cast<float4*>(other + gp * 4) = make_float4(r[1], r[2], r[3], r[4]);
   }
+}
+
+// ---- streaming: the per-frame reset mask and the pose the front kernels see (m4d_stream_prepare) ----
+// reset[s] = force_all || new_traj[s]; a reset sample's outputs are discarded (the masked level close writes constants), but its
+// pose still drives the level fronts: it gets a fixed benign motion -- identity rotation, translation (0,0,1) -- instead of what
+// it came with (a trajectory's first frame typically carries trans = 0: 0/0 queries nobody reads).  Continuing samples: a copy.
+__global__ void __launch_bounds__(64)
+stream_prepare_kernel(const unsigned char* __restrict__ new_traj, int force_all, const float* __restrict__ rot, int rot_c,
+                      const float* __restrict__ trans, int b, unsigned char* __restrict__ reset, float* __restrict__ rot_out,
+                      float* __restrict__ trans_out) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= b) return;
+  const bool r = force_all != 0 || new_traj[s] != 0;
+  reset[s] = r ? 1 : 0;
+  for (int k = 0; k < rot_c; ++k) rot_out[s * rot_c + k] = r ? ((rot_c == 4 && k == 0) ? 1.0f : 0.0f) : rot[s * rot_c + k];
+  for (int k = 0; k < 3; ++k) trans_out[s * 3 + k] = r ? (k == 2 ? 1.0f : 0.0f) : trans[s * 3 + k];
 }
 
 // ---- convolution epilogue: + bias, leaky_relu (m4depth_network.py:84,87,123,133) -----
@@ -453,8 +482,33 @@ extern "C" int m4d_level_post(const float* refiner_out, const float* rot, int ro
   M4D_CHECK_ARG((((uintptr_t)other) & 15u) == 0);
   int gx = m4d_blocks((long long)h * w, 256);
   if (gx > 4096) gx = 4096;
-  m4d_launch(level_post_kernel, dim3(gx, b), dim3(256), 0, (hipStream_t)stream,
-                     refiner_out, rot, rot_c, trans, cam_f, cam_c, h, w, scale, parallax, depth, other, depth_state);
+  m4d_launch(level_post_kernel<false>, dim3(gx, b), dim3(256), 0, (hipStream_t)stream,
+                     refiner_out, rot, rot_c, trans, cam_f, cam_c, h, w, scale, parallax, depth, other, depth_state,
+                     (const unsigned char*)nullptr, 0.f);
+  return M4D_LAUNCH_RESULT();
+}
+
+extern "C" int m4d_level_post_m(const float* refiner_out, const float* rot, int rot_c, const float* trans,
+                                const float* cam_f, const float* cam_c, int b, int h, int w, float scale,
+                                float* parallax, float* depth, float* other, float* depth_state,
+                                const unsigned char* reset, float reset_parallax, void* stream) {
+  M4D_CHECK_ARG(refiner_out && rot && trans && cam_f && cam_c && parallax && depth && other && depth_state && reset);
+  M4D_CHECK_ARG(b > 0 && h > 0 && w > 0 && (rot_c == 3 || rot_c == 4));
+  M4D_CHECK_ARG((((uintptr_t)other) & 15u) == 0);
+  int gx = m4d_blocks((long long)h * w, 256);
+  if (gx > 4096) gx = 4096;
+  m4d_launch(level_post_kernel<true>, dim3(gx, b), dim3(256), 0, (hipStream_t)stream,
+                     refiner_out, rot, rot_c, trans, cam_f, cam_c, h, w, scale, parallax, depth, other, depth_state,
+                     reset, reset_parallax);
+  return M4D_LAUNCH_RESULT();
+}
+
+extern "C" int m4d_stream_prepare(const unsigned char* new_traj, int force_all, const float* rot, int rot_c, const float* trans,
+                                  int b, unsigned char* reset, float* rot_out, float* trans_out, void* stream) {
+  M4D_CHECK_ARG(new_traj && rot && trans && reset && rot_out && trans_out);
+  M4D_CHECK_ARG(b > 0 && (rot_c == 3 || rot_c == 4));
+  m4d_launch(stream_prepare_kernel, dim3((unsigned)m4d_blocks(b, 64)), dim3(64), 0, (hipStream_t)stream,
+             new_traj, force_all, rot, rot_c, trans, b, reset, rot_out, trans_out);
   return M4D_LAUNCH_RESULT();
 }
 

@@ -26,6 +26,7 @@ struct TailArgs {
   const float* rot; int rot_c; const float* trans; const float* cam_f; const float* cam_c;
   int h, w, tiles_x; float scale;
   float* parallax; float* depth; float* other; float* depth_state;
+  const unsigned char* reset; float reset_parallax;   // MASK: per-sample reset flags [b] and the level's reset parallax
 };
 
 // (Measured: an 8 x 4-tile instantiation for the small maps of the coarse levels -- a quarter of the work per workgroup --
@@ -39,6 +40,9 @@ constexpr int kMW = kTW + 2, kMH = kTH + 2, kMP = kMW * kMH;     // conv6 positi
 constexpr int kXS = 36, kMS = 20;                                // LDS row strides (floats): 32 + 4, 16 + 4
 constexpr int kW6 = 9 * 16 * kXS, kW7 = 9 * 8 * kMS;               // w7: only 8 of the 16 packed cout rows are kept (5 used)
 
+// MASK (streaming, m4d_refiner_tail_m): the workgroup's image is blockIdx.y, so a reset sample is a workgroup-uniform branch that
+// writes the reset constants (m4depth_network.py:198-214, what m4d_pyramid_reset writes) and skips the refiner work.
+template <bool MASK>
 __global__ void __launch_bounds__(256, 2)
 refiner_tail_kernel(const TailArgs a) {
   extern __shared__ __align__(16) float lds[];
@@ -54,6 +58,19 @@ refiner_tail_kernel(const TailArgs a) {
   if ((nb & 7) == 0) blk = (blk & 7) * (nb >> 3) + (blk >> 3);       // one band of tiles per XCD
   const int tile_y = (blk / a.tiles_x) * kTH, tile_x = (blk % a.tiles_x) * kTW;
   const float* ximg = a.x + (long long)bi * a.h * a.w * 32;
+  if (MASK && a.reset[bi]) {
+    if (t < kTW * kTH) {
+      const int oy = tile_y + (t >> 4), ox = tile_x + (t & 15);
+      if (oy < a.h && ox < a.w) {
+        const long long gp = ((long long)bi * a.h + oy) * a.w + ox;
+        a.parallax[gp] = a.reset_parallax;
+        a.depth[gp] = 1000.0f;
+        a.depth_state[gp] = 1000.0f;
+        *reinterpret_cast<float4*>(a.other + gp * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    return;
+  }
 
   // ---- stage A: input halo (zero outside the image) and both weight sets -> LDS.  Unconditional loads (clamped
   // coordinates + select): a branch around a load makes hipcc wait for it at the merge.
@@ -168,6 +185,32 @@ refiner_tail_kernel(const TailArgs a) {
 
 }  // namespace
 
+namespace {
+
+int launch_tail(bool mask, const float* x32, const float* w6p, const float* b6, const float* w7p, const float* b7,
+                const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
+                int b, int h, int w, float scale, float* parallax, float* depth, float* other, float* depth_state,
+                const unsigned char* reset, float reset_parallax, void* stream) {
+  TailArgs a;
+  a.x = x32; a.w6 = w6p; a.b6 = b6; a.w7 = w7p; a.b7 = b7; a.rot = rot; a.rot_c = rot_c; a.trans = trans;
+  a.cam_f = cam_f; a.cam_c = cam_c; a.h = h; a.w = w; a.scale = scale;
+  a.parallax = parallax; a.depth = depth; a.other = other; a.depth_state = depth_state;
+  a.reset = reset; a.reset_parallax = reset_parallax;
+  a.tiles_x = (w + kTW - 1) / kTW;
+  const int tiles = a.tiles_x * ((h + kTH - 1) / kTH);
+  constexpr size_t lds = (size_t)(kXP * kXS + kMP * kMS + kW6 + kW7) * sizeof(float);          // 75.5 KB
+  if (mask) {
+    M4D_LDS_OPT_IN(&refiner_tail_kernel<true>);
+    m4d_launch(refiner_tail_kernel<true>, dim3(tiles, b), dim3(256), lds, (hipStream_t)stream, a);
+  } else {
+    M4D_LDS_OPT_IN(&refiner_tail_kernel<false>);
+    m4d_launch(refiner_tail_kernel<false>, dim3(tiles, b), dim3(256), lds, (hipStream_t)stream, a);
+  }
+  return M4D_LAUNCH_RESULT();
+}
+
+}  // namespace
+
 extern "C" int m4d_refiner_tail(const float* x32, const float* w6p, const float* b6, const float* w7p, const float* b7,
                                 const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
                                 int b, int h, int w, float scale, float* parallax, float* depth, float* other,
@@ -175,14 +218,17 @@ extern "C" int m4d_refiner_tail(const float* x32, const float* w6p, const float*
   M4D_CHECK_ARG(x32 && w6p && b6 && w7p && b7 && trans && cam_f && cam_c && parallax && depth && other);
   M4D_CHECK_ARG(b > 0 && h > 0 && w > 0 && (rot == nullptr || rot_c == 3 || rot_c == 4));
   M4D_CHECK_ARG(((((uintptr_t)x32 | (uintptr_t)w6p | (uintptr_t)w7p | (uintptr_t)other)) & 15u) == 0);
-  TailArgs a;
-  a.x = x32; a.w6 = w6p; a.b6 = b6; a.w7 = w7p; a.b7 = b7; a.rot = rot; a.rot_c = rot_c; a.trans = trans;
-  a.cam_f = cam_f; a.cam_c = cam_c; a.h = h; a.w = w; a.scale = scale;
-  a.parallax = parallax; a.depth = depth; a.other = other; a.depth_state = depth_state;
-  a.tiles_x = (w + kTW - 1) / kTW;
-  const int tiles = a.tiles_x * ((h + kTH - 1) / kTH);
-  constexpr size_t lds = (size_t)(kXP * kXS + kMP * kMS + kW6 + kW7) * sizeof(float);          // 75.5 KB
-  M4D_LDS_OPT_IN(&refiner_tail_kernel);
-  m4d_launch(refiner_tail_kernel, dim3(tiles, b), dim3(256), lds, (hipStream_t)stream, a);
-  return M4D_LAUNCH_RESULT();
+  return launch_tail(false, x32, w6p, b6, w7p, b7, rot, rot_c, trans, cam_f, cam_c, b, h, w, scale, parallax, depth, other,
+                     depth_state, nullptr, 0.f, stream);
+}
+
+extern "C" int m4d_refiner_tail_m(const float* x32, const float* w6p, const float* b6, const float* w7p, const float* b7,
+                                  const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
+                                  int b, int h, int w, float scale, float* parallax, float* depth, float* other,
+                                  float* depth_state, const unsigned char* reset, float reset_parallax, void* stream) {
+  M4D_CHECK_ARG(x32 && w6p && b6 && w7p && b7 && trans && cam_f && cam_c && parallax && depth && other && depth_state && reset);
+  M4D_CHECK_ARG(b > 0 && h > 0 && w > 0 && (rot == nullptr || rot_c == 3 || rot_c == 4));
+  M4D_CHECK_ARG(((((uintptr_t)x32 | (uintptr_t)w6p | (uintptr_t)w7p | (uintptr_t)other)) & 15u) == 0);
+  return launch_tail(true, x32, w6p, b6, w7p, b7, rot, rot_c, trans, cam_f, cam_c, b, h, w, scale, parallax, depth, other,
+                     depth_state, reset, reset_parallax, stream);
 }

@@ -35,6 +35,7 @@ struct Tail6Args {
   const float* rot; int rot_c; const float* trans; const float* cam_f; const float* cam_c;
   int h, w, tiles_x, tiles_per_image, items; float scale;
   float* parallax; float* depth; float* other; float* depth_state;
+  const unsigned char* reset; float reset_parallax;   // MASK: per-sample reset flags [b] and the level's reset parallax
 };
 
 constexpr int kTW = 14, kTH = 10;                                // output tile
@@ -47,6 +48,9 @@ constexpr int kOffMid = 3 * kXPart;                              // 48768
 constexpr int kOffW7 = kOffMid + 3 * kMPart;                     // 67584
 constexpr int kLds = kOffW7 + 5 * 3 * 512;                       // 75264 B
 
+// MASK (streaming, m4d_refiner_tail6_m): a tile lies inside one image, so a reset sample's tile is a workgroup-uniform branch that
+// writes the reset constants (m4depth_network.py:198-214, what m4d_pyramid_reset writes) and skips the refiner work.
+template <bool MASK>
 __global__ void __launch_bounds__(256, 2)
 refiner_tail6_kernel(const Tail6Args a) {
   extern __shared__ __align__(16) unsigned char lds[];
@@ -82,6 +86,20 @@ refiner_tail6_kernel(const Tail6Args a) {
     const int bi = item / a.tiles_per_image, tile = item - bi * a.tiles_per_image;
     const int tile_y = (tile / a.tiles_x) * kTH, tile_x = (tile % a.tiles_x) * kTW;
     const float* ximg = a.x + (long long)bi * a.h * a.w * 32;
+    if (MASK && a.reset[bi]) {                                   // no LDS touched: the barrier at the end of the last tile suffices
+      if (t < kTW * kTH) {
+        const int py = t / kTW, pxl = t - py * kTW;
+        const int oy = tile_y + py, ox = tile_x + pxl;
+        if (oy < a.h && ox < a.w) {
+          const long long gp = ((long long)bi * a.h + oy) * a.w + ox;
+          a.parallax[gp] = a.reset_parallax;
+          a.depth[gp] = 1000.0f;
+          a.depth_state[gp] = 1000.0f;
+          *reinterpret_cast<float4*>(a.other + gp * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      continue;
+    }
 
     // ---- stage A: input halo (zero outside the image), split into three bf16 planes
     {
@@ -234,6 +252,36 @@ refiner_tail6_kernel(const Tail6Args a) {
 
 }  // namespace
 
+namespace {
+
+int launch_tail6(bool mask, const float* x32, const void* w6f, const float* b6, const void* w7f, const float* b7,
+                 const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
+                 int b, int h, int w, float scale, float* parallax, float* depth, float* other, float* depth_state,
+                 const unsigned char* reset, float reset_parallax, void* stream) {
+  Tail6Args a;
+  a.x = x32; a.w6 = reinterpret_cast<const unsigned char*>(w6f); a.b6 = b6; a.w7 = reinterpret_cast<const unsigned char*>(w7f); a.b7 = b7;
+  a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c; a.h = h; a.w = w; a.scale = scale;
+  a.parallax = parallax; a.depth = depth; a.other = other; a.depth_state = depth_state;
+  a.reset = reset; a.reset_parallax = reset_parallax;
+  a.tiles_x = (w + kTW - 1) / kTW;
+  a.tiles_per_image = a.tiles_x * ((h + kTH - 1) / kTH);
+  const long long items = (long long)a.tiles_per_image * b;
+  M4D_CHECK_ARG(items < (1ll << 31));
+  a.items = (int)items;
+  const int max_wg = 2 * m4d_device_cus();
+  const dim3 grid((unsigned)(items < max_wg ? items : max_wg));
+  if (mask) {
+    M4D_LDS_OPT_IN_BYTES(kLds, &refiner_tail6_kernel<true>);
+    m4d_launch(refiner_tail6_kernel<true>, grid, dim3(256), (size_t)kLds, (hipStream_t)stream, a);
+  } else {
+    M4D_LDS_OPT_IN_BYTES(kLds, &refiner_tail6_kernel<false>);
+    m4d_launch(refiner_tail6_kernel<false>, grid, dim3(256), (size_t)kLds, (hipStream_t)stream, a);
+  }
+  return M4D_LAUNCH_RESULT();
+}
+
+}  // namespace
+
 // include/m4depth_hip.h: m4d_refiner_tail6
 extern "C" int m4d_refiner_tail6(const float* x32, const void* w6f, const float* b6, const void* w7f, const float* b7,
                                  const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
@@ -242,17 +290,18 @@ extern "C" int m4d_refiner_tail6(const float* x32, const void* w6f, const float*
   M4D_CHECK_ARG(x32 && w6f && b6 && w7f && b7 && trans && cam_f && cam_c && parallax && depth && other);
   M4D_CHECK_ARG(b > 0 && h > 0 && w > 0 && (rot == nullptr || rot_c == 3 || rot_c == 4));
   M4D_CHECK_ARG(((((uintptr_t)x32 | (uintptr_t)w6f | (uintptr_t)w7f | (uintptr_t)other)) & 15u) == 0);
-  Tail6Args a;
-  a.x = x32; a.w6 = reinterpret_cast<const unsigned char*>(w6f); a.b6 = b6; a.w7 = reinterpret_cast<const unsigned char*>(w7f); a.b7 = b7;
-  a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c; a.h = h; a.w = w; a.scale = scale;
-  a.parallax = parallax; a.depth = depth; a.other = other; a.depth_state = depth_state;
-  a.tiles_x = (w + kTW - 1) / kTW;
-  a.tiles_per_image = a.tiles_x * ((h + kTH - 1) / kTH);
-  const long long items = (long long)a.tiles_per_image * b;
-  M4D_CHECK_ARG(items < (1ll << 31));
-  a.items = (int)items;
-  M4D_LDS_OPT_IN_BYTES(kLds, &refiner_tail6_kernel);
-  const int max_wg = 2 * m4d_device_cus();
-  m4d_launch(refiner_tail6_kernel, dim3((unsigned)(items < max_wg ? items : max_wg)), dim3(256), (size_t)kLds, (hipStream_t)stream, a);
-  return M4D_LAUNCH_RESULT();
+  return launch_tail6(false, x32, w6f, b6, w7f, b7, rot, rot_c, trans, cam_f, cam_c, b, h, w, scale, parallax, depth, other,
+                      depth_state, nullptr, 0.f, stream);
+}
+
+// include/m4depth_hip.h: m4d_refiner_tail6_m
+extern "C" int m4d_refiner_tail6_m(const float* x32, const void* w6f, const float* b6, const void* w7f, const float* b7,
+                                   const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
+                                   int b, int h, int w, float scale, float* parallax, float* depth, float* other,
+                                   float* depth_state, const unsigned char* reset, float reset_parallax, void* stream) {
+  M4D_CHECK_ARG(x32 && w6f && b6 && w7f && b7 && trans && cam_f && cam_c && parallax && depth && other && depth_state && reset);
+  M4D_CHECK_ARG(b > 0 && h > 0 && w > 0 && (rot == nullptr || rot_c == 3 || rot_c == 4));
+  M4D_CHECK_ARG(((((uintptr_t)x32 | (uintptr_t)w6f | (uintptr_t)w7f | (uintptr_t)other)) & 15u) == 0);
+  return launch_tail6(true, x32, w6f, b6, w7f, b7, rot, rot_c, trans, cam_f, cam_c, b, h, w, scale, parallax, depth, other,
+                      depth_state, reset, reset_parallax, stream);
 }

@@ -49,6 +49,9 @@ def build_parser():
                         "file, e.g. pretrained_weights/midair): used instead of <ckpt_dir>/train for the initial weights")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--graph", action="store_true", help="replay the sequence forward from a hipGraph")
+    p.add_argument("--stream", action="store_true",
+                   help="predict: run the frames as B independent streams with per-sample trajectory resets (M4Depth.stream_step; "
+                        "with --graph replayed from network.GraphedStream)")
     p.add_argument("--host_input", action="store_true",
                    help="synthetic eval: hand every batch over from pinned HOST memory (the PCIe copy is part of the step) and "
                         "print the frames/s of the loop -- the PCIe-inclusive rate, next to bench.py's HBM-resident one")
@@ -194,8 +197,19 @@ def train(args, ablation, rank, world, dev):
     return 0
 
 
+def _stream_frame(frame, dev):
+    """One frame for ``M4Depth.stream_step``: every input on the device (new_traj included: the per-sample reset mask is built
+    there)."""
+    out = {k: frame[k].to(dev, non_blocking=True) for k in ("RGB_im", "rot", "trans", "new_traj")}
+    out["camera"] = {k: v.to(dev, non_blocking=True) for k, v in frame["camera"].items()}
+    return out
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.stream and args.mode != "predict":
+        parser.error("--stream is a --mode=predict option")
     rank, world, _, dev = D.init_from_env()
     if dev.type != "cuda":
         raise SystemExit("m4depth_amd.main needs a GPU: the hot path has no CPU fallback")
@@ -214,6 +228,19 @@ def main(argv=None):
             batches = list(batches)                # generation is not part of the measured loop
     else:
         batches, _ = dataset_batches(args, "predict" if args.mode == "predict" else "eval", rank, world, dev)
+    stream_runner = []
+
+    def predict(frame):
+        if not args.stream:
+            return model.predict_step(frame)["depth"]
+        sf = _stream_frame(frame, dev)
+        if not args.graph:
+            return model.stream_step(sf)["depth"]
+        if not stream_runner:
+            from .network import GraphedStream
+            stream_runner.append(GraphedStream(model, sf))
+        return stream_runner[0](sf)["depth"]
+
     import time
     n_frames, t_loop = 0, None
     for batch_idx, data in enumerate(batches):
@@ -225,7 +252,7 @@ def main(argv=None):
             n_frames += data["RGB_im"].shape[0] * data["RGB_im"].shape[1]
         if data["RGB_im"].dim() == 4:            # streaming frame of a real dataset (db_seq_len None)
             if args.mode == "predict":
-                preds.append(model.predict_step(data)["depth"].cpu().numpy())
+                preds.append(predict(data).cpu().numpy())
             else:
                 model.test_step(data)
             continue
@@ -233,7 +260,7 @@ def main(argv=None):
             for t in range(data["RGB_im"].shape[1]):
                 frame = {k: data[k][:, t] for k in ("depth", "RGB_im", "rot", "trans", "new_traj")}
                 frame["camera"] = data["camera"]
-                preds.append(model.predict_step(frame)["depth"].cpu().numpy())
+                preds.append(predict(frame).cpu().numpy())
             continue
         if args.graph:
             if runner is None:

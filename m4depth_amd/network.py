@@ -785,18 +785,27 @@ class DepthEstimatorLevel(torch.nn.Module):
                 and bool(lib.m4d_level_front_small_supported(c, self.nbre_cuts, self.dscv_range, self.sncv_range)))
 
     def forward(self, curr_f_maps, prev_l_est, rot, trans, camera, new_traj, prev_f_maps=None, prev_t_depth=None,
-                curr_f_normalized=None):
+                curr_f_normalized=None, reset_mask=None, reset_parallax=None):
         """``curr_f_normalized`` (inference, optional): the per-cut normalised ``curr_f_maps`` computed ahead of the level
-        (``wants_prenormalized``): the level then opens with ONE launch and the tensor becomes its ``prev_f_maps``."""
+        (``wants_prenormalized``): the level then opens with ONE launch and the tensor becomes its ``prev_f_maps``.
+
+        ``reset_mask`` (streaming inference, optional): a [b] device mask of the samples whose trajectory starts at this frame.
+        ``new_traj`` is then never read: the full level step runs for every sample and closes with the masked tail, which gives a
+        masked sample the reset estimate (parallax ``reset_parallax``, depth 1000, other 0) and state (depth_prev_t 1000, prev_f_maps
+        its normalised features: m4depth_network.py:208-214) and every other sample the normal step on its own state (:216-260)."""
         curr_f_maps = as_f32(curr_f_maps, "curr_f_maps")
         b, h, w, c = curr_f_maps.shape
         dev = curr_f_maps.device
         k = self.nbre_cuts
+        if reset_mask is not None and (self.is_training or prev_f_maps is not None or prev_t_depth is not None):
+            raise RuntimeError("DepthEstimatorLevel: a reset mask is for inference on the level's own state (not training mode)")
         use_state = (not self.is_training) and prev_f_maps is None and prev_t_depth is None    # :192
         if not self.is_training:
             self._ensure_state((b, h, w, c), dev)
         nt = new_traj
-        if isinstance(nt, torch.Tensor):
+        if reset_mask is not None:
+            nt = False                                 # per-sample resets happen in the masked close: no host read
+        elif isinstance(nt, torch.Tensor):
             nt = bool(nt.reshape(-1)[0].item())       # "sequences are synchronized over the batch" (:207)
         elif not isinstance(nt, bool):
             nt = bool(np.asarray(nt).reshape(-1)[0])
@@ -918,6 +927,7 @@ class DepthEstimatorLevel(torch.nn.Module):
             debug_tap("encoder_map", self.lvl_depth, curr_f_maps)
             debug_tap("f_input", self.lvl_depth, self.last_f_input)
         # "depth_estimator" (:244-260)
+        mask_kw = {} if reset_mask is None else {"reset": reset_mask, "reset_parallax": float(reset_parallax)}
         convs = list(self.disp_refiner.prep_conv_layers) + list(self.disp_refiner.est_d_conv_layers)
         if (fused_refiner_tail and dev.type == "cuda" and len(convs) == 7 and convs[5].weight is not None
                 and tuple(convs[5].weight.shape[:2]) == (16, 32) and tuple(convs[6].weight.shape[:2]) == (5, 16)):
@@ -931,11 +941,12 @@ class DepthEstimatorLevel(torch.nn.Module):
             tail_fn = nops.refiner_tail6 if split else nops.refiner_tail
             para_curr_l, depth, other = _timed("tail", self.lvl_depth, lambda: tail_fn(
                 x, w6p, convs[5].bias, w7p, convs[6].bias, rot_t, tr, {"f": cf, "c": cc}, scale,
-                depth_state=self.depth_prev_t if not self.is_training else None))
+                depth_state=self.depth_prev_t if not self.is_training else None, **mask_kw))
         else:
             prev_out = self.disp_refiner(f_input)
             para_curr_l, depth, other = _timed("post", self.lvl_depth, lambda: nops.level_post(
-                prev_out[0], rot_t, tr, {"f": cf, "c": cc}, scale, depth_state=self.depth_prev_t if not self.is_training else None))
+                prev_out[0], rot_t, tr, {"f": cf, "c": cc}, scale, depth_state=self.depth_prev_t if not self.is_training else None,
+                **mask_kw))
         if not self.is_training:
             # the normalised features ARE the new prev_f_maps (:211, :259): the level's spare buffer, or -- the one-launch opening of
             # a coarse level -- the caller's tensor, borrowed and only read (the level's own two buffers stay its own: _spare_f)
@@ -1063,6 +1074,45 @@ class DepthEstimatorPyramid(torch.nn.Module):
         for lvl in order:
             self.levels[lvl].reset_commit()
         return ests
+
+    def ensure_stream_state(self, f_pyr):
+        """Allocate (or keep) every level's state for the feature pyramid ``f_pyr`` of one streamed frame; True when any level's
+        state was (re)allocated -- the frame is then a reset for every sample (host-known, no device read)."""
+        fresh = False
+        for lvl, level in enumerate(self.levels):
+            before = level._own
+            level._ensure_state(tuple(f_pyr[lvl].shape), f_pyr[lvl].device)
+            fresh = fresh or level._own is not before
+        return fresh
+
+    def stream_forward(self, f_pyr, sample, local_cameras, reset_mask):
+        """One frame of B independent streams (streaming inference): the plain coarse -> fine level loop, every level on its
+        own state, closed by the masked tail (``reset_mask`` [b] on the device: samples whose trajectory starts here).  No
+        ``new_traj`` read, no pyramid-reset shortcut, no pipelining.  The coarse levels that open with one launch get their
+        normalised features written straight into their own spare state buffer (the same kernel as ``prenormalize``): every
+        level's ``prev_f_maps`` stays one of its two own buffers, so a captured graph can carry the state across replays.
+        Returns the per-level estimates, fine -> coarse (one entry of ``forward``'s result)."""
+        if self.is_training:
+            raise RuntimeError("stream_forward is inference only: the model is in training mode")
+        n_lvls = len(self.levels)
+        self.ensure_stream_state(f_pyr)
+        bsz = f_pyr[0].shape[0]
+        jobs = [lvl for lvl in range(n_lvls)
+                if self.levels[lvl].wants_prenormalized(bsz, f_pyr[lvl].shape[1], f_pyr[lvl].shape[2], f_pyr[lvl].shape[3])]
+        n_curr = [None] * n_lvls
+        if jobs:
+            outs = _timed("norm", "levels", lambda: nops.normalize_levels(
+                [(f_pyr[lvl], self.levels[lvl].nbre_cuts) for lvl in jobs], outs=[self.levels[lvl]._spare_f for lvl in jobs]))
+            for lvl, o in zip(jobs, outs):
+                n_curr[lvl] = o
+        ests = []
+        pv = 1.0                                       # the reset parallax: 1 at the coarsest level, x2 per finer level (:203)
+        for lvl in range(n_lvls - 1, -1, -1):
+            d_est = None if not ests else dict(ests[-1])
+            ests.append(self.levels[lvl](f_pyr[lvl], d_est, sample["rot"], sample["trans"], local_cameras[lvl], None,
+                                         curr_f_normalized=n_curr[lvl], reset_mask=reset_mask, reset_parallax=pv))
+            pv *= 2.0
+        return ests[::-1]
 
     def _forward_pipelined(self, f_maps_pyrs, traj_samples, local_cameras, n_streams, encoder=None, n_maps_pyrs=None,
                            resume=None):
@@ -1535,6 +1585,66 @@ class M4Depth(torch.nn.Module):
             self._update_metrics(gt, est, 80.)
         return self._metric_results()
 
+    def _stream_inputs(self, frame):
+        """Validated device tensors of one streamed frame (``stream_step``)."""
+        if self.model_settings["is_training"] or self.d_estimator.is_training:
+            raise RuntimeError("stream_step: streaming inference needs a model built with is_training=False")
+        if not isinstance(frame, dict):
+            raise TypeError("stream_step: expected a dict frame")
+        for k in ("RGB_im", "rot", "trans", "new_traj", "camera"):
+            if k not in frame:
+                raise KeyError(f"stream_step: the frame has no '{k}'")
+        rgb = frame["RGB_im"]
+        if not isinstance(rgb, torch.Tensor) or rgb.dim() != 4 or rgb.shape[-1] != 3:
+            raise ValueError(f"stream_step: RGB_im must be a [b,H,W,3] tensor, got {tuple(getattr(rgb, 'shape', ()))}")
+        b = rgb.shape[0]
+        want = {"rot": None, "trans": (b, 3), "new_traj": (b,)}
+        tensors = {"RGB_im": rgb, "rot": frame["rot"], "trans": frame["trans"], "new_traj": frame["new_traj"],
+                   "camera['f']": frame["camera"]["f"], "camera['c']": frame["camera"]["c"]}
+        for k, t in tensors.items():
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"stream_step: {k} must be a torch.Tensor")
+        rot = frame["rot"]
+        if rot.dim() != 2 or rot.shape[0] != b or rot.shape[1] not in (3, 4):
+            raise ValueError(f"stream_step: rot must be [b,3] or [b,4] with b = {b}, got {tuple(rot.shape)}")
+        for k in ("trans", "new_traj"):
+            if tuple(frame[k].shape) != want[k]:
+                raise ValueError(f"stream_step: {k} must have shape {want[k]}, got {tuple(frame[k].shape)}")
+        if frame["new_traj"].dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"stream_step: new_traj must be bool or uint8, got {frame['new_traj'].dtype}")
+        for k in ("f", "c"):
+            if tuple(frame["camera"][k].shape) != (b, 2):
+                raise ValueError(f"stream_step: camera['{k}'] must have shape ({b}, 2), got {tuple(frame['camera'][k].shape)}")
+        for k, t in tensors.items():
+            if not t.is_cuda:
+                raise RuntimeError(f"stream_step: {k} is on {t.device}; streaming inference runs on the MI355X (no host reads, "
+                                   "no CPU fallback): move the frame to the device first")
+        return frame
+
+    @torch.no_grad()
+    def stream_step(self, frame, out=None, force_reset=False):
+        """One frame of B independent camera streams (online inference, the reference's --mode=predict loop, main.py:150-172),
+        with a per-sample trajectory reset: ``frame`` = {"RGB_im" [b,H,W,3], "rot" [b,3|4], "trans" [b,3], "new_traj" [b] bool /
+        uint8, "camera": {"f", "c"} [b,2]}, all on the device.  Sample s gets exactly what a batch-synchronised run of its own
+        stream gives: ``new_traj[s]`` set -> the reset estimate and state (m4depth_network.py:206-214), clear -> the normal step
+        on its own state (:216-260).  The first frame after ``reset_state()`` (or a change of geometry), and any frame with
+        ``force_reset``, resets every sample.  Never synchronises with the host.  Returns {"depth" [b,H,W,1], "new_traj"};
+        ``out`` (optional): the depth destination."""
+        frame = self._stream_inputs(frame)
+        self.step_counter += 1
+        rgb = frame["RGB_im"]
+        b, h, w = rgb.shape[:3]
+        self.encoder.set_sequence_batch(b)
+        f_pyr = self.encoder(rgb)
+        force = self.d_estimator.ensure_stream_state(f_pyr) or bool(force_reset)
+        reset, rot, trans = nops.stream_prepare(frame["new_traj"], force, frame["rot"], frame["trans"])
+        local_cameras = nops.camera_pyramid(frame["camera"], len(self.d_estimator.levels))
+        ests = self.d_estimator.stream_forward(f_pyr, {"rot": rot, "trans": trans}, local_cameras, reset)
+        self.last_estimates = [ests]
+        self.last_reset_mask = reset
+        depth = _timed("resize", 0, lambda: nops.resize_nearest(ests[0]["depth"], h, w, out=out))
+        return {"depth": depth, "new_traj": frame["new_traj"]}
+
     @torch.no_grad()
     def predict_step(self, data):
         """m4depth_network.py:476-489."""
@@ -1866,6 +1976,111 @@ class SegmentedSequence(GraphedSequence):
 
     def _replay(self):
         self._play(lambda n: self.graph[n].replay())
+
+
+class GraphedStream:
+    """``M4Depth.stream_step`` replayed from captured hipGraphs: B independent camera streams, one frame per call, per-sample
+    resets from a device mask (no host read anywhere on the path).
+
+    Each level's feature state ping-pongs between its two own buffers (``DepthEstimatorLevel._spare_f``): a frame reads one and
+    writes the other, so the frame's graph depends on the parity of the frame.  Two graphs are captured, one per parity, from
+    the same memory pool (they replay on one stream, one after the other), and replayed alternately; the host tracks the parity.
+    Both write the one static ``depth`` output.  Like ``GraphedSequence``: its own stream, static input buffers
+    (``input_buffers()``), the packed weights refreshed in place when the parameters changed.
+
+    The first frame after construction or ``reset_state()`` resets every sample whatever ``new_traj`` says: for that frame the
+    static ``new_traj`` buffer is set to all-true around the replay (the captured ``m4d_stream_prepare`` then builds an all-set
+    mask) and given back its contents afterwards.  (``M4Depth.reset_state()`` would drop the state buffers the graphs read: the
+    runner refuses to replay after it -- use the runner's own ``reset_state()``.)"""
+
+    def __init__(self, model, example_frame, warmup=2):
+        self.model = model
+        frame = model._stream_inputs(example_frame)
+        nt = frame["new_traj"]
+        self.static = {"RGB_im": frame["RGB_im"].clone(), "rot": as_f32(frame["rot"], "rot").clone(),
+                       "trans": as_f32(frame["trans"], "trans").clone(),
+                       "new_traj": (nt.view(torch.uint8) if nt.dtype == torch.bool else nt).clone()}
+        self.camera = {k: as_f32(v, f"camera[{k}]").clone() for k, v in frame["camera"].items()}
+        b, h, w = self.static["RGB_im"].shape[:3]
+        model.prepack()
+        self.stream = torch.cuda.Stream()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self.depth = torch.empty((b, h, w, 1), dtype=torch.float32, device=self.static["RGB_im"].device)
+            for i in range(max(warmup, 1)):
+                model.stream_step(self._frame(), out=self.depth, force_reset=(i == 0))
+        torch.cuda.current_stream().wait_stream(self.stream)
+        torch.cuda.synchronize()
+        levels = model.d_estimator.levels
+        self.graphs, self._post_state, self._post_estimates = [], [], []
+        pool = None
+        for _ in range(2):                              # parity 0, then 1: each capture leaves the host-side state flipped
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool, stream=self.stream):
+                model.stream_step(self._frame(), out=self.depth)
+            pool = g.pool()
+            self.graphs.append(g)
+            self._post_state.append([l.prev_f_maps for l in levels])
+            self._post_estimates.append(model.last_estimates)
+        self.parity = 0                                 # back at the parity the first graph was captured for
+        self._owned = [l._own for l in levels]
+        self._nt_saved = torch.empty_like(self.static["new_traj"])
+        self.weights_stamp = model.weights_stamp()
+        self._force = True
+
+    def _frame(self):
+        return {"RGB_im": self.static["RGB_im"], "rot": self.static["rot"], "trans": self.static["trans"],
+                "new_traj": self.static["new_traj"], "camera": self.camera}
+
+    def input_buffers(self):
+        """The graphs' static inputs ({"RGB_im", "rot", "trans", "new_traj", "camera": {"f", "c"}}): a producer that writes the
+        next frame straight into them and passes them back to ``__call__`` skips the hand-over copies."""
+        return dict(self._frame(), camera=self.camera)
+
+    def reset_state(self):
+        """The next frame resets every sample."""
+        self._force = True
+
+    def _copy(self, name, src, dst):
+        if not isinstance(src, torch.Tensor) or not src.is_cuda:
+            raise RuntimeError(f"GraphedStream: {name} must be a device tensor")
+        if tuple(src.shape) != tuple(dst.shape):
+            raise ValueError(f"GraphedStream: {name} has shape {tuple(src.shape)}, the graphs were captured for {tuple(dst.shape)}")
+        if src.dtype == torch.bool and dst.dtype == torch.uint8:
+            src = src.view(torch.uint8)
+        if src.data_ptr() != dst.data_ptr():
+            dst.copy_(src, non_blocking=True)
+
+    def __call__(self, frame=None):
+        """Copy ``frame`` (same keys as ``stream_step``) into the static inputs, replay this parity's graph, return
+        {"depth": the static [b,H,W,1] output, "new_traj"}."""
+        if frame is not None:
+            for k in ("RGB_im", "rot", "trans", "new_traj"):
+                self._copy(k, frame[k], self.static[k])
+            for k in self.camera:
+                self._copy(f"camera[{k}]", frame["camera"][k], self.camera[k])
+        if any(l._own is not own for l, own in zip(self.model.d_estimator.levels, self._owned)):
+            raise RuntimeError("GraphedStream: the model's level state was reset or reallocated after the capture (M4Depth.reset_state?) "
+                               "-- the graphs read the old buffers; use GraphedStream.reset_state() or build a new runner")
+        stamp = self.model.weights_stamp()
+        if stamp != self.weights_stamp:
+            if [p for p, _ in stamp] != [p for p, _ in self.weights_stamp]:
+                raise RuntimeError("a convolution parameter was REPLACED (new address) after this hipGraph was captured: the "
+                                   "graph still reads the old buffers -- update weights in place or build a new GraphedStream")
+            self.model.prepack()
+            self.weights_stamp = stamp
+        force, self._force = self._force, False
+        if force:
+            self._nt_saved.copy_(self.static["new_traj"])
+            self.static["new_traj"].fill_(1)
+        self.graphs[self.parity].replay()
+        if force:
+            self.static["new_traj"].copy_(self._nt_saved)
+        for l, prev in zip(self.model.d_estimator.levels, self._post_state[self.parity]):
+            l.prev_f_maps = prev                        # the host-side view of the state follows the replayed frame
+        self.model.last_estimates = self._post_estimates[self.parity]
+        self.parity ^= 1
+        return {"depth": self.depth, "new_traj": self.static["new_traj"] if frame is None else frame["new_traj"]}
 
 
 def make_runner(model, example, warmup=2, autotune=None):

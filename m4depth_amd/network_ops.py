@@ -34,11 +34,14 @@ def resize_bilinear_v1(x, out_h, out_w, mul=1.0):
     return out
 
 
-def resize_nearest(x, out_h, out_w):
-    """tf.image.resize(method=NEAREST_NEIGHBOR), m4depth_network.py:368."""
+def resize_nearest(x, out_h, out_w, out=None):
+    """tf.image.resize(method=NEAREST_NEIGHBOR), m4depth_network.py:368; ``out`` (optional): the [b,out_h,out_w,c] destination."""
     x = as_f32(x, "x")
     b, ih, iw, c = x.shape
-    out = torch.empty((b, out_h, out_w, c), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((b, out_h, out_w, c), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (b, out_h, out_w, c):
+        raise ValueError(f"resize_nearest: out has shape {tuple(out.shape)}, expected {(b, out_h, out_w, c)}")
     check(lib.m4d_resize_nearest(dptr(x, "x"), b, ih, iw, c, int(out_h), int(out_w), dptr(out), stream_ptr()),
           "m4d_resize_nearest")
     return out
@@ -113,25 +116,40 @@ def pyramid_reset(levels, b):
     return ests
 
 
-def normalize_levels(maps):
+def normalize_levels(maps, outs=None):
     """The per-cut normalisation of several feature maps in ONE launch (m4d_normalize_levels; the bits of ``normalize_cuts``).
-    ``maps`` = [(tensor [n,h,w,C], cuts), ...] (at most 8); returns the normalised tensors in the same order."""
+    ``maps`` = [(tensor [n,h,w,C], cuts), ...] (at most 8); returns the normalised tensors in the same order.  ``outs``
+    (optional): one destination per map (the streaming path writes straight into each level's own state buffer)."""
     from ._lib import NormLevel
     n = len(maps)
     arr = (NormLevel * n)()
-    outs = []
+    dests, outs = outs, []
     for i, (x, cuts) in enumerate(maps):
         x = as_f32(x, "features")
-        out = torch.empty_like(x)
+        out = torch.empty_like(x) if dests is None else dests[i]
+        if tuple(out.shape) != tuple(x.shape):
+            raise ValueError(f"normalize_levels: destination {i} has shape {tuple(out.shape)}, the map {tuple(x.shape)}")
         arr[i] = NormLevel(dptr(x, "features").value, dptr(out).value, int(x.shape[0] * x.shape[1] * x.shape[2]), int(x.shape[3]), int(cuts))
         outs.append(out)
     check(lib.m4d_normalize_levels(arr, n, stream_ptr()), "m4d_normalize_levels")
     return outs
 
 
-def level_post(refiner_out, rot, trans, camera, scale, depth_state=None):
+def _reset_mask(reset, b, depth_state):
+    """The uint8 [b] device mask of a masked level close (``reset`` bool or uint8); the masked kernels need ``depth_state``."""
+    if reset.dtype == torch.bool:
+        reset = reset.view(torch.uint8)
+    if tuple(reset.shape) != (b,):
+        raise ValueError(f"reset mask must have shape ({b},), got {tuple(reset.shape)}")
+    if depth_state is None:
+        raise ValueError("a masked level close writes the reset samples' depth_state: depth_state is required")
+    return dptr(reset, "reset", torch.uint8)
+
+
+def level_post(refiner_out, rot, trans, camera, scale, depth_state=None, reset=None, reset_parallax=1.0):
     """Fused tail of a level (m4depth_network.py:247-260): returns (parallax,
-    depth, other); ``depth_state`` (optional) receives the depth as well."""
+    depth, other); ``depth_state`` (optional) receives the depth as well.  ``reset`` (streaming): a [b] device mask -- masked
+    samples get the reset constants (m4d_level_post_m: parallax ``reset_parallax``, depth 1000, other 0, depth_state 1000)."""
     ro = as_f32(refiner_out, "refiner_out")
     b, h, w, five = ro.shape
     if five != 5:
@@ -143,6 +161,12 @@ def level_post(refiner_out, rot, trans, camera, scale, depth_state=None):
     para = torch.empty((b, h, w, 1), dtype=torch.float32, device=ro.device)
     depth = torch.empty_like(para)
     other = torch.empty((b, h, w, 4), dtype=torch.float32, device=ro.device)
+    if reset is not None:
+        rp = _reset_mask(reset, b, depth_state)
+        check(lib.m4d_level_post_m(dptr(ro), dptr(rot, "rot"), rot.shape[1], dptr(tr), dptr(f), dptr(c), b, h, w,
+                                   float(scale), dptr(para), dptr(depth), dptr(other), dptr(depth_state, "depth_state"),
+                                   rp, float(reset_parallax), stream_ptr()), "m4d_level_post_m")
+        return para, depth, other
     check(lib.m4d_level_post(dptr(ro), dptr(rot, "rot"), rot.shape[1], dptr(tr), dptr(f), dptr(c), b, h, w,
                              float(scale), dptr(para), dptr(depth), dptr(other), dptr(depth_state, "depth_state"),
                              stream_ptr()), "m4d_level_post")
@@ -682,9 +706,9 @@ def pack_refiner_tail_weights6(k6_hwio, k7_hwio):
     return w6, w7
 
 
-def refiner_tail6(x32, w6f, b6, w7f, b7, rot, trans, camera, scale, depth_state=None):
+def refiner_tail6(x32, w6f, b6, w7f, b7, rot, trans, camera, scale, depth_state=None, reset=None, reset_parallax=1.0):
     """refiner_tail with float32 operands split into three bf16 terms on the bf16 matrix cores (csrc/m4d_tail6.hip);
-    w6f / w7f from pack_refiner_tail_weights6 (int16 views on the device)."""
+    w6f / w7f from pack_refiner_tail_weights6 (int16 views on the device).  ``reset``: as ``level_post`` (m4d_refiner_tail6_m)."""
     x = as_f32(x32, "x32")
     b, h, w, c = x.shape
     if c != 32:
@@ -696,6 +720,13 @@ def refiner_tail6(x32, w6f, b6, w7f, b7, rot, trans, camera, scale, depth_state=
     para = torch.empty((b, h, w, 1), dtype=torch.float32, device=x.device)
     depth = torch.empty_like(para)
     other = torch.empty((b, h, w, 4), dtype=torch.float32, device=x.device)
+    if reset is not None:
+        rp = _reset_mask(reset, b, depth_state)
+        check(lib.m4d_refiner_tail6_m(dptr(x, "x32"), dptr(w6f, "w6f", torch.int16), dptr(b6, "b6"), dptr(w7f, "w7f", torch.int16),
+                                      dptr(b7, "b7"), dptr(rot, "rot"), rot.shape[1], dptr(tr), dptr(f), dptr(cc), b, h, w, float(scale),
+                                      dptr(para), dptr(depth), dptr(other), dptr(depth_state, "depth_state"), rp,
+                                      float(reset_parallax), stream_ptr()), "m4d_refiner_tail6_m")
+        return para, depth, other
     check(lib.m4d_refiner_tail6(dptr(x, "x32"), dptr(w6f, "w6f", torch.int16), dptr(b6, "b6"), dptr(w7f, "w7f", torch.int16),
                                 dptr(b7, "b7"), dptr(rot, "rot"), rot.shape[1], dptr(tr), dptr(f), dptr(cc), b, h, w, float(scale),
                                 dptr(para), dptr(depth), dptr(other), dptr(depth_state, "depth_state"), stream_ptr()),
@@ -703,8 +734,9 @@ def refiner_tail6(x32, w6f, b6, w7f, b7, rot, trans, camera, scale, depth_state=
     return para, depth, other
 
 
-def refiner_tail(x32, w6p, b6, w7p, b7, rot, trans, camera, scale, depth_state=None):
-    """conv(32->16)+lrelu, conv(16->5) and the level tail (level_post) in one launch: returns (parallax, depth, other)."""
+def refiner_tail(x32, w6p, b6, w7p, b7, rot, trans, camera, scale, depth_state=None, reset=None, reset_parallax=1.0):
+    """conv(32->16)+lrelu, conv(16->5) and the level tail (level_post) in one launch: returns (parallax, depth, other).
+    ``reset``: as ``level_post`` (m4d_refiner_tail_m)."""
     x = as_f32(x32, "x32")
     b, h, w, c = x.shape
     if c != 32:
@@ -716,6 +748,13 @@ def refiner_tail(x32, w6p, b6, w7p, b7, rot, trans, camera, scale, depth_state=N
     para = torch.empty((b, h, w, 1), dtype=torch.float32, device=x.device)
     depth = torch.empty_like(para)
     other = torch.empty((b, h, w, 4), dtype=torch.float32, device=x.device)
+    if reset is not None:
+        rp = _reset_mask(reset, b, depth_state)
+        check(lib.m4d_refiner_tail_m(dptr(x, "x32"), dptr(w6p, "w6p"), dptr(b6, "b6"), dptr(w7p, "w7p"), dptr(b7, "b7"),
+                                     dptr(rot, "rot"), rot.shape[1], dptr(tr), dptr(f), dptr(cc), b, h, w, float(scale),
+                                     dptr(para), dptr(depth), dptr(other), dptr(depth_state, "depth_state"), rp,
+                                     float(reset_parallax), stream_ptr()), "m4d_refiner_tail_m")
+        return para, depth, other
     check(lib.m4d_refiner_tail(dptr(x, "x32"), dptr(w6p, "w6p"), dptr(b6, "b6"), dptr(w7p, "w7p"), dptr(b7, "b7"),
                                dptr(rot, "rot"), rot.shape[1], dptr(tr), dptr(f), dptr(cc), b, h, w, float(scale),
                                dptr(para), dptr(depth), dptr(other), dptr(depth_state, "depth_state"), stream_ptr()),
@@ -733,3 +772,26 @@ def camera_pyramid(camera, levels):
     check(lib.m4d_camera_pyramid(dptr(f.reshape(b, 2), "camera['f']"), dptr(c.reshape(b, 2), "camera['c']"), b, int(levels),
                                  dptr(out[0]), dptr(out[1]), stream_ptr()), "m4d_camera_pyramid")
     return [{"f": out[0, l], "c": out[1, l]} for l in range(levels)]
+
+
+def stream_prepare(new_traj, force_all, rot, trans):
+    """One streamed frame's reset mask and pose (m4d_stream_prepare): ``new_traj`` [b] bool / uint8 on the device, ``force_all``
+    a host bool.  Returns (reset uint8 [b], rot [b,rot_c], trans [b,3]) -- reset samples carry identity rotation and
+    translation (0,0,1) in the pose copy, continuing samples their own pose."""
+    rot = as_f32(rot, "rot")
+    tr = as_f32(trans, "trans")
+    if rot.dim() != 2 or rot.shape[1] not in (3, 4):
+        raise ValueError('Rotation must be expressed as a small angle (x,y,z) or a quaternion (w,x,y,z)')
+    b = rot.shape[0]
+    if tuple(tr.shape) != (b, 3):
+        raise ValueError(f"stream_prepare: trans must have shape ({b}, 3), got {tuple(tr.shape)}")
+    nt = new_traj.view(torch.uint8) if new_traj.dtype == torch.bool else new_traj
+    if tuple(nt.shape) != (b,):
+        raise ValueError(f"stream_prepare: new_traj must have shape ({b},), got {tuple(nt.shape)}")
+    reset = torch.empty((b,), dtype=torch.uint8, device=rot.device)
+    rot_out = torch.empty_like(rot)
+    tr_out = torch.empty_like(tr)
+    check(lib.m4d_stream_prepare(dptr(nt, "new_traj", torch.uint8), int(bool(force_all)), dptr(rot, "rot"), rot.shape[1],
+                                 dptr(tr, "trans"), b, dptr(reset, "reset", torch.uint8), dptr(rot_out), dptr(tr_out), stream_ptr()),
+          "m4d_stream_prepare")
+    return reset, rot_out, tr_out

@@ -1,7 +1,8 @@
 """The kernel nodes of the captured sequence forward (network.GraphedSequence, what bench.py replays) at a batch size, from the
 HIP runtime's own dump of the instantiated graph (DEBUG_HIP_GRAPH_DOT_PRINT=1: graph_* files in the working directory; the
 largest is the sequence graph): DOT file + one line per distinct kernel; exits non-zero if any node is not one of
-libm4depth_hip.so's kernels.  python tools/dump_graph_nodes.py --batch 32 --out profiles/x.dot"""
+libm4depth_hip.so's kernels.  python tools/dump_graph_nodes.py --batch 32 --out profiles/x.dot
+--stream: the per-frame graphs of network.GraphedStream (streaming inference) instead of the sequence graph."""
 import argparse, collections, glob, os, re, shutil, sys, tempfile
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=1)
@@ -10,6 +11,7 @@ ap.add_argument("--width", type=int, default=1280)
 ap.add_argument("--levels", type=int, default=6)
 ap.add_argument("--frames", type=int, default=4)
 ap.add_argument("--out", required=True)
+ap.add_argument("--stream", action="store_true", help="dump network.GraphedStream's per-frame graphs")
 a = ap.parse_args()
 out = os.path.abspath(a.out)
 os.environ["DEBUG_HIP_GRAPH_DOT_PRINT"] = "1"            # read by the HIP runtime when it instantiates a graph
@@ -29,10 +31,18 @@ samples, cam = S.make_sequence(a.batch, a.frames, a.height, a.width, seed=1)
 d = {k: torch.stack([torch.from_numpy(s[k]).to(dev) for s in samples], dim=1) for k in ("depth", "RGB_im", "rot", "trans")}
 d["new_traj"] = torch.stack([torch.from_numpy(s["new_traj"]) for s in samples], dim=1)
 d["camera"] = {k: torch.from_numpy(v).to(dev) for k, v in cam.items()}
-model.compile(metrics=M.default_metrics())
-model.test_step(d)
-runner = net.GraphedSequence(model, d)
-runner(d)
+if a.stream:
+    frame = {k: d[k][:, 0].contiguous() for k in ("RGB_im", "rot", "trans")}
+    frame["new_traj"] = torch.zeros(a.batch, dtype=torch.bool, device=dev)
+    frame["camera"] = d["camera"]
+    runner = net.GraphedStream(model, frame)
+    for _ in range(3):
+        runner(frame)
+else:
+    model.compile(metrics=M.default_metrics())
+    model.test_step(d)
+    runner = net.GraphedSequence(model, d)
+    runner(d)
 torch.cuda.synchronize()
 best, names = None, []
 for f in glob.glob(os.path.join(work, "*")):
