@@ -206,6 +206,15 @@ void m4d_wino6_set_stamps(unsigned long long* device_buffer);
 int m4d_conv3x3_wino6_bias_act_ks(const float* x, const void* wu6, const float* bias, int b, int h, int w,
                                   int Cin, int Cout, int CoutPad, float slope, float* out, int kernel,
                                   int stagger_us, int stagger_phases, void* stream);
+/* The same convolution with every float32 operand split into TWO fp16 terms after a power-of-two scale (per Winograd tile
+ * for the input, per output channel for the weights), three fp16 MFMA products per term pair, float32 accumulation
+ * (csrc/m4d_wino_f16.hip; error against float64 at the level of the bf16 three-term split).  wuh = network_ops.
+ * pack_conv_weights_winof16: [Cin/16][CoutPad/64][16][2][2][64][8] fp16 followed by [CoutPad] int16 weight exponents.
+ * One workgroup per (16x16-pixel tile, 64 output channels) at every grid size; stagger_us / stagger_phases as in
+ * m4d_conv3x3_wino6_bias_act_ks.  Additive entry point: ABI 6 unchanged. */
+int m4d_conv3x3_winof16_bias_act_ks(const float* x, const void* wuh, const float* bias, int b, int h, int w,
+                                    int Cin, int Cout, int CoutPad, float slope, float* out,
+                                    int stagger_us, int stagger_phases, void* stream);
 
 /* The tail of a level in one kernel: the last two DispRefiner convolutions (32 -> 16 + leaky_relu(0.1), 16 -> 5;
  * m4depth_network.py:109-135) and m4d_level_post (:247-260).  x32 [b,h,w,32]; w6p [9][16][32] = kernel[ky][kx][k][n] as

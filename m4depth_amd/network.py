@@ -53,8 +53,12 @@ winograd2_min_workgroups = int(_os.environ.get("M4D_WINO2_MIN_WG", "60"))
 
 # Arithmetic of the wide Winograd layers: "bf16x3" = float32 operands split exactly into three bf16 terms, six bf16 MFMA
 # products, float32 accumulation (csrc/m4d_wino6.hip: float32 accuracy -- error against float64 0.8x that of the fp32
-# MFMA kernels, tools/bench_wino6.py -- at 2.67x less matrix-core time); "f32" = the fp32-MFMA kernels everywhere.
-conv_arith = _os.environ.get("M4D_CONV_ARITH", "bf16x3")
+# MFMA kernels, tools/bench_wino6.py -- at 2.67x less matrix-core time); "f16x2" (default) = the same layers with float32
+# operands scaled by powers of two (per Winograd tile / per output channel) and split into two fp16 terms, three fp16 MFMA
+# products (csrc/m4d_wino_f16.hip: error against float64 at the bf16x3 level) -- every other kernel
+# (latency-first, small-map, fused tail, training) keeps its bf16x3 form under "f16x2"; "f32" = the fp32-MFMA kernels everywhere.
+conv_arith = _os.environ.get("M4D_CONV_ARITH", "f16x2")
+_SPLIT_ARITHS = ("bf16x3", "f16x2")          # the arithmetics that run the 16-bit split kernels
 # Smallest grid ((tile, 64-cout) units) those kernels take: 30 = the narrow layers of level 3 (30 tiles: 96 -> 64, and 64 -> 32 as
 # half units) as well, +0.8 % frames/s at batch 1 against 40 (rounds 2-4: those two on the fp32-MFMA Winograd / direct kernels);
 # 20 (level 4's wide layers too) measured the same as 30
@@ -88,11 +92,11 @@ if _os.environ.get("M4D_WINO6_VARIANT") or _os.environ.get("M4D_WINO6_HALF_MAX_W
 # bound by how fast ONE CU streams its slice of the weights, not by the matrix core: -2 us per layer on the 240-channel first
 # layers, nothing elsewhere (tools/bench_small_convs.py); +0.8 % frames/s at batch 1.  0 = the fp32-MFMA small-map kernel.
 _small_conv_split_env = _os.environ.get("M4D_SMALL_CONV_SPLIT", "1") == "1"
-small_conv_split = _small_conv_split_env and conv_arith == "bf16x3"
+small_conv_split = _small_conv_split_env and conv_arith in _SPLIT_ARITHS
 
 
 # The fused level tail (conv 32->16, conv 16->5, level_post) in the same bf16-split arithmetic (csrc/m4d_tail6.hip) when
-# conv_arith is "bf16x3"; 0 = the fp32-MFMA tail (csrc/m4d_tail.hip) always.
+# conv_arith is a 16-bit split ("f16x2" or "bf16x3": the bf16x3 tail either way); 0 = the fp32-MFMA tail (csrc/m4d_tail.hip) always.
 tail_split = _os.environ.get("M4D_TAIL_SPLIT", "1") == "1"
 
 # The encoder's convolutions choose their kernel from the per-image grid x the sequence batch (1 = from the per-image grid alone:
@@ -104,13 +108,13 @@ import contextlib as _contextlib
 
 @_contextlib.contextmanager
 def conv_arithmetic(arith):
-    """Run the enclosed calls with ``conv_arith`` = "bf16x3" or "f32" (what ``M4D_CONV_ARITH`` selects at import) and
-    everything derived from it switched consistently; the previous setting is restored on exit.  Not thread-safe."""
+    """Run the enclosed calls with ``conv_arith`` = "f16x2", "bf16x3" or "f32" (what ``M4D_CONV_ARITH`` selects at import)
+    and everything derived from it switched consistently; the previous setting is restored on exit.  Not thread-safe."""
     global conv_arith, small_conv_split
-    if arith not in ("bf16x3", "f32"):
-        raise ValueError(f"conv arithmetic must be 'bf16x3' or 'f32', not {arith!r}")
+    if arith not in _SPLIT_ARITHS + ("f32",):
+        raise ValueError(f"conv arithmetic must be 'f16x2', 'bf16x3' or 'f32', not {arith!r}")
     old = (conv_arith, small_conv_split)
-    conv_arith, small_conv_split = arith, _small_conv_split_env and arith == "bf16x3"
+    conv_arith, small_conv_split = arith, _small_conv_split_env and arith in _SPLIT_ARITHS
     try:
         yield
     finally:
@@ -118,7 +122,8 @@ def conv_arithmetic(arith):
 
 
 def _use_winograd(b, h, w, cin, cout, stride):
-    """0 = direct convolution; 6 = the bf16-split Winograd kernel (m4d_wino6.hip); 1 = Winograd kernel 1 (16x8 tile,
+    """0 = direct convolution; 6 = the 16-bit-split Winograd kernel (m4d_wino6.hip under "bf16x3", m4d_wino_f16.hip under
+    "f16x2": ``forward`` picks it from ``conv_arith``); 1 = Winograd kernel 1 (16x8 tile,
     16-channel chunks, 2 N-tiles per workgroup); 2 = kernel 2 (16x16 tile, 8-channel chunks: half the weight traffic per flop -- ahead on the large maps).
     Winograd only pays when the launch fills the chip: the thresholds are workgroup counts (measured per layer of the
     384x1280 pyramid, profiles/r01_step_launches_b1_wino.txt: level 3 and coarser stay on the direct kernel, which can
@@ -127,7 +132,7 @@ def _use_winograd(b, h, w, cin, cout, stride):
         return 0
     n32 = -(-cout // 32)
     t16 = b * (-(-h // 16)) * (-(-w // 16))
-    if conv_arith == "bf16x3" and cin % 16 == 0 and cin >= 32 and cout >= wino6_min_cout and t16 * (-(-cout // 64)) >= wino6_min_workgroups:
+    if conv_arith in _SPLIT_ARITHS and cin % 16 == 0 and cin >= 32 and cout >= wino6_min_cout and t16 * (-(-cout // 64)) >= wino6_min_workgroups:
         return 6                                                # 64-cout units; a last group of <= 32 channels runs one N-tile
     if cin % 4 == 0 and t16 * n32 >= winograd2_min_workgroups:
         return 2
@@ -153,7 +158,7 @@ small_map_stride2 = _os.environ.get("M4D_CONV_SMALL_S2", "1") == "1"     # the c
 
 # The latency-first small-map convolution (csrc/m4d_convlat.hip, round 5): every layer that may take the one-launch small-map
 # kernels (``small_maps_ok``, stride 1, Cin >= 16, Cin % 4 == 0) on maps of at most this many pixels (batch included) when
-# conv_arith is "bf16x3".  K is split over waves and workgroups until a wave owns one or two 16-channel chunks and requests
+# conv_arith is "f16x2" or "bf16x3" (bf16x3 kernels either way).  K is split over waves and workgroups until a wave owns one or two 16-channel chunks and requests
 # everything it needs in one memory round trip; the K slices of different workgroups reach the NEXT layer as partial-sum slabs
 # (network_ops.PartialAct) that it adds while staging.  Levels 4-6 at batch 1: 59 / 50 / 52 us of refiner convolutions per
 # level -> 38 / 37 / 48 (tools/bench_lat_convs.py).  0 = the round-2/3 small-map kernels.
@@ -425,7 +430,7 @@ class _Conv3x3SameTF(torch.nn.Module):
 
     def lat_eligible(self, b, h, w, cin):
         """Would ``forward`` run this layer on the latency-first small-map kernel for an input of this shape?"""
-        if not (self.small_maps_ok and conv_arith == "bf16x3" and cin >= 16 and cin % 4 == 0 and self.stride in (1, 2)):
+        if not (self.small_maps_ok and conv_arith in _SPLIT_ARITHS and cin >= 16 and cin % 4 == 0 and self.stride in (1, 2)):
             return False
         eff_b = self.dispatch_batch if self.per_image_dispatch else b
         if self.stride == 2:                              # the stride-2 encoder layers: by OUTPUT pixels
@@ -449,6 +454,17 @@ class _Conv3x3SameTF(torch.nn.Module):
             wu, cpad = nops.pack_conv_weights_wino6(self._hwio_numpy(cin_pad))
             return torch.from_numpy(wu.view("int16")).to(self.weight.device), cpad
         return self._cache.get(("wino6", cin_pad), _stamp(self.weight), build)
+
+    def _packed_weights_winof16(self, cin_pad=None):
+        """(wuh int16 bits, CoutPad) for m4d_conv3x3_winof16_bias_act_ks: U = G g G^T scaled per output channel and split
+        into two fp16 terms on the host, then the exponents."""
+        if cin_pad is not None and cin_pad == self.weight.shape[1]:
+            cin_pad = None
+
+        def build():
+            wu, cpad = nops.pack_conv_weights_winof16(self._hwio_numpy(cin_pad))
+            return torch.from_numpy(wu.view("int16")).to(self.weight.device), cpad
+        return self._cache.get(("winof16", cin_pad), _stamp(self.weight), build)
 
     def _hwio_device(self):
         """The TF-layout [3,3,Cin,Cout] kernel as a contiguous device tensor (the encoder-head kernel reads it directly)."""
@@ -502,16 +518,19 @@ class _Conv3x3SameTF(torch.nn.Module):
                                                                      stride=self.stride))
         wino = _use_winograd(eff_b, h_, w_, cin_, self.out_channels, self.stride)
         if wino == 6:
-            wu, cpad = self._packed_weights_wino6(cin_)
+            # "f16x2": one workgroup per (tile, 64 couts) at every batch -- ahead of the bf16x3 persistent kernel at batch 32 too
+            # (DESIGN.md section 6), so the kernel choice does not depend on the batch at all
+            f16 = conv_arith == "f16x2"
+            wu, cpad = self._packed_weights_winof16(cin_) if f16 else self._packed_weights_wino6(cin_)
             stag = self.launch_stagger_us(b_, h_, w_)
             kern = wino6_kernel
-            if kern == 0 and wino6_pair_min_units > 0 and b_ <= wino6_stagger_max_batch and cin_ >= 32:
+            if not f16 and kern == 0 and wino6_pair_min_units > 0 and b_ <= wino6_stagger_max_batch and cin_ >= 32:
                 units = b_ * (-(-h_ // 16)) * (-(-w_ // 16)) * (cpad // 64)
                 if wino6_pair_min_units <= units < int(lib.m4d_wino6_persistent_min_units()):
                     kern = 16 + max(1, min(wino6_pair_units, 15))
             return _timed("conv", self.tag, lambda: nops.conv3x3_wino6_bias_act(
                 x_nhwc, wu, self.bias, self.out_channels, cpad, act, kernel=kern, stagger_us=stag,
-                stagger_phases=wino6_stagger_phases))
+                stagger_phases=wino6_stagger_phases, arith=conv_arith))
         if wino:
             wu, cpad = self._packed_weights_winograd(16 if wino == 1 else 8, cin_)     # cin_ > Cin: zero-padded input
             fn = nops.conv3x3_wino_bias_act if wino == 1 else nops.conv3x3_wino2_bias_act
@@ -936,7 +955,7 @@ class DepthEstimatorLevel(torch.nn.Module):
                 x = conv(x, slope=0.1, final=(ci == 4))                   # the fused tail reads a finished tensor
                 if debug_tap is not None:
                     debug_tap(f"refiner_conv{ci + 1}", self.lvl_depth, x.dense() if isinstance(x, nops.PartialAct) else x)
-            split = tail_split and conv_arith == "bf16x3"
+            split = tail_split and conv_arith in _SPLIT_ARITHS
             w6p, w7p = self._tail_weights(convs, split)
             tail_fn = nops.refiner_tail6 if split else nops.refiner_tail
             para_curr_l, depth, other = _timed("tail", self.lvl_depth, lambda: tail_fn(
@@ -1336,7 +1355,7 @@ class M4Depth(torch.nn.Module):
                 conv._packed_weights()
                 if small_conv_split and conv.small_maps_ok and conv.stride == 1 and 16 <= cin <= 256 and cin % 4 == 0:
                     conv._packed_weights_small6()
-                if conv.small_maps_ok and conv_arith == "bf16x3" and cin >= 16 and cin % 4 == 0 and (
+                if conv.small_maps_ok and conv_arith in _SPLIT_ARITHS and cin >= 16 and cin % 4 == 0 and (
                         (conv.stride == 1 and max(lat_conv_max_pixels, lat_conv_narrow_max_pixels) > 0)
                         or (conv.stride == 2 and max(lat_conv_s2_max_pixels, lat_conv_mw_max_pixels) > 0)):
                     conv._packed_weights_lat()
@@ -1350,6 +1369,7 @@ class M4Depth(torch.nn.Module):
                         conv._packed_weights_wino6()    # the dispatch's own condition (_use_winograd): a replayed hipGraph is
                                                         # refreshed through prepack() alone, so every layout a layer CAN be
                                                         # dispatched to must be (re)built here (round 4 left 64 -> 32 out)
+                        conv._packed_weights_winof16()
         for lvl in self.d_estimator.levels:
             convs = list(lvl.disp_refiner.prep_conv_layers) + list(lvl.disp_refiner.est_d_conv_layers)
             c0 = convs[0] if convs else None
@@ -1360,13 +1380,14 @@ class M4Depth(torch.nn.Module):
                 c0._packed_weights_winograd(8, cin_pad)
                 if small_conv_split and cin_pad <= 256:
                     c0._packed_weights_small6(cin_pad)
-                if conv_arith == "bf16x3" and lat_conv_max_pixels > 0:
+                if conv_arith in _SPLIT_ARITHS and lat_conv_max_pixels > 0:
                     c0._packed_weights_lat(cin_pad)
                 if cin_pad % 16 == 0 and cin_pad >= 32 and c0.out_channels >= min(wino6_min_cout, 32):
                     c0._packed_weights_wino6(cin_pad)
+                    c0._packed_weights_winof16(cin_pad)
             if len(convs) == 7 and convs[5].weight is not None and convs[5].weight.is_cuda \
                     and tuple(convs[5].weight.shape[:2]) == (16, 32) and tuple(convs[6].weight.shape[:2]) == (5, 16):
-                lvl._tail_weights(convs, tail_split and conv_arith == "bf16x3")
+                lvl._tail_weights(convs, tail_split and conv_arith in _SPLIT_ARITHS)
         return self
 
     def invalidate_packed(self):

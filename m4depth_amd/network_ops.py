@@ -403,6 +403,34 @@ def pack_conv_weights_wino6(kernel_hwio):
     return w.reshape(nch, ng, 16, 2, 3, 64, 8), cpad
 
 
+def pack_conv_weights_winof16(kernel_hwio):
+    """The filter transform U of pack_conv_weights_wino6 (the same float32 values), scaled per output channel n by 2^t_n
+    (|2^t_n U| < 2^15, exact) and split into two fp16 terms (round to nearest: hi = fp16(u), lo = fp16(u - hi)) in the
+    B-fragment order of m4d_conv3x3_winof16_bias_act_ks: [Cin/16][CoutPad/64][16 positions][2 N-tiles][2 parts][64 lanes][8]
+    fp16 bits, followed by the CoutPad exponents t_n as int16.  numpy in, (flat numpy uint16, CoutPad) out."""
+    import numpy as np
+    k = np.asarray(kernel_hwio, dtype=np.float64)
+    assert k.shape[:2] == (3, 3)
+    cin, cout = k.shape[2], k.shape[3]
+    G = np.array(_WINO_G, np.float64)
+    U = np.einsum('ij,jkco,lk->ilco', G, k, G)                   # [4,4,Cin,Cout]
+    nch, ng = -(-cin // 16), -(-cout // 64)
+    cpad = ng * 64
+    full = np.zeros((16, nch * 16, cpad), np.float32)
+    full[:, :cin, :cout] = U.reshape(16, cin, cout).astype(np.float32)
+    if not np.isfinite(full).all():
+        raise ValueError("pack_conv_weights_winof16: non-finite weight")
+    amax = np.abs(full).max(axis=(0, 1)).astype(np.float64)      # [cpad]
+    texp = np.where(amax > 0, 15 - np.frexp(amax)[1], 0).astype(np.int64)   # amax < 2^E  ->  2^t amax < 2^15
+    scaled = full.astype(np.float64) * np.ldexp(1.0, texp)[None, None, :]    # exact: a power of two
+    hi = scaled.astype(np.float16)
+    lo = (scaled - hi.astype(np.float64)).astype(np.float16)
+    parts = np.stack([hi, lo]).view(np.uint16)                   # [2][pos][cin][cout]
+    parts = parts.reshape(2, 16, nch, 2, 8, ng, 2, 32)           # part, pos, chunk, k_half, e, n-group, n-tile, j
+    w = np.ascontiguousarray(parts.transpose(2, 5, 1, 6, 0, 3, 7, 4))   # chunk, group, pos, n-tile, part, k_half, j, e
+    return np.concatenate([w.reshape(-1), texp.astype(np.int16).view(np.uint16)]), cpad
+
+
 def pack_conv_weights_small6(kernel_hwio):
     """A TF HWIO [3,3,Cin,Cout] kernel split exactly into three bf16 terms per weight, for m4d_conv3x3_small6_bias_act:
     [ceil(Cin/16)][9 taps][CoutPad][3 parts][16 channels] bf16 (uint16 bits), Cin zero-padded to a multiple of 16, CoutPad = Cout
@@ -540,12 +568,29 @@ def conv3x3_small6_bias_act(x, wp6, bias, cout, cout_pad, slope=0.1):
     return out
 
 
-def conv3x3_wino6_bias_act(x, wu6, bias, cout, cout_pad, slope=0.1, kernel=0, stagger_us=0, stagger_phases=16):
+def conv3x3_winof16_bias_act(x, wuh, bias, cout, cout_pad, slope=0.1, stagger_us=0, stagger_phases=16):
+    """The convolution of conv3x3_wino6_bias_act with float32 operands split into two fp16 terms after a power-of-two scale
+    (per Winograd tile / per output channel), three fp16 MFMA products per term pair, float32 accumulation
+    (csrc/m4d_wino_f16.hip).  ``wuh`` = pack_conv_weights_winof16 on the device (int16)."""
+    x = as_f32(x, "x")
+    b, h, w, cin = x.shape
+    out = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)
+    check(lib.m4d_conv3x3_winof16_bias_act_ks(dptr(x, "x"), dptr(wuh, "wuh", torch.int16), dptr(bias, "bias"), b, h, w, cin,
+                                              int(cout), int(cout_pad), float(slope), dptr(out), int(stagger_us),
+                                              int(stagger_phases), stream_ptr()),
+          "m4d_conv3x3_winof16_bias_act_ks")
+    return out
+
+
+def conv3x3_wino6_bias_act(x, wu6, bias, cout, cout_pad, slope=0.1, kernel=0, stagger_us=0, stagger_phases=16, arith="bf16x3"):
     """3x3 stride-1 TF-'SAME' convolution + bias + leaky_relu(slope): Winograd F(2x2,3x3), float32 operands split into
     three bf16 terms, six bf16 MFMA products per term pair, float32 accumulation.  ``kernel``: 0 = chosen from the grid,
     1 = one workgroup per (tile, 64 couts) (csrc/m4d_wino6.hip), 2 = persistent workgroups (csrc/m4d_wino6p.hip); same bits.
     ``stagger_us`` > 0: the one-workgroup-per-unit kernel starts its first round of workgroups in ``stagger_phases`` groups spread
-    over that many microseconds (a per-launch ARGUMENT, m4d_conv3x3_wino6_bias_act_ks; same bits)."""
+    over that many microseconds (a per-launch ARGUMENT, m4d_conv3x3_wino6_bias_act_ks; same bits).  ``arith`` = "f16x2": the
+    same layer on the fp16 two-term kernel (conv3x3_winof16_bias_act; ``wu6`` = pack_conv_weights_winof16, ``kernel`` ignored)."""
+    if arith == "f16x2":
+        return conv3x3_winof16_bias_act(x, wu6, bias, cout, cout_pad, slope, stagger_us=stagger_us, stagger_phases=stagger_phases)
     x = as_f32(x, "x")
     b, h, w, cin = x.shape
     out = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)

@@ -71,7 +71,7 @@ def _lat_ok(b, h, w, cin, stride):
     """Small maps (the coarse levels of a training crop) run forward and data gradient on the latency-first kernel
     (csrc/m4d_convlat.hip: float32 operands as exact 3 x bf16 splits) instead of the fp32-MFMA split-K pair."""
     from . import network as net
-    return (stride == 1 and net.conv_arith == "bf16x3" and cin >= 16 and cin % 4 == 0 and b * h * w <= net.lat_conv_max_pixels
+    return (stride == 1 and net.conv_arith in net._SPLIT_ARITHS and cin >= 16 and cin % 4 == 0 and b * h * w <= net.lat_conv_max_pixels
             and train_lat_convs)
 
 

@@ -39,8 +39,9 @@ TARGETS = {
                 [CS + "m4d_sncv.hip", CS + "m4d_sncv_small.h", CS + "m4d_common.h"]),
     "wino_l1_128_128": (["tools/bench_conv_one.py", "--iters", "5", "--winograd", "2"], ["conv3x3_wino4_kernel"],
                         [CS + "m4d_wino.hip"]),
-    "wino6_l1_128_128": (["tools/bench_conv_one.py", "--iters", "5", "--winograd", "6"], ["conv3x3_wino6_kernel", "conv3x3_wino6p_kernel"],
-                         [CS + "m4d_wino6.hip", CS + "m4d_wino6p.hip", CS + "Makefile"]),      # (the Makefile: W6FLAGS picks the split)
+    # (the key keeps bench.py's name for the level-1 Winograd layer; the kernel is the default "f16x2" one)
+    "wino6_l1_128_128": (["tools/bench_conv_one.py", "--iters", "5", "--winograd", "7"], ["conv3x3_winof16_kernel"],
+                         [CS + "m4d_wino_f16.hip", CS + "Makefile"]),
     "conv_l1_128_128": (["tools/bench_conv_one.py", "--iters", "5", "--winograd", "0"], ["conv3x3_mfma_kernel"],
                         [CS + "m4d_conv.hip"]),
 }
