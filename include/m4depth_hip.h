@@ -496,6 +496,15 @@ int m4d_conv3x3_lat(const float* x, int s_in, long long x_slab_floats, const flo
 int m4d_conv3x3s_lat(const float* x, int s_in, long long x_slab_floats, const float* x_bias, float x_slope,
                      const void* wp, const float* bias, int b, int h, int w, int Cin, int Cout, int stride, float slope,
                      int mt, int kw, int s_out, float* out, long long out_slab_floats, void* stream);
+/* m4d_conv3x3_lat with every float32 operand split into TWO fp16 terms after a power-of-two scale (per output pixel and wave
+ * K range from the pixel's 3x3 window for the input, per output channel for the weights), three fp16 MFMA products per term
+ * pair, float32 accumulation (csrc/m4d_convlat_f16.hip).  The slabs it writes and reads are m4d_conv3x3_lat's (raw, unscaled
+ * float32 partial sums), so the two kernels chain either way.  wp = network_ops.pack_conv_weights_lat_f16:
+ * [Cout/32][Cin/16][9 taps][2 parts][64 lanes][8] fp16 followed by [Cout/32 * 32] int16 weight exponents, 16-byte aligned.
+ * Stride 1, mt = 1 / 2 / 4 (no M-over-waves form).  Deterministic.  Additive entry point: ABI 6 unchanged. */
+int m4d_conv3x3_lat_f16(const float* x, int s_in, long long x_slab_floats, const float* x_bias, float x_slope,
+                        const void* wp, const float* bias, int b, int h, int w, int Cin, int Cout, float slope,
+                        int mt, int kw, int s_out, float* out, long long out_slab_floats, void* stream);
 /* out = leaky_relu(bias + slab_0 + ... + slab_{s_in-1}, slope), slabs added in slab order: the finished form of a partial-sum
  * activation, for consumers that do not add the slabs themselves and for inspection.  C % 4 == 0. */
 int m4d_partial_finish(const float* x, int s_in, long long x_slab_floats, const float* bias, float slope,

@@ -55,8 +55,9 @@ winograd2_min_workgroups = int(_os.environ.get("M4D_WINO2_MIN_WG", "60"))
 # products, float32 accumulation (csrc/m4d_wino6.hip: float32 accuracy -- error against float64 0.8x that of the fp32
 # MFMA kernels, tools/bench_wino6.py -- at 2.67x less matrix-core time); "f16x2" (default) = the same layers with float32
 # operands scaled by powers of two (per Winograd tile / per output channel) and split into two fp16 terms, three fp16 MFMA
-# products (csrc/m4d_wino_f16.hip: error against float64 at the bf16x3 level) -- every other kernel
-# (latency-first, small-map, fused tail, training) keeps its bf16x3 form under "f16x2"; "f32" = the fp32-MFMA kernels everywhere.
+# products (csrc/m4d_wino_f16.hip: error against float64 at the bf16x3 level), and the stride-1
+# latency-first layers likewise (csrc/m4d_convlat_f16.hip, ``lat_arith``) -- every other kernel (small-map, fused tail,
+# training) keeps its bf16x3 form under "f16x2"; "f32" = the fp32-MFMA kernels everywhere.
 conv_arith = _os.environ.get("M4D_CONV_ARITH", "f16x2")
 _SPLIT_ARITHS = ("bf16x3", "f16x2")          # the arithmetics that run the 16-bit split kernels
 # Smallest grid ((tile, 64-cout) units) those kernels take: 30 = the narrow layers of level 3 (30 tiles: 96 -> 64, and 64 -> 32 as
@@ -171,6 +172,13 @@ lat_conv_s2_max_pixels = int(_os.environ.get("M4D_LAT_CONV_S2_PX", "0"))
 # ... and the narrow short-K stride-2 encoder layers (Cin, Cout <= 64: 32 -> 32 at 192x640 and 64 -> 64 at 96x320 of the 384x1280
 # pyramid, fp32-MFMA direct kernels of ~25 us each at batch 1) in the kernel's M-over-waves form, up to this many OUTPUT pixels
 lat_conv_mw_max_pixels = int(_os.environ.get("M4D_LAT_CONV_MW_PX", "0"))
+# Arithmetic of those layers when conv_arith is "f16x2": "f16x2" (default) = the stride-1 layers on the fp16 two-term kernel
+# (csrc/m4d_convlat_f16.hip: three fp16 MFMA products per term pair instead of six bf16 ones, per-pixel-window input scales);
+# "bf16x3" = the bf16x3 kernel (the A side of an A/B against the Winograd change alone).  The stride-2 and M-over-waves forms
+# stay bf16x3.  Under conv_arith "bf16x3" every latency-first layer is bf16x3 whatever this says.
+lat_arith = _os.environ.get("M4D_LAT_ARITH", "f16x2")
+if lat_arith not in _SPLIT_ARITHS:
+    raise ValueError(f"M4D_LAT_ARITH must be 'f16x2' or 'bf16x3', not {lat_arith!r}")
 
 # DSCV and SNCV of a small level (<= 6000 pixels) in one launch (m4d_dscv_sncv_fwd).  0 = two launches.
 fused_cost_volumes = _os.environ.get("M4D_FUSED_COST_VOLUMES", "1") == "1"
@@ -428,6 +436,21 @@ class _Conv3x3SameTF(torch.nn.Module):
             return torch.from_numpy(wp.view("int16")).to(self.weight.device)
         return self._cache.get(("lat", cin_pad), _stamp(self.weight), build)
 
+    def _packed_weights_lat_f16(self, cin_pad=None):
+        """wp (int16 bits) for m4d_conv3x3_lat_f16: the TF kernel scaled per output channel and split into two fp16 terms,
+        MFMA B-fragment order, then the exponents."""
+        if cin_pad is not None and cin_pad == self.weight.shape[1]:
+            cin_pad = None
+
+        def build():
+            wp = nops.pack_conv_weights_lat_f16(self._hwio_numpy(cin_pad))
+            return torch.from_numpy(wp.view("int16")).to(self.weight.device)
+        return self._cache.get(("lat_f16", cin_pad), _stamp(self.weight), build)
+
+    def lat_f16(self, mw=False):
+        """Does this layer's latency-first form run on the fp16 two-term kernel (m4d_conv3x3_lat_f16)?"""
+        return conv_arith == "f16x2" and lat_arith == "f16x2" and self.stride == 1 and not mw
+
     def lat_eligible(self, b, h, w, cin):
         """Would ``forward`` run this layer on the latency-first small-map kernel for an input of this shape?"""
         if not (self.small_maps_ok and conv_arith in _SPLIT_ARITHS and cin >= 16 and cin % 4 == 0 and self.stride in (1, 2)):
@@ -511,9 +534,14 @@ class _Conv3x3SameTF(torch.nn.Module):
         # does not run its coarse encoder levels on the latency kernels of a single small map.
         eff_b = self.dispatch_batch if self.per_image_dispatch else b_
         if self.lat_eligible(b_, h_, w_, cin_):
-            wl = self._packed_weights_lat(cin_)
+            mw = self._lat_mw(b_, h_, w_, cin_)
             # (configuration from the per-image grid x the dispatch batch, like the kernel choice: the same in every launch mode)
-            cfg = nops.lat_config(eff_b, h_, w_, cin_, self.out_channels, final, self.stride, mw=self._lat_mw(b_, h_, w_, cin_))
+            cfg = nops.lat_config(eff_b, h_, w_, cin_, self.out_channels, final, self.stride, mw=mw)
+            if self.lat_f16(mw):
+                wl = self._packed_weights_lat_f16(cin_)
+                return _timed("conv", self.tag, lambda: nops.conv3x3_lat_f16(x_nhwc, wl, self.bias, self.out_channels, act,
+                                                                         config=cfg))
+            wl = self._packed_weights_lat(cin_)
             return _timed("conv", self.tag, lambda: nops.conv3x3_lat(x_nhwc, wl, self.bias, self.out_channels, act, config=cfg,
                                                                      stride=self.stride))
         wino = _use_winograd(eff_b, h_, w_, cin_, self.out_channels, self.stride)
@@ -1359,6 +1387,8 @@ class M4Depth(torch.nn.Module):
                         (conv.stride == 1 and max(lat_conv_max_pixels, lat_conv_narrow_max_pixels) > 0)
                         or (conv.stride == 2 and max(lat_conv_s2_max_pixels, lat_conv_mw_max_pixels) > 0)):
                     conv._packed_weights_lat()
+                    if conv.stride == 1:
+                        conv._packed_weights_lat_f16()   # (whatever the arithmetic now: conv_arithmetic() may switch it later)
                 if cin == 3 or (conv.stride == 2 and cin == 16 and conv.out_channels == 16):
                     conv._hwio_device()                # the encoder's level-0 kernels read the TF layout directly
                 if conv.stride == 1 and cin >= 16 and cin % 2 == 0:
@@ -1382,6 +1412,7 @@ class M4Depth(torch.nn.Module):
                     c0._packed_weights_small6(cin_pad)
                 if conv_arith in _SPLIT_ARITHS and lat_conv_max_pixels > 0:
                     c0._packed_weights_lat(cin_pad)
+                    c0._packed_weights_lat_f16(cin_pad)
                 if cin_pad % 16 == 0 and cin_pad >= 32 and c0.out_channels >= min(wino6_min_cout, 32):
                     c0._packed_weights_wino6(cin_pad)
                     c0._packed_weights_winof16(cin_pad)

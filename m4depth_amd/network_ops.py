@@ -463,6 +463,31 @@ def pack_conv_weights_lat(kernel_hwio):
     return np.ascontiguousarray(parts.transpose(5, 2, 1, 0, 3, 6, 4)).reshape(ng, nch, 9, 3, 64, 8)
 
 
+def pack_conv_weights_lat_f16(kernel_hwio):
+    """The TF HWIO [3,3,Cin,Cout] kernel of pack_conv_weights_lat scaled per output channel n by 2^t_n (|2^t_n w| < 2^15,
+    exact) and split into two fp16 terms (round to nearest: hi = fp16(w), lo = fp16(w - hi)) in the B-fragment order
+    m4d_conv3x3_lat_f16 loads into operand registers: [ceil(Cout/32)][ceil(Cin/16)][9 taps][2 parts][64 lanes][8] fp16 bits
+    (lane = k_half * 32 + cout % 32, element e = channel 8 k_half + e of the chunk; zero padded), followed by the
+    ceil(Cout/32) * 32 exponents t_n as int16.  numpy in, flat numpy uint16 out."""
+    import numpy as np
+    k = np.asarray(kernel_hwio, dtype=np.float32)
+    assert k.shape[:2] == (3, 3)
+    cin, cout = k.shape[2], k.shape[3]
+    nch, ng = -(-cin // 16), -(-cout // 32)
+    full = np.zeros((9, nch * 16, ng * 32), np.float32)
+    full[:, :cin, :cout] = k.reshape(9, cin, cout)
+    if not np.isfinite(full).all():
+        raise ValueError("pack_conv_weights_lat_f16: non-finite weight")
+    amax = np.abs(full).max(axis=(0, 1)).astype(np.float64)      # [ng * 32]
+    texp = np.where(amax > 0, 15 - np.frexp(amax)[1], 0).astype(np.int64)   # amax < 2^E  ->  2^t amax < 2^15
+    scaled = full.astype(np.float64) * np.ldexp(1.0, texp)[None, None, :]    # exact: a power of two
+    hi = scaled.astype(np.float16)
+    lo = (scaled - hi.astype(np.float64)).astype(np.float16)
+    parts = np.stack([hi, lo]).view(np.uint16).reshape(2, 9, nch, 2, 8, ng, 32)   # part, tap, chunk, k_half, e, group, n
+    w = np.ascontiguousarray(parts.transpose(5, 2, 1, 0, 3, 6, 4))               # group, chunk, tap, part, k_half, n, e
+    return np.concatenate([w.reshape(-1), texp.astype(np.int16).view(np.uint16)])
+
+
 class PartialAct:
     """An activation that exists as K-slice partial sums: ``slabs`` [S,b,h,w,C] raw sums of m4d_conv3x3_lat's K slices, to be
     added in slab order, + ``bias``, leaky_relu(``slope``) -- which the consuming m4d_conv3x3_lat does while it stages its
@@ -554,6 +579,28 @@ def conv3x3_lat(x, wp, bias, cout, slope=0.1, final=False, config=None, stride=1
     check(lib.m4d_conv3x3s_lat(dptr(xs, "x"), s_in, slab, dptr(x_bias, "x_bias"), float(x_slope), dptr(wp, "wp", torch.int16),
                                dptr(bias, "bias"), b, h, w, cin, int(cout), int(stride), act, mt, kw, s_out, dptr(out),
                                b * oh * ow * int(cout), stream_ptr()), "m4d_conv3x3s_lat")
+    return out[0] if s_out == 1 else PartialAct(out, bias, act)
+
+
+def conv3x3_lat_f16(x, wp, bias, cout, slope=0.1, final=False, config=None):
+    """conv3x3_lat (stride 1) on m4d_conv3x3_lat_f16: float32 operands scaled by powers of two and split into two fp16 terms,
+    three fp16 MFMA products per term pair (csrc/m4d_convlat_f16.hip).  ``wp`` = pack_conv_weights_lat_f16 on the device
+    (int16).  Takes and returns what conv3x3_lat does: its ``PartialAct`` slabs are the same raw float32 partial sums."""
+    if isinstance(x, PartialAct):
+        xs, s_in, x_bias, x_slope = x.slabs, x.slabs.shape[0], x.bias, x.slope
+        b, h, w, cin = x.shape
+        slab = b * h * w * cin
+    else:
+        xs = as_f32(x, "x")
+        s_in, x_bias, x_slope = 1, None, 1.0
+        b, h, w, cin = xs.shape
+        slab = 0
+    mt, kw, s_out = config if config is not None else lat_config(b, h, w, cin, cout, final)
+    act = 1.0 if slope is None else float(slope)
+    out = torch.empty((s_out, b, h, w, cout), dtype=torch.float32, device=xs.device)
+    check(lib.m4d_conv3x3_lat_f16(dptr(xs, "x"), s_in, slab, dptr(x_bias, "x_bias"), float(x_slope), dptr(wp, "wp", torch.int16),
+                                  dptr(bias, "bias"), b, h, w, cin, int(cout), act, mt, kw, s_out, dptr(out),
+                                  b * h * w * int(cout), stream_ptr()), "m4d_conv3x3_lat_f16")
     return out[0] if s_out == 1 else PartialAct(out, bias, act)
 
 

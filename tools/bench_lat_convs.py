@@ -1,12 +1,19 @@
 """The refiner convolutions of the coarse levels on m4d_conv3x3_lat (csrc/m4d_convlat.hip): us per layer as a dependent chain
 replayed from a hipGraph (no host launch overhead), the default configuration (network_ops.lat_config) beside every other
-(mt, kw, s_out) and beside conv3x3_small6 -- the table the defaults were read from.  `python tools/bench_lat_convs.py [sweep]`"""
+(mt, kw, s_out) and beside conv3x3_small6 -- the table the defaults were read from; then the coarse stride-1 encoder layers of an
+encoder batch of two frames.  `python tools/bench_lat_convs.py [sweep] [--arith f16x2|bf16x3]`: the arithmetic of the latency
+kernel (f16x2 = m4d_conv3x3_lat_f16, csrc/m4d_convlat_f16.hip; default bf16x3)."""
 import os, sys, itertools, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from m4depth_amd import network_ops as nops
 dev = torch.device("cuda:0")
-SWEEP = len(sys.argv) > 1 and sys.argv[1] == "sweep"
+SWEEP = "sweep" in sys.argv[1:]
+ARITH = sys.argv[sys.argv.index("--arith") + 1] if "--arith" in sys.argv else "bf16x3"
+assert ARITH in ("bf16x3", "f16x2")
+LAT = nops.conv3x3_lat_f16 if ARITH == "f16x2" else nops.conv3x3_lat
+PACK = nops.pack_conv_weights_lat_f16 if ARITH == "f16x2" else nops.pack_conv_weights_lat
+print(f"latency-first kernel arithmetic: {ARITH}")
 
 
 def timed(fn, reps=20):
@@ -35,7 +42,7 @@ for (h, w, cin0) in [(6, 20, 472), (12, 40, 240), (24, 80, 240), (48, 160, 128)]
     layers = []
     for ci, co in zip(chans[:-1], chans[1:]):
         k = (torch.randn(3, 3, ci, co) * (2.0 / (9 * ci)) ** 0.5).numpy()
-        wl = torch.from_numpy(nops.pack_conv_weights_lat(k).view("int16")).to(dev)
+        wl = torch.from_numpy(PACK(k).view("int16")).to(dev)
         w6, cpad = nops.pack_conv_weights_small6(k)
         layers.append((wl, torch.from_numpy(w6.view("int16")).to(dev), cpad, torch.zeros(co, device=dev), ci, co))
     x0 = torch.randn(1, h, w, cin0, device=dev)
@@ -44,7 +51,7 @@ for (h, w, cin0) in [(6, 20, 472), (12, 40, 240), (24, 80, 240), (48, 160, 128)]
         x = x0
         for i, (wl, _, _, bz, ci, co) in enumerate(layers[:n]):
             cfg = override if (override is not None and i == n - 1) else None
-            x = nops.conv3x3_lat(x, wl, bz, co, 0.1, final=(i == 4), config=cfg)
+            x = LAT(x, wl, bz, co, 0.1, final=(i == 4), config=cfg)
         return x
 
     def chain_small6(n):
@@ -79,3 +86,14 @@ for (h, w, cin0) in [(6, 20, 472), (12, 40, 240), (24, 80, 240), (48, 160, 128)]
                     print("   ", (mt, kw, so), "failed:", str(e)[:80])
             res.sort()
             print(f"   layer {n} {ci}->{co}: " + "  ".join(f"{c}:{t:.1f}" for t, c in res[:8]) + f"  ... worst {res[-1][1]}:{res[-1][0]:.1f}")
+
+# the coarse stride-1 encoder layers (96 -> 128 at 24x80, 128 -> 192 at 12x40) of an encoder batch of two frames, configured from
+# the per-image grid x the sequence batch 1 as the model does; each hands partial slabs on (finished here by partial_finish)
+for (h, w, ci, co) in [(24, 80, 96, 128), (12, 40, 128, 192)]:
+    k = (torch.randn(3, 3, ci, co) * (2.0 / (9 * ci)) ** 0.5).numpy()
+    wl = torch.from_numpy(PACK(k).view("int16")).to(dev)
+    bz = torch.zeros(co, device=dev)
+    x0 = torch.randn(2, h, w, ci, device=dev)
+    cfg = nops.lat_config(1, h, w, ci, co)
+    t = timed(lambda: LAT(x0, wl, bz, co, 0.1, config=cfg))
+    print(f"encoder 2x{h}x{w} lat    : {ci}->{co} {t:5.1f} {cfg}")
