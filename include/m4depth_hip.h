@@ -528,7 +528,8 @@ int m4d_conv3x3_small6_bias_act(const float* x, const void* wp6, const float* bi
 /* DomainNormalization (m4depth_network.py:44-48) fused with the leaky_relu(slope) that follows it
  * at encoder level 0 (:82-84; slope = 1 for the normalisation alone).  x, out [b,h,w,C] (C = 16 or
  * 32); mean and the two-pass variance over (h,w) per (b,c); (x-mean)/(var+1e-12); l2-normalise
- * over channels; scale*n + bias.  workspace: m4d_dinl_workspace_floats(b, C) floats. */
+ * over channels; scale*n + bias.  workspace: m4d_dinl_workspace_floats(b, C) floats = b*512*C double partial sums, then
+ * mean [b][C] and var [b][C] (floats) at its end. */
 long long m4d_dinl_workspace_floats(int b, int C);
 /* ... written into a [b,out_h,out_w,C] buffer at (off_y,off_x) (see m4d_bias_act_padded). */
 int m4d_dinl_fwd_padded(const float* x, const float* scale, const float* bias, int b, int h, int w, int C,
@@ -554,7 +555,8 @@ int m4d_enc_level0_fwd(const float* images, int bsz, long long stride_b, long lo
                        float dn_slope, const float* w2_hwio, const float* bias2, float slope,
                        int b, int h, int w, float* workspace, float* out, void* stream);
 /* m4d_enc_level0_fwd as its two halves: the statistics passes (mean / var [b,16] of conv1's output per image and channel;
- * workspace >= b * kDinlMaxBlocks * 16 floats = m4d_dinl_workspace_floats(b,16) minus the mean / var tail) and the fused
+ * workspace >= m4d_dinl_workspace_floats(b,16) - 2*b*16 floats, 8-byte aligned: the double partial sums without the mean / var
+ * tail) and the fused
  * normalise + stride-2 convolution pass reading them.  Per-image arithmetic: the statistics of all frames of a sequence may be
  * taken in one call and the frames applied in several (same bits as m4d_enc_level0_fwd on any grouping). */
 int m4d_enc_level0_stats(const float* images, int bsz, long long stride_b, long long stride_t,

@@ -5,7 +5,9 @@
 //     two-pass variance TF computes) and ONE apply pass, instead of ~12 passes over the
 //     largest activation of the network ([b,H,W,16]);
 //   * the 7 depth metrics of metrics.py in one pass over (gt, est).
-// Partial sums are combined in a fixed order (no atomics): results are run-to-run identical.
+// Partial sums are combined in a fixed order (no atomics): results are run-to-run identical.  The DINL statistics are summed
+// in double from the first add on: a frame whose mean dwarfs its spread, or a flat frame (an all-zero one included), keeps
+// its digits, and the mean of a constant channel is exact, so its variance is exactly 0.
 #include <cstdlib>
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
@@ -13,12 +15,14 @@
 namespace {
 
 constexpr int kDinlMaxBlocks = 512;
+// Workspace of the DINL entry points, per image: kDinlMaxBlocks x C double partials, then mean [b][C], var [b][C] (floats)
+__host__ __device__ constexpr long long dinl_partial_floats(int b, int C) { return 2LL * b * kDinlMaxBlocks * C; }
 
 // pass 0: sum x ; pass 1: sum (x - mean)^2, per (batch, channel); C % 4 == 0, C/4 divides 256
 __global__ void __launch_bounds__(256)
 dinl_partial_kernel(const float* __restrict__ x, const float* __restrict__ mean, int hw, int C, int pass,
-                    float* __restrict__ partial) {
-  __shared__ float4 sh[256];
+                    double* __restrict__ partial) {
+  __shared__ double sh[4][256];
   const int bi = blockIdx.y;
   const int c4n = C >> 2;
   const int ppi = 256 / c4n;                       // pixels per block iteration
@@ -26,36 +30,38 @@ dinl_partial_kernel(const float* __restrict__ x, const float* __restrict__ mean,
   const float* xb = x + (long long)bi * hw * C;
   float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
   if (pass == 1) m = *reinterpret_cast<const float4*>(mean + bi * C + c4 * 4);
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int p = blockIdx.x * ppi + po; p < hw; p += gridDim.x * ppi) {
     float4 v = *reinterpret_cast<const float4*>(xb + (long long)p * C + c4 * 4);
     if (pass == 1) {
       v.x = v.x - m.x; v.y = v.y - m.y; v.z = v.z - m.z; v.w = v.w - m.w;
       v.x = v.x * v.x; v.y = v.y * v.y; v.z = v.z * v.z; v.w = v.w * v.w;
     }
-    acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    acc[0] += (double)v.x; acc[1] += (double)v.y; acc[2] += (double)v.z; acc[3] += (double)v.w;
   }
-  sh[threadIdx.x] = acc;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) sh[e][threadIdx.x] = acc[e];
   __syncthreads();
   if (po == 0) {                                   // fixed-order combine of the ppi partials of this channel group
-    float4 s = sh[c4];
-    for (int r = 1; r < ppi; ++r) {
-      const float4 v = sh[r * c4n + c4];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    double* pp = partial + ((long long)bi * gridDim.x + blockIdx.x) * C + c4 * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      double s = sh[e][c4];
+      for (int r = 1; r < ppi; ++r) s += sh[e][r * c4n + c4];
+      pp[e] = s;
     }
-    *reinterpret_cast<float4*>(partial + ((long long)bi * gridDim.x + blockIdx.x) * C + c4 * 4) = s;
   }
 }
 
 // 256 lanes: lane (j, c) sums every (256/C)-th partial of channel c, then the 256/C sub-sums are
 // combined in index order -- a fixed summation tree, so the result is run-to-run identical.
 __global__ void __launch_bounds__(256)
-dinl_finalize_kernel(const float* __restrict__ partial, int nblk, int C, int hw, float* __restrict__ out) {
+dinl_finalize_kernel(const double* __restrict__ partial, int nblk, int C, int hw, float* __restrict__ out) {
   __shared__ double sh[256];
   const int bi = blockIdx.x;
   const int c = threadIdx.x % C, j = threadIdx.x / C, nj = 256 / C;
   double s = 0.0;
-  for (int k = j; k < nblk; k += nj) s += (double)partial[((long long)bi * nblk + k) * C + c];
+  for (int k = j; k < nblk; k += nj) s += partial[((long long)bi * nblk + k) * C + c];
   sh[threadIdx.x] = s;
   __syncthreads();
   if (j == 0) {
@@ -113,17 +119,17 @@ template <int C>
 __global__ void __launch_bounds__(256)
 enc_head_conv_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias,
                      int h, int w, int bsz, long long stride_b, long long stride_t,
-                     float* __restrict__ out, float* __restrict__ partial) {
-  __shared__ float sh[4][C];
+                     float* __restrict__ out, double* __restrict__ partial) {
+  __shared__ double sh[4][C];
   const int bi = blockIdx.y;
   const int hw = h * w;
   // image bi = frame (bi / bsz) of sequence (bi % bsz): the frames of a [b,T,H,W,3] batch are encoded in one launch,
   // frame-major, straight from the sequence tensor (no stacking copy)
   const float* ib = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
   float* ob = out + (long long)bi * hw * C;
-  float csum[C];
+  double csum[C];
 #pragma unroll
-  for (int c = 0; c < C; ++c) csum[c] = 0.f;
+  for (int c = 0; c < C; ++c) csum[c] = 0.0;
   for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {
     const int y = p / w, x = p - y * w;
     typedef float f2 __attribute__((ext_vector_type(2)));         // packed v_pk_mul_f32 / v_pk_add_f32: two channels per op
@@ -152,13 +158,13 @@ enc_head_conv_kernel(const float* __restrict__ img, const float* __restrict__ w2
     for (int c = 0; c < C; c += 4) {
       float4 o = make_float4(acc[c] + bias[c], acc[c + 1] + bias[c + 1], acc[c + 2] + bias[c + 2], acc[c + 3] + bias[c + 3]);
       *reinterpret_cast<float4*>(ob + (long long)p * C + c) = o;
-      csum[c] += o.x; csum[c + 1] += o.y; csum[c + 2] += o.z; csum[c + 3] += o.w;
+      csum[c] += (double)o.x; csum[c + 1] += (double)o.y; csum[c + 2] += (double)o.z; csum[c + 3] += (double)o.w;
     }
   }
   // fixed-order reduction: butterfly inside the wave, then the 4 waves in index order
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    float v = csum[c];
+    double v = csum[c];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][c] = v;
@@ -291,9 +297,12 @@ __device__ __forceinline__ f32x4 enc0_conv1(const float* window_base, const int 
 constexpr int kE0TW = 128, kE0TH = 8;              // statistics tile (pixels)
 constexpr int kE0RS = (kE0TW + 2) * 3;             // floats per staged RGB row (390)
 
-// The shift of the single-pass statistics (PASS 2 below): conv1 + bias at the image's centre pixel -- one sample of the very
-// distribution whose moments are taken, so (mean - K)^2 is of the order of the variance and sum (y - K)^2 - (sum (y - K))^2 / n
-// cancels nothing to speak of.  Evaluated with the same expression by the statistics kernel and by its finalisation.
+// The shift of the single-pass statistics (PASS 2 below): conv1 + bias at the image's centre pixel.  On a typical frame it is one
+// sample of the very distribution whose moments are taken, and var = S2 / n - (S1 / n)^2 cancels little.  On a frame whose
+// centre is unlike the rest (a flat or dark frame with a bright centre, a grey one with a black centre) (mean - K)^2 exceeds the
+// variance by up to ~n: the sums are therefore taken in double from the first add on (y - K of two floats is exact in double),
+// and the cancellation costs ~n x 1e-16 instead of every digit.  Evaluated with the same expression by the statistics kernel
+// and by its finalisation.
 __device__ __forceinline__ float enc0_shift(const float* __restrict__ ib, const float* __restrict__ w27, const float* __restrict__ bias,
                                             int h, int w, int j) {
   const int cy = h / 2, cx = w / 2;
@@ -307,19 +316,20 @@ __device__ __forceinline__ float enc0_shift(const float* __restrict__ ib, const 
   return y;
 }
 
-// PASS 0: per-channel sums of conv1 + bias; PASS 1: sums of squared deviations from `mean` -- partials in the layout of
+// PASS 0: per-channel sums of conv1 + bias; PASS 1: sums of squared deviations from `mean` -- double partials in the layout of
 // dinl_partial_kernel ([image][block][16]), finished by dinl_finalize_kernel.  A workgroup walks tiles blockIdx.x, + gridDim.x, ...
 // PASS 2 (round 6): BOTH moments in one pass -- S1 = sum (y - K), S2 = sum (y - K)^2 with the per-image, per-channel shift K of
-// enc0_shift -- partials [image][block][32] (16 x S1, 16 x S2), finished by enc0_moments_finalize_kernel: the level-0 statistics are
-// then TWO dependent launches instead of four (RGB totals, analytic mean, squared deviations, finalisation), 20 us less at the head
-// of a batch-1 step's critical path.
+// enc0_shift -- double partials [image][block][32] (16 x S1, 16 x S2), finished by enc0_moments_finalize_kernel: the level-0
+// statistics are then TWO dependent launches instead of four (RGB totals, analytic mean, squared deviations, finalisation), 20 us
+// less at the head of a batch-1 step's critical path.  Every sum is a double, per lane, through the butterfly and the workgroup
+// combine, in a fixed order.
 template <int PASS>
 __global__ void __launch_bounds__(256)
 enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias,
                   const float* __restrict__ mean, int h, int w, int bsz, long long stride_b, long long stride_t,
-                  int tiles_x, int n_tiles, float* __restrict__ partial) {
+                  int tiles_x, int n_tiles, double* __restrict__ partial) {
   __shared__ float tile[(kE0TH + 2) * kE0RS];      // 15.6 KB
-  __shared__ float sh[4][16];
+  __shared__ double sh[2][4][16];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int j = lane & 15, g = lane >> 4;
   const int bi = blockIdx.y;
@@ -328,7 +338,8 @@ enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   enc0_lane_setup(w27, lane, kE0RS, koff, wb);
   const float bias_j = bias[j];
   const float mean_j = PASS == 1 ? mean[bi * 16 + j] : (PASS == 2 ? enc0_shift(ib, w27, bias, h, w, j) : 0.f);
-  float csum = 0.f, csum2 = 0.f;
+  const double shift_j = (double)mean_j;
+  double csum = 0.0, csum2 = 0.0;
   for (int ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
     const int y0 = (ti / tiles_x) * kE0TH, x0 = (ti % tiles_x) * kE0TW;
     __syncthreads();                               // the previous tile has been consumed
@@ -350,8 +361,13 @@ enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
           const bool valid = y0 + yl < h && x0 + 16 * ct + 4 * g + r < w;
           float v = acc[r] + bias_j;
           if (PASS == 1) { v = v - mean_j; v = v * v; }
-          if (PASS == 2) { v = v - mean_j; csum2 += valid ? v * v : 0.f; }
-          csum += valid ? v : 0.f;
+          if (PASS == 2) {
+            const double d = valid ? (double)v - shift_j : 0.0;
+            csum += d;
+            csum2 = fma(d, d, csum2);
+          } else {
+            csum += valid ? (double)v : 0.0;
+          }
         }
       }
     }
@@ -359,26 +375,23 @@ enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   csum += __shfl_xor(csum, 16);                    // the four pixel groups of a channel: fixed butterfly
   csum += __shfl_xor(csum, 32);
   if (PASS == 2) {
-    __shared__ float sh2[4][16];
     csum2 += __shfl_xor(csum2, 16);
     csum2 += __shfl_xor(csum2, 32);
-    if (lane < 16) { sh[wv][lane] = csum; sh2[wv][lane] = csum2; }
-    __syncthreads();
-    float* po = partial + ((long long)bi * gridDim.x + blockIdx.x) * 32;
-    if (t < 16) po[t] = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
-    else if (t < 32) po[t] = ((sh2[0][t - 16] + sh2[1][t - 16]) + sh2[2][t - 16]) + sh2[3][t - 16];
-    return;
   }
-  if (lane < 16) sh[wv][lane] = csum;
+  if (lane < 16) { sh[0][wv][lane] = csum; sh[1][wv][lane] = csum2; }
   __syncthreads();
-  if (t < 16) partial[((long long)bi * gridDim.x + blockIdx.x) * 16 + t] = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
+  constexpr int NQ = PASS == 2 ? 32 : 16;          // 16 x S1 (+ 16 x S2)
+  if (t < NQ) {
+    const int q = t >> 4, c = t & 15;
+    partial[((long long)bi * gridDim.x + blockIdx.x) * NQ + t] = ((sh[q][0][c] + sh[q][1][c]) + sh[q][2][c]) + sh[q][3][c];
+  }
 }
 
-// mean = K + S1 / n, var = S2 / n - (S1 / n)^2 (the biased variance of tf.math.reduce_variance) from the PASS-2 partials, in
-// double, partials added in block order by a fixed tree: run-to-run identical.  One workgroup per image; thread (c, j): channel c
+// mean = K + S1 / n, var = S2 / n - (S1 / n)^2 (the biased variance of tf.math.reduce_variance) from the PASS-2 double partials,
+// added in block order by a fixed tree: run-to-run identical.  One workgroup per image; thread (c, j): channel c
 // (32 columns: 16 x S1, 16 x S2), every 8th block from j.
 __global__ void __launch_bounds__(256)
-enc0_moments_finalize_kernel(const float* __restrict__ img, const float* __restrict__ partial, int nblk, const float* __restrict__ w27,
+enc0_moments_finalize_kernel(const float* __restrict__ img, const double* __restrict__ partial, int nblk, const float* __restrict__ w27,
                              const float* __restrict__ bias, int h, int w, int bsz, long long stride_b, long long stride_t,
                              float* __restrict__ mean, float* __restrict__ var) {
   __shared__ double sh[256];
@@ -386,10 +399,10 @@ enc0_moments_finalize_kernel(const float* __restrict__ img, const float* __restr
   const int c = t & 31, j = t >> 5;
   // (the kernel is a latency chain on the head of the step: all of a thread's partials are requested before the first add, and
   //  the shift -- 27 dependent scalar loads + multiply-adds -- is evaluated by 16 other threads meanwhile)
-  float pv[32];
+  double pv[32];
   const int cnt = (nblk - j + 7) / 8;
 #pragma unroll
-  for (int i = 0; i < 32; ++i) pv[i] = i < cnt ? partial[((long long)bi * nblk + j + 8 * i) * 32 + c] : 0.f;
+  for (int i = 0; i < 32; ++i) pv[i] = i < cnt ? partial[((long long)bi * nblk + j + 8 * i) * 32 + c] : 0.0;
   __shared__ float s_shift[16];
   if (t >= 240) {
     const float* ib0 = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
@@ -397,7 +410,7 @@ enc0_moments_finalize_kernel(const float* __restrict__ img, const float* __restr
   }
   double s = 0.0;
 #pragma unroll
-  for (int i = 0; i < 32; ++i) s += (double)pv[i];                 // block order j, j + 8, ...: fixed
+  for (int i = 0; i < 32; ++i) s += pv[i];                         // block order j, j + 8, ...: fixed
   sh[t] = s;
   __syncthreads();
   if (t < 32) {
@@ -598,7 +611,7 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
 }  // namespace
 
 extern "C" long long m4d_dinl_workspace_floats(int b, int C) {
-  return (long long)b * (kDinlMaxBlocks + 2) * C;
+  return dinl_partial_floats(b, C) + 2LL * b * C;
 }
 
 extern "C" int m4d_dinl_fwd(const float* x, const float* scale, const float* bias, int b, int h, int w, int C,
@@ -618,13 +631,13 @@ extern "C" int m4d_dinl_fwd_padded(const float* x, const float* scale, const flo
   const int ppi = 256 / (C / 4);
   int nblk = (hw + ppi * 8 - 1) / (ppi * 8);
   if (nblk > kDinlMaxBlocks) nblk = kDinlMaxBlocks;
-  float* partial = workspace;
-  float* mean = workspace + (long long)b * kDinlMaxBlocks * C;
+  double* partial = reinterpret_cast<double*>(workspace);
+  float* mean = workspace + dinl_partial_floats(b, C);
   float* var = mean + (long long)b * C;
   m4d_launch(dinl_partial_kernel, dim3(nblk, b), dim3(256), 0, s, x, (const float*)nullptr, hw, C, 0, partial);
-  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, partial, nblk, C, hw, mean);
+  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk, C, hw, mean);
   m4d_launch(dinl_partial_kernel, dim3(nblk, b), dim3(256), 0, s, x, (const float*)mean, hw, C, 1, partial);
-  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, partial, nblk, C, hw, var);
+  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk, C, hw, var);
   int gx = m4d_blocks(hw, 256);
   if (gx > 2048) gx = 2048;
   if (C == 16) m4d_launch(dinl_apply_kernel<16>, dim3(gx, b), dim3(256), 0, s, x, mean, var, scale, bias, hw, w, slope, out, out_h, out_w, off_y, off_x);
@@ -644,17 +657,17 @@ extern "C" int m4d_enc_head_fwd(const float* images, int bsz, long long stride_b
   int nblk = (hw + 256 * 8 - 1) / (256 * 8);       // (4x more, smaller workgroups: same kernel time, slower finalize)
   if (nblk > kDinlMaxBlocks) nblk = kDinlMaxBlocks;
   if (nblk < 1) nblk = 1;
-  float* partial = workspace;
-  float* mean = workspace + (long long)b * kDinlMaxBlocks * C;
+  double* partial = reinterpret_cast<double*>(workspace);
+  float* mean = workspace + dinl_partial_floats(b, C);
   float* var = mean + (long long)b * C;
   m4d_launch(enc_head_conv_kernel<16>, dim3(nblk, b), dim3(256), 0, s, images, w_hwio, bias, h, w, bsz, stride_b, stride_t,
                      raw_out, partial);
-  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, partial, nblk, C, hw, mean);
+  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk, C, hw, mean);
   const int ppi = 256 / (C / 4);
   int nblk2 = (hw + ppi * 8 - 1) / (ppi * 8);
   if (nblk2 > kDinlMaxBlocks) nblk2 = kDinlMaxBlocks;
   m4d_launch(dinl_partial_kernel, dim3(nblk2, b), dim3(256), 0, s, (const float*)raw_out, (const float*)mean, hw, C, 1, partial);
-  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, partial, nblk2, C, hw, var);
+  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk2, C, hw, var);
   return M4D_LAUNCH_RESULT();
 }
 
@@ -666,41 +679,42 @@ extern "C" int m4d_enc_level0_stats(const float* images, int bsz, long long stri
                                     float* mean, float* var, void* stream) {
   M4D_CHECK_ARG(images && w1_hwio && bias1 && workspace && mean && var);
   M4D_CHECK_ARG(b > 0 && h > 0 && w > 0 && bsz > 0 && b % bsz == 0 && stride_b >= 0 && stride_t >= 0);
+  M4D_CHECK_ARG((((uintptr_t)workspace) & 7u) == 0);
   hipStream_t s = (hipStream_t)stream;
   const int C = 16, hw = h * w;
   const int tiles_x = (w + kE0TW - 1) / kE0TW, n_tiles = tiles_x * ((h + kE0TH - 1) / kE0TH);
   const int nblk = n_tiles < kDinlMaxBlocks ? n_tiles : kDinlMaxBlocks;
-  float* partial = workspace;
-  static int single_pass = -1;                     // M4D_ENC0_SINGLE_PASS=0: round 5's four launches (A/B timing)
-  if (single_pass < 0) { const char* e = getenv("M4D_ENC0_SINGLE_PASS"); single_pass = e ? atoi(e) : 1; }
-  if (single_pass) {
-    // 32 floats per block in the same workspace -> at most 256 blocks per image; BALANCED: every workgroup the same number of tiles
+  double* partial = reinterpret_cast<double*>(workspace);
+  // process-wide settings, read once (thread-safe initialisation of a function-local static) and never written again
+  static const int single_pass = [] { const char* e = getenv("M4D_ENC0_SINGLE_PASS"); return e ? atoi(e) : 1; }();
+  static const int analytic_mean_env = [] { const char* e = getenv("M4D_ENC0_ANALYTIC_MEAN"); return e ? atoi(e) : 1; }();
+  if (single_pass) {   // M4D_ENC0_SINGLE_PASS=0: round 5's four launches (A/B timing)
+    // 32 doubles per block in the same workspace -> at most 256 blocks per image; BALANCED: every workgroup the same number of tiles
     // (384x1280: 480 tiles -> 240 workgroups of exactly two, not 224 of two + 32 of one)
     const int cap = kDinlMaxBlocks / 2, per = (n_tiles + cap - 1) / cap;
     const int nb2 = (n_tiles + per - 1) / per;
     m4d_launch(enc0_stats_kernel<2>, dim3(nb2, b), dim3(256), 0, s, images, w1_hwio, bias1, (const float*)nullptr, h, w, bsz,
                stride_b, stride_t, tiles_x, n_tiles, partial);
-    m4d_launch(enc0_moments_finalize_kernel, dim3(b), dim3(256), 0, s, images, (const float*)partial, nb2, w1_hwio, bias1, h, w, bsz,
+    m4d_launch(enc0_moments_finalize_kernel, dim3(b), dim3(256), 0, s, images, (const double*)partial, nb2, w1_hwio, bias1, h, w, bsz,
                stride_b, stride_t, mean, var);
     return M4D_LAUNCH_RESULT();
   }
-  static int analytic_mean = -1;                   // M4D_ENC0_ANALYTIC_MEAN=0: the mean from a convolution pass instead
-  if (analytic_mean < 0) { const char* e = getenv("M4D_ENC0_ANALYTIC_MEAN"); analytic_mean = e ? atoi(e) : 1; }
-  if (analytic_mean && (h == 1 || w == 1)) analytic_mean = 0;      // (one border row / column would be excluded twice)
+  // M4D_ENC0_ANALYTIC_MEAN=0: the mean from a convolution pass instead; on one row / column a border would be excluded twice
+  const bool analytic_mean = analytic_mean_env && h > 1 && w > 1;
   if (analytic_mean) {
     int nb3 = (hw + 256 * 16 - 1) / (256 * 16);
     if (nb3 > kDinlMaxBlocks) nb3 = kDinlMaxBlocks;
-    m4d_launch(enc0_rgb_total_kernel, dim3(nb3, b), dim3(256), 0, s, images, hw, bsz, stride_b, stride_t, partial);
-    m4d_launch(enc0_mean_kernel, dim3(b), dim3(256), 0, s, images, (const float*)partial, nb3, w1_hwio, bias1, h, w, bsz,
+    m4d_launch(enc0_rgb_total_kernel, dim3(nb3, b), dim3(256), 0, s, images, hw, bsz, stride_b, stride_t, workspace);
+    m4d_launch(enc0_mean_kernel, dim3(b), dim3(256), 0, s, images, (const float*)workspace, nb3, w1_hwio, bias1, h, w, bsz,
                        stride_b, stride_t, mean);
   } else {
     m4d_launch(enc0_stats_kernel<0>, dim3(nblk, b), dim3(256), 0, s, images, w1_hwio, bias1, (const float*)nullptr, h, w, bsz,
                        stride_b, stride_t, tiles_x, n_tiles, partial);
-    m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, partial, nblk, C, hw, mean);
+    m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk, C, hw, mean);
   }
   m4d_launch(enc0_stats_kernel<1>, dim3(nblk, b), dim3(256), 0, s, images, w1_hwio, bias1, (const float*)mean, h, w, bsz,
                      stride_b, stride_t, tiles_x, n_tiles, partial);
-  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, partial, nblk, C, hw, var);
+  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk, C, hw, var);
   return M4D_LAUNCH_RESULT();
 }
 
@@ -725,7 +739,7 @@ extern "C" int m4d_enc_level0_fwd(const float* images, int bsz, long long stride
                                    float dn_slope, const float* w2_hwio, const float* bias2, float slope,
                                    int b, int h, int w, float* workspace, float* out, void* stream) {
   M4D_CHECK_ARG(workspace && b > 0);
-  float* mean = workspace + (long long)b * kDinlMaxBlocks * 16;
+  float* mean = workspace + dinl_partial_floats(b, 16);
   float* var = mean + (long long)b * 16;
   const int rc = m4d_enc_level0_stats(images, bsz, stride_b, stride_t, w1_hwio, bias1, b, h, w, workspace, mean, var, stream);
   if (rc != 0) return rc;

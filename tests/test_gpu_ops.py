@@ -902,9 +902,11 @@ def test_encoder_level0_without_intermediate(M, dev, weights, b, h, w):
 @pytest.mark.parametrize("b,h,w,offset,spread", [(2, 96, 272, 0.0, 1.0), (1, 384, 1280, 0.0, 1.0), (3, 37, 53, 0.9, 0.01), (1, 130, 260, 50.0, 0.5)])
 def test_encoder_level0_statistics_single_pass(M, dev, b, h, w, offset, spread):
     """m4d_enc_level0_stats, round 6: mean and variance of the (never written) 3 -> 16 convolution output from ONE pass over the
-    image -- shifted moments sum (y - K), sum (y - K)^2 with K = the convolution at the centre pixel, merged in double -- instead
-    of four launches (RGB totals, analytic mean, squared deviations, finalisation).  Against the float64 moments of the oracle's
-    convolution, also on images whose mean dwarfs their spread (where an unshifted E[y^2] - E[y]^2 loses every digit)."""
+    image -- shifted moments sum (y - K), sum (y - K)^2 with K = the convolution at the centre pixel, summed in double per lane,
+    through the workgroup combine and the finalisation -- instead of four launches (RGB totals, analytic mean, squared
+    deviations, finalisation).  Against the float64 moments of the oracle's convolution, also on images whose mean dwarfs their
+    spread (where an unshifted E[y^2] - E[y]^2 in float32 loses every digit); frames whose centre pixel is unlike the rest are
+    in test_gpu_reductions.py."""
     from m4depth_amd import network_ops as nops
     rng = np.random.default_rng(h + w)
     img = (offset + spread * rng.random([b, h, w, 3])).astype(F)

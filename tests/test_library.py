@@ -67,6 +67,20 @@ def test_argument_validation_without_gpu():
                             fake, 3, None, None, 0, 1.0, None, None) == 1                    # rot_c not in {3,4}
 
 
+def test_dinl_workspace_covers_double_partials():
+    """m4d_dinl_workspace_floats(b, C): the double partial sums of every DINL entry point (512 workgroups x C channels of the
+    two-pass forms; 256 workgroups x 32 moments of the single-pass level-0 statistics), then the mean / var tail of 2*b*C floats
+    that encoder_head reads at the end; m4d_enc_level0_stats rejects a workspace that is not 8-byte aligned."""
+    from m4depth_amd._lib import lib
+    for b in (1, 2, 7, 64):
+        for C in (16, 32):
+            n = lib.m4d_dinl_workspace_floats(b, C)
+            assert n >= b * 512 * C * 2 + 2 * b * C, (b, C, n)
+        assert lib.m4d_dinl_workspace_floats(b, 16) >= b * 256 * 32 * 2 + 2 * b * 16
+    fake, odd = ctypes.c_void_p(4096), ctypes.c_void_p(4100)      # never dereferenced: validation fails first
+    assert lib.m4d_enc_level0_stats(fake, 1, 0, 0, fake, fake, 1, 4, 4, odd, fake, fake, None) == 1
+
+
 def test_missing_library_is_loud(monkeypatch, tmp_path):
     import importlib
     from m4depth_amd import _lib
