@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define M4D_ABI_VERSION 6   /* 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
+#define M4D_ABI_VERSION 6   /* 6: + m4d_depth_metrics_per_sample, m4d_metrics_per_sample_workspace_bytes (per-sample metrics of batched streaming evaluation; additive within ABI 6); 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
 
 /* Library / device introspection (no GPU work). */
 int m4d_abi_version(void);
@@ -587,6 +587,16 @@ int m4d_depth_metrics(const float* gt, const float* est, long long n, float max_
 int m4d_depth_metrics_strided(const float* gt, long long per_image, long long gt_image_stride, const float* est,
                               long long n, float max_d, void* workspace, float* out7, float* total7, float count,
                               float* mean7, void* stream);
+/* The same 7 metrics for each sample of a batch on its own (batched streaming evaluation, main.py --eval_streams): gt, est are
+ * [b][per_image] floats, sample s at gt + s * gt_stride / est + s * est_stride (strides >= per_image).  rows [b][7] floats:
+ * row s is bit for bit what m4d_depth_metrics(gt_s, est_s, per_image, ...) writes to out7 (the same block partition, one
+ * finalize workgroup per sample, the same fixed summation order; no atomics).  new_traj, active: uint8 [b] device masks;
+ * counted [b] uint8 = active[s] && !new_traj[s] (read by the kernel only).  workspace:
+ * m4d_metrics_per_sample_workspace_bytes(b) bytes (b x 512 x 9 doubles).  Additive entry point: ABI 6 unchanged. */
+long long m4d_metrics_per_sample_workspace_bytes(int b);
+int m4d_depth_metrics_per_sample(const float* gt, long long gt_stride, const float* est, long long est_stride, int b,
+                                 long long per_image, float max_d, const unsigned char* new_traj, const unsigned char* active,
+                                 void* workspace, float* rows, unsigned char* counted, void* stream);
 
 /* ---- training without MIOpen (train_step, m4depth_network.py:371-399: tf.GradientTape through every Conv2D) ---------- */
 

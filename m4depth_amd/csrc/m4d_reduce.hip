@@ -261,6 +261,86 @@ metrics_finalize_kernel(const double* __restrict__ partial, int nblk, float* __r
   }
 }
 
+// ---- the same metrics per sample of a batch (batched streaming evaluation) -----------------------------------------
+// Sample s = blockIdx.y is scored alone, with the block partition and per-thread element order m4d_depth_metrics uses for
+// one image of n floats (gridDim.x = min(ceil(n / 256), kMetricBlocks)): its float partials, their double combine and the
+// finalize below are those of metrics_partial_kernel / metrics_finalize_kernel, so row s is the same bits as a call on
+// image s by itself.  Partials: [b][gridDim.x][kMetricSums] doubles.
+__global__ void __launch_bounds__(256)
+metrics_partial_ps_kernel(const float* __restrict__ gt_raw, long long gt_stride, const float* __restrict__ est_raw,
+                          long long est_stride, long long n, float max_d, double* __restrict__ partial) {
+  const float* gt_img = gt_raw + (long long)blockIdx.y * gt_stride;
+  const float* est_img = est_raw + (long long)blockIdx.y * est_stride;
+  float s[kMetricSums];
+#pragma unroll
+  for (int k = 0; k < kMetricSums; ++k) s[k] = 0.f;
+  const long long step = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+    const float gt = fminf(fmaxf(gt_img[i], 0.0f), max_d);
+    const float est = fminf(fmaxf(est_img[i], 0.001f), max_d);
+    const bool m = gt > 1e-6f;
+    const float diff = gt - est;
+    const float lg = logf(gt + 1e-6f), le = logf(est + 1e-6f);
+    const bool m2 = lg > 1e-6f;
+    const float th = fmaxf(gt / est, est / gt);
+    if (m) {
+      s[0] += 1.0f;
+      s[1] += fabsf(diff) / (gt + 1e-6f);
+      s[2] += diff * diff / (gt + 1e-6f);
+      s[3] += diff * diff;
+      s[6] += th < 1.25f ? 1.0f : 0.0f;
+      s[7] += th < 1.5625f ? 1.0f : 0.0f;
+      s[8] += th < 1.953125f ? 1.0f : 0.0f;
+    }
+    if (m2) { s[4] += 1.0f; s[5] += (lg - le) * (lg - le); }
+  }
+  __shared__ double sh[4][kMetricSums];
+#pragma unroll
+  for (int k = 0; k < kMetricSums; ++k) {
+    double v = (double)s[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kMetricSums)
+    partial[((long long)blockIdx.y * gridDim.x + blockIdx.x) * kMetricSums + threadIdx.x] =
+        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+// one workgroup per sample: the fixed-order finalize of metrics_finalize_kernel into rows[s][7], and the counting flag
+// counted[s] = active[s] && !new_traj[s] (the masks are read here, never by the host)
+__global__ void __launch_bounds__(kMetricSums * 32)
+metrics_finalize_ps_kernel(const double* __restrict__ partial, int nblk, const unsigned char* __restrict__ new_traj,
+                           const unsigned char* __restrict__ active, float* __restrict__ rows, unsigned char* __restrict__ counted) {
+  __shared__ double sub[kMetricSums * 32];
+  __shared__ double tot[kMetricSums];
+  const int smp = blockIdx.x;
+  const double* pp = partial + (long long)smp * nblk * kMetricSums;
+  const int q = threadIdx.x % kMetricSums, j = threadIdx.x / kMetricSums;
+  double s = 0.0;
+  for (int k = j; k < nblk; k += 32) s += pp[(long long)k * kMetricSums + q];
+  sub[threadIdx.x] = s;
+  __syncthreads();
+  if (j == 0) {
+    for (int r = 1; r < 32; ++r) s += sub[r * kMetricSums + q];
+    tot[q] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double cnt = tot[0] > 1.0 ? tot[0] : 1.0, cnt2 = tot[4] > 1.0 ? tot[4] : 1.0;
+    float* out7 = rows + (long long)smp * 7;
+    out7[0] = (float)(tot[1] / cnt);
+    out7[1] = (float)(tot[2] / cnt);
+    out7[2] = sqrtf((float)(tot[3] / cnt));
+    out7[3] = sqrtf((float)(tot[5] / cnt2));
+    out7[4] = (float)(tot[6] / cnt);
+    out7[5] = (float)(tot[7] / cnt);
+    out7[6] = (float)(tot[8] / cnt);
+    counted[smp] = (active[smp] != 0 && new_traj[smp] == 0) ? 1 : 0;
+  }
+}
+
 
 // ---- encoder level 0 WITHOUT its [b,H,W,16] intermediate (m4d_enc_level0_fwd) ------------------------------------------
 // The head of the network (m4depth_network.py:79-87 with DINL) is conv3x3(RGB, 3 -> 16) -> DomainNormalization ->
@@ -765,4 +845,24 @@ extern "C" int m4d_depth_metrics_strided(const float* gt, long long per_image, l
 extern "C" int m4d_depth_metrics(const float* gt, const float* est, long long n, float max_d, void* workspace,
                                  float* out7, float* total7, float count, float* mean7, void* stream) {
   return m4d_depth_metrics_strided(gt, n, n, est, n, max_d, workspace, out7, total7, count, mean7, stream);
+}
+
+extern "C" long long m4d_metrics_per_sample_workspace_bytes(int b) {
+  return b > 0 ? (long long)b * kMetricBlocks * kMetricSums * sizeof(double) : 0;
+}
+
+extern "C" int m4d_depth_metrics_per_sample(const float* gt, long long gt_stride, const float* est, long long est_stride,
+                                            int b, long long per_image, float max_d, const unsigned char* new_traj,
+                                            const unsigned char* active, void* workspace, float* rows, unsigned char* counted,
+                                            void* stream) {
+  M4D_CHECK_ARG(gt && est && new_traj && active && workspace && rows && counted);
+  M4D_CHECK_ARG(b > 0 && b <= 65535 && per_image > 0 && gt_stride >= per_image && est_stride >= per_image);
+  hipStream_t s = (hipStream_t)stream;
+  long long g = (per_image + 255) / 256;
+  const int nblk = (int)(g < kMetricBlocks ? g : kMetricBlocks);              // the partition of m4d_depth_metrics(n = per_image)
+  m4d_launch(metrics_partial_ps_kernel, dim3(nblk, b), dim3(256), 0, s, gt, gt_stride, est, est_stride, per_image, max_d,
+             (double*)workspace);
+  m4d_launch(metrics_finalize_ps_kernel, dim3(b), dim3(kMetricSums * 32), 0, s, (const double*)workspace, nblk, new_traj, active,
+             rows, counted);
+  return M4D_LAUNCH_RESULT();
 }

@@ -16,7 +16,8 @@ hardware suggests:
 Batches come out as the dict ``M4Depth.train_step / test_step`` take: RGB_im [b,T,H,W,3],
 depth [b,T,H,W,1], rot [b,T,4], trans [b,T,3] on the device, new_traj [b,T] (host bool tensor: it steers
 control flow), camera {f [b,2], c [b,2]}.  Streaming evaluation (db_seq_len None) yields single
-frames without the T axis, batch 1, like the reference.
+frames without the T axis, batch 1, like the reference; the ``eval_streams`` use case (``SlotDataset``) yields B frames of
+B whole trajectories per step, with per-sample poses, intrinsics and device masks.
 """
 from __future__ import annotations
 
@@ -105,6 +106,77 @@ class SequenceDataset:
             yield loader._assemble(raws, rows)
 
 
+class SlotDataset:
+    """Streaming evaluation with B parallel slots: one item per step of the ``stream_eval.schedule`` table, a dict
+        RGB_im [B,H,W,3], depth [B,H,W,1], rot [B,4], trans [B,3], camera {f, c} [B,2] -- per sample (KITTI has per-frame
+                   intrinsics) -- on the device;
+        reset    uint8 [B] device: the slot restarts its state (the frame's own new_traj, the forced reset of the first frame
+                   of an assignment, an idle slot) -- the ``new_traj`` input of ``M4Depth.stream_step``;
+        new_traj uint8 [B] device: the frame's own new_traj (csv id == 0; set for an idle slot) -- it decides, with
+        active   uint8 [B] device: the slot holds a frame of the schedule, whether the frame is counted;
+        cells    the host int64 [B,2] (trajectory, frame) row of the schedule (-1 for an idle slot).
+    The host decompresses the active frames of a step in a pool of min(B, 8) threads (PIL releases the GIL), in the prefetch
+    thread; the device decodes them with the per-modality kernels.  An idle slot (the tail of the schedule) is fed its last
+    frame again, taken from the previous step's device tensors: nothing is read or decoded for it."""
+
+    def __init__(self, loader, trajectories, sched, prefetch=2):
+        self.loader, self.trajectories, self.schedule, self.prefetch = loader, trajectories, sched, prefetch
+        self.n = int(sched.cells.shape[0])
+        self.n_slots = int(sched.n_slots)
+
+    def cardinality(self):
+        return self.n
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        loader, sched, trajs = self.loader, self.schedule, self.trajectories
+        B = self.n_slots
+
+        def producer():
+            with ThreadPoolExecutor(max_workers=max(1, min(B, 8))) as pool:
+                for step in range(self.n):
+                    live = [s for s in range(B) if sched.cells[step, s, 0] >= 0]
+                    rows = [trajs[sched.feed[step, s, 0]][sched.feed[step, s, 1]] for s in range(B)]
+                    raws = list(pool.map(lambda s: loader._load_raw(rows[s]), live))
+                    yield step, live, raws, rows
+
+        prev = None
+        for step, live, raws, rows in _Prefetcher(producer, self.prefetch):
+            prev = self._assemble(step, live, raws, rows, prev)
+            yield prev
+
+    def _assemble(self, step, live, raws, rows, prev):
+        loader, sched = self.loader, self.schedule
+        B, dev = self.n_slots, loader.device
+        if len(live) == B:
+            rgb, depth = loader._decode_device(raws)
+        else:                                                     # idle slots: the previous step's frame of the slot
+            rgb_l, depth_l = loader._decode_device(raws)
+            rgb = prev["RGB_im"].clone()
+            depth = prev["depth"].clone() if depth_l is not None else None
+            idx = torch.tensor(live, dtype=torch.long, device=dev)
+            rgb[idx] = rgb_l
+            if depth is not None:
+                depth[idx] = depth_l
+        pose = np.array([[r['qw'], r['qx'], r['qy'], r['qz'], r['tx'], r['ty'], r['tz']] for r in rows], np.float32)
+        cam = [loader._camera(r) for r in rows]
+        f = np.array([c[0] for c in cam], np.float32)
+        c = np.array([c[1] for c in cam], np.float32)
+        active = sched.cells[step, :, 0] >= 0
+        own = np.array([r['id'] == 0 for r in rows]) | ~active
+        masks = np.stack([sched.reset[step] | own, own, active]).astype(np.uint8)
+        masks_d = loader._to_device(masks)
+        out = {"RGB_im": rgb, "rot": loader._to_device(pose[:, :4]), "trans": loader._to_device(pose[:, 4:]),
+               "camera": {"f": loader._to_device(f), "c": loader._to_device(c)},
+               "reset": masks_d[0], "new_traj": masks_d[1], "active": masks_d[2], "cells": sched.cells[step].copy()}
+        if depth is not None:
+            out["depth"] = depth
+        return out
+
+
 class DataLoaderGeneric():
     """Superclass for other dataset dataloaders (dataloaders/generic.py:10-259)."""
 
@@ -114,7 +186,8 @@ class DataLoaderGeneric():
         self.build_functions = {"train": self._build_train_dataset,
                                 "finetune": self._build_train_dataset,
                                 "eval": self._build_eval_dataset,
-                                "predict": self._build_eval_dataset}
+                                "predict": self._build_eval_dataset,
+                                "eval_streams": self._build_slot_eval_dataset}
         self.augment = None
         self.settings = None
         self.db_name = dataset_name
@@ -256,7 +329,7 @@ class DataLoaderGeneric():
 
     # -- dataset construction ---------------------------------------------------------------
     def get_dataset(self, usecase, settings, batch_size=3, out_size=None, device=None, seed=42, prefetch=2,
-                    shard=(0, 1)):
+                    shard=(0, 1), slot_policy="lpt"):
         ''' Builds the dataset (dataloaders/generic.py:50-82).
             * usecase : train, finetune, eval or predict
             * settings: DataloaderParameters (db_path_config, records_path, db_seq_len, seq_len, augment)
@@ -264,7 +337,9 @@ class DataLoaderGeneric():
                         a global batch is ``world`` consecutive per-rank batches of the (identically seeded, identically
                         shuffled) chunk list and rank r reads, decompresses and decodes only its own slice.  Every rank
                         gets the same number of batches (the remainder that does not fill a global batch is dropped,
-                        like ``batch(drop_remainder=True)``), so per-step collectives never deadlock. '''
+                        like ``batch(drop_remainder=True)``), so per-step collectives never deadlock.
+            * usecase "eval_streams": streaming evaluation with whole trajectories dealt into ``batch_size`` parallel slots
+                        (``SlotDataset``; ``slot_policy`` "lpt" or "arrival", see stream_eval.schedule). '''
         if out_size is None:
             self._set_output_size()
         else:
@@ -288,6 +363,7 @@ class DataLoaderGeneric():
         self.plan_rng = np.random.default_rng(plan_seq)
         self.rng = np.random.default_rng(aug_seq.spawn(self.shard_world)[self.shard_rank])
         self.prefetch = prefetch
+        self.slot_policy = slot_policy
         self.streaming = False
         if usecase == "train" and (self.db_seq_len is None or self.seq_len is None):
             raise Exception('db_seq_len and seq_len must be defined in train mode')
@@ -355,6 +431,18 @@ class DataLoaderGeneric():
             for row in frames:
                 yield [[row]]
         return SequenceDataset(self, plan, len(frames), self.prefetch)
+
+    def _build_slot_eval_dataset(self):
+        """Streaming evaluation, B trajectories at a time (main.py --eval_streams B): see ``SlotDataset``."""
+        self.augment = False
+        if self.db_seq_len is not None:
+            raise ValueError("slot streaming evaluation runs whole trajectories: db_seq_len must be None")
+        if self.shard_world > 1:
+            raise ValueError("streaming evaluation (db_seq_len None) is sequential: it cannot be sharded")
+        from ..stream_eval import schedule
+        trajectories = self._get_trajectories()
+        sched = schedule([len(t) for t in trajectories], self.batch_size, self.slot_policy)
+        return SlotDataset(self, trajectories, sched, self.prefetch)
 
     # -- augmentation (device tensors; one random draw per sequence, as in the reference) --------
     def _uniform(self, lo, hi):

@@ -27,7 +27,7 @@ class DataLoaderKittiRaw(DataLoaderGeneric):
                 (float(f32(row['cx'] * self.out_size[1])), float(f32(row['cy'] * self.out_size[0]))))
 
     def _depth_crop(self):
-        return self.eval_crop if self.usecase == "eval" else None          # kitti.py:48-50
+        return self.eval_crop if self.usecase in ("eval", "eval_streams") else None          # kitti.py:48-50
 
     def _perform_augmentation(self):
         self._augmentation_step_color(invert_color=False)

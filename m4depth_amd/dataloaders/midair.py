@@ -30,7 +30,7 @@ class DataLoaderMidAir(DataLoaderGeneric):
 
     def get_dataset(self, usecase, settings, batch_size=3, out_size=[384, 384], crop=False, **kw):
         self.crop = crop
-        if (usecase == "eval" or usecase == "predict") and self.crop:
+        if usecase in ("eval", "eval_streams", "predict") and self.crop:
             raise AttributeError("Crop option should be disabled when evaluating or predicting samples")
         return super(DataLoaderMidAir, self).get_dataset(usecase, settings, batch_size=batch_size, out_size=out_size, **kw)
 

@@ -11,6 +11,8 @@ Flag names follow ``m4depth_options.py`` where the flag exists there.  Like the
 reference it writes the 7 metrics with ``%.18e`` (one per line, as np.savetxt does for the 1-D list) to
 ``<ckpt_dir>/perfs-<dataset>.txt`` (main.py:144-148).  With several ranks the batch
 is sharded (m4depth_amd.dist) and the metric accumulators are all-gathered over RCCL.
+``--eval_streams B`` runs a dataset's streaming evaluation (no ``--db_seq_len``) with B whole trajectories side by side
+(m4depth_amd.stream_eval) and writes the same perfs file as the one-frame-at-a-time loop.
 """
 from __future__ import annotations
 
@@ -52,6 +54,13 @@ def build_parser():
     p.add_argument("--stream", action="store_true",
                    help="predict: run the frames as B independent streams with per-sample trajectory resets (M4Depth.stream_step; "
                         "with --graph replayed from network.GraphedStream)")
+    p.add_argument("--eval_streams", type=int, default=0, metavar="N",
+                   help="eval / validation on a dataset's whole trajectories (no --db_seq_len): run N trajectories side by side "
+                        "as the samples of M4Depth.stream_step (with --graph replayed from network.GraphedStream), score each "
+                        "sample on the device and fold the scores in the sequential run's order -- the same perfs file as the "
+                        "one-frame-at-a-time loop.  0 = that loop")
+    p.add_argument("--eval_streams_policy", default="lpt", choices=["lpt", "arrival"],
+                   help="--eval_streams: the order trajectories are dealt to free slots (lpt = longest first, arrival = csv order)")
     p.add_argument("--host_input", action="store_true",
                    help="synthetic eval: hand every batch over from pinned HOST memory (the PCIe copy is part of the step) and "
                         "print the frames/s of the loop -- the PCIe-inclusive rate, next to bench.py's HBM-resident one")
@@ -106,6 +115,10 @@ def dataset_batches(args, usecase, rank, world, dev):
                  for k, v in json.load(fh).items() if not k.startswith("_")}    # m4depth_options.py:88-94
     loader = dl.get_loader(args.dataset)
     settings = dl.DataloaderParameters(roots, args.records_path, args.db_seq_len, args.seq_len, not args.no_augmentation)
+    if usecase == "eval_streams":
+        kw = {"out_size": [args.height, args.width]} if args.height and args.width else {}
+        return loader.get_dataset(usecase, settings, batch_size=args.eval_streams, device=dev, seed=args.seed,
+                                  slot_policy=args.eval_streams_policy, **kw), loader.depth_type
     streaming = usecase in ("eval", "predict") and args.db_seq_len is None
     if streaming and world > 1:
         raise SystemExit("streaming evaluation (no --db_seq_len) is sequential: run it on one rank")
@@ -205,12 +218,69 @@ def _stream_frame(frame, dev):
     return out
 
 
+def _check_eval_streams(parser, args):
+    if args.eval_streams < 0:
+        parser.error("--eval_streams must be >= 0")
+    if not args.eval_streams:
+        return
+    if args.mode not in ("eval", "validation"):
+        parser.error("--eval_streams is a --mode=eval / --mode=validation option")
+    if args.dataset == "synthetic":
+        parser.error("--eval_streams runs the trajectories of a real dataset (--dataset midair | tartanair | kitti-raw)")
+    if args.db_seq_len is not None:
+        parser.error("--eval_streams evaluates whole trajectories: it excludes --db_seq_len")
+
+
+def eval_streams(args, model, dev):
+    """Streaming evaluation with ``--eval_streams`` B slots (m4depth_amd.stream_eval): per step one ``stream_step`` (or a
+    ``GraphedStream`` replay) and one per-sample metric launch into a preallocated [n_steps,B,7] / [n_steps,B] device log; no
+    host read of any mask.  After the last step: one copy of the log to the host, the fold in the sequential order, and the
+    folded (total, count) loaded into the compiled metrics for the writer."""
+    import time
+    from . import network_ops as nops
+    from . import stream_eval as SE
+    ds, _ = dataset_batches(args, "eval_streams", 0, 1, dev)
+    sched = ds.schedule
+    n_steps, B = sched.cells.shape[:2]
+    rows = torch.empty((n_steps, B, 7), dtype=torch.float32, device=dev)
+    counted = torch.empty((n_steps, B), dtype=torch.uint8, device=dev)
+    active = (sched.cells[..., 0] >= 0).sum(axis=1)                # the schedule's, known on the host without a device read
+    runner, t0 = None, None
+    for step, batch in enumerate(ds):
+        if step == 1:                                              # the first step is the warm-up (allocations, graph capture)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        frame = {"RGB_im": batch["RGB_im"], "rot": batch["rot"], "trans": batch["trans"], "new_traj": batch["reset"],
+                 "camera": batch["camera"]}
+        if args.graph:
+            if runner is None:
+                from .network import GraphedStream
+                runner = GraphedStream(model, frame)
+            est = runner(frame)["depth"]
+        else:
+            est = model.stream_step(frame)["depth"]
+        nops.depth_metrics_per_sample(batch["depth"], est, batch["new_traj"], batch["active"], 80., rows=rows[step],
+                                      counted=counted[step])
+    rows_h, counted_h = rows.cpu().numpy(), counted.cpu().numpy()
+    if t0 is not None:
+        dt = time.perf_counter() - t0
+        n = int(active[1:].sum())
+        print(f"eval_streams {B} slots ({args.eval_streams_policy}, {'graph' if args.graph else 'eager'}): {n / dt:.1f} "
+              f"sample-frames/s over {n} active sample-frames of {n_steps - 1} steps (the first step excluded)")
+    total, count = SE.fold(rows_h, counted_h, sched.cells)
+    for i, m in enumerate(model.compiled_metrics):
+        m.load_state(torch.tensor(total[i], dtype=torch.float32, device=dev), count)
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.stream and args.mode != "predict":
         parser.error("--stream is a --mode=predict option")
+    _check_eval_streams(parser, args)
     rank, world, _, dev = D.init_from_env()
+    if args.eval_streams and world > 1:
+        raise SystemExit("streaming evaluation (--eval_streams) is sequential over the trajectories: run it on one rank")
     if dev.type != "cuda":
         raise SystemExit("m4depth_amd.main needs a GPU: the hot path has no CPU fallback")
     ablation = ablation_from_args(args)
@@ -222,7 +292,10 @@ def main(argv=None):
     runner = None
     preds = []
     host_input = args.host_input and args.dataset == "synthetic" and args.mode != "predict"
-    if args.dataset == "synthetic":
+    if args.eval_streams:
+        eval_streams(args, model, dev)
+        batches = ()
+    elif args.dataset == "synthetic":
         batches = synthetic_batches(args, rank, world, dev, on_host=host_input)
         if host_input:
             batches = list(batches)                # generation is not part of the measured loop

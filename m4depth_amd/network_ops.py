@@ -259,6 +259,46 @@ def depth_metrics(gt, est, max_d=80.0, total=None, count=0, mean=None):
     return out
 
 
+def _batch_stride(t, name):
+    """Batch stride of a [b, ...] float32 device tensor whose images are dense (t[0] contiguous) -- a slice such as
+    ``depth[:, -1]`` of a sequence batch is read in place."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected a float32 device tensor")
+    if t.dim() < 2 or not t[0].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < t[0].numel()):
+        raise ValueError(f"{name}: expected [b, ...] with dense images at a batch stride, got strides {t.stride()}")
+    return t.stride(0) if t.shape[0] > 1 else t[0].numel()
+
+
+def depth_metrics_per_sample(gt, est, new_traj, active, max_d=80.0, rows=None, counted=None):
+    """The 7 metrics of ``depth_metrics`` for every sample of a batch on its own, in one launch pair: returns (rows [b,7] float32,
+    counted [b] uint8), device tensors; row s is bit for bit ``depth_metrics(gt[s:s+1], est[s:s+1])``.  ``counted[s]`` =
+    active[s] and not new_traj[s], computed on the device (uint8 [b] masks, never read by the host); nothing synchronises.
+    ``rows`` / ``counted`` may be views into a preallocated log (one step's row of an [n_steps,b,7] / [n_steps,b] tensor)."""
+    b = est.shape[0]
+    per_image = est[0].numel()
+    if gt.shape[0] != b or gt[0].numel() != per_image:
+        raise ValueError(f"gt {tuple(gt.shape)} and est {tuple(est.shape)} differ in size")
+    for name, m in (("new_traj", new_traj), ("active", active)):
+        if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != (b,):
+            raise ValueError(f"{name}: expected a uint8 / bool [{b}] device tensor")
+    new_traj = new_traj.view(torch.uint8) if new_traj.dtype == torch.bool else new_traj
+    active = active.view(torch.uint8) if active.dtype == torch.bool else active
+    gs, es = _batch_stride(gt, "gt"), _batch_stride(est, "est")
+    if rows is None:
+        rows = torch.empty((b, 7), dtype=torch.float32, device=est.device)
+    if counted is None:
+        counted = torch.empty(b, dtype=torch.uint8, device=est.device)
+    if tuple(rows.shape) != (b, 7) or tuple(counted.shape) != (b,):
+        raise ValueError(f"rows must be [{b},7] and counted [{b}], got {tuple(rows.shape)} and {tuple(counted.shape)}")
+    ws = _workspace("metrics_ps", int(lib.m4d_metrics_per_sample_workspace_bytes(b)), est.device)
+    check(lib.m4d_depth_metrics_per_sample(ctypes.c_void_p(gt.data_ptr()), gs, ctypes.c_void_p(est.data_ptr()), es, b, per_image,
+                                           float(max_d), dptr(new_traj, "new_traj", torch.uint8),
+                                           dptr(active, "active", torch.uint8), dptr(ws), dptr(rows, "rows"),
+                                           dptr(counted, "counted", torch.uint8), stream_ptr()),
+          "m4d_depth_metrics_per_sample")
+    return rows, counted
+
+
 def pack_conv_weights(kernel_hwio):
     """Re-pack a TF HWIO [3,3,Cin,Cout] kernel for m4d_conv3x3_bias_act:
     [ceil(Cin/16)][9][CoutPad][16], CoutPad = Cout rounded up to 32, the 16 input channels of a
