@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define M4D_ABI_VERSION 6   /* 6: + m4d_depth_metrics_per_sample, m4d_metrics_per_sample_workspace_bytes (per-sample metrics of batched streaming evaluation; additive within ABI 6); 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
+#define M4D_ABI_VERSION 6   /* 6: + m4d_train_log_step, m4d_train_log_workspace_bytes (device-side step log of the replayed training step; additive within ABI 6); 6: + m4d_depth_metrics_per_sample, m4d_metrics_per_sample_workspace_bytes (per-sample metrics of batched streaming evaluation; additive within ABI 6); 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
 
 /* Library / device introspection (no GPU work). */
 int m4d_abi_version(void);
@@ -324,6 +324,18 @@ int m4d_loss_level_fwd(const float* pred_depth, const float* gt_depth, int b, in
 int m4d_loss_level_bwd(const float* pred_depth, const float* gt_depth, const float* stats2,
                        const float* g_out, int b, int h, int w, int H, int W, int velodyne,
                        float* g_pred, void* stream);
+
+/* Step log of a (graph-replayed) training step, train_step's metric update (m4depth_network.py:418-427) without a host read:
+ * RMSE_log of the last frame = sqrt(masked mean of (log(gt+1e-6) - log(est+1e-6))^2), mask log(gt+1e-6) > 1e-6, with gt
+ * [b][H][W] (image stride gt_stride floats: a frame slice of the [b,T,H,W,1] batch) clamped to [0, 80] and est, the finest
+ * estimate [b,h,w,1], resized to HxW by m4d_resize_nearest's index rule (inline) and clamped to [0.001, 80] (metrics.py:24-28).
+ * Writes [*loss, rmse_log] to log[(*counter % log_rows) * 2 ..], then *counter += 1; sets *first_bad = the pre-increment
+ * counter of the first non-finite loss (sticky: only while *first_bad < 0).  Block partials in double, fixed-order finish: the
+ * same bits every run.  workspace: m4d_train_log_workspace_bytes() bytes. */
+long long m4d_train_log_workspace_bytes(void);
+int m4d_train_log_step(const float* loss, const float* gt, long long gt_stride, const float* est, int b, int H, int W,
+                       int h, int w, float* log, int log_rows, long long* counter, long long* first_bad,
+                       void* workspace, void* stream);
 
 /* ---- m4depth_network.py: DepthEstimatorLevel glue -------------------------------- */
 

@@ -307,6 +307,73 @@ loss_level_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ 
   }
 }
 
+
+// ---- the step log of a replayed training step (train_step's RMSE_log + the loss, m4depth_network.py:418-427) ----------
+// Pass 1: block partials of the masked squared log error of the last frame, the estimate resized by nearest neighbour with
+// the index rule of resize_nearest_kernel (inline, never materialised).  Per-thread sums in double, one wave64 shuffle tree
+// and a fixed combine of the 4 waves: the same bits every run.  partial[blk] = (sum, count).
+constexpr int kLogBlocks = 512;
+
+// torch.clamp: NaN stays NaN (then fails the mask on the log, as in metrics.masked_reduce_mean)
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+
+__global__ void __launch_bounds__(256)
+train_log_partial_kernel(const float* __restrict__ gt, long long gt_stride, const float* __restrict__ est, int H, int W,
+                         int h, int w, long long n, double* __restrict__ partial) {
+  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+  double s = 0.0, c = 0.0;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
+    const int ox = (int)(p % W);
+    const long long r = p / W;
+    const int oy = (int)(r % H);
+    const long long bi = r / H;
+    const int iy = min((int)floorf(((float)oy + 0.5f) * sy), h - 1);
+    const int ix = min((int)floorf(((float)ox + 0.5f) * sx), w - 1);
+    const float g = clamp_nan(gt[bi * gt_stride + (long long)oy * W + ox], 0.0f, 80.0f);
+    const float e = clamp_nan(est[(bi * h + iy) * w + ix], 0.001f, 80.0f);
+    const float lg = logf(g + 1e-6f), le = logf(e + 1e-6f);
+    if (lg > 1e-6f) {
+      const float d = lg - le;
+      s += (double)(d * d);
+      c += 1.0;
+    }
+  }
+  __shared__ double sh[2][4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); c += __shfl_down(c, o); }
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = c; }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    partial[2 * blockIdx.x + threadIdx.x] = ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
+}
+
+// Pass 2, one workgroup: lane t sums partials t, t + 256, ... in index order, then a fixed halving tree; lane 0 writes
+// [loss, sqrt(mean)] into row counter % log_rows, raises the counter and, on the first non-finite loss, latches first_bad.
+__global__ void __launch_bounds__(256)
+train_log_finish_kernel(const double* __restrict__ partial, int nblk, const float* __restrict__ loss, float* __restrict__ log,
+                        int log_rows, long long* __restrict__ counter, long long* __restrict__ first_bad) {
+  __shared__ double ss[256], sc[256];
+  double s = 0.0, c = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 256) { s += partial[2 * k]; c += partial[2 * k + 1]; }
+  ss[threadIdx.x] = s; sc[threadIdx.x] = c;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) { ss[threadIdx.x] += ss[threadIdx.x + off]; sc[threadIdx.x] += sc[threadIdx.x + off]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float mean = (float)(ss[0] / (sc[0] > 1.0 ? sc[0] : 1.0));
+    const float l = loss[0];
+    const long long step = counter[0];
+    long long row = step % log_rows;
+    if (row < 0) row += log_rows;
+    log[2 * row] = l;
+    log[2 * row + 1] = sqrtf(mean);
+    if (!isfinite(l) && first_bad[0] < 0) first_bad[0] = step;
+    counter[0] = step + 1;
+  }
+}
+
 }  // namespace
 
 extern "C" int m4d_resize_bilinear_v1_bwd(const float* g_out, int b, int ih, int iw, int c, int oh, int ow,
@@ -412,5 +479,22 @@ extern "C" int m4d_loss_level_bwd(const float* pred_depth, const float* gt_depth
   const long long total = (long long)b * h * w;
   m4d_launch(loss_level_bwd_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream, pred_depth, gt_depth,
                      stats2, g_out, b, h, w, H, W, velodyne, g_pred);
+  return M4D_LAUNCH_RESULT();
+}
+
+extern "C" long long m4d_train_log_workspace_bytes(void) { return 2LL * kLogBlocks * (long long)sizeof(double); }
+
+extern "C" int m4d_train_log_step(const float* loss, const float* gt, long long gt_stride, const float* est, int b, int H, int W,
+                                  int h, int w, float* log, int log_rows, long long* counter, long long* first_bad,
+                                  void* workspace, void* stream) {
+  M4D_CHECK_ARG(loss && gt && est && log && counter && first_bad && workspace);
+  M4D_CHECK_ARG(b > 0 && H > 0 && W > 0 && h > 0 && w > 0 && log_rows > 0 && gt_stride >= (long long)H * W);
+  const long long n = (long long)b * H * W;
+  long long g = (n + 255) / 256;
+  const int nblk = (int)(g < kLogBlocks ? g : kLogBlocks);
+  hipStream_t s = (hipStream_t)stream;
+  m4d_launch(train_log_partial_kernel, dim3(nblk), dim3(256), 0, s, gt, gt_stride, est, H, W, h, w, n, (double*)workspace);
+  m4d_launch(train_log_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, nblk, loss, log, log_rows, counter,
+             first_bad);
   return M4D_LAUNCH_RESULT();
 }

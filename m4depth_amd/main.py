@@ -23,6 +23,7 @@ import sys
 import numpy as np
 import torch
 
+from . import checkpoints as CK
 from . import dist as D
 from . import synthetic as S
 from .metrics import default_metrics
@@ -66,6 +67,19 @@ def build_parser():
                         "print the frames/s of the loop -- the PCIe-inclusive rate, next to bench.py's HBM-resident one")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--save_every", type=int, default=0, help="train: checkpoint every N steps (0 = at the end)")
+    p.add_argument("--summary_interval", type=int, default=1200,
+                   help="train --graph: read the device-side step log every N steps (m4depth_options.py:47-49); it is also "
+                        "read at every epoch end and before every checkpoint")
+    p.add_argument("--max_keep", type=int, default=0,
+                   help="train: keep only the newest N checkpoints of <ckpt_dir>/train (0 = keep all)")
+    p.add_argument("--enable_validation", action="store_true",
+                   help="train: checkpoint at every epoch end and validate that checkpoint in-process (--mode=validation on "
+                        "--val_dataset / --val_records_path, seq_len 4 / db_seq_len 4), keeping the best-N in <ckpt_dir>/best")
+    p.add_argument("--val_records_path", default=None, help="--enable_validation: trajectory csv files of the validation set")
+    p.add_argument("--val_dataset", default="kitti-raw", choices=["midair", "tartanair", "kitti-raw"],
+                   help="--enable_validation: the validation set's dataset")
+    p.add_argument("--keep_top_n", type=int, default=1,
+                   help="validation: how many best checkpoints <ckpt_dir>/best keeps (callbacks.py:173-240)")
     # ablation flags, spelled as in m4depth_options.py:67-84
     for flag in ("DINL", "SNCV", "time_recurr", "feature_normalization", "feature_subdivision", "level_memory"):
         p.add_argument(f"--no_{flag}", action="store_true")
@@ -100,19 +114,24 @@ def _upload(data, dev):
     return out
 
 
+def dataset_roots(db_path_config):
+    """{dataset: root directory} of the json file (relative roots are relative to the file), m4depth_options.py:88-94."""
+    import json
+    cfg_dir = os.path.dirname(os.path.abspath(db_path_config))
+    with open(db_path_config) as fh:
+        return {k: (v if os.path.isabs(v) else os.path.normpath(os.path.join(cfg_dir, v)))
+                for k, v in json.load(fh).items() if not k.startswith("_")}
+
+
 def dataset_batches(args, usecase, rank, world, dev):
     """Batches of one of the reference's datasets (main.py:67,77,120,152).  Returns (iterable, depth_type).
     With several ranks the PER-RANK batch is batch_size / world; the loader shards the chunk list itself
     (``shard=(rank, world)``): every rank gets the same number of batches and reads / decodes only its own
     sequences.  Streaming evaluation is inherently sequential and stays single-rank."""
-    import json
     from . import dataloaders as dl
     if args.db_path_config is None or args.records_path is None:
         raise SystemExit("--dataset %s needs --db_path_config and --records_path" % args.dataset)
-    cfg_dir = os.path.dirname(os.path.abspath(args.db_path_config))
-    with open(args.db_path_config) as fh:
-        roots = {k: (v if os.path.isabs(v) else os.path.normpath(os.path.join(cfg_dir, v)))
-                 for k, v in json.load(fh).items() if not k.startswith("_")}    # m4depth_options.py:88-94
+    roots = dataset_roots(args.db_path_config)
     loader = dl.get_loader(args.dataset)
     settings = dl.DataloaderParameters(roots, args.records_path, args.db_seq_len, args.seq_len, not args.no_augmentation)
     if usecase == "eval_streams":
@@ -136,16 +155,18 @@ def _train_dir(args):
 def latest_checkpoint(args):
     """Newest ``ckpt-<step>.npz`` of <ckpt_dir>/train (the role of tf.train.latest_checkpoint,
     callbacks.py:84), or None."""
-    d = _train_dir(args)
-    if not os.path.isdir(d):
-        return None
-    steps = sorted(int(f[5:-4]) for f in os.listdir(d) if f.startswith("ckpt-") and f.endswith(".npz"))
-    return (os.path.join(d, f"ckpt-{steps[-1]}.npz"), steps[-1]) if steps else None
+    return CK.latest_checkpoint(_train_dir(args))
+
+
+def read_weights(path):
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files if not k.startswith("opt.")}
 
 
 def load_weights(args, ablation):
-    """Weights for eval / predict: the latest training checkpoint when there is one (callbacks.py:104-111),
-    otherwise the seeded random initialisation."""
+    """Weights for eval / predict: the checkpoint <ckpt_dir>/best/checkpoint names when the best-N manager made one
+    (main.py:116,156), else the latest training checkpoint when there is one (callbacks.py:104-111),
+    otherwise the seeded random initialisation.  Training and validation read <ckpt_dir>/train only."""
     if args.tf_checkpoint:
         from . import tf_checkpoint as TC
         prefix = TC.latest_checkpoint(args.tf_checkpoint) if os.path.isdir(args.tf_checkpoint) else args.tf_checkpoint
@@ -153,27 +174,80 @@ def load_weights(args, ablation):
             raise SystemExit("no TensorFlow checkpoint found in %s" % args.tf_checkpoint)
         print("Restoring weights from TensorFlow checkpoint %s" % prefix)
         return TC.load_m4depth_weights(prefix, args.arch_depth)
+    best = CK.best_checkpoint(args.ckpt_dir) if args.mode in ("eval", "predict") else None
+    if best is not None:
+        print("Restoring weights from %s" % best)
+        return read_weights(best)
     ck = latest_checkpoint(args)
     if ck is not None:
         print("Restoring weights from %s" % ck[0])
-        with np.load(ck[0]) as z:
-            return {k: z[k] for k in z.files if not k.startswith("opt.")}
+        return read_weights(ck[0])
     return S.init_weights(args.arch_depth, seed=42, ablation=ablation)
 
 
-def train(args, ablation, rank, world, dev):
+def _set_capturable(opt, flag, dev):
+    """Adam's ``capturable`` follows the launch mode, whichever mode wrote the optimizer state that was resumed: a captured
+    step needs its step counters on the device, an eager one on the host (load_state_dict restores the saved flag)."""
+    for g in opt.param_groups:
+        g["capturable"] = flag
+    for st in opt.state.values():
+        if "step" in st and torch.is_tensor(st["step"]):
+            st["step"] = st["step"].to(device=dev if flag else "cpu", dtype=torch.float32)
+
+
+def _geometry(data):
+    return ({k: tuple(data[k].shape) for k in ("depth", "RGB_im", "rot", "trans")},
+            {k: tuple(v.shape) for k, v in data["camera"].items()})
+
+
+def check_graph_batch(data, geometry=None):
+    """A replayed training step has fixed shapes and its trajectory resets baked in: every batch must have the captured
+    batch's geometry and ``new_traj`` set on frame 0 only.  Raises ValueError otherwise."""
+    nt = np.asarray(data["new_traj"].cpu() if torch.is_tensor(data["new_traj"]) else data["new_traj"], dtype=bool)
+    if nt.ndim != 2 or not nt[:, 0].all() or nt[:, 1:].any():
+        raise ValueError("--graph: every training sequence must start a trajectory on frame 0 and only there "
+                         f"(new_traj {nt.astype(int).tolist()}); the replayed step has its resets baked in")
+    if geometry is not None and _geometry(data) != geometry:
+        raise ValueError(f"--graph: a training batch of geometry {_geometry(data)} differs from the captured one {geometry}; "
+                         "the replayed step has fixed shapes")
+
+
+def default_epochs(args, rank, world, dev):
+    """(number of epochs, epoch -> iterable of batches) of ``--mode=train|finetune`` on ``--dataset``."""
+    if args.dataset == "synthetic":
+        return 1, lambda epoch: synthetic_batches(args, rank, world, dev)
+    return args.epochs, lambda epoch: dataset_batches(args, args.mode, rank, world, dev)[0]
+
+
+def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
     """main.py:73-109: Adam(1e-4), RMSE_log as the tracked metric, resume from the latest checkpoint.
     Several ranks = data parallel: the global batch is sharded and the gradients are averaged with
-    one RCCL all-reduce per step (dist.all_reduce_gradients)."""
+    one RCCL all-reduce per step (dist.all_reduce_gradients).
+
+    ``--graph``: the first batch runs the eager warm-up step of ``training.GraphedTrainStep`` (a real step: the same
+    trajectory as the eager loop), the step is captured once, and every later batch is copied into its static buffers and
+    replayed; each step ends with the device-side step log (``training.TrainStepLog``), read every ``--summary_interval``
+    steps, before a checkpoint and at every epoch end -- the host reads nothing per step.
+
+    TerminateOnNaN (callbacks.py:69-132): a non-finite loss ends training with status 1; nothing of that epoch is saved (in
+    graph mode the steps replayed after the bad one are discarded with it) and the checkpoints on disk stay as they are.
+
+    ``epochs`` = (count, epoch -> batches) (default: the dataset's, ``default_epochs``); ``depth_type`` defaults to the
+    dataset's."""
+    import time
     from . import training as TR
     from .metrics import RootMeanSquaredLogError
     torch.manual_seed(42)                                                       # tf.random.set_seed(42), main.py:76
-    depth_type = {"kitti-raw": "velodyne"}.get(args.dataset, "map")              # the loader's depth_type (main.py:79)
+    if depth_type is None:
+        depth_type = {"kitti-raw": "velodyne"}.get(args.dataset, "map")          # the loader's depth_type (main.py:79)
+    n_epochs, epoch_batches = epochs if epochs is not None else default_epochs(args, rank, world, dev)
     model = M4Depth(depth_type=depth_type, nbre_levels=args.arch_depth, ablation_settings=ablation, is_training=True)
     model.load_numpy_weights(load_weights(args, ablation), dev)
     TR.set_trainable(model)
-    opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, eps=1e-7)   # Keras Adam: epsilon 1e-7
-    model.compile(optimizer=opt, metrics=[RootMeanSquaredLogError()])
+    opt = torch.optim.Adam(model.parameters(), lr=args.learning_rate, eps=1e-7,   # Keras Adam: epsilon 1e-7
+                           capturable=args.graph)
+    rmse_log = RootMeanSquaredLogError()
+    model.compile(optimizer=opt, metrics=[rmse_log])
     ck = latest_checkpoint(args)
     step0 = 0
     if ck is not None:
@@ -181,33 +255,139 @@ def train(args, ablation, rank, world, dev):
         opt_path = ck[0][:-4] + ".opt.pt"
         if os.path.isfile(opt_path):
             opt.load_state_dict(torch.load(opt_path, map_location=dev))
+            _set_capturable(opt, args.graph, dev)
     sync = D.all_reduce_gradients if world > 1 else None
+    saved = set()
 
     def save(step):
-        if rank != 0:
-            return
+        if rank != 0 or step in saved:
+            return None
+        saved.add(step)
         os.makedirs(_train_dir(args), exist_ok=True)
         path = os.path.join(_train_dir(args), f"ckpt-{step}.npz")
         np.savez(path, **model.numpy_weights())
         torch.save(opt.state_dict(), path[:-4] + ".opt.pt")
         print("saved", path)
+        CK.prune_checkpoints(_train_dir(args), args.max_keep)
+        return path
 
-    step = step0
-    for epoch in range(args.epochs if args.dataset != "synthetic" else 1):
-        if args.dataset == "synthetic":
-            batches = synthetic_batches(args, rank, world, dev)
-        else:
-            batches, _ = dataset_batches(args, args.mode, rank, world, dev)
-        for data in batches:
-            out = model.train_step(data, grad_sync=sync)
-            step += 1
-            if rank == 0:
-                print(f"step {step}: loss {float(out['loss']):.6f}  RMSE_log {float(out['RMSE_log']):.6f}")
+    def report(step, loss, rmse):
+        if rank == 0:
+            print(f"step {step}: loss {loss:.6f}  RMSE_log {rmse:.6f}")
+
+    step_log = runner = geometry = None
+    logged = [step0]                                  # graph mode: the last step whose log row the host has read
+
+    def read_log():
+        """Graph mode: hands the unread log rows to the host (prints, the compiled RMSE_log Mean); returns the step of the first
+        non-finite loss or None."""
+        rows, first_bad = step_log.read()
+        for i, (loss, rmse) in enumerate(rows):
+            if first_bad >= 0 and i + logged[0] - step0 >= first_bad:
+                break                                 # the steps after the bad one are discarded
+            rmse_log._update(torch.tensor(rmse))
+            report(logged[0] + i + 1, float(loss), float(rmse_log.result()))
+        logged[0] += len(rows)
+        return step0 + first_bad + 1 if first_bad >= 0 else None
+
+    step, t0, n_timed, nan_step = step0, None, 0, None
+    for epoch in range(n_epochs):
+        for data in epoch_batches(epoch):
+            if args.graph:
+                check_graph_batch(data, geometry)
+                if runner is None:
+                    geometry = _geometry(data)
+                    step_log = TR.TrainStepLog(max(args.summary_interval, 1) + 1, dev)
+                    runner = TR.GraphedTrainStep(model, data, opt, warmup=1, grad_sync=sync, step_log=step_log)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                else:
+                    runner(data)
+                    n_timed += 1
+                step += 1
+                if (step - step0) % max(args.summary_interval, 1) == 0 or (args.save_every and step % args.save_every == 0):
+                    nan_step = read_log()
+            else:
+                out = model.train_step(data, grad_sync=sync)
+                step += 1
+                loss = float(out["loss"])
+                if t0 is None:
+                    t0 = time.perf_counter()
+                else:
+                    n_timed += 1
+                if not np.isfinite(loss):
+                    nan_step = step
+                else:
+                    report(step, loss, float(out["RMSE_log"]))
+            if nan_step is not None:
+                break
             if args.save_every and step % args.save_every == 0:
                 save(step)
+        if args.graph and nan_step is None and runner is not None:
+            nan_step = read_log()
+        if nan_step is not None:
+            print(f"step {nan_step}: non-finite loss, training stopped (TerminateOnNaN): nothing of epoch {epoch + 1} is saved")
+            return 1
+        if args.enable_validation:
+            path = save(step)
+            if path is None and rank == 0:
+                path = os.path.join(_train_dir(args), f"ckpt-{step}.npz")
+            if rank == 0:
+                validate_checkpoint(args, ablation, dev, path)
+    if n_timed and rank == 0:
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"train ({'graph' if args.graph else 'eager'}): {n_timed / dt:.2f} steps/s over {n_timed} steps "
+              "(the first step excluded)")
     if not args.save_every or step % args.save_every != 0:
         save(step)
     return 0
+
+
+def validation_args(args):
+    """The options of the in-process validation of ``--enable_validation`` (callbacks.py:149-170): --mode=validation on the
+    validation set at seq_len 4 / db_seq_len 4, the training batch size and --height / --width."""
+    import copy
+    v = copy.copy(args)
+    v.mode, v.dataset, v.records_path = "validation", args.val_dataset, args.val_records_path
+    v.seq_len = v.db_seq_len = 4
+    v.eval_streams, v.graph, v.stream, v.host_input, v.tf_checkpoint = 0, False, False, False, None
+    return v
+
+
+def validate_checkpoint(args, ablation, dev, path):
+    """``--mode=validation`` of the checkpoint file ``path`` on a separate inference model (nothing shared with the training
+    model or its captured step); writes what that mode writes."""
+    from . import network_ops as nops
+    vargs = validation_args(args)
+    print("Validating %s on %s" % (path, vargs.dataset))
+    torch.cuda.synchronize()
+    with nops.private_workspaces():                    # the captured training step's scratch buffers stay its own
+        model = M4Depth(nbre_levels=vargs.arch_depth, ablation_settings=ablation)
+        model.load_numpy_weights(read_weights(path), dev)
+        model.compile(metrics=default_metrics())
+        metrics = evaluate(vargs, model, 0, 1, dev)
+        write_perfs(vargs, model, metrics)
+        del model
+        torch.cuda.synchronize()
+    write_validation(vargs, metrics)
+    return metrics
+
+
+def write_perfs(args, model, metrics):
+    os.makedirs(args.ckpt_dir, exist_ok=True)
+    path = os.path.join(args.ckpt_dir, "perfs-" + args.dataset + ".txt")
+    np.savetxt(path, metrics, fmt='%.18e', delimiter='\t', newline='\n')      # main.py:147 (1-D: one metric per line)
+    for m, v in zip(model.compiled_metrics, metrics):
+        print(f"{m.name}: {v:.6f}")
+    print("wrote", path)
+
+
+def write_validation(args, metrics):
+    """main.py:132-142: the best-N manager judges the latest training checkpoint, and one line goes to validation-perfs.txt."""
+    CK.BestCheckpointManager(_train_dir(args), os.path.join(args.ckpt_dir, "best"), keep_top_n=args.keep_top_n) \
+        .update_backup(dict(zip(CK.METRIC_COLUMNS, metrics)))
+    CK.append_validation_perfs(args.ckpt_dir, metrics)
 
 
 def _stream_frame(frame, dev):
@@ -272,23 +452,9 @@ def eval_streams(args, model, dev):
         m.load_state(torch.tensor(total[i], dtype=torch.float32, device=dev), count)
 
 
-def main(argv=None):
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    if args.stream and args.mode != "predict":
-        parser.error("--stream is a --mode=predict option")
-    _check_eval_streams(parser, args)
-    rank, world, _, dev = D.init_from_env()
-    if args.eval_streams and world > 1:
-        raise SystemExit("streaming evaluation (--eval_streams) is sequential over the trajectories: run it on one rank")
-    if dev.type != "cuda":
-        raise SystemExit("m4depth_amd.main needs a GPU: the hot path has no CPU fallback")
-    ablation = ablation_from_args(args)
-    if args.mode in ("train", "finetune"):
-        return train(args, ablation, rank, world, dev)
-    model = M4Depth(nbre_levels=args.arch_depth, ablation_settings=ablation)
-    model.load_numpy_weights(load_weights(args, ablation), dev)
-    model.compile(metrics=default_metrics())
+def evaluate(args, model, rank, world, dev):
+    """The eval / validation / predict loop of ``model`` (compiled with the 7 metrics): returns the metrics all-gathered over the
+    ranks (numpy [7]), or None for predict (rank 0 has then written predictions.npy)."""
     runner = None
     preds = []
     host_input = args.host_input and args.dataset == "synthetic" and args.mode != "predict"
@@ -348,7 +514,7 @@ def main(argv=None):
         if rank == 0:
             os.makedirs(args.ckpt_dir, exist_ok=True)
             np.save(os.path.join(args.ckpt_dir, "predictions.npy"), np.concatenate(preds, axis=0))
-        return 0
+        return None
     if host_input and t_loop is not None:
         torch.cuda.synchronize()
         dt = time.perf_counter() - t_loop
@@ -356,16 +522,55 @@ def main(argv=None):
             print(f"host-resident input (pinned memory, PCIe copy inside the step): {n_frames / dt:.1f} frames/s per rank "
                   f"over {n_frames} frames")
     gathered = D.all_gather_metric_states(model.compiled_metrics, dev)
-    metrics = D.reduce_metric_states(gathered).cpu().numpy()
-    if rank == 0:
-        os.makedirs(args.ckpt_dir, exist_ok=True)
-        path = os.path.join(args.ckpt_dir, "perfs-" + args.dataset + ".txt")
-        np.savetxt(path, metrics, fmt='%.18e', delimiter='\t', newline='\n')      # main.py:147 (1-D: one metric per line)
-        for m, v in zip(model.compiled_metrics, metrics):
-            print(f"{m.name}: {v:.6f}")
-        print("wrote", path)
-    return 0
+    return D.reduce_metric_states(gathered).cpu().numpy()
 
+
+def check_train_args(parser, args, world=None):
+    """Refusals of the training workflow's options.  ``world``: the number of ranks (default: WORLD_SIZE of the environment,
+    what dist.init_from_env will see)."""
+    if world is None:
+        world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.summary_interval < 1:
+        parser.error("--summary_interval must be >= 1")
+    if args.max_keep < 0:
+        parser.error("--max_keep must be >= 0")
+    if args.keep_top_n < 1:
+        parser.error("--keep_top_n must be >= 1")
+    if args.enable_validation:
+        if args.val_records_path is None:
+            parser.error("--enable_validation needs --val_records_path (the validation set's trajectory csv files)")
+        if args.db_path_config is None:
+            parser.error("--enable_validation needs --db_path_config (the validation set's dataset root)")
+        if world > 1:
+            parser.error("--enable_validation runs in-process on one GPU: it is refused with several ranks")
+    if args.graph and args.mode in ("train", "finetune") and world > 1:
+        parser.error("--graph training is refused with several ranks (RCCL inside a captured training step is not supported)")
+
+
+def main(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.stream and args.mode != "predict":
+        parser.error("--stream is a --mode=predict option")
+    _check_eval_streams(parser, args)
+    check_train_args(parser, args)
+    rank, world, _, dev = D.init_from_env()
+    if args.eval_streams and world > 1:
+        raise SystemExit("streaming evaluation (--eval_streams) is sequential over the trajectories: run it on one rank")
+    if dev.type != "cuda":
+        raise SystemExit("m4depth_amd.main needs a GPU: the hot path has no CPU fallback")
+    ablation = ablation_from_args(args)
+    if args.mode in ("train", "finetune"):
+        return train(args, ablation, rank, world, dev)
+    model = M4Depth(nbre_levels=args.arch_depth, ablation_settings=ablation)
+    model.load_numpy_weights(load_weights(args, ablation), dev)
+    model.compile(metrics=default_metrics())
+    metrics = evaluate(args, model, rank, world, dev)
+    if metrics is not None and rank == 0:
+        write_perfs(args, model, metrics)
+        if args.mode == "validation":
+            write_validation(args, metrics)
+    return 0
 
 if __name__ == "__main__":
     sys.exit(main())

@@ -200,6 +200,25 @@ def _workspace(key, nbytes, device):
 _zero_ws_cache = {}
 
 
+class private_workspaces:
+    """Inside: every workspace of ``_workspace`` / ``zeroed_workspace`` is a fresh one, and on exit the caches are restored as
+    they were.  For a second model run in a process that holds a captured graph (the in-process validation of a replayed
+    training step): it neither writes into nor re-sizes a buffer the graph has baked in, whatever stream handles it gets.
+    The caller synchronises before leaving (the buffers made inside are dropped on exit)."""
+
+    def __enter__(self):
+        self._saved = (dict(_ws_cache), dict(_zero_ws_cache))
+        _ws_cache.clear()
+        _zero_ws_cache.clear()
+        return self
+
+    def __exit__(self, *exc):
+        for cache, saved in zip((_ws_cache, _zero_ws_cache), self._saved):
+            cache.clear()
+            cache.update(saved)
+        return False
+
+
 def zeroed_workspace(key, shape, device):
     """A persistent float32 buffer of ``shape`` per (purpose, shape, device, stream), zero-filled ONCE when it is created:
     for buffers whose padding elements are never written (the channel-padded refiner input).  Created outside any
@@ -298,6 +317,34 @@ def depth_metrics_per_sample(gt, est, new_traj, active, max_d=80.0, rows=None, c
           "m4d_depth_metrics_per_sample")
     return rows, counted
 
+
+
+def train_log_step(loss, gt, est, log, counter, first_bad):
+    """The step log of a training step (m4d_train_log_step): [loss, RMSE_log of the last frame] into row ``counter % rows`` of
+    ``log`` [rows, 2] float32, ``counter`` += 1, ``first_bad`` latched to the step index of the first non-finite loss -- all on
+    the device, nothing synchronises, so it can be the last node of a captured step.  ``loss`` [] / [1] float32, ``gt`` the
+    last frame's full-resolution ground truth [b,H,W(,1)] (a frame slice such as ``depth[:, -1]`` is read in place), ``est``
+    the finest estimate [b,h,w,1]; ``counter`` / ``first_bad`` int64 [1] device tensors."""
+    if not isinstance(loss, torch.Tensor) or loss.numel() != 1:
+        raise ValueError("loss: expected a one-element float32 device tensor")
+    est = as_f32(est, "est")
+    b, h, w = est.shape[:3]
+    if est.dim() != 4 or est.shape[3] != 1:
+        raise ValueError(f"est: expected [b,h,w,1], got {tuple(est.shape)}")
+    gs = _batch_stride(gt, "gt")
+    if gt.shape[0] != b or gt.dim() not in (3, 4) or (gt.dim() == 4 and gt.shape[3] != 1):
+        raise ValueError(f"gt {tuple(gt.shape)} is not the [b,H,W,1] ground truth of est {tuple(est.shape)}")
+    H, W = gt.shape[1:3]
+    if log.dim() != 2 or log.shape[1] != 2:
+        raise ValueError(f"log: expected [rows, 2], got {tuple(log.shape)}")
+    for name, t in (("counter", counter), ("first_bad", first_bad)):
+        if not isinstance(t, torch.Tensor) or t.numel() != 1:
+            raise ValueError(f"{name}: expected a one-element int64 device tensor")
+    ws = _workspace("train_log", int(lib.m4d_train_log_workspace_bytes()), est.device)
+    check(lib.m4d_train_log_step(dptr(loss.reshape(1), "loss"), ctypes.c_void_p(gt.data_ptr()), gs, dptr(est, "est"), b, H, W,
+                                 h, w, dptr(log, "log"), log.shape[0], dptr(counter, "counter", torch.int64),
+                                 dptr(first_bad, "first_bad", torch.int64), dptr(ws), stream_ptr()), "m4d_train_log_step")
+    return log
 
 def pack_conv_weights(kernel_hwio):
     """Re-pack a TF HWIO [3,3,Cin,Cout] kernel for m4d_conv3x3_bias_act:

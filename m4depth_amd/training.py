@@ -417,13 +417,17 @@ class GraphedTrainStep:
     host synchronisation and fixed shapes, so it is captured once and replayed: the host then
     only copies the next batch into the static input buffers.
 
+    ``step_log`` (optional, a ``TrainStepLog``): every step, the warm-up steps included, ends with its device-side log
+    entry, so the host reads losses and metrics only when it wants to.
+
     Requirements: an optimizer whose step is capturable (``torch.optim.Adam(..., capturable=True)``),
     the batch layout of ``example`` for every later call, ``new_traj`` = first frame only (it is
     host-side control flow baked into the capture).  The eager warm-up steps (packed-weight and
     workspace allocation) are REAL optimizer steps on ``example``."""
 
-    def __init__(self, model, example, optimizer, warmup=3, grad_sync=None):
+    def __init__(self, model, example, optimizer, warmup=3, grad_sync=None, step_log=None):
         self.model, self.optimizer = model, optimizer
+        self.step_log = step_log
         self.static = {k: example[k].clone() for k in ("depth", "RGB_im", "rot", "trans")}
         self.camera = {k: v.clone() for k, v in example["camera"].items()}
         self.new_traj = example["new_traj"]
@@ -458,7 +462,10 @@ class GraphedTrainStep:
         if self.grad_sync is not None:
             self.grad_sync([p for g in self.optimizer.param_groups for p in g["params"]])
         self.optimizer.step()
-        return loss.detach(), preds[-1][0]["depth"].detach()
+        loss, est = loss.detach(), preds[-1][0]["depth"].detach()
+        if self.step_log is not None:                  # the last node of the step: warm-up steps are logged too
+            self.step_log.record(loss, self.static["depth"][:, -1], est)
+        return loss, est
 
     def __call__(self, data=None):
         """Copies ``data`` into the static buffers, replays the step; returns (loss, finest depth
@@ -473,3 +480,32 @@ class GraphedTrainStep:
         self.graph.replay()
         self.model.step_counter += 1
         return self.loss, self.est
+
+
+class TrainStepLog:
+    """Device-side log of training steps (m4d_train_log_step): ``rows`` x [loss, RMSE_log] in a ring, a step counter and the
+    sticky index of the first non-finite loss, written by one fused launch pair at the end of each step and read by the host
+    only at ``read()`` -- the replayed step (``GraphedTrainStep``) then never synchronises."""
+
+    def __init__(self, rows, device):
+        self.rows = int(rows)
+        if self.rows < 1:
+            raise ValueError("TrainStepLog: rows must be >= 1")
+        self.log = torch.zeros((self.rows, 2), dtype=torch.float32, device=device)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self.first_bad = torch.full((1,), -1, dtype=torch.int64, device=device)
+        self.read_up_to = 0                                    # steps already handed to the host
+
+    def record(self, loss, gt, est):
+        nops.train_log_step(loss, gt, est, self.log, self.counter, self.first_bad)
+
+    def read(self):
+        """(rows [n,2] float32 numpy of the steps logged since the last read, in step order; first_bad or -1).  Raises when
+        more than ``rows`` steps went by unread (the ring overwrote some)."""
+        log, counter, first_bad = self.log.cpu().numpy(), int(self.counter.item()), int(self.first_bad.item())
+        n = counter - self.read_up_to
+        if n > self.rows:
+            raise RuntimeError(f"TrainStepLog: {n} steps since the last read overflow the {self.rows}-row log")
+        idx = [(self.read_up_to + i) % self.rows for i in range(n)]
+        self.read_up_to = counter
+        return log[idx], first_bad
