@@ -16,7 +16,13 @@ batch 1); N > 1 GPUs -> configs[3] (global batch 32 N: 32 sequences per rank, 25
 (32 on one GPU = configs[2]).  Inputs are resident in HBM before the timed region.
 ``value`` = all frames processed by all ranks / max-over-ranks time.
 
-The JSON line also carries
+A plain run does only what that figure needs: it sets up, warms up, times the ``--steps`` steps once, writes
+``--dump-outputs`` if asked, and prints the JSON line.  ``--full`` adds everything else (``run_plan``), all of it after the
+timed region:
+  the per-kernel rooflines (an eager re-run of the workload under HIP events), the BASELINE configs[2] leg (batch 32),
+  the CPU baselines and the GPU-vs-oracle parity checks, and the timed region repeated ``--repeat-regions`` times.
+
+With ``--full`` the JSON line also carries
   roofline          -- the dominant kernel of the step, the level-1 refiner 128->128 convolution (Winograd F(2x2,3x3),
                        float32 operands split into three bf16 terms on the bf16 matrix cores): the MFMA flops the kernel
                        EXECUTES / HIP-event time on the launch stream, against the dense peak of the MFMA type it issues
@@ -36,6 +42,7 @@ import argparse
 import hashlib
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -56,7 +63,7 @@ TRAFFIC_JSON = os.path.join(ROOT, "profiles", "pmc_traffic.json")
 HOT_KERNELS = ("pre", "norm", "front", "dscv", "sncv", "dscv_sncv", "tail", "post", "resize")     # network._timed names of the hot path
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
@@ -69,9 +76,12 @@ def parse():
     p.add_argument("--levels", type=int, default=6)
     p.add_argument("--dscv-range", type=int, default=4)
     p.add_argument("--sncv-range", type=int, default=3)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-kernel-timing", action="store_true")
-    p.add_argument("--no-configs2", action="store_true", help="skip the batch-32 (BASELINE configs[2]) leg of the default run")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: per-kernel rooflines, the batch-32 (BASELINE "
+                        "configs[2]) leg, CPU baselines + parity checks, repeated timed regions (run_plan)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and parity checks")
+    p.add_argument("--no-kernel-timing", action="store_true", help="--full without the per-kernel rooflines")
+    p.add_argument("--no-configs2", action="store_true", help="--full without the batch-32 (BASELINE configs[2]) leg")
     p.add_argument("--configs2-steps", type=int, default=5)
     p.add_argument("--eager", action="store_true", help="do not replay the step from a hipGraph")
     p.add_argument("--host-input", action="store_true",
@@ -80,14 +90,26 @@ def parse():
                    help="graph (default) = ONE hipGraph per step, the frames pipelined on the graph's internal streams; tape = the same "
                         "(frame, level) wavefront as launch tapes of libm4depth_hip.so replayed as plain stream launches (no hipGraph; "
                         "measured 3 %% slower, kept as the graph-free launcher)")
-    p.add_argument("--repeat-regions", type=int, default=3,
-                   help="timed regions of --steps steps run back to back; the first is the line's value, all are in ms_per_step_runs")
+    p.add_argument("--repeat-regions", type=int, default=None,
+                   help="timed regions of --steps steps run back to back; the first is the line's value, all are in "
+                        "ms_per_step_runs (default 3 with --full, else 1)")
     p.add_argument("--in-flight", type=int, default=1,
                    help="independent sequence batches in flight (each on its own stream and model state); 1 = the quoted number")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0): the "
                         "metrics test_step returns and the depth map of the sequence's last frame (dump_outputs)")
-    return p.parse_args()
+    return p.parse_args(argv)
+
+
+def run_plan(args):
+    """What a run does besides the headline figure.  A plain run: nothing (one timed region).  ``--full``: the per-kernel
+    timing, the configs[2] leg and the CPU baselines with the parity checks, each unless its ``--no-*`` option drops it, and
+    three timed regions.  An explicit ``--repeat-regions`` holds in either mode; the legs that also need the default workload,
+    one GPU or the graph launcher check that in main."""
+    return {"kernel_timing": args.full and not args.no_kernel_timing,
+            "configs2": args.full and not args.no_configs2,
+            "cpu_baseline": args.full and not args.no_cpu_baseline,
+            "repeat_regions": args.repeat_regions if args.repeat_regions is not None else (3 if args.full else 1)}
 
 
 class EventTimer:
@@ -375,7 +397,7 @@ def eager_timed_steps(model, data, timer, batch, steps, torch):
 
 
 def configs2_leg(args, weights, dev, timer, torch, M, net, D):
-    """BASELINE configs[2] ("384x1280 6-level seq_len=4, batch 32, 1xMI355X (HBM-roofline run)") inside the default run: the
+    """BASELINE configs[2] ("384x1280 6-level seq_len=4, batch 32, 1xMI355X (HBM-roofline run)") inside a --full run: the
     same test_step at batch 32 -- own model (own recurrent state), hipGraph replay, ``--configs2-steps`` timed replays between
     synchronisations, then two eager steps under the kernel timer for the roofline fractions.  Returns the ``configs2``
     object of the JSON line (same definitions as the top-level keys)."""
@@ -579,12 +601,15 @@ def report_head(args, world, dt, per_rank_s):
 
 def main():
     args = parse()
+    plan = run_plan(args)
+    args.repeat_regions = plan["repeat_regions"]
     import torch
     if check_world(args, os.environ, torch.cuda.device_count()) == "relaunch":
         cmd = torchrun_command(args.gpus, sys.argv[1:])
         print(f"[bench] --gpus {args.gpus} invoked without a launcher: starting the ranks with {' '.join(cmd[1:10])} ...",
               file=sys.stderr, flush=True)
-        os.execv(cmd[0], cmd)
+        # a child process, not exec: this one has already opened the HIP runtime (device_count)
+        sys.exit(subprocess.run(cmd).returncode)
     from m4depth_amd import dist as D
     rank, world, local_rank, dev = D.init_from_env()
     if not torch.cuda.is_available():
@@ -603,7 +628,7 @@ def main():
     data = make_batch(args, rank, dev, torch)
 
     timer = EventTimer(torch)
-    if not args.no_kernel_timing:
+    if plan["kernel_timing"]:
         net.kernel_timer = timer
 
     for _ in range(max(args.warmup, 1)):                 # eager warm-up: state and scratch allocation
@@ -707,13 +732,13 @@ def main():
     # event records while the GPU spins, so an event pair brackets the kernel's execution, not the host's launch latency
     # (without it the small kernels of the coarse levels read 3-10x too long: the GPU runs ahead of the eager host loop).
     n_eager = 0
-    if not args.no_kernel_timing and rank == 0:          # (report work of rank 0 alone: the other ranks are done after the gathers)
+    if plan["kernel_timing"] and rank == 0:              # (report work of rank 0 alone: the other ranks are done after the gathers)
         n_eager = eager_timed_steps(model, data, timer, args.batch, min(args.steps, 5), torch)
 
     roof1 = kernel_rooflines(args, args.batch, timer, net, n_eager) if (timer.events and rank == 0) else {}
     # BASELINE configs[2] beside the default configs[1] line (one GPU, default workload only): the same step at batch 32
     configs2 = None
-    if (world == 1 and args.batch == 1 and not args.no_configs2 and not args.eager and args.in_flight == 1 and args.schedule == "graph"
+    if (world == 1 and args.batch == 1 and plan["configs2"] and not args.eager and args.in_flight == 1 and args.schedule == "graph"
             and (args.height, args.width, args.levels, args.seq_len) == (384, 1280, 6, 4)):
         configs2 = configs2_leg(args, weights, dev, timer, torch, M, net, D)
 
@@ -785,7 +810,7 @@ def main():
         rf["launches_per_step"] = launches_per_step
         rf["ms_per_step_runs"] = out["ms_per_step_runs"]
         rf["box_kind_probe"] = probe
-    if not args.no_cpu_baseline and world == 1:
+    if plan["cpu_baseline"] and world == 1:
         cb, (W, samples, cam, ref, ref_seq) = cpu_baseline(args.height, args.width, args.levels, args.dscv_range, args.sncv_range,
                                                            seq_len=args.seq_len, keep=True)
         out["cpu_baseline"] = cb

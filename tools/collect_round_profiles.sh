@@ -26,9 +26,9 @@ timeout 1200 bash tools/pmc_wino6.sh > /dev/null 2>&1; cp gpurun_out/pmc/wino6.t
 fi
 
 
-timeout 600 python bench.py --steps 20 --host-input > $OUT/bench_b1.json 2> $OUT/bench_b1.err;                      need $OUT/bench_b1.json
-timeout 600 python bench.py --steps 10 --batch 8 --no-cpu-baseline > $OUT/bench_b8.json 2> $OUT/bench_b8.err;       need $OUT/bench_b8.json
-timeout 600 python bench.py --steps 5 --warmup 2 --batch 32 --no-cpu-baseline > $OUT/bench_b32.json 2> $OUT/bench_b32.err; need $OUT/bench_b32.json
+timeout 600 python bench.py --full --steps 20 --host-input > $OUT/bench_b1.json 2> $OUT/bench_b1.err;                      need $OUT/bench_b1.json
+timeout 600 python bench.py --full --steps 10 --batch 8 --no-cpu-baseline > $OUT/bench_b8.json 2> $OUT/bench_b8.err;       need $OUT/bench_b8.json
+timeout 600 python bench.py --full --steps 5 --warmup 2 --batch 32 --no-cpu-baseline > $OUT/bench_b32.json 2> $OUT/bench_b32.err; need $OUT/bench_b32.json
 
 for B in 1 32; do
   rm -rf /tmp/prof_${TAG}_b$B
@@ -77,7 +77,7 @@ done
 # the latency-first small-map convolution: every configuration per coarse-level layer, beside conv3x3_small6 (network_ops.lat_config's table)
 timeout 900 python tools/bench_lat_convs.py sweep > $OUT/lat_conv_sweep.txt 2>&1; need $OUT/lat_conv_sweep.txt
 # BASELINE configs[4] (768x2560, search ranges 6 / 6): fused fronts of levels 1-4 (m4d_level_front_r)
-timeout 600 python bench.py --height 768 --width 2560 --dscv-range 6 --sncv-range 6 --steps 10 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.err; need $OUT/bench_config4.json
+timeout 600 python bench.py --full --height 768 --width 2560 --dscv-range 6 --sncv-range 6 --steps 10 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.err; need $OUT/bench_config4.json
 
 timeout 600 python tools/bench_train.py > $OUT/bench_train.json 2>/dev/null; need $OUT/bench_train.json
 head -c 400 $OUT/bench_b1.json; echo
