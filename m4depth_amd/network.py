@@ -29,6 +29,7 @@ M4depthAblationParameters = namedtuple('M4depthAblationParameters',
 
 _CV_ACCUM = {"fp32_round": 0, "fp16_seq": 1}
 
+import contextlib as _contextlib
 import os as _os
 
 # bench.py installs an object with ``run(name, level, thunk)`` here to bracket the
@@ -37,74 +38,52 @@ kernel_timer = None
 # tools/determinism_stress.py installs ``tap(name, level, tensor)`` here to keep copies of intermediate activations (the
 # encoder maps and the refiner layers, which nothing else retains); None = no overhead.
 debug_tap = None
+
+# -- Settings.  Every M4D_* variable below is set by a test, a tool or bench.py (INTEGRATION.md section 4 lists who sets it);
+# -- the plain constants were switches once: their other values were measured no better and removed (DESIGN_HISTORY.md).
+
 # Winograd F(2x2,3x3) for the wide stride-1 layers (csrc/m4d_wino.hip): 2.25x fewer MFMA flops, equal to the direct
 # convolution up to float32 rounding (max difference ~1e-6 of the output range).  Measured per layer (tools/bench_wino.py):
 # 1.26-1.49x at batch 1, 1.16-1.39x at batch 8 for 64/128 output channels; the 96- and 32-wide layers (one N-tile per
 # workgroup) gain only on small grids.  0 = always the direct convolution.
 winograd_conv = _os.environ.get("M4D_WINOGRAD", "1") == "1"
-
-
-# Smallest grid (workgroups of Winograd kernel 2) for which a layer leaves the direct convolution.  Round 1 used 200 (a
-# launch that fills the chip on its own); inside the frame pipeline the chip is shared with other frames' kernels anyway and
-# the 2.25x fewer MFMA flops win from 60 workgroups on: level 3 of the 384x1280 pyramid (30 tiles x 2-4 N-tiles) moves to
-# Winograd, +2 % frames/s at batch 1 (1050 -> 1074; 30: 1047).
-winograd2_min_workgroups = int(_os.environ.get("M4D_WINO2_MIN_WG", "60"))
-
+# Smallest grid (workgroups of Winograd kernel 2) for which a layer leaves the direct convolution: inside the frame pipeline
+# the chip is shared with other frames' kernels anyway and the 2.25x fewer MFMA flops win from 60 workgroups on (level 3 of the
+# 384x1280 pyramid: 30 tiles x 2-4 N-tiles), +2 % frames/s at batch 1 against a launch that fills the chip on its own (200).
+_WINO2_MIN_WORKGROUPS = 60
 
 # Arithmetic of the wide Winograd layers: "bf16x3" = float32 operands split exactly into three bf16 terms, six bf16 MFMA
 # products, float32 accumulation (csrc/m4d_wino6.hip: float32 accuracy -- error against float64 0.8x that of the fp32
 # MFMA kernels, tools/bench_wino6.py -- at 2.67x less matrix-core time); "f16x2" (default) = the same layers with float32
 # operands scaled by powers of two (per Winograd tile / per output channel) and split into two fp16 terms, three fp16 MFMA
 # products (csrc/m4d_wino_f16.hip: error against float64 at the bf16x3 level), and the stride-1
-# latency-first layers likewise (csrc/m4d_convlat_f16.hip, ``lat_arith``) -- every other kernel (small-map, fused tail,
+# latency-first layers likewise (csrc/m4d_convlat_f16.hip) -- every other kernel (small-map, fused tail,
 # training) keeps its bf16x3 form under "f16x2"; "f32" = the fp32-MFMA kernels everywhere.
 conv_arith = _os.environ.get("M4D_CONV_ARITH", "f16x2")
 _SPLIT_ARITHS = ("bf16x3", "f16x2")          # the arithmetics that run the 16-bit split kernels
 # Smallest grid ((tile, 64-cout) units) those kernels take: 30 = the narrow layers of level 3 (30 tiles: 96 -> 64, and 64 -> 32 as
-# half units) as well, +0.8 % frames/s at batch 1 against 40 (rounds 2-4: those two on the fp32-MFMA Winograd / direct kernels);
-# 20 (level 4's wide layers too) measured the same as 30
+# half units) as well, +0.8 % frames/s at batch 1 against 40; 20 (level 4's wide layers too) measured the same as 30
 wino6_min_workgroups = int(_os.environ.get("M4D_WINO6_MIN_WG", "30"))
 # Which kernel serves those layers (an ARGUMENT of m4d_conv3x3_wino6_bias_act_k, same bits either way): 0 = the library chooses
 # from the grid (persistent workgroups, csrc/m4d_wino6p.hip, wherever a CU gets more than one (tile, 64-cout) unit), 1 = one
 # workgroup per unit always (csrc/m4d_wino6.hip), 2 = persistent always.  A/B timing only.
 wino6_kernel = int(_os.environ.get("M4D_WINO6_KERNEL", "0"))
-# Round 6: launches of wino6_pair_min_units ... (persistent threshold - 1) units at a launch batch <= 4 (the level-1 refiner layers
-# at batch 1: 960 / 480 units) on persistent workgroups of wino6_pair_units CONSECUTIVE units each (kernel = 16 + n of
-# m4d_conv3x3_wino6_bias_act_ks): a tile's cout groups share a halo fetch and the DMA stream runs through the unit boundary
-# (4.4 us instead of ~7 for prologue + epilogue), while the dispatcher still places the workgroups as CUs free (the static
-# one-range-per-CU form did not pay inside the frame pipeline).  0 = off (one workgroup per unit).  Same bits.
-wino6_pair_min_units = int(_os.environ.get("M4D_WINO6_PAIR_MIN_UNITS", "0"))
-wino6_pair_units = int(_os.environ.get("M4D_WINO6_PAIR_UNITS", "2"))
-# Narrowest layer the bf16-split Winograd kernels serve: a cout group of <= 32 channels runs as a HALF unit (one N-tile), so the
+# Narrowest layer the 16-bit-split Winograd kernels serve: a cout group of <= 32 channels runs as a HALF unit (one N-tile), so the
 # refiner's 64 -> 32 layer is one half unit per tile: 35.7 -> 29.0 us on level 1, 20.8 -> 12.4 on level 2 against the fp32-MFMA
-# Winograd kernel that served it in rounds 2-4 (= 64 here), +0.9 % / +1.1 % frames/s at batch 1 / 32
-# (profiles/r04_wino6_half_units.txt)
-wino6_min_cout = int(_os.environ.get("M4D_WINO6_MIN_COUT", "32"))
-# (experiments build only, include/m4depth_hip_experiments.h) which kernel serves the bf16-split layers -- same bits either
-# way: 2 = the wide kernel m4d_wino6w.hip wherever it applies, 3 = the half-tile kernel m4d_wino6h.hip
-if _os.environ.get("M4D_WINO6_VARIANT") or _os.environ.get("M4D_WINO6_HALF_MAX_WG"):
-    from ._lib import require_experiments as _require_experiments
-    _require_experiments("M4D_WINO6_VARIANT / M4D_WINO6_HALF_MAX_WG")
-    if _os.environ.get("M4D_WINO6_VARIANT"):
-        lib.m4d_wino6_set_variant(int(_os.environ["M4D_WINO6_VARIANT"]))
-    if _os.environ.get("M4D_WINO6_HALF_MAX_WG"):       # grids up to this many workgroups take the half-tile kernel (default 0 = none)
-        lib.m4d_wino6_set_half_tile_max_workgroups(int(_os.environ["M4D_WINO6_HALF_MAX_WG"]))
-# The one-launch small-map convolution in the same arithmetic (csrc/m4d_conv.hip conv3x3_small6_kernel).  These launches are
-# bound by how fast ONE CU streams its slice of the weights, not by the matrix core: -2 us per layer on the 240-channel first
-# layers, nothing elsewhere (tools/bench_small_convs.py); +0.8 % frames/s at batch 1.  0 = the fp32-MFMA small-map kernel.
-_small_conv_split_env = _os.environ.get("M4D_SMALL_CONV_SPLIT", "1") == "1"
-small_conv_split = _small_conv_split_env and conv_arith in _SPLIT_ARITHS
-
+# Winograd kernel, +0.9 % / +1.1 % frames/s at batch 1 / 32 (profiles/r04_wino6_half_units.txt)
+_WINO6_MIN_COUT = 32
+# The one-launch small-map convolution in the same arithmetic (csrc/m4d_conv.hip conv3x3_small6_kernel) whenever the arithmetic
+# is a 16-bit split.  These launches are bound by how fast ONE CU streams its slice of the weights, not by the matrix core:
+# -2 us per layer on the 240-channel first layers, nothing elsewhere (tools/bench_small_convs.py); +0.8 % frames/s at batch 1.
+small_conv_split = conv_arith in _SPLIT_ARITHS
 
 # The fused level tail (conv 32->16, conv 16->5, level_post) in the same bf16-split arithmetic (csrc/m4d_tail6.hip) when
 # conv_arith is a 16-bit split ("f16x2" or "bf16x3": the bf16x3 tail either way); 0 = the fp32-MFMA tail (csrc/m4d_tail.hip) always.
 tail_split = _os.environ.get("M4D_TAIL_SPLIT", "1") == "1"
 
-# The encoder's convolutions choose their kernel from the per-image grid x the sequence batch (1 = from the per-image grid alone:
-# rounds 1-3, which ran the coarse encoder levels of a batch-32 evaluation on the single-small-map latency kernels).
+# The encoder's convolutions choose their kernel from the per-image grid x the sequence batch (0 = from the per-image grid alone,
+# which runs the coarse encoder levels of a batch-32 evaluation on the single-small-map latency kernels).
 encoder_batch_dispatch = _os.environ.get("M4D_ENCODER_BATCH_DISPATCH", "1") == "1"
-
-import contextlib as _contextlib
 
 
 @_contextlib.contextmanager
@@ -115,7 +94,7 @@ def conv_arithmetic(arith):
     if arith not in _SPLIT_ARITHS + ("f32",):
         raise ValueError(f"conv arithmetic must be 'f16x2', 'bf16x3' or 'f32', not {arith!r}")
     old = (conv_arith, small_conv_split)
-    conv_arith, small_conv_split = arith, _small_conv_split_env and arith in _SPLIT_ARITHS
+    conv_arith, small_conv_split = arith, arith in _SPLIT_ARITHS
     try:
         yield
     finally:
@@ -124,7 +103,7 @@ def conv_arithmetic(arith):
 
 def _use_winograd(b, h, w, cin, cout, stride):
     """0 = direct convolution; 6 = the 16-bit-split Winograd kernel (m4d_wino6.hip under "bf16x3", m4d_wino_f16.hip under
-    "f16x2": ``forward`` picks it from ``conv_arith``); 1 = Winograd kernel 1 (16x8 tile,
+    "f16x2": ``plan`` picks it from ``conv_arith``); 1 = Winograd kernel 1 (16x8 tile,
     16-channel chunks, 2 N-tiles per workgroup); 2 = kernel 2 (16x16 tile, 8-channel chunks: half the weight traffic per flop -- ahead on the large maps).
     Winograd only pays when the launch fills the chip: the thresholds are workgroup counts (measured per layer of the
     384x1280 pyramid, profiles/r01_step_launches_b1_wino.txt: level 3 and coarser stay on the direct kernel, which can
@@ -133,9 +112,9 @@ def _use_winograd(b, h, w, cin, cout, stride):
         return 0
     n32 = -(-cout // 32)
     t16 = b * (-(-h // 16)) * (-(-w // 16))
-    if conv_arith in _SPLIT_ARITHS and cin % 16 == 0 and cin >= 32 and cout >= wino6_min_cout and t16 * (-(-cout // 64)) >= wino6_min_workgroups:
+    if conv_arith in _SPLIT_ARITHS and cin % 16 == 0 and cin >= 32 and cout >= _WINO6_MIN_COUT and t16 * (-(-cout // 64)) >= wino6_min_workgroups:
         return 6                                                # 64-cout units; a last group of <= 32 channels runs one N-tile
-    if cin % 4 == 0 and t16 * n32 >= winograd2_min_workgroups:
+    if cin % 4 == 0 and t16 * n32 >= _WINO2_MIN_WORKGROUPS:
         return 2
     t8 = b * (-(-h // 8)) * (-(-w // 16))
     if cout % 64 == 0 and t8 * (cout // 64) >= 400:
@@ -145,50 +124,29 @@ def _use_winograd(b, h, w, cin, cout, stride):
     return 0
 
 
-# Refiner input padded to a multiple of 8 channels (levels 2-6: 58k + 6 = 122, 238, 470): the padding channels are
-# zero in a persistent buffer and meet zero weights, so every sum is unchanged bit for bit, and the first refiner layer
-# of level 2 becomes eligible for the 8-channel-chunk Winograd kernels (122 -> 128).  0 = exact-width input.
-pad_refiner_input = _os.environ.get("M4D_PAD_REFINER_INPUT", "1") == "1"
+def _padded_refiner_width(f_in):
+    """The refiner input is padded to a multiple of 8 channels (levels 2-6: 58k + 6 = 122, 238, 470): the padding channels are
+    zero in a persistent buffer and meet zero weights, so every sum is unchanged bit for bit, and the first refiner layer
+    of level 2 becomes eligible for the 8-channel-chunk Winograd kernels (122 -> 128).  Inference on the GPU only: training
+    and CPU tensors take the exact width."""
+    return (f_in + 7) // 8 * 8
+
 
 # DispRefiner layers on maps of at most this many pixels (batch included) and at most 256 input channels run as ONE
 # launch with the K split inside the workgroup (m4d_conv3x3_small_bias_act) instead of split-K + reduce: levels 4-6 at
-# batch 1, +2.5 % frames/s (tools/ab_bench.sh).  Refiner layers only: their batch is the caller's batch in every launch
-# mode, so the pipelined and the single-stream forward keep choosing the same kernel (bitwise-neutrality test).  0 = off.
+# batch 1, +2.5 % frames/s (tools/ab_bench.sh), and the coarse stride-2 encoder layers likewise (by OUTPUT pixels).  The
+# refiner's batch is the caller's batch in every launch mode, so the pipelined and the single-stream forward keep choosing the
+# same kernel (bitwise-neutrality test).  0 = off.
 small_map_conv_pixels = int(_os.environ.get("M4D_CONV_SMALL_PX", "2048"))
-small_map_stride2 = _os.environ.get("M4D_CONV_SMALL_S2", "1") == "1"     # the coarse stride-2 encoder layers on the one-launch kernel too
 
-# The latency-first small-map convolution (csrc/m4d_convlat.hip, round 5): every layer that may take the one-launch small-map
+# The latency-first small-map convolution (csrc/m4d_convlat.hip): every layer that may take the one-launch small-map
 # kernels (``small_maps_ok``, stride 1, Cin >= 16, Cin % 4 == 0) on maps of at most this many pixels (batch included) when
-# conv_arith is "f16x2" or "bf16x3" (bf16x3 kernels either way).  K is split over waves and workgroups until a wave owns one or two 16-channel chunks and requests
-# everything it needs in one memory round trip; the K slices of different workgroups reach the NEXT layer as partial-sum slabs
-# (network_ops.PartialAct) that it adds while staging.  Levels 4-6 at batch 1: 59 / 50 / 52 us of refiner convolutions per
-# level -> 38 / 37 / 48 (tools/bench_lat_convs.py).  0 = the round-2/3 small-map kernels.
+# conv_arith is "f16x2" (the fp16 two-term kernel, csrc/m4d_convlat_f16.hip) or "bf16x3".  K is split over waves and workgroups
+# until a wave owns one or two 16-channel chunks and requests everything it needs in one memory round trip; the K slices of
+# different workgroups reach the NEXT layer as partial-sum slabs (network_ops.PartialAct) that it adds while staging.  Levels 4-6
+# at batch 1: 59 / 50 / 52 us of refiner convolutions per level -> 38 / 37 / 48 (tools/bench_lat_convs.py).  0 = the one-launch
+# small-map kernels.  (The kernel's stride-2 and M-over-waves forms stay in the library, measured and not dispatched: DESIGN.md.)
 lat_conv_max_pixels = int(_os.environ.get("M4D_LAT_CONV_PX", "2048"))
-# ... and the narrow layers (Cout <= 32: one cout group, the Winograd kernels run them as half units on 30-120 workgroups) up to
-# this many pixels: level 3's 64 -> 32 layer at batch 1 (48x160)
-lat_conv_narrow_max_pixels = int(_os.environ.get("M4D_LAT_CONV_NARROW_PX", "0"))
-# ... and the stride-2 encoder layers whose OUTPUT has at most this many pixels (sequence batch included)
-lat_conv_s2_max_pixels = int(_os.environ.get("M4D_LAT_CONV_S2_PX", "0"))
-# ... and the narrow short-K stride-2 encoder layers (Cin, Cout <= 64: 32 -> 32 at 192x640 and 64 -> 64 at 96x320 of the 384x1280
-# pyramid, fp32-MFMA direct kernels of ~25 us each at batch 1) in the kernel's M-over-waves form, up to this many OUTPUT pixels
-lat_conv_mw_max_pixels = int(_os.environ.get("M4D_LAT_CONV_MW_PX", "0"))
-# Arithmetic of those layers when conv_arith is "f16x2": "f16x2" (default) = the stride-1 layers on the fp16 two-term kernel
-# (csrc/m4d_convlat_f16.hip: three fp16 MFMA products per term pair instead of six bf16 ones, per-pixel-window input scales);
-# "bf16x3" = the bf16x3 kernel (the A side of an A/B against the Winograd change alone).  The stride-2 and M-over-waves forms
-# stay bf16x3.  Under conv_arith "bf16x3" every latency-first layer is bf16x3 whatever this says.
-lat_arith = _os.environ.get("M4D_LAT_ARITH", "f16x2")
-if lat_arith not in _SPLIT_ARITHS:
-    raise ValueError(f"M4D_LAT_ARITH must be 'f16x2' or 'bf16x3', not {lat_arith!r}")
-
-# DSCV and SNCV of a small level (<= 6000 pixels) in one launch (m4d_dscv_sncv_fwd).  0 = two launches.
-fused_cost_volumes = _os.environ.get("M4D_FUSED_COST_VOLUMES", "1") == "1"
-# ... and the level's opening glue (level_pre) in that launch too (m4d_level_front_small, round 6): a coarse level opens with ONE
-# launch.  Its features arrive per-cut normalised: the normalisation depends on the encoder alone, so the coarse levels' maps of all
-# frames of an encoder batch are normalised in one launch right behind the encoder (m4d_normalize_levels), off the levels'
-# coarse-to-fine latency chains.  0 = level_pre_normalize + dscv_sncv (two dependent launches per level).  Same bits.
-small_level_front = _os.environ.get("M4D_SMALL_LEVEL_FRONT", "1") == "1"
-# level_pre and the per-cut normalisation of a level in one launch (m4d_level_pre_normalize).  0 = two launches.
-fused_level_front = _os.environ.get("M4D_FUSED_LEVEL_FRONT", "1") == "1"
 
 # The whole level front (normalise + level_pre + DSCV + SNCV -> complete refiner-input rows) as ONE kernel
 # (csrc/m4d_front.hip) wherever it has an instantiation: the default settings and 16 channels x 1-2 cuts or 32 x 2 (levels 1-3
@@ -196,15 +154,10 @@ fused_level_front = _os.environ.get("M4D_FUSED_LEVEL_FRONT", "1") == "1"
 # the separate kernels.  M4D_FUSED_FRONT=0 = the separate kernels everywhere (same bits).
 fused_front = _os.environ.get("M4D_FUSED_FRONT", "1") == "1"
 fused_front_min_pixels = int(_os.environ.get("M4D_FUSED_FRONT_MIN_PX", "0"))
-# The geometries of levels 4-6 (24 / 32 channels per cut x 4 cuts, 24 x 8) have instantiations too (round 3); on maps of at
+# The geometries of levels 4-6 (24 / 32 channels per cut x 4 cuts, 24 x 8) have instantiations too; on maps of at
 # most this many pixels (batch included: levels 4-6 at batch 1-3) the one-launch small-map cost-volume kernel stays -- a
 # handful of 8x8 tiles cannot fill the chip -- above it (batch >= 4) the fused front writes whole refiner-input rows.
 fused_front_coarse_min_pixels = int(_os.environ.get("M4D_FUSED_FRONT_COARSE_MIN_PX", "6000"))
-
-# Encoder level 0 as two fused kernels (direct 3->16 convolution + bias + DINL statistics; DINL apply fused into the
-# stride-2 convolution's input staging) instead of MIOpen conv + bias pass + 3 DINL passes + conv: no MIOpen kernel is
-# left in the inference path.  0 = the unfused sequence.
-fused_encoder_head = _os.environ.get("M4D_FUSED_ENCODER_HEAD", "1") == "1"
 
 # The last two refiner convolutions (32->16, 16->5) and the level tail in ONE kernel (csrc/m4d_tail.hip).  0 = three launches.
 fused_refiner_tail = _os.environ.get("M4D_FUSED_TAIL", "1") == "1"
@@ -217,50 +170,33 @@ fused_refiner_tail = _os.environ.get("M4D_FUSED_TAIL", "1") == "1"
 # capture in which two streams wait on each other's events alternately (tools/debug_multistream_capture.py).
 # 0 disables (single stream).
 level_pipeline_streams = int(_os.environ.get("M4D_LEVEL_PIPELINE", "8"))
-# Redundant (transitively implied) cross-stream waits of the pipelined forward.  They change how ROCm's hipGraph executor lays the
-# captured graph out on its streams, so they are knobs, measured (profiles/r04_graph_executor.txt):
-#   M4D_PIPE_FORK_FRAMES = frames (beside frame 0 and the late encoder's first frame) whose stream waits for the fork event
-#   explicitly: "all" (rounds 1-3) or a list like "1,2"; M4D_PIPE_SKIP_ENC_WAIT=1: a frame of the late encoder batch does not
-#   wait for that batch's event when the previous frame (same batch) is waited for anyway.
-_pf = _os.environ.get("M4D_PIPE_FORK_FRAMES", "1,2")
-pipeline_fork_frames = None if _pf == "all" else {int(v) for v in _pf.split(",") if v.strip() != ""}
-pipeline_skip_implied_encoder_wait = _os.environ.get("M4D_PIPE_SKIP_ENC_WAIT", "1") == "1"
-# A reset frame (new_traj: six state-seeding launches of a few microseconds) shares the stream of the frame that follows it: the
-# first full frame's coarse-to-fine chain then has no cross-stream wait in front of every level (round 5: each such wait is a
-# ~4.7 us gap in the executor's queue, profiles/r05_queue_trace_b1_graph.txt, on a chain that runs with the chip otherwise idle).
-pipeline_merge_reset_frame = _os.environ.get("M4D_PIPE_MERGE_RESET", "1") == "1"
+# Frames (= streams) beside frame 0 and the late encoder's first frame that wait for the pipelined forward's fork event
+# explicitly.  The wait is implied by their wait for the previous frame's level, but the redundant edge changes how ROCm's
+# hipGraph executor lays the captured graph out on its streams: measured, profiles/r04_graph_executor.txt.
+_PIPELINE_FORK_FRAMES = (1, 2)
 # The staggered first round of the one-per-CU Winograd kernel (csrc/m4d_wino6.hip): an ARGUMENT of every launch
-# (m4d_conv3x3_wino6_bias_act_ks, ABI 6 -- no library state).  The value is a per-MODEL setting (M4Depth.set_wino6_stagger ->
+# (m4d_conv3x3_wino6_bias_act_ks -- no library state).  The value is a per-MODEL setting (M4Depth.set_wino6_stagger ->
 # every layer's ``wino6_stagger_us``); a layer that was never told falls back to this module default.  Which launches carry it:
-# grids of >= wino6_stagger_min_wg workgroups at a launch batch <= wino6_stagger_max_batch (the launches that put one workgroup on
-# every CU at batch 1-4: the level-1 / level-2 refiner layers and the encoder's 240-workgroup layers).  Whether GraphedSequence
+# grids of >= _WINO6_STAGGER_MIN_WG workgroups at a launch batch <= _WINO6_STAGGER_MAX_BATCH (the launches that put one workgroup
+# on every CU at batch 1-4: the level-1 / level-2 refiner layers and the encoder's 240-workgroup layers).  Whether GraphedSequence
 # captures the sequence both ways and keeps the faster graph (the effect's sign depends on the box): wino6_stagger_autotune.
 wino6_stagger_us = int(_os.environ.get("M4D_WINO6_STAGGER_US", "9"))
-wino6_stagger_phases = int(_os.environ.get("M4D_WINO6_STAGGER_PHASES", "16"))
-wino6_stagger_min_wg = int(_os.environ.get("M4D_WINO6_STAGGER_MIN_WG", "200"))
-wino6_stagger_max_batch = int(_os.environ.get("M4D_WINO6_STAGGER_MAX_BATCH", "4"))
+_WINO6_STAGGER_PHASES = 16
+_WINO6_STAGGER_MIN_WG = 200
+_WINO6_STAGGER_MAX_BATCH = 4
 wino6_stagger_autotune = _os.environ.get("M4D_STAGGER_AUTOTUNE", "1") == "1"
-# The sequence step as four hipGraphs on two real streams (SegmentedSequence) where the sequence allows it: make_runner().
-segmented_step = _os.environ.get("M4D_SEGMENTED", "0") == "1"
-segmented_resumed_first = _os.environ.get("M4D_SEG_RESUMED_FIRST", "1") == "1"
-segmented_resumed_on_main = _os.environ.get("M4D_SEG_RESUMED_ON_MAIN", "0") == "1"
 wino6_stagger_force = _os.environ.get("M4D_STAGGER_FORCE", "")           # "staggered" / "lock_step": keep that graph whatever the timing
 # The reset frame of all levels in ONE launch (m4d_pyramid_reset) instead of one state-seeding launch per level: the six launches
 # depend on each other only through the upsampling of constant maps, and they sit on the critical path of a batch-1 step.
 fused_pyramid_reset = _os.environ.get("M4D_FUSED_RESET", "1") == "1"
-# Encoding every frame on its own stream too (instead of one encoder pass batched over the frames, before the
-# decoder) was measured slightly slower (633 vs 643 frames/s at batch 1): the batched pass has 4x fewer launches.
 # Encoder level 0 (conv 3->16, DINL, conv 16->16 stride 2) as m4d_enc_level0_fwd: three passes that recompute the first
 # convolution from the RGB frames instead of writing / re-reading its full-resolution 16-channel output.  0 = the two-call head.
 fused_encoder_level0 = _os.environ.get("M4D_FUSED_ENC0", "1") == "1"
-pipeline_encoder_per_frame = _os.environ.get("M4D_PIPELINE_ENCODER", "0") == "1"
-# Encoder in two batches instead: frames [0, split) before the decoder, frames [split, T) on frame `split`'s stream.
+# Encoder in two batches: frames [0, split) before the decoder, frames [split, T) on frame `split`'s stream.  (Encoding every
+# frame on its own stream instead was measured slower, 633 vs 643 frames/s at batch 1: a batched pass has 4x fewer launches.)
 pipeline_encoder_split = int(_os.environ.get("M4D_PIPELINE_ENCODER_SPLIT", "2"))
 # With the split: level 0's DINL statistics of every frame are taken in the first batch's launches (per-image arithmetic, same bits).
 encoder_stats_up_front = _os.environ.get("M4D_ENC_STATS_UP_FRONT", "1") == "1"
-# A/B knob (rounds 5's behaviour): a stride-1 encoder layer on the latency-first kernel always hands partial slabs on, also when
-# its stride-2 consumer cannot add them (then m4d_partial_finish runs as a launch of its own).
-encoder_s1_partial_always = _os.environ.get("M4D_ENC_S1_PARTIAL", "0") == "1"
 
 
 def _stack_frames(samples):
@@ -396,102 +332,59 @@ class _Conv3x3SameTF(torch.nn.Module):
             hwio = np.concatenate([hwio, np.zeros(hwio.shape[:2] + (cin_pad - hwio.shape[2], hwio.shape[3]), hwio.dtype)], axis=2)
         return hwio
 
-    def _packed_weights(self, cin_pad=None):
-        """(wp, CoutPad) for m4d_conv3x3_bias_act, packed from the live OIHW parameter (re-packed when it changes)."""
+    def can_use(self, layout, cin):
+        """The STATIC condition of a packed layout: can this layer, reading ``cin`` input channels (its own, or a zero-padded
+        input's), ever be dispatched to a kernel that reads it -- whatever the map size, the batch and the arithmetic?
+        ``plan`` only names layouts for which this holds (asserted where a layout is built), and ``M4Depth.prepack`` builds
+        exactly those."""
+        cout, s1 = self.out_channels, self.stride == 1
+        small = self.small_maps_ok and s1 and cin >= 16 and cin % 4 == 0
+        wino = s1 and cin >= 16 and cin % 2 == 0
+        if layout == "direct":
+            return True
+        if layout == "hwio":                              # the encoder's level-0 kernels (FeaturePyramid, not ``plan``)
+            return cin == 3 or (self.stride == 2 and cin == 16 and cout == 16)
+        if layout == "wino16":
+            return wino
+        if layout == "wino8":
+            return wino and cin % 4 == 0
+        if layout in ("wino6", "winof16"):
+            return wino and cin % 16 == 0 and cin >= 32 and cout >= _WINO6_MIN_COUT
+        if layout == "small6":
+            return small and cin <= 256
+        if layout in ("lat", "lat_f16"):
+            return small
+        raise KeyError(layout)
+
+    def packed(self, layout, cin_pad=None):
+        """The weights in ``layout`` (a key of ``_LAYOUTS``) on the layer's device, packed from the live OIHW parameter and
+        re-packed when it changes: (tensor, CoutPad) for the layouts that carry one, the tensor otherwise."""
+        if layout == "hwio":
+            return self._cache.get(("hwio",), _stamp(self.weight), lambda: self.weight.detach().permute(2, 3, 1, 0).contiguous())
         if cin_pad is not None and cin_pad == self.weight.shape[1]:
             cin_pad = None
+        pack, int16, has_cout_pad = _LAYOUTS[layout]
 
         def build():
-            wp, cpad = nops.pack_conv_weights(self._hwio_numpy(cin_pad))
-            return torch.from_numpy(wp).to(self.weight.device), cpad
-        return self._cache.get(("direct", cin_pad), _stamp(self.weight), build)
+            # ``plan`` may only name a layout whose static condition holds: ``prepack`` builds those and no others, so a layout
+            # that breaks the rule is caught here, where it would be built late (tests/test_conv_dispatch.py checks every row)
+            assert self.can_use(layout, cin_pad or self.weight.shape[1]), (self.tag, layout, cin_pad)
+            res = pack(self._hwio_numpy(cin_pad))
+            wp, cpad = res if has_cout_pad else (res, None)
+            wp = torch.from_numpy(wp.view("int16") if int16 else wp).to(self.weight.device)
+            return (wp, cpad) if has_cout_pad else wp
+        return self._cache.get((layout, cin_pad), _stamp(self.weight), build)
 
-    def _packed_weights_winograd(self, chunk=16, cin_pad=None):
-        """(wu, CoutPad) for m4d_conv3x3_wino_bias_act (chunk 16) / wino2 (chunk 8): U = G g G^T, transformed on the host."""
-        if cin_pad is not None and cin_pad == self.weight.shape[1]:
-            cin_pad = None
-
-        def build():
-            wu, cpad = nops.pack_conv_weights_winograd(self._hwio_numpy(cin_pad), chunk=chunk)
-            return torch.from_numpy(wu).to(self.weight.device), cpad
-        return self._cache.get(("wino", chunk, cin_pad), _stamp(self.weight), build)
-
-    def _packed_weights_small6(self, cin_pad=None):
-        """(wp6 int16 bits, CoutPad) for m4d_conv3x3_small6_bias_act: the TF kernel split into three bf16 terms on the host."""
-        if cin_pad is not None and cin_pad == self.weight.shape[1]:
-            cin_pad = None
-
-        def build():
-            wp, cpad = nops.pack_conv_weights_small6(self._hwio_numpy(cin_pad))
-            return torch.from_numpy(wp.view("int16")).to(self.weight.device), cpad
-        return self._cache.get(("small6", cin_pad), _stamp(self.weight), build)
-
-    def _packed_weights_lat(self, cin_pad=None):
-        """wp (int16 bits) for m4d_conv3x3_lat: the TF kernel split into three bf16 terms, MFMA B-fragment order."""
-        if cin_pad is not None and cin_pad == self.weight.shape[1]:
-            cin_pad = None
-
-        def build():
-            wp = nops.pack_conv_weights_lat(self._hwio_numpy(cin_pad))
-            return torch.from_numpy(wp.view("int16")).to(self.weight.device)
-        return self._cache.get(("lat", cin_pad), _stamp(self.weight), build)
-
-    def _packed_weights_lat_f16(self, cin_pad=None):
-        """wp (int16 bits) for m4d_conv3x3_lat_f16: the TF kernel scaled per output channel and split into two fp16 terms,
-        MFMA B-fragment order, then the exponents."""
-        if cin_pad is not None and cin_pad == self.weight.shape[1]:
-            cin_pad = None
-
-        def build():
-            wp = nops.pack_conv_weights_lat_f16(self._hwio_numpy(cin_pad))
-            return torch.from_numpy(wp.view("int16")).to(self.weight.device)
-        return self._cache.get(("lat_f16", cin_pad), _stamp(self.weight), build)
-
-    def lat_f16(self, mw=False):
+    def lat_f16(self):
         """Does this layer's latency-first form run on the fp16 two-term kernel (m4d_conv3x3_lat_f16)?"""
-        return conv_arith == "f16x2" and lat_arith == "f16x2" and self.stride == 1 and not mw
+        return conv_arith == "f16x2" and self.stride == 1
 
     def lat_eligible(self, b, h, w, cin):
         """Would ``forward`` run this layer on the latency-first small-map kernel for an input of this shape?"""
-        if not (self.small_maps_ok and conv_arith in _SPLIT_ARITHS and cin >= 16 and cin % 4 == 0 and self.stride in (1, 2)):
+        if not (self.small_maps_ok and conv_arith in _SPLIT_ARITHS and cin >= 16 and cin % 4 == 0 and self.stride == 1):
             return False
         eff_b = self.dispatch_batch if self.per_image_dispatch else b
-        if self.stride == 2:                              # the stride-2 encoder layers: by OUTPUT pixels
-            opx = eff_b * (-(-h // 2)) * (-(-w // 2))
-            return self._lat_mw(b, h, w, cin) or (small_map_stride2 and opx <= lat_conv_s2_max_pixels)
-        limit = max(lat_conv_max_pixels, lat_conv_narrow_max_pixels) if self.out_channels <= 32 else lat_conv_max_pixels
-        return eff_b * h * w <= limit
-
-    def _lat_mw(self, b, h, w, cin):
-        """The M-over-waves form of the latency-first kernel for this (stride-2, narrow, short-K) layer?"""
-        eff_b = self.dispatch_batch if self.per_image_dispatch else b
-        return (self.stride == 2 and cin % 16 == 0 and cin <= 64 and self.out_channels <= 64
-                and small_map_conv_pixels < eff_b * (-(-h // 2)) * (-(-w // 2)) <= lat_conv_mw_max_pixels)
-
-    def _packed_weights_wino6(self, cin_pad=None):
-        """(wu6 int16 bits, CoutPad) for m4d_conv3x3_wino6_bias_act: U = G g G^T split into three bf16 terms on the host."""
-        if cin_pad is not None and cin_pad == self.weight.shape[1]:
-            cin_pad = None
-
-        def build():
-            wu, cpad = nops.pack_conv_weights_wino6(self._hwio_numpy(cin_pad))
-            return torch.from_numpy(wu.view("int16")).to(self.weight.device), cpad
-        return self._cache.get(("wino6", cin_pad), _stamp(self.weight), build)
-
-    def _packed_weights_winof16(self, cin_pad=None):
-        """(wuh int16 bits, CoutPad) for m4d_conv3x3_winof16_bias_act_ks: U = G g G^T scaled per output channel and split
-        into two fp16 terms on the host, then the exponents."""
-        if cin_pad is not None and cin_pad == self.weight.shape[1]:
-            cin_pad = None
-
-        def build():
-            wu, cpad = nops.pack_conv_weights_winof16(self._hwio_numpy(cin_pad))
-            return torch.from_numpy(wu.view("int16")).to(self.weight.device), cpad
-        return self._cache.get(("winof16", cin_pad), _stamp(self.weight), build)
-
-    def _hwio_device(self):
-        """The TF-layout [3,3,Cin,Cout] kernel as a contiguous device tensor (the encoder-head kernel reads it directly)."""
-        return self._cache.get(("hwio",), _stamp(self.weight), lambda: self.weight.detach().permute(2, 3, 1, 0).contiguous())
+        return eff_b * h * w <= lat_conv_max_pixels
 
     def same_pads(self, h, w):
         """TF 'SAME' (before, after) pads for rows and columns at this stride."""
@@ -504,10 +397,43 @@ class _Conv3x3SameTF(torch.nn.Module):
         """The staggered-first-round argument of this layer's Winograd launch on a [b,h,w] map: the layer's (= its model's) setting
         on launches that put a workgroup on every CU, 0 elsewhere.  Pure function of the layer and the shape -- no global state."""
         us = wino6_stagger_us if self.wino6_stagger_us is None else self.wino6_stagger_us
-        if us <= 0 or b > wino6_stagger_max_batch:
+        if us <= 0 or b > _WINO6_STAGGER_MAX_BATCH:
             return 0
         units = b * (-(-h // 16)) * (-(-w // 16)) * (-(-self.out_channels // 64))
-        return int(us) if units >= wino6_stagger_min_wg else 0
+        return int(us) if units >= _WINO6_STAGGER_MIN_WG else 0
+
+    def plan(self, b, h, w, cin, final=True):
+        """What ``forward`` does with a [b,h,w,cin] input: the kernel (a key of ``_CONV_LAUNCH``), the packed layout it reads and
+        the launch extras.  Pure: launches nothing, touches no tensor.
+        The encoder is run on frames stacked along the batch axis, and how many are stacked depends on the launch mode
+        (all T frames, two batches in the pipelined forward, one frame when streaming): its kernel choice must not
+        depend on that, or the modes stop being bit-identical -- it is decided from the per-image grid x the SEQUENCE batch
+        (``dispatch_batch``, set by the model from its input: the same in every launch mode), so that a batch-32 evaluation
+        does not run its coarse encoder levels on the latency kernels of a single small map."""
+        eff_b = self.dispatch_batch if self.per_image_dispatch else b
+        cout, s = self.out_channels, self.stride
+        if self.lat_eligible(b, h, w, cin):
+            # (configuration from the per-image grid x the dispatch batch, like the kernel choice: the same in every launch mode)
+            kernel = "lat_f16" if self.lat_f16() else "lat"
+            p = ConvPlan(kernel, kernel, nops.lat_config(eff_b, h, w, cin, cout, final), None, None)
+            return p
+        wino = _use_winograd(eff_b, h, w, cin, cout, s)
+        one_launch = (not wino and self.small_maps_ok and 16 <= cin <= 256 and cin % 4 == 0
+                      and eff_b * (-(-h // s)) * (-(-w // s)) <= small_map_conv_pixels)
+        if wino == 6:
+            # "f16x2": one workgroup per (tile, 64 couts) at every batch -- ahead of the bf16x3 persistent kernel at batch 32 too
+            # (DESIGN.md section 6), so the kernel choice does not depend on the batch at all
+            p = ConvPlan("wino6", "winof16" if conv_arith == "f16x2" else "wino6", None, wino6_kernel,
+                         self.launch_stagger_us(b, h, w))
+        elif wino:
+            p = ConvPlan("wino", "wino16", None, None, None) if wino == 1 else ConvPlan("wino2", "wino8", None, None, None)
+        elif one_launch and s == 1 and small_conv_split:
+            p = ConvPlan("small6", "small6", None, None, None)
+        elif one_launch:                                  # one launch instead of split-K + reduce (stride 2: by OUTPUT pixels)
+            p = ConvPlan("small", "direct", None, None, None)
+        else:
+            p = ConvPlan("direct", "direct", None, None, None)
+        return p
 
     def forward(self, x_nhwc, slope=None, final=True):
         """Convolution + bias (+ leaky_relu(slope) when ``slope`` is given): ONE hand-written HIP kernel.  There is no CPU /
@@ -525,59 +451,49 @@ class _Conv3x3SameTF(torch.nn.Module):
             self._build(x_nhwc.shape[-1], x_nhwc.device)
         if self.stride not in (1, 2):
             raise ValueError(f"stride {self.stride} is not supported by the HIP convolution")
-        b_, h_, w_, cin_ = x_nhwc.shape
+        p = self.plan(*x_nhwc.shape, final)
+        wts = self.packed(p.layout, x_nhwc.shape[-1])      # (more channels than the layer's Cin: a zero-padded input)
+        launch = _CONV_LAUNCH[p.kernel][1]
         act = 1.0 if slope is None else slope
-        # The encoder is run on frames stacked along the batch axis, and how many are stacked depends on the launch mode
-        # (all T frames, two batches in the pipelined forward, one frame when streaming): its kernel choice must not
-        # depend on that, or the modes stop being bit-identical -- decide from the per-image grid x the SEQUENCE batch
-        # (``dispatch_batch``, set by the model from its input: the same in every launch mode), so that a batch-32 evaluation
-        # does not run its coarse encoder levels on the latency kernels of a single small map.
-        eff_b = self.dispatch_batch if self.per_image_dispatch else b_
-        if self.lat_eligible(b_, h_, w_, cin_):
-            mw = self._lat_mw(b_, h_, w_, cin_)
-            # (configuration from the per-image grid x the dispatch batch, like the kernel choice: the same in every launch mode)
-            cfg = nops.lat_config(eff_b, h_, w_, cin_, self.out_channels, final, self.stride, mw=mw)
-            if self.lat_f16(mw):
-                wl = self._packed_weights_lat_f16(cin_)
-                return _timed("conv", self.tag, lambda: nops.conv3x3_lat_f16(x_nhwc, wl, self.bias, self.out_channels, act,
-                                                                         config=cfg))
-            wl = self._packed_weights_lat(cin_)
-            return _timed("conv", self.tag, lambda: nops.conv3x3_lat(x_nhwc, wl, self.bias, self.out_channels, act, config=cfg,
-                                                                     stride=self.stride))
-        wino = _use_winograd(eff_b, h_, w_, cin_, self.out_channels, self.stride)
-        if wino == 6:
-            # "f16x2": one workgroup per (tile, 64 couts) at every batch -- ahead of the bf16x3 persistent kernel at batch 32 too
-            # (DESIGN.md section 6), so the kernel choice does not depend on the batch at all
-            f16 = conv_arith == "f16x2"
-            wu, cpad = self._packed_weights_winof16(cin_) if f16 else self._packed_weights_wino6(cin_)
-            stag = self.launch_stagger_us(b_, h_, w_)
-            kern = wino6_kernel
-            if not f16 and kern == 0 and wino6_pair_min_units > 0 and b_ <= wino6_stagger_max_batch and cin_ >= 32:
-                units = b_ * (-(-h_ // 16)) * (-(-w_ // 16)) * (cpad // 64)
-                if wino6_pair_min_units <= units < int(lib.m4d_wino6_persistent_min_units()):
-                    kern = 16 + max(1, min(wino6_pair_units, 15))
-            return _timed("conv", self.tag, lambda: nops.conv3x3_wino6_bias_act(
-                x_nhwc, wu, self.bias, self.out_channels, cpad, act, kernel=kern, stagger_us=stag,
-                stagger_phases=wino6_stagger_phases, arith=conv_arith))
-        if wino:
-            wu, cpad = self._packed_weights_winograd(16 if wino == 1 else 8, cin_)     # cin_ > Cin: zero-padded input
-            fn = nops.conv3x3_wino_bias_act if wino == 1 else nops.conv3x3_wino2_bias_act
-            return _timed("conv", self.tag, lambda: fn(x_nhwc, wu, self.bias, self.out_channels, cpad, act))
-        wp, cpad = self._packed_weights(cin_)
-        if (self.small_maps_ok and self.stride == 1 and eff_b * h_ * w_ <= small_map_conv_pixels and 16 <= cin_ <= 256
-                and cin_ % 4 == 0):
-            if small_conv_split:
-                wp6, cpad6 = self._packed_weights_small6(cin_)
-                return _timed("conv", self.tag, lambda: nops.conv3x3_small6_bias_act(
-                    x_nhwc, wp6, self.bias, self.out_channels, cpad6, act))
-            return _timed("conv", self.tag, lambda: nops.conv3x3_small_bias_act(
-                x_nhwc, wp, self.bias, self.out_channels, cpad, act))
-        if (self.small_maps_ok and self.stride == 2 and small_map_stride2 and 16 <= cin_ <= 256 and cin_ % 4 == 0
-                and eff_b * (-(-h_ // 2)) * (-(-w_ // 2)) <= small_map_conv_pixels):
-            return _timed("conv", self.tag, lambda: nops.conv3x3_small_bias_act(      # one launch instead of split-K + reduce
-                x_nhwc, wp, self.bias, self.out_channels, cpad, act, stride=2))
-        return _timed("conv", self.tag, lambda: nops.conv3x3_bias_act(
-            x_nhwc, wp, self.bias, self.out_channels, cpad, act, stride=self.stride))
+        return _timed("conv", self.tag, lambda: launch(self, x_nhwc, wts, act, p))
+
+
+ConvPlan = namedtuple("ConvPlan", ("kernel", "layout", "lat_config", "wino6_kernel", "stagger_us"))
+
+# Packed weight layouts: pack function over the host HWIO kernel, whether the device copy is viewed as int16 (bf16 / fp16 bit
+# patterns), whether the pack function returns (weights, CoutPad).  ``_Conv3x3SameTF.can_use`` has each layout's condition.
+_LAYOUTS = {
+    "direct": (nops.pack_conv_weights, False, True),               # m4d_conv3x3_bias_act and the fp32 one-launch small-map kernel
+    "wino16": (lambda k: nops.pack_conv_weights_winograd(k, chunk=16), False, True),    # U = G g G^T, transformed on the host
+    "wino8": (lambda k: nops.pack_conv_weights_winograd(k, chunk=8), False, True),
+    "small6": (nops.pack_conv_weights_small6, True, True),         # the kernel split into three bf16 terms
+    "lat": (nops.pack_conv_weights_lat, True, False),              # ... in MFMA B-fragment order
+    "lat_f16": (nops.pack_conv_weights_lat_f16, True, False),      # scaled per output channel, two fp16 terms, then the exponents
+    "wino6": (nops.pack_conv_weights_wino6, True, True),           # U split into three bf16 terms
+    "winof16": (nops.pack_conv_weights_winof16, True, True),       # U scaled per output channel, two fp16 terms, then the exponents
+    "hwio": (None, False, False),                                  # the TF layout itself (the encoder's level-0 kernels read it)
+}
+
+# kernel of a ConvPlan -> (the network_ops wrapper it runs on, the launch: (layer, input, packed weights, slope, plan))
+_CONV_LAUNCH = {
+    "lat": ("conv3x3_lat", lambda c, x, w, act, p: nops.conv3x3_lat(
+        x, w, c.bias, c.out_channels, act, config=p.lat_config, stride=c.stride)),
+    "lat_f16": ("conv3x3_lat_f16", lambda c, x, w, act, p: nops.conv3x3_lat_f16(
+        x, w, c.bias, c.out_channels, act, config=p.lat_config)),
+    "wino6": ("conv3x3_wino6_bias_act", lambda c, x, w, act, p: nops.conv3x3_wino6_bias_act(
+        x, w[0], c.bias, c.out_channels, w[1], act, kernel=p.wino6_kernel, stagger_us=p.stagger_us,
+        stagger_phases=_WINO6_STAGGER_PHASES, arith=conv_arith)),
+    "wino": ("conv3x3_wino_bias_act", lambda c, x, w, act, p: nops.conv3x3_wino_bias_act(
+        x, w[0], c.bias, c.out_channels, w[1], act)),
+    "wino2": ("conv3x3_wino2_bias_act", lambda c, x, w, act, p: nops.conv3x3_wino2_bias_act(
+        x, w[0], c.bias, c.out_channels, w[1], act)),
+    "small6": ("conv3x3_small6_bias_act", lambda c, x, w, act, p: nops.conv3x3_small6_bias_act(
+        x, w[0], c.bias, c.out_channels, w[1], act)),
+    "small": ("conv3x3_small_bias_act", lambda c, x, w, act, p: nops.conv3x3_small_bias_act(
+        x, w[0], c.bias, c.out_channels, w[1], act, stride=c.stride)),
+    "direct": ("conv3x3_bias_act", lambda c, x, w, act, p: nops.conv3x3_bias_act(
+        x, w[0], c.bias, c.out_channels, w[1], act, stride=c.stride)),
+}
 
 
 class DomainNormalization(torch.nn.Module):
@@ -635,7 +551,7 @@ class FeaturePyramid(torch.nn.Module):
             conv.dispatch_batch = b
 
     def _head_ok(self, images):
-        return (self.use_dinl and fused_encoder_head and images.is_cuda and images.shape[-1] == 3
+        return (self.use_dinl and images.is_cuda and images.shape[-1] == 3
                 and self.conv_layers_s1[0].out_channels == 16 and self.conv_layers_s2[0].out_channels <= 32
                 and self.conv_layers_s1[0].weight is not None)
 
@@ -646,7 +562,7 @@ class FeaturePyramid(torch.nn.Module):
         if not (self._head_ok(images) and fused_encoder_level0 and self.conv_layers_s2[0].out_channels == 16):
             return None
         conv_s1 = self.conv_layers_s1[0]
-        return _timed("enc0_stats", 0, lambda: nops.encoder_level0_stats(images, conv_s1._hwio_device(), conv_s1.bias))
+        return _timed("enc0_stats", 0, lambda: nops.encoder_level0_stats(images, conv_s1.packed("hwio"), conv_s1.bias))
 
     def forward(self, images, head_stats=None):
         """``images``: [b,H,W,3], or a ``network_ops.FrameStack`` (the frames of a sequence batch, encoded in one pass)."""
@@ -664,24 +580,21 @@ class FeaturePyramid(torch.nn.Module):
                 if fused_encoder_level0 and conv_s2.out_channels == 16:
                     # one call, no [b,H,W,16] intermediate: the 3 -> 16 convolution recomputed on the matrix cores per pass
                     feature_maps = _timed("enc0", 0, lambda: nops.encoder_level0(
-                        feature_maps, conv_s1._hwio_device(), conv_s1.bias, dn_layer.scale, dn_layer.bias,
-                        conv_s2._hwio_device(), conv_s2.bias, 0.1, stats=head_stats))
+                        feature_maps, conv_s1.packed("hwio"), conv_s1.bias, dn_layer.scale, dn_layer.bias,
+                        conv_s2.packed("hwio"), conv_s2.bias, 0.1, stats=head_stats))
                     outputs.append(feature_maps)
                     continue
-                wp2, cpad2 = conv_s2._packed_weights()
-                feature_maps = nops.encoder_head(feature_maps, conv_s1._hwio_device(), conv_s1.bias, dn_layer.scale, dn_layer.bias,
+                wp2, cpad2 = conv_s2.packed("direct")
+                feature_maps = nops.encoder_head(feature_maps, conv_s1.packed("hwio"), conv_s1.bias, dn_layer.scale, dn_layer.bias,
                                                  wp2, conv_s2.bias, conv_s2.out_channels, cpad2, 0.1)
                 outputs.append(feature_maps)
                 continue
             if self.use_dinl and i == 0:
                 tmp = dn_layer(conv_s1(feature_maps), slope=0.1)
             else:
-                # (consumed by conv_s2 alone: on the latency-first small-map kernels it may stay K-slice partial sums -- but only
-                #  when conv_s2 is itself such a kernel and adds the slabs while it stages; otherwise the slabs would need a
-                #  finishing launch of their own, a dependent launch on the encoder's latency chain)
-                fb, fh, fw = feature_maps.shape[:3]
-                takes_slabs = conv_s2.lat_eligible(fb, fh, fw, conv_s1.out_channels)
-                tmp = conv_s1(feature_maps, slope=0.1, final=not (takes_slabs or encoder_s1_partial_always))
+                # (a finished tensor: conv_s2, stride 2, never runs on the latency-first kernel, so K-slice partial sums would need
+                #  a finishing launch of their own, a dependent launch on the encoder's latency chain)
+                tmp = conv_s1(feature_maps, slope=0.1)
             feature_maps = conv_s2(tmp, slope=0.1)
             outputs.append(feature_maps)
         return outputs
@@ -769,7 +682,7 @@ class DepthEstimatorLevel(torch.nn.Module):
     def reset_job(self, curr_f_maps):
         """This level's buffers for the one-launch pyramid reset (``nops.pyramid_reset``), or None when its reset branch has to
         go through ``forward`` (training, features kept raw, a cut width the group kernel does not cover)."""
-        if self.is_training or not fused_level_front or not self.ablation.normalize_features:
+        if self.is_training or not self.ablation.normalize_features:
             return None
         if not isinstance(curr_f_maps, torch.Tensor) or not curr_f_maps.is_cuda or curr_f_maps.dim() != 4:
             return None
@@ -787,22 +700,13 @@ class DepthEstimatorLevel(torch.nn.Module):
         """Packed weights of the fused level tail (conv 32->16, conv 16->5), built once per device: the fp32-MFMA kernel's
         (m4d_refiner_tail) or, ``split``, the bf16-split kernel's B fragments (m4d_refiner_tail6)."""
         def build():
-            k6 = convs[5].weight.detach().permute(2, 3, 1, 0).cpu().numpy()
-            k7 = convs[6].weight.detach().permute(2, 3, 1, 0).cpu().numpy()
-            w6, w7 = nops.pack_refiner_tail_weights(k6, k7)
+            pack = nops.pack_refiner_tail_weights6 if split else nops.pack_refiner_tail_weights
             dev = convs[5].weight.device
-            return torch.from_numpy(w6).to(dev), torch.from_numpy(w7).to(dev)
-        def build6():
-            k6 = convs[5].weight.detach().permute(2, 3, 1, 0).cpu().numpy()
-            k7 = convs[6].weight.detach().permute(2, 3, 1, 0).cpu().numpy()
-            w6, w7 = nops.pack_refiner_tail_weights6(k6, k7)
-            dev = convs[5].weight.device
-            return torch.from_numpy(w6.view("int16")).to(dev), torch.from_numpy(w7.view("int16")).to(dev)
+            return tuple(torch.from_numpy(w.view("int16") if split else w).to(dev)
+                         for w in pack(convs[5]._hwio_numpy(), convs[6]._hwio_numpy()))
         if getattr(self, "_tail_cache", None) is None:
             self._tail_cache = _PackCache()
-        if split:
-            return self._tail_cache.get("tail6", _stamp(convs[5].weight, convs[6].weight), build6)
-        return self._tail_cache.get("tail", _stamp(convs[5].weight, convs[6].weight), build)
+        return self._tail_cache.get("tail6" if split else "tail", _stamp(convs[5].weight, convs[6].weight), build)
 
     def _vector_processing(self, f_map, out=None):
         if self.ablation.normalize_features:                                          # :179-182
@@ -816,7 +720,7 @@ class DepthEstimatorLevel(torch.nn.Module):
         """Does a [b,h,w,c] map of this level take the big-tile fused front (``m4d_level_front_r``)?  (size and shape part of
         ``forward``'s decision)"""
         k = self.nbre_cuts
-        F_st = (self.f_in + 7) // 8 * 8 if pad_refiner_input else self.f_in
+        F_st = _padded_refiner_width(self.f_in)
         return (fused_front and b * h * w > (fused_front_min_pixels if k <= 2 else max(fused_front_min_pixels, fused_front_coarse_min_pixels))
                 and bool(lib.m4d_level_front_supported(c, k, self.dscv_range, self.sncv_range, F_st)))
 
@@ -825,7 +729,7 @@ class DepthEstimatorLevel(torch.nn.Module):
         should the caller hand it per-cut normalised features (``forward(..., curr_f_normalized=...)``,
         ``network_ops.normalize_levels``)?"""
         ab = self.ablation
-        return (small_level_front and fused_cost_volumes and fused_level_front and not self.is_training
+        return (not self.is_training
                 and ab.SNCV and ab.time_recurr and ab.normalize_features and ab.level_memory
                 and b * h * w <= 6000 and not self._front_by_size(b, h, w, c)
                 and bool(lib.m4d_pyramid_reset_supported(c, self.nbre_cuts))
@@ -858,15 +762,14 @@ class DepthEstimatorLevel(torch.nn.Module):
             nt = bool(np.asarray(nt).reshape(-1)[0])
         ab = self.ablation
         F_in = self.f_in
-        F_st = (F_in + 7) // 8 * 8 if (pad_refiner_input and dev.type == "cuda" and not self.is_training) else F_in
+        F_st = _padded_refiner_width(F_in) if (dev.type == "cuda" and not self.is_training) else F_in
         # the fused level front: normalisation, upsampling, both cost volumes and the log features in one launch
-        use_front = (fused_front and use_state and not nt and dev.type == "cuda" and self._spare_f is not None
+        use_front = (use_state and not nt and dev.type == "cuda" and self._spare_f is not None
                      and ab.SNCV and ab.time_recurr and ab.normalize_features and ab.level_memory
-                     and b * h * w > (fused_front_min_pixels if k <= 2 else max(fused_front_min_pixels, fused_front_coarse_min_pixels))
-                     and bool(lib.m4d_level_front_supported(c, k, self.dscv_range, self.sncv_range, F_st)))
+                     and self._front_by_size(b, h, w, c))
         # a coarse level whose features arrive normalised: level_pre + DSCV + SNCV in one launch (m4d_level_front_small)
         use_small = (curr_f_normalized is not None and not use_front and use_state and not nt and dev.type == "cuda"
-                     and kernel_timer_allows_small_front() and self.wants_prenormalized(b, h, w, c)
+                     and self.wants_prenormalized(b, h, w, c)
                      and tuple(curr_f_normalized.shape) == (b, h, w, c))
         # normalised current features land in the spare state buffer: after the level
         # ran they ARE the new prev_f_maps (:211, :259) -- a pointer swap, not a copy.
@@ -877,7 +780,7 @@ class DepthEstimatorLevel(torch.nn.Module):
             curr_f = self._spare_f
         elif use_small:
             curr_f = as_f32(curr_f_normalized, "curr_f_normalized")
-        elif (fused_level_front and self.ablation.normalize_features and dev.type == "cuda" and not self.is_training
+        elif (self.ablation.normalize_features and dev.type == "cuda" and not self.is_training
                 and prev_f_maps is None and self._spare_f is not None and c % self.nbre_cuts == 0):
             curr_f = self._spare_f
             norm_job = (curr_f_maps, self.nbre_cuts, curr_f)
@@ -924,14 +827,14 @@ class DepthEstimatorLevel(torch.nn.Module):
         log_ptr = ctypes.c_void_p(fin_ptr + 4 * (F_in - 1)) if time_recurr else None      # channel F_in - 1 of a stride-F_st row
         # DSCV (:220-221) -> f_input[..., 0:9k]; time-recurrence feature (:238) -> f_input[..., -1]
         prev_f = as_f32(prev_f_maps, "prev_f_maps")
-        kt_on = kernel_timer is not None and getattr(kernel_timer, "enabled", True)
-        if use_front:
+        if use_front or use_small:                    # the coarser level's estimate: upsampled inside the front kernels
             pp = po = None
             ph = pw = 0
             if prev_l_est is not None:
                 pp = as_f32(prev_l_est["parallax"], "prev_l_est['parallax']")
                 po = as_f32(prev_l_est["other"], "prev_l_est['other']")
                 ph, pw = pp.shape[1:3]
+        if use_front:
             check(_timed("front", self.lvl_depth, lambda: lib.m4d_level_front_r(
                 dptr(curr_f_maps, "curr_f_maps"), dptr(curr_f), dptr(prev_f), dptr(as_f32(prev_t_depth, "prev_t_depth")),
                 dptr(pp), dptr(po), ph, pw, dptr(rot_t), rot_t.shape[1], dptr(tr), dptr(cf), dptr(cc),
@@ -939,19 +842,13 @@ class DepthEstimatorLevel(torch.nn.Module):
                 stream_ptr())), "m4d_level_front_r")
             para_prev_t = para_prev_l = None
         elif use_small:
-            pp = po = None
-            ph = pw = 0
-            if prev_l_est is not None:
-                pp = as_f32(prev_l_est["parallax"], "prev_l_est['parallax']")
-                po = as_f32(prev_l_est["other"], "prev_l_est['other']")
-                ph, pw = pp.shape[1:3]
             # (timed as "dscv_sncv" by bench.py: the launch that opens the level in the graph)
             check(_timed("dscv_sncv", self.lvl_depth, lambda: lib.m4d_level_front_small(
                 dptr(curr_f), dptr(prev_f), dptr(as_f32(prev_t_depth, "prev_t_depth")), dptr(pp), dptr(po), ph, pw,
                 dptr(rot_t), rot_t.shape[1], dptr(tr), dptr(cf), dptr(cc), b, h, w, c, k, self.dscv_range, self.sncv_range,
                 _CV_ACCUM[self.cv_accum], ctypes.c_void_p(fin_ptr), F_st, scale, stream_ptr())), "m4d_level_front_small")
             para_prev_t = para_prev_l = None
-        elif fused_cost_volumes and self.ablation.SNCV and dev.type == "cuda" and b * h * w <= 6000:
+        elif self.ablation.SNCV and dev.type == "cuda" and b * h * w <= 6000:
             # small maps: both (independent) cost volumes in one launch (timed as "dscv_sncv" by bench.py: the launch the graph replays)
             check(_timed("dscv_sncv", self.lvl_depth, lambda: lib.m4d_dscv_sncv_fwd(
                 dptr(curr_f), dptr(prev_f), dptr(para_prev_t), dptr(para_prev_l), dptr(rot_t), rot_t.shape[1],
@@ -1001,10 +898,12 @@ class DepthEstimatorLevel(torch.nn.Module):
         return {"other": other, "depth": depth, "parallax": para_curr_l}
 
 
-def kernel_timer_allows_small_front():
-    """(bench.py's per-kernel timer brackets the launches the graph replays: nothing to switch off -- kept as the one place
-    where a measurement mode could ask for the separate kernels)"""
-    return True
+def anti_diagonals(frames, n_lvls):
+    """The (frame, level step) cells of ``frames`` x ``range(n_lvls)`` by anti-diagonals, earlier frame first inside one:
+    step l of frame t right after step l of frame t - 1.  The issue order of the frame pipeline."""
+    frames = list(frames)
+    return [(frames[i], diag - i) for diag in range(len(frames) + n_lvls - 1)
+            for i in range(max(0, diag - n_lvls + 1), min(len(frames), diag + 1))]
 
 
 class DepthEstimatorPyramid(torch.nn.Module):
@@ -1053,8 +952,8 @@ class DepthEstimatorPyramid(torch.nn.Module):
         return 0 if torch.cuda.is_current_stream_capturing() else n_streams      # eager: streams reused round-robin
 
     def forward(self, f_maps_pyrs, traj_samples, camera, training=False, encoder=None, n_maps_pyrs=None):
-        """``f_maps_pyrs`` = per-frame feature pyramids, or None with ``encoder`` given: the pipelined path then
-        encodes every frame on that frame's stream (overlapping with the decoder of the frames before it).
+        """``f_maps_pyrs`` = per-frame feature pyramids; an entry may be None with ``encoder`` given (the pipelined path
+        only): those frames are the late encoder batch, encoded on the stream of the first of them.
         ``n_maps_pyrs`` (optional) = per frame the ``prenormalize``d maps of that frame's pyramid (None entries allowed)."""
         d_est_seq = []
         n_lvls = len(self.levels)
@@ -1068,8 +967,6 @@ class DepthEstimatorPyramid(torch.nn.Module):
         n_pipe = self.pipeline_streams_for(traj_samples, dev)
         if n_pipe >= 2:
             return self._forward_pipelined(f_maps_pyrs, traj_samples, local_cameras, n_pipe, encoder, n_maps_pyrs)
-        if f_maps_pyrs is None:
-            f_maps_pyrs = [encoder(sample['RGB_im']) for sample in traj_samples]
         if n_maps_pyrs is None:
             n_maps_pyrs = [None] * len(f_maps_pyrs)
         for seq_i, (f_pyr_curr, sample) in enumerate(zip(f_maps_pyrs, traj_samples)):
@@ -1161,18 +1058,13 @@ class DepthEstimatorPyramid(torch.nn.Module):
             pv *= 2.0
         return ests[::-1]
 
-    def _forward_pipelined(self, f_maps_pyrs, traj_samples, local_cameras, n_streams, encoder=None, n_maps_pyrs=None,
-                           resume=None):
+    def _forward_pipelined(self, f_maps_pyrs, traj_samples, local_cameras, n_streams, encoder=None, n_maps_pyrs=None):
         """The same loop as a wavefront over (frame, level) on ``n_streams`` HIP streams: frame t runs on
         stream t % n; before level l of frame t it waits for the event recorded after level l of frame
         t-1 (the level's temporal memory).  Inside a stream the levels stay in coarse-to-fine order.
         Works eagerly and under hipGraph capture (the side streams fork from / join the capturing one;
-        under capture the caller guarantees one stream per frame).
-
-        ``resume`` = {frame: its estimates so far, coarse -> fine}: those (frame, level) cells ran BEFORE this call, ordered ahead
-        of it on the calling stream (``SegmentedSequence``: the reset frame and the first full frame's coarse levels are graphs of
-        their own); the wavefront continues from there -- every feature pyramid is given, only the streams with work left fork
-        and join, and a wait for a cell that ran earlier is dropped (the calling stream orders it)."""
+        under capture the caller guarantees one stream per frame).  ``f_maps_pyrs``: per frame its feature pyramid, or
+        None for the frames of the late encoder batch, which ``encoder`` encodes on the stream of the first of them."""
         n_lvls = len(self.levels)
         main = torch.cuda.current_stream()
         if getattr(self, "_streams", None) is None or len(self._streams) < n_streams:
@@ -1183,108 +1075,76 @@ class DepthEstimatorPyramid(torch.nn.Module):
         fork.record(main)
         keep.append(fork)
         n_fr = len(traj_samples)
-        ran = set() if resume is None else {(f, l) for f, ests in resume.items() for l in range(len(ests))}
 
         def is_reset(f):
             nt = traj_samples[f]["new_traj"]
             return bool(nt.reshape(-1)[0].item()) if isinstance(nt, torch.Tensor) else bool(np.asarray(nt).reshape(-1)[0])
-        # frame -> stream: one per frame; with pipeline_merge_reset_frame a reset frame rides on the next frame's stream
+        # frame -> stream: one per frame, but a reset frame (new_traj: six state-seeding launches of a few microseconds) rides on
+        # the stream of the frame that follows it: the first full frame's coarse-to-fine chain then has no cross-stream wait in
+        # front of every level (each such wait is a ~4.7 us gap in the executor's queue, profiles/r05_queue_trace_b1_graph.txt, on
+        # a chain that runs with the chip otherwise idle)
         stream_of = list(range(n_fr))
-        if resume is not None and segmented_resumed_on_main:
-            # a frame under way continues on the CALLING stream (-1), the others fork
-            stream_of = [-1 if 0 < len(resume.get(f, [])) < n_lvls else f for f in range(n_fr)]
-        if pipeline_merge_reset_frame and resume is None:
-            for f in range(n_fr - 1):
-                if is_reset(f) and not is_reset(f + 1):
-                    stream_of[f] = f + 1
+        for f in range(n_fr - 1):
+            if is_reset(f) and not is_reset(f + 1):
+                stream_of[f] = f + 1
 
         def launches_encoder(f):
-            """Frame ``f`` issues an encoder pass on its own stream (reads the input images, produced on the main stream)."""
-            return f_maps_pyrs is None or (f_maps_pyrs[f] is None and (f == 0 or f_maps_pyrs[f - 1] is not None))
+            """Frame ``f`` issues the late encoder pass on its own stream (reads the input images, produced on the main stream)."""
+            return f_maps_pyrs[f] is None and (f == 0 or f_maps_pyrs[f - 1] is not None)
 
         def needs_fork(i_st):
             """Does stream ``i_st`` wait for the fork event itself?  It MUST when it hosts frame 0 (nothing else orders it behind
             the main stream's encoder -- also when a merged reset frame moved frame 0 onto it) or a frame that launches an encoder
             pass.  For the others the wait is implied by their wait for the previous frame's level -- but the redundant edge is not
             neutral: ROCm 7.2's hipGraph executor assigns nodes to its four streams from the edges it sees.
-            ``pipeline_fork_frames`` = the streams (= frames, one stream per frame under capture) that keep the explicit wait."""
-            hosted = [f for f in range(n_fr) if stream_of[f] % n_streams == i_st]
-            if resume is not None:                    # nothing but the fork orders a resumed frame behind the calling stream
+            ``_PIPELINE_FORK_FRAMES`` = the streams (= frames, one stream per frame under capture) that keep the explicit wait."""
+            if i_st == 0 or i_st >= n_fr:
                 return True
-            if i_st == 0 or i_st >= n_fr or f_maps_pyrs is None:
+            if any(f == 0 or launches_encoder(f) for f in range(n_fr) if stream_of[f] % n_streams == i_st):
                 return True
-            if any(f == 0 or launches_encoder(f) for f in hosted):
-                return True
-            return pipeline_fork_frames is None or i_st in pipeline_fork_frames
-        # the streams that host a (frame, level) cell of this call (all of them unless the call resumes a sequence)
-        active = [i_st for i_st in range(len(streams))
-                  if resume is None or any((f, l) not in ran for f in range(n_fr)
-                                           if stream_of[f] >= 0 and stream_of[f] % n_streams == i_st for l in range(n_lvls))]
-        for i_st in active:
+            return i_st in _PIPELINE_FORK_FRAMES
+        for i_st, st in enumerate(streams):
             if needs_fork(i_st):
-                streams[i_st].wait_event(fork)        # encoder outputs / inputs are produced on the main stream
+                st.wait_event(fork)                   # encoder outputs / inputs are produced on the main stream
         done = {}
-        late_encoder = None
         n_pyrs = list(n_maps_pyrs) if n_maps_pyrs is not None else [None] * n_fr
-        f_pyrs = [None] * n_fr if resume is None else list(f_maps_pyrs)
+        f_pyrs = list(f_maps_pyrs)
         d_est = [None] * n_fr                         # per frame: estimates so far, coarse -> fine
-        if resume is not None:
-            for f, ests in resume.items():
-                d_est[f] = list(ests)
         # (Measured, tools/step_profile.py + tools/ab_bench.sh: the late encoder batch below is independent of the first
         # frames' decoder, yet issuing it FIRST so that it runs beside their coarse-level chain costs 4.5 % -- chip-filling
         # kernels delay the chain's small ones; where it is issued now it overlaps the first level-1 pass instead.)
-        # Issue order = anti-diagonals of the (frame, level) grid: level l of frame t right after level l of frame
-        # t-1.  Every stream still sees its own frame coarse -> fine, but the launch (and hipGraph node) order puts
-        # the next frame's coarse levels ahead of the current frame's fine ones.
+        # Issue order = anti-diagonals of the (frame, level) grid: every stream still sees its own frame coarse -> fine, but the
+        # launch (and hipGraph node) order puts the next frame's coarse levels ahead of the current frame's fine ones.
         # (The capture order matters to ROCm's hipGraph executor: a node's FIRST-captured child continues its parent's node list
         # on the same executor stream.  Frame-major order gives the same layout as this one; later-frame-first inside a diagonal
         # or level-major order turn the lists level-major and cost 16 %: profiles/r04_graph_executor.txt.)
-        order = [(seq_i, diag - seq_i) for diag in range(n_fr + n_lvls - 1)
-                 for seq_i in range(max(0, diag - n_lvls + 1), min(n_fr, diag + 1))]
-
-        if pipeline_merge_reset_frame:
+        order = anti_diagonals(range(n_fr), n_lvls)
+        if stream_of[0] != 0:
             # a merged reset frame must be ISSUED before the frame it shares the stream with reaches the same level: issue the
             # whole reset frame first (it is six tiny launches)
             # (only the reset frame that OPENS the sequence: a later one waits on the frame before it, level by level, and keeps
             # its place on the anti-diagonals -- still ahead of the frame it shares the stream with)
-            merged = [f for f in range(n_fr) if stream_of[f] != f and f == 0]
-            order = [(f, l) for f in merged for l in range(n_lvls)] + [(f, l) for (f, l) in order if f not in merged]
+            order = [(0, l) for l in range(n_lvls)] + [(f, l) for (f, l) in order if f != 0]
         fused_reset_frames = set()
-        order = [cell for cell in order if cell not in ran]
-        if resume is not None and segmented_resumed_first:
-            # the cells of a frame that was under way when the call resumed go FIRST: they depend on nothing inside this call, and
-            # the hipGraph executor lays a graph out in capture order
-            part = {f for f in resume if 0 < len(resume[f]) < n_lvls}
-            order = [c for c in order if c[0] in part] + [c for c in order if c[0] not in part]
         for seq_i, l in order:
             lvl = n_lvls - 1 - l
             sample = traj_samples[seq_i]
-            st = main if stream_of[seq_i] < 0 else streams[stream_of[seq_i] % n_streams]
+            st = streams[stream_of[seq_i] % n_streams]
             with torch.cuda.stream(st):
-                if l == 0:
-                    if f_maps_pyrs is None:          # per-frame encoder on the frame's own stream
-                        f_pyrs[seq_i] = encoder(sample['RGB_im'])
-                        n_pyrs[seq_i] = self.prenormalize(f_pyrs[seq_i], sample['RGB_im'].shape[0])
-                    elif f_maps_pyrs[seq_i] is not None:
-                        f_pyrs[seq_i] = f_maps_pyrs[seq_i]
-                    elif f_pyrs[seq_i] is None:      # first frame of the late encoder batch: encode all remaining frames here
-                        rest = [i for i in range(seq_i, n_fr) if f_maps_pyrs[i] is None]
-                        bsz = sample['RGB_im'].shape[0]
-                        tail = encoder(_stack_frames([traj_samples[i] for i in rest]))
-                        ntail = self.prenormalize(tail, bsz)     # the coarse levels' normalised maps of the whole batch: one launch
-                        for j, i in enumerate(rest):
-                            f_pyrs[i] = [lvl[j * bsz:(j + 1) * bsz] for lvl in tail]
-                            n_pyrs[i] = self._frame_slice(ntail, j, bsz)
-                        enc_done = torch.cuda.Event()
-                        enc_done.record(st)
-                        keep.append(enc_done)
-                        late_encoder = (seq_i, enc_done)
-                    elif not (pipeline_skip_implied_encoder_wait and seq_i - 1 >= late_encoder[0]):
-                        # a later frame of that batch: its features come from another stream (implied by the wait on the
-                        # previous frame's level below when that frame is of the same encoder batch)
-                        st.wait_event(late_encoder[1])
-                if seq_i > 0 and stream_of[seq_i - 1] != stream_of[seq_i] and (seq_i - 1, l) not in ran:
+                if l == 0 and f_pyrs[seq_i] is None:
+                    # first frame of the late encoder batch: encode all remaining frames here (the later ones need no wait of
+                    # their own for it: their wait on the previous frame's level below implies it)
+                    rest = [i for i in range(seq_i, n_fr) if f_maps_pyrs[i] is None]
+                    bsz = sample['RGB_im'].shape[0]
+                    tail = encoder(_stack_frames([traj_samples[i] for i in rest]))
+                    ntail = self.prenormalize(tail, bsz)     # the coarse levels' normalised maps of the whole batch: one launch
+                    for j, i in enumerate(rest):
+                        f_pyrs[i] = [lvl[j * bsz:(j + 1) * bsz] for lvl in tail]
+                        n_pyrs[i] = self._frame_slice(ntail, j, bsz)
+                    enc_done = torch.cuda.Event()
+                    enc_done.record(st)
+                    keep.append(enc_done)
+                if seq_i > 0 and stream_of[seq_i - 1] != stream_of[seq_i]:
                     st.wait_event(done[(seq_i - 1, lvl)])           # (same stream: ordered by the stream itself)
                 if l == 0 and seq_i == 0:
                     # a reset frame that opens the sequence: ONE launch seeds every level (a later reset frame would have to wait
@@ -1309,7 +1169,7 @@ class DepthEstimatorPyramid(torch.nn.Module):
                 done[(seq_i, lvl)] = ev
                 d_est[seq_i] = [est] if d_est[seq_i] is None else d_est[seq_i] + [est]
         d_est_seq = [ests[::-1] for ests in d_est]
-        for st in (streams[i_st] for i_st in active):  # join
+        for st in streams:                            # join
             ev = torch.cuda.Event()
             ev.record(st)
             main.wait_event(ev)
@@ -1373,49 +1233,30 @@ class M4Depth(torch.nn.Module):
                 conv.load_hwio(weights[f"lvl.{lvl.lvl_depth}.conv.{i}.kernel"], weights[f"lvl.{lvl.lvl_depth}.conv.{i}.bias"], device)
         return self.prepack()
 
-    def prepack(self):
-        """Build every packed weight layout a layer can be dispatched to (direct, Winograd 16 / 8-channel chunks) NOW:
-        which one is used depends on the batch and map size, packing is host work (a device-to-host copy), and that must
-        never happen lazily inside a hipGraph capture."""
+    def prepack_jobs(self):
+        """(layer, input channels, packed layouts) for every convolution and every width of input it is given -- its own Cin,
+        and for a level's first refiner layer the zero-padded refiner input (``DepthEstimatorLevel.forward``) as well: every
+        layout whose static condition (``_Conv3x3SameTF.can_use``) holds, i.e. every layout ``plan`` can name."""
         for conv in self.modules():
-            if isinstance(conv, _Conv3x3SameTF) and conv.weight is not None and conv.weight.is_cuda:
+            if isinstance(conv, _Conv3x3SameTF) and conv.weight is not None:
                 cin = conv.weight.shape[1]
-                conv._packed_weights()
-                if small_conv_split and conv.small_maps_ok and conv.stride == 1 and 16 <= cin <= 256 and cin % 4 == 0:
-                    conv._packed_weights_small6()
-                if conv.small_maps_ok and conv_arith in _SPLIT_ARITHS and cin >= 16 and cin % 4 == 0 and (
-                        (conv.stride == 1 and max(lat_conv_max_pixels, lat_conv_narrow_max_pixels) > 0)
-                        or (conv.stride == 2 and max(lat_conv_s2_max_pixels, lat_conv_mw_max_pixels) > 0)):
-                    conv._packed_weights_lat()
-                    if conv.stride == 1:
-                        conv._packed_weights_lat_f16()   # (whatever the arithmetic now: conv_arithmetic() may switch it later)
-                if cin == 3 or (conv.stride == 2 and cin == 16 and conv.out_channels == 16):
-                    conv._hwio_device()                # the encoder's level-0 kernels read the TF layout directly
-                if conv.stride == 1 and cin >= 16 and cin % 2 == 0:
-                    conv._packed_weights_winograd(16)
-                    if cin % 4 == 0:
-                        conv._packed_weights_winograd(8)
-                    if cin % 16 == 0 and cin >= 32 and conv.out_channels >= min(wino6_min_cout, 32):
-                        conv._packed_weights_wino6()    # the dispatch's own condition (_use_winograd): a replayed hipGraph is
-                                                        # refreshed through prepack() alone, so every layout a layer CAN be
-                                                        # dispatched to must be (re)built here (round 4 left 64 -> 32 out)
-                        conv._packed_weights_winof16()
+                yield conv, cin, [k for k in _LAYOUTS if conv.can_use(k, cin)]
+        for lvl in self.d_estimator.levels:
+            c0 = lvl.disp_refiner.prep_conv_layers[0]
+            if c0.weight is not None and c0.weight.shape[1] % 8 != 0:
+                cin_pad = _padded_refiner_width(c0.weight.shape[1])
+                yield c0, cin_pad, [k for k in _LAYOUTS if c0.can_use(k, cin_pad)]
+
+    def prepack(self):
+        """Build every packed weight layout a layer can be dispatched to NOW: which one is used depends on the batch, the map
+        size and the arithmetic, packing is host work (a device-to-host copy), and that must never happen lazily inside a
+        hipGraph capture.  A replayed hipGraph is refreshed through this method alone."""
+        for conv, cin, layouts in self.prepack_jobs():
+            if conv.weight.is_cuda:
+                for layout in layouts:
+                    conv.packed(layout, cin)
         for lvl in self.d_estimator.levels:
             convs = list(lvl.disp_refiner.prep_conv_layers) + list(lvl.disp_refiner.est_d_conv_layers)
-            c0 = convs[0] if convs else None
-            if pad_refiner_input and c0 is not None and c0.weight is not None and c0.weight.is_cuda and c0.weight.shape[1] % 8 != 0:
-                cin_pad = (c0.weight.shape[1] + 7) // 8 * 8           # the zero-padded refiner input (DepthEstimatorLevel.forward)
-                c0._packed_weights(cin_pad)
-                c0._packed_weights_winograd(16, cin_pad)
-                c0._packed_weights_winograd(8, cin_pad)
-                if small_conv_split and cin_pad <= 256:
-                    c0._packed_weights_small6(cin_pad)
-                if conv_arith in _SPLIT_ARITHS and lat_conv_max_pixels > 0:
-                    c0._packed_weights_lat(cin_pad)
-                    c0._packed_weights_lat_f16(cin_pad)
-                if cin_pad % 16 == 0 and cin_pad >= 32 and c0.out_channels >= min(wino6_min_cout, 32):
-                    c0._packed_weights_wino6(cin_pad)
-                    c0._packed_weights_winof16(cin_pad)
             if len(convs) == 7 and convs[5].weight is not None and convs[5].weight.is_cuda \
                     and tuple(convs[5].weight.shape[:2]) == (16, 32) and tuple(convs[6].weight.shape[:2]) == (5, 16):
                 lvl._tail_weights(convs, tail_split and conv_arith in _SPLIT_ARITHS)
@@ -1506,9 +1347,7 @@ class M4Depth(torch.nn.Module):
         n_maps_pyrs = None
         same_shape = all(s['RGB_im'].shape == traj_samples[0]['RGB_im'].shape for s in traj_samples)
         self.encoder.set_sequence_batch(traj_samples[0]['RGB_im'].shape[0])
-        if pipeline_encoder_per_frame and self.d_estimator.pipeline_streams_for(traj_samples, dev) >= 2:
-            f_maps_pyrs = None                     # encoded per frame, on the frame's stream, inside the decoder pipeline
-        elif pipeline_encoder_split > 0 and n_fr > pipeline_encoder_split and same_shape \
+        if pipeline_encoder_split > 0 and n_fr > pipeline_encoder_split and same_shape \
                 and self.d_estimator.pipeline_streams_for(traj_samples, dev) >= 2:
             # frames [0, split) now, the rest on the stream of frame `split`: the second encoder batch runs underneath
             # the (launch-latency-bound) coarse levels of the first full frame instead of in front of them
@@ -1772,16 +1611,16 @@ class GraphedSequence:
             self._capture_autotuned(base_us)
         else:
             self.graph, self.depth = self._capture()
-            self.stagger_us = base_us if batch <= wino6_stagger_max_batch else 0    # what the captured Winograd launches carry
+            self.stagger_us = base_us if batch <= _WINO6_STAGGER_MAX_BATCH else 0    # what the captured Winograd launches carry
         self.weights_stamp = model.weights_stamp()
 
     @staticmethod
     def wants_autotune(batch, stagger_us, autotune=None):
         """Is the sequence captured twice (staggered / lock-step Winograd first round) and the faster graph kept?  Only where the
-        stagger applies at all: batch <= ``wino6_stagger_max_batch`` -- never at BASELINE configs[2] / configs[3]'s 32 sequences per
+        stagger applies at all: batch <= ``_WINO6_STAGGER_MAX_BATCH`` -- never at BASELINE configs[2] / configs[3]'s 32 sequences per
         rank, so the ranks of an 8-GPU run all replay the same graph form and none spends the 1.4 s."""
         want = wino6_stagger_autotune if autotune is None else bool(autotune)
-        return bool(want and stagger_us > 0 and batch <= wino6_stagger_max_batch)
+        return bool(want and stagger_us > 0 and batch <= _WINO6_STAGGER_MAX_BATCH)
 
     def _capture(self):
         graph = torch.cuda.CUDAGraph()
@@ -1830,11 +1669,11 @@ class GraphedSequence:
                 for c in cands:
                     self.graph = c[1]
                     for _ in range(settle):
-                        self._replay()
+                        self.graph.replay()
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
                     for _ in range(reps):
-                        self._replay()
+                        self.graph.replay()
                     e1.record()
                     e1.synchronize()
                     c[3].append(e0.elapsed_time(e1))
@@ -1851,12 +1690,7 @@ class GraphedSequence:
         for c in cands:
             if c is not best:
                 c[4] = None
-                self._reset_graph(c[1])                 # the loser's graph and its memory pool
-
-    @staticmethod
-    def _reset_graph(graph):
-        for g in (graph.values() if isinstance(graph, dict) else [graph]):
-            g.reset()
+                c[1].reset()                            # the loser's graph and its memory pool
 
     def _samples(self):
         nt = torch.unbind(self.new_traj, dim=1)
@@ -1899,135 +1733,8 @@ class GraphedSequence:
                                    "graph still reads the old buffers -- update weights in place or build a new GraphedSequence")
             self.model.prepack()                        # packed copies in place -- the graph reads the same addresses
             self.weights_stamp = stamp
-        self._replay()
-        return self.depth
-
-    def _replay(self):
         self.graph.replay()
-
-
-class SegmentedSequence(GraphedSequence):
-    """The same sequence forward as FOUR hipGraphs replayed on two real HIP streams, for the one overlap ROCm 7.2's hipGraph
-    executor does not give a single captured graph (inside one graph the second encoder batch starts only
-    when the first full frame's coarse-to-fine chain has run -- ~350 us of a nearly idle chip per batch-1 step):
-
-        calling stream:  [a: encoder batch a (reset frame + first full frame), statistics of all frames, pyramid reset]
-                         [c: first full frame, levels n..2 -- a latency chain of small kernels] -> wait(b) ->
-                         [d: that frame's level 1 + the remaining frames as the (frame, level) wavefront, final upsampling]
-        side stream:     wait(a) -> [b: encoder batch b (the remaining frames) + their normalised coarse maps]
-
-    so that b's chip-filling kernels run BESIDE c's small ones.  Same kernels, same arguments, same order per buffer as
-    ``GraphedSequence`` (bit-identical results: tests/test_gpu_model.py).  Needs a sequence that opens with a reset frame followed
-    by at least two full frames (``eligible``); every other shape of work stays with ``GraphedSequence``."""
-
-    @staticmethod
-    def eligible(model, example):
-        nt = example["new_traj"]
-        nt = nt if isinstance(nt, torch.Tensor) else torch.as_tensor(np.asarray(nt))
-        pat = [bool(v) for v in nt[0].reshape(-1).tolist()]
-        return bool(example["RGB_im"].is_cuda and not model.model_settings["is_training"] and fused_pyramid_reset
-                    and len(pat) >= 3 and pat[0] and not any(pat[1:]) and level_pipeline_streams >= len(pat))
-
-    def __init__(self, model, example, warmup=2, autotune=None):
-        if not self.eligible(model, example):
-            raise ValueError("SegmentedSequence: needs a CUDA inference sequence [reset frame, >= 2 full frames]")
-        self.stream_b = torch.cuda.Stream()
-        self._ev_a, self._ev_b = torch.cuda.Event(), torch.cuda.Event()
-        super().__init__(model, example, warmup=warmup, autotune=autotune)
-
-    # -- the forward, cut into its four segments; ``run(name, fn)`` issues one --------------------------------------------
-    def _segments(self, run):
-        model, enc, dest = self.model, self.model.encoder, self.model.d_estimator
-        samples = self._samples()
-        n_fr, n_lvls, k = self.seq_len, len(dest.levels), 2
-        bsz = int(self.static["RGB_im"].shape[0])
-        S = {}
-
-        def split(pyr, n):
-            return [[lvl[t * bsz:(t + 1) * bsz] for lvl in pyr] for t in range(n)]
-
-        def seg_a():
-            model.step_counter += 1
-            enc.set_sequence_batch(bsz)
-            stats = enc.head_stats(_stack_frames(samples)) if encoder_stats_up_front else None
-            if stats is not None:
-                head = enc(_stack_frames(samples[:k]), head_stats=(stats[0][:k * bsz], stats[1][:k * bsz]))
-                S["late_stats"] = (stats[0][k * bsz:], stats[1][k * bsz:])
-            else:
-                head = enc(_stack_frames(samples[:k]))
-                S["late_stats"] = None
-            S["f"] = split(head, k)
-            nhead = dest.prenormalize(head, bsz)
-            S["n"] = [dest._frame_slice(nhead, t, bsz) for t in range(k)]
-            S["cams"] = nops.camera_pyramid(self.camera, n_lvls)
-            fused = dest._reset_all_levels(S["f"][0], samples[0]["new_traj"])
-            if fused is None:
-                raise RuntimeError("SegmentedSequence: the one-launch pyramid reset refused this model")
-            S["est"] = {0: fused}
-
-        def seg_b():
-            tail = enc(_stack_frames(samples[k:]), head_stats=S["late_stats"]) if S["late_stats"] is not None \
-                else enc(_stack_frames(samples[k:]))
-            ntail = dest.prenormalize(tail, bsz)
-            S["f"] = S["f"] + split(tail, n_fr - k)
-            S["n"] = S["n"] + [dest._frame_slice(ntail, j, bsz) for j in range(n_fr - k)]
-
-        def seg_c():
-            ests = []
-            smp = samples[1]
-            for l in range(n_lvls - 1):
-                lvl = n_lvls - 1 - l
-                ests.append(dest.levels[lvl](S["f"][1][lvl], dict(ests[-1]) if ests else None, smp["rot"], smp["trans"],
-                                             S["cams"][lvl], smp["new_traj"],
-                                             curr_f_normalized=None if S["n"][1] is None else S["n"][1][lvl]))
-            S["est"][1] = ests
-
-        def seg_d():
-            d_maps = dest._forward_pipelined(S["f"], samples, S["cams"], n_fr, n_maps_pyrs=S["n"], resume=S["est"])
-            model.last_estimates = d_maps
-            h, w = samples[-1]["RGB_im"].shape[1:3]
-            S["depth"] = nops.resize_nearest(d_maps[-1][0]["depth"], h, w)
-
-        for name, fn in (("a", seg_a), ("b", seg_b), ("c", seg_c), ("d", seg_d)):
-            run(name, fn)
-        return S["depth"]
-
-    def _play(self, issue):
-        """The four segments on the current stream and the side stream, with the two cross-stream edges."""
-        cur = torch.cuda.current_stream()
-        issue("a")
-        self._ev_a.record(cur)
-        with torch.cuda.stream(self.stream_b):
-            self.stream_b.wait_event(self._ev_a)
-            issue("b")
-            self._ev_b.record(self.stream_b)
-        issue("c")
-        cur.wait_event(self._ev_b)
-        issue("d")
-
-    def _run(self):
-        """Eager pass (warm-up: allocates the per-stream scratch the captures will reuse)."""
-        fns = {}
-
-        def collect(name, fn):
-            fns[name] = fn
-            if name == "d":                               # all four closures exist: issue them in replay order
-                self._play(lambda n: fns[n]())
-        return self._segments(collect)
-
-    def _capture(self):
-        graphs = {}
-
-        def run(name, fn):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self.stream_b if name == "b" else self.stream):
-                fn()
-            graphs[name] = g
-        out = self._segments(run)
-        return graphs, out
-
-    def _replay(self):
-        self._play(lambda n: self.graph[n].replay())
+        return self.depth
 
 
 class GraphedStream:
@@ -2136,194 +1843,13 @@ class GraphedStream:
 
 
 def make_runner(model, example, warmup=2, autotune=None):
-    """The hipGraph runner of a sequence step: ``SegmentedSequence`` where the module setting asks for it and the sequence is
-    eligible, ``GraphedSequence`` otherwise."""
-    if segmented_step and SegmentedSequence.eligible(model, example):
-        return SegmentedSequence(model, example, warmup=warmup, autotune=autotune)
+    """The hipGraph runner of a sequence step (what bench.py builds)."""
     return GraphedSequence(model, example, warmup=warmup, autotune=autotune)
 
 
-class TapedSequence:
-    """The sequence forward as LAUNCH TAPES (csrc/m4d_tape.hip) replayed on real HIP streams -- the (frame, level) wavefront
-    of ``DepthEstimatorPyramid._forward_pipelined`` WITHOUT hipGraph:
-
-        stream 0        enc_a: camera pyramid, encoder batch of frames < split, the reset frame's levels
-        encoder stream  enc_b: encoder batch of the remaining frames
-        stream t        level L, L-1, ... 1 of full frame t, one tape per (frame, level); level l of frame t waits for the
-                        event recorded after level l of frame t - 1 (its temporal memory) and for its encoder batch
-
-    A tape replay costs the host one C loop (~3 us per launch, ~180 launches per 4-frame step) and issues plain stream
-    launches.  Measured (round 3): a chain of small kernels is NOT slowed by chip-filling kernels when
-    both are plain stream launches (340 us against ~700 us as soon as either side is a hipGraph replay;
-    profiles/r03_stream_vs_graph_probe.txt), yet the whole step is 3 % slower this way than as ONE hipGraph (1326-1338 against
-    1379 frames/s): the step is bound by chip-time, not by the chains.  An EXPERIMENT since round 4: needs a
-    ``make EXPERIMENTS=1`` build of the library (raises otherwise); same kernels in the same per-stream order: bit-identical
-    results (tests/test_gpu_model.py, skipped on the product library); ``bench.py --schedule tape``."""
-
-    def __init__(self, model, example, warmup=2, encoder_split=None):
-        from ._lib import require_experiments
-        require_experiments("network.TapedSequence (the launch tape, csrc/m4d_tape.hip)")
-        self.model = model
-        nt = example["new_traj"]
-        self.new_traj = nt.clone() if isinstance(nt, torch.Tensor) else torch.as_tensor(np.asarray(nt))
-        flags = [bool(v) for v in self.new_traj[0].reshape(-1).tolist()]
-        if len(flags) < 2 or not flags[0] or any(flags[1:]):
-            raise ValueError("TapedSequence: expected a sequence that starts with new_traj and continues without")
-        # rot / trans are kept frame-major ([T,b,k]) so that a frame's slice is contiguous at every batch size: a non-contiguous
-        # slice would make the level wrappers launch a framework copy kernel, which a tape cannot record.  The batch-major
-        # [b,T,k] views of the same memory are what input_buffers() hands out.
-        self._rot = example["rot"].transpose(0, 1).contiguous()
-        self._trans = example["trans"].transpose(0, 1).contiguous()
-        self.static = {"RGB_im": example["RGB_im"].clone(), "rot": self._rot.transpose(0, 1), "trans": self._trans.transpose(0, 1)}
-        self.camera = {k: v.clone().contiguous() for k, v in example["camera"].items()}
-        self.seq_len = T = self.static["RGB_im"].shape[1]
-        self.n_lvls = L = len(model.d_estimator.levels)
-        self.split = min(max(1, pipeline_encoder_split if encoder_split is None else int(encoder_split)), T)
-        model.prepack()
-        # Stream priorities (plain streams honour them, a hipGraph's executor streams do not): the frames are consumed in
-        # order, so frame t's kernels go ahead of frame t + 1's whenever both have workgroups waiting for a CU.
-        # M4D_TAPE_PRIORITIES = comma list for streams[0..T-1] + the late-encoder stream (torch: lower = more urgent).
-        prio = [int(v) for v in _os.environ.get("M4D_TAPE_PRIORITIES", "").split(",") if v.strip() != ""]
-        pr = lambda i: prio[min(i, len(prio) - 1)] if prio else 0
-        self.streams = [torch.cuda.Stream(priority=pr(t)) for t in range(T)]   # [0]: encoder batch a + reset frame; [t]: full frame t
-        self.s_enc = torch.cuda.Stream(priority=pr(T))
-        self.ctx = {}
-        segs = [("enc_a", self.streams[0], self._seg_enc_a)]
-        if self.split < T:
-            segs.append(("enc_b", self.s_enc, lambda: self._encode(self.split, T)))
-        for t in range(1, T):
-            for l in range(L):
-                segs.append(((t, l), self.streams[t], lambda t=t, l=l: self._seg_level(t, l)))
-        cur = torch.cuda.current_stream()
-        for _ in range(max(warmup, 1)):                     # eager passes: state, scratch (keyed by stream), packed weights
-            for _, st, fn in segs:
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    fn()
-                torch.cuda.synchronize()
-        self._pools, self.tapes = [], {}
-        import warnings
-        for name, st, fn in segs:
-            # Recorded under a torch graph capture: the library's launches go to the tape, the torch graph stays EMPTY (the
-            # forward launches nothing but libm4depth_hip.so kernels) and only its private memory pool matters -- it pins
-            # the address of every tensor the segment allocates.
-            g = torch.cuda.CUDAGraph()
-            with warnings.catch_warnings(record=True) as caught:
-                warnings.simplefilter("always")
-                with torch.cuda.graph(g, stream=st):
-                    tid = int(lib.m4d_tape_begin())
-                    if tid < 0:
-                        raise RuntimeError("m4d_tape_begin: this thread is already recording a tape")
-                    try:
-                        fn()
-                    finally:
-                        n_rec = int(lib.m4d_tape_end())
-            if not any("CUDA Graph is empty" in str(w.message) for w in caught):
-                # torch captured something: a framework kernel (a copy of a non-contiguous input, a fill) sits in this
-                # segment of the forward and would be missing from the replay
-                raise RuntimeError(f"TapedSequence: segment {name} of the forward launched framework kernels beside "
-                                   "libm4depth_hip.so's; it cannot be replayed from a launch tape (use GraphedSequence)")
-            self._pools.append(g)
-            self.tapes[name] = (tid, n_rec, st)
-        torch.cuda.synchronize()
-        self.depth = self.ctx["depth"]
-        self.weights_stamp = model.weights_stamp()
-        self._ev = {name: torch.cuda.Event() for name in self.tapes}
-        self._ev_start, self._ev_join = torch.cuda.Event(), torch.cuda.Event()
-        # issue order: anti-diagonals of the (frame, level) grid, as in DepthEstimatorPyramid._forward_pipelined
-        self._order = [(t, diag - (t - 1)) for diag in range((T - 1) + L - 1)
-                       for t in range(max(1, diag - L + 2), min(T - 1, diag + 1) + 1)]
-
-    def __del__(self):
-        try:
-            for tid, _, _ in self.tapes.values():
-                lib.m4d_tape_free(tid)
-        except Exception:
-            pass
-
-    def launches_per_step(self):
-        return sum(n for _, n, _ in self.tapes.values())
-
-    def _samples(self):
-        nt = torch.unbind(self.new_traj, dim=1)
-        return [{"RGB_im": self.static["RGB_im"][:, t], "rot": self._rot[t], "trans": self._trans[t], "new_traj": nt[t]}
-                for t in range(self.seq_len)]
-
-    def _encode(self, a, b):
-        samples = self._samples()
-        bsz = samples[0]["RGB_im"].shape[0]
-        self.model.encoder.set_sequence_batch(bsz)
-        out = self.model.encoder(_stack_frames(samples[a:b]))
-        for j, t in enumerate(range(a, b)):
-            self.ctx[("f", t)] = [lvl[j * bsz:(j + 1) * bsz] for lvl in out]
-
-    def _seg_enc_a(self):
-        self.ctx["cams"] = nops.camera_pyramid(self.camera, self.n_lvls)
-        self._encode(0, self.split)
-        self.ctx[("est", 0)] = []
-        for l in range(self.n_lvls):
-            self._level(0, l)                              # the reset frame: state seeding only
-
-    def _seg_level(self, t, l):
-        if l == 0:
-            self.ctx[("est", t)] = []
-        self._level(t, l)
-        if l == self.n_lvls - 1 and t == self.seq_len - 1:
-            h, w = self.static["RGB_im"].shape[2:4]
-            self.ctx["depth"] = nops.resize_nearest(self.ctx[("est", t)][-1]["depth"], h, w)
-            self.model.last_estimates = [self.ctx[("est", i)][::-1] for i in range(self.seq_len)]
-
-    def _level(self, t, l):
-        """Level l (0 = coarsest) of frame t."""
-        sample = self._samples()[t]
-        ests = self.ctx[("est", t)]
-        lvl = self.n_lvls - 1 - l
-        prev = None if not ests else dict(ests[-1])
-        ests.append(self.model.d_estimator.levels[lvl](self.ctx[("f", t)][lvl], prev, sample["rot"], sample["trans"],
-                                                      self.ctx["cams"][lvl], sample["new_traj"]))
-
-    def input_buffers(self):
-        return dict(self.static, camera=self.camera)
-
-    def _replay(self, name):
-        tid, _, st = self.tapes[name]
-        check(lib.m4d_tape_replay(tid, ctypes.c_void_p(st.cuda_stream)), "m4d_tape_replay")
-        self._ev[name].record(st)
-
-    def __call__(self, data=None):
-        if data is not None:
-            for k in self.static:
-                if tuple(data[k].shape) != tuple(self.static[k].shape):
-                    raise ValueError(f"TapedSequence: {k} has shape {tuple(data[k].shape)}, recorded {tuple(self.static[k].shape)}")
-                if data[k].data_ptr() != self.static[k].data_ptr():
-                    self.static[k].copy_(data[k], non_blocking=True)
-            for k in self.camera:
-                if data["camera"][k].data_ptr() != self.camera[k].data_ptr():
-                    self.camera[k].copy_(data["camera"][k], non_blocking=True)
-        stamp = self.model.weights_stamp()
-        if stamp != self.weights_stamp:
-            if [p for p, _ in stamp] != [p for p, _ in self.weights_stamp]:
-                raise RuntimeError("a convolution parameter was REPLACED after these tapes were recorded: build a new TapedSequence")
-            self.model.prepack()
-            self.weights_stamp = stamp
-        cur = torch.cuda.current_stream()
-        T, ev = self.seq_len, self._ev
-        self._ev_start.record(cur)
-        for st in self.streams + [self.s_enc]:
-            st.wait_event(self._ev_start)
-        self._replay("enc_a")
-        if "enc_b" in self.tapes:
-            self._replay("enc_b")
-        for (t, l) in self._order:
-            st = self.streams[t]
-            if l == 0:
-                st.wait_event(ev["enc_a"])                     # the reset frame's state, the camera pyramid (+ frame t's features)
-                if t >= self.split:
-                    st.wait_event(ev["enc_b"])
-            if t > 1:
-                st.wait_event(ev[(t - 1, l)])
-            self._replay((t, l))
-        self._ev_join.record(self.streams[T - 1])
-        cur.wait_event(self._ev_join)
-        return self.depth
-
+def __getattr__(name):
+    # the launch-tape schedule is an experiment with a module of its own: not imported with the product
+    if name == "TapedSequence":
+        from .tape_schedule import TapedSequence
+        return TapedSequence
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -110,3 +110,20 @@ def test_launch_tape_bookkeeping_without_gpu():
     assert lib.m4d_tape_end() == 0 and lib.m4d_tape_end() == -1
     assert lib.m4d_tape_length(t) == 0 and lib.m4d_tape_length(t + 1000) == -1
     assert lib.m4d_tape_free(t) == 0 and lib.m4d_tape_free(t) != 0 and lib.m4d_tape_length(t) == -1
+
+
+def test_integration_doc_lists_exactly_the_switches_the_package_reads():
+    """INTEGRATION.md section 4 has one table row per ``M4D_*`` environment variable named in m4depth_amd/*.py, and no other:
+    a switch cannot be added, or retired, without the document following."""
+    import glob
+    in_code = set()
+    for path in glob.glob(os.path.join(ROOT, "m4depth_amd", "*.py")):
+        in_code |= set(re.findall(r"\bM4D_[A-Z0-9_]+", open(path).read()))
+    in_code.discard("M4D_ABI_VERSION")                   # the header's version macro (named in a comment of _lib.py), no switch
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 4. Kernel-selection switches"):]
+    in_table = set()
+    for line in section.splitlines():
+        if line.startswith("| `M4D_"):
+            in_table |= set(re.findall(r"\bM4D_[A-Z0-9_]+", line.split("|")[1]))
+    assert in_table == in_code, (sorted(in_code - in_table), sorted(in_table - in_code))

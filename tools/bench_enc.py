@@ -18,8 +18,8 @@ def timeit(fn, n=20):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / n
 c1, c2, dn = enc.conv_layers_s1[0], enc.conv_layers_s2[0], enc.dn_layers[0]
-wp2, cpad2 = c2._packed_weights()
-head = lambda: nops.encoder_head(img, c1._hwio_device(), c1.bias, dn.scale, dn.bias, wp2, c2.bias, 16, cpad2, 0.1)
+wp2, cpad2 = c2.packed("direct")
+head = lambda: nops.encoder_head(img, c1.packed("hwio"), c1.bias, dn.scale, dn.bias, wp2, c2.bias, 16, cpad2, 0.1)
 print(f"encoder head (3->16 conv + DINL stats + DINL-fused stride-2 16->16): {timeit(head):.1f} us")
 print(f"whole encoder, 2 frames: {timeit(lambda: enc(img)):.1f} us")
 g = torch.cuda.CUDAGraph()

@@ -14,7 +14,7 @@ model = M.M4Depth(nbre_levels=6); model.load_numpy_weights(S.init_weights(6, see
 img = torch.rand(a.frames, 384, 1280, 3, device=dev)
 enc = model.encoder
 c1, c2, dn = enc.conv_layers_s1[0], enc.conv_layers_s2[0], enc.dn_layers[0]
-fn = lambda: nops.encoder_level0(img, c1._hwio_device(), c1.bias, dn.scale, dn.bias, c2._hwio_device(), c2.bias, 0.1)
+fn = lambda: nops.encoder_level0(img, c1.packed("hwio"), c1.bias, dn.scale, dn.bias, c2.packed("hwio"), c2.bias, 0.1)
 for _ in range(3): fn()
 torch.cuda.synchronize()
 g = torch.cuda.CUDAGraph()
