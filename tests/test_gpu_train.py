@@ -19,22 +19,22 @@ pytestmark = pytest.mark.gpu
 L, H, W, T, B = 2, 32, 48, 3, 2
 
 
-def _data(seed):
+def _data(seed, B=B, T=T, H=H, W=W):
     samples, cam = synthetic.make_sequence(B, T, H, W, seed=seed)
     data = {k: np.stack([s[k] for s in samples], axis=1) for k in ("RGB_im", "depth", "rot", "trans", "new_traj")}
     data["camera"] = cam
     return data
 
 
-def _model(dev, wts, depth_type="map"):
+def _model(dev, wts, depth_type="map", L=L, dscv_range=2, sncv_range=2):
     import m4depth_amd as M
     from m4depth_amd import training as TR
-    model = M.M4Depth(depth_type=depth_type, nbre_levels=L, is_training=True, dscv_range=2, sncv_range=2)
+    model = M.M4Depth(depth_type=depth_type, nbre_levels=L, is_training=True, dscv_range=dscv_range, sncv_range=sncv_range)
     model.load_numpy_weights(wts, dev)
     return TR.set_trainable(model), TR
 
 
-def _named_grads(model):
+def _named_grads(model, L=L):
     out = {}
     enc = model.encoder
     for i in range(L):
@@ -51,20 +51,21 @@ def _named_grads(model):
     return out
 
 
-@pytest.mark.parametrize("depth_type", ["map", "velodyne"])
-def test_loss_and_gradients_match_oracle(dev, depth_type):
-    wts = synthetic.init_weights(nbre_levels=L, seed=3, dscv_range=2, sncv_range=2, bias_std=0.05)
-    data = _data(21)
+def _loss_and_gradients_case(dev, depth_type, L=L, H=H, W=W, T=T, B=B, dscv_range=2, sncv_range=2, check=True):
+    """One training step's loss, parallax pyramids and parameter gradients on the device against autodiff of the
+    restatement.  Every figure is printed before anything is asserted; returns them (``check=False``: measure only)."""
+    wts = synthetic.init_weights(nbre_levels=L, seed=3, dscv_range=dscv_range, sncv_range=sncv_range, bias_std=0.05)
+    data = _data(21, B, T, H, W)
     if depth_type == "velodyne":                       # sparse ground truth: holes are zeros
         rng = np.random.default_rng(0)
         data["depth"] = data["depth"] * (rng.random(data["depth"].shape) > 0.6)
         data["depth"] = data["depth"].astype(np.float32)
     tw = {k: torch.from_numpy(v).requires_grad_(True) for k, v in wts.items()}
     tdata = {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) and v.dtype != np.bool_ else v) for k, v in data.items()}
-    ref_loss, ref_preds = OT.train_loss(tw, tdata, L, dscv_range=2, sncv_range=2, depth_type=depth_type)
+    ref_loss, ref_preds = OT.train_loss(tw, tdata, L, dscv_range=dscv_range, sncv_range=sncv_range, depth_type=depth_type)
     ref_loss.backward()
 
-    model, TR = _model(dev, wts, depth_type)
+    model, TR = _model(dev, wts, depth_type, L, dscv_range, sncv_range)
     ddata = to_dev(data, dev)
     samples = TR.unstack_sequence(ddata)
     preds = model([samples, ddata["camera"]], training=True)
@@ -72,23 +73,57 @@ def test_loss_and_gradients_match_oracle(dev, depth_type):
     loss = model.m4depth_loss(gts, preds)
     loss.backward()
 
+    fig = {"loss": loss.item(), "ref_loss": ref_loss.item(), "parallax": {}, "grad": {}, "ref_grads": {}}
+    for t in range(1, T):
+        for lvl in range(L):
+            got, want = npy(preds[t][lvl]["parallax"]), ref_preds[t][lvl]["parallax"].detach().numpy()
+            over = np.abs(got - want) - (1e-5 + 2e-3 * np.abs(want))
+            fig["parallax"][(t, lvl)] = (float(np.max(np.abs(got - want) / (np.abs(want) + 1e-5 / 2e-3))), int((over > 0).sum()), got.size)
+    # enc.s1.0.bias feeds the DINL mean subtraction: its true gradient is 0 and both sides hold rounding
+    # noise, hence the floor (1e-4 of the largest gradient norm in the model)
+    floor = 1e-4 * max(float(np.linalg.norm(v.grad.numpy())) for v in tw.values())
+    for name, g in _named_grads(model, L).items():
+        want = tw[name].grad.numpy()
+        got = npy(g).reshape(want.shape)
+        fig["grad"][name] = float(np.linalg.norm(got - want) / max(np.linalg.norm(want), floor))
+        fig["ref_grads"][name] = want
+    fig["floor"] = floor
+    worst = max(fig["grad"].items(), key=lambda kv: kv[1])
+    print(f"loss {fig['loss']!r} vs {fig['ref_loss']!r}: relative {abs(fig['loss'] - fig['ref_loss']) / abs(fig['ref_loss']):.3e}")
+    for (t, lvl), (e, n_over, n) in fig["parallax"].items():
+        print(f"parallax frame {t} level {lvl + 1}: max |diff| / (|ref| + 5e-3) = {e:.3e}, {n_over} of {n} outside rtol 2e-3 / atol 1e-5")
+    for name, e in sorted(fig["grad"].items(), key=lambda kv: -kv[1])[:8]:
+        print(f"gradient {name}: relative L2 error {e:.3e}")
+    print("worst gradient", worst)
+    if not check:
+        return fig
     for t in range(1, T):
         for lvl in range(L):
             np.testing.assert_allclose(npy(preds[t][lvl]["parallax"]), ref_preds[t][lvl]["parallax"].detach().numpy(),
                                        rtol=2e-3, atol=1e-5)
     assert abs(loss.item() - ref_loss.item()) <= 1e-4 * abs(ref_loss.item()), (loss.item(), ref_loss.item())
-    worst = ("", 0.0)
-    # enc.s1.0.bias feeds the DINL mean subtraction: its true gradient is 0 and both sides hold rounding
-    # noise, hence the floor (1e-4 of the largest gradient norm in the model)
-    floor = 1e-4 * max(float(np.linalg.norm(v.grad.numpy())) for v in tw.values())
-    for name, g in _named_grads(model).items():
-        want = tw[name].grad.numpy()
-        got = npy(g).reshape(want.shape)
-        err = np.linalg.norm(got - want) / max(np.linalg.norm(want), floor)
-        if err > worst[1]:
-            worst = (name, err)
+    for name, err in fig["grad"].items():
         assert err < 5e-3, f"{name}: relative L2 gradient error {err:.3e}"
-    print("worst gradient", worst)
+    return fig
+
+
+@pytest.mark.parametrize("depth_type", ["map", "velodyne"])
+def test_loss_and_gradients_match_oracle(dev, depth_type):
+    _loss_and_gradients_case(dev, depth_type)
+
+
+def test_loss_and_gradients_match_oracle_fullsize(dev):
+    """The same comparison on one whole step of the training recipe: 6 levels, 384 x 384 crops, 4 frames, batch 3, the default
+    search ranges (DSCV 4, SNCV 3), depth type "map", the default convolution arithmetic (levels 4-6 on the latency-first
+    kernels).  ``fullsize`` in the name: the collection order runs it at the end of the GPU suite.
+
+    The bars of the small model hold unchanged.  Measured on an MI355X (profiles/train_backward_recipe.txt): loss 9.8e-8
+    relative (bar 1e-4); parallax at most 5.6e-4 of |ref| + 5e-3 (frame 2, level 2), no pixel outside rtol 2e-3 / atol 1e-5;
+    worst parameter enc.s1.0.kernel at 1.37e-3 of its own L2 norm (bar 5e-3), then enc.s1.4.kernel 1.29e-3 and enc.s2.4.kernel
+    1.27e-3; every refiner parameter below 4e-5.  The float32 restatement itself is 1.67e-3 (enc.s1.0.kernel) and 2.11e-3
+    (enc.s1.4.kernel) away from its float64 evaluation: the device is as close to the reference as the reference's
+    arithmetic allows."""
+    _loss_and_gradients_case(dev, "map", L=6, H=384, W=384, T=4, B=3, dscv_range=4, sncv_range=3)
 
 
 def test_train_step_reduces_the_loss(dev):
