@@ -640,6 +640,34 @@ int m4d_decode_rgb8_resize(const uint8_t* images, int n, int ih, int iw, int oh,
 int m4d_decode_depth_resize(const void* raw, int kind, int n, int ih, int iw, int oh, int ow,
                             const float* rgb_resized, const int crop[4], float* out, void* stream);
 
+/* ---- prediction export (main.py --mode=predict --save_dir): the mirror of the decoders above ------------------ */
+
+/* The depth estimate of a frame batch -> what goes to disk, in one launch.  est [b,h,w,1], gt [b,h,w,1] (may be NULL),
+ * rgb [b,h,w,3] in 0..1 (may be NULL): float32, image i at ptr + i * stride ELEMENTS (est_stride, gt_stride >= h*w,
+ * rgb_stride >= 3*h*w: views of larger buffers are read in place); est is read once per pixel.  Outputs are dense:
+ *   depth16 [b,h,w] uint16, format 0 none (depth16 may be NULL), 1 kitti16, 2 midair16 -- the encodings kind 1 / kind 0 of
+ *           m4d_decode_depth_resize read back;
+ *   panels  [b, n_panels*h, w, 3] uint8: n_panels (0..4) RGB8 images stacked vertically in the order of panel_kinds (a HOST
+ *           array): 0 rgb, 1 est, 2 gt, 3 err;  lut [257,3] uint8 in device memory, row 256 = the colour of invalid pixels
+ *           (needed by kinds 1..3; gt by 2, 3; rgb by 0).
+ * float32, one IEEE rounding per operation, in this order (rintf = round half to even):
+ *   valid(d)  = isfinite(d) && d > 0
+ *   kitti16   : valid -> (uint16) min(max(rintf(d * 256.0f), 1.0f), 65535.0f), else 0
+ *   midair16  : valid -> bits of half_rne(512.0f / d), else 0x7C00 (an overflowing quotient is 0x7C00 as well; the Mid-Air
+ *               decoder reads 0x7C00 as depth 0)
+ *   est / gt  : valid -> lut[(int) rintf(min(max((1.0f/d - 1.0f/far) / (1.0f/near - 1.0f/far), 0.0f), 1.0f) * 255.0f)],
+ *               else lut[256] -- inverse depth, linear between far and near
+ *   err       : est and gt valid -> lut[(int) rintf(min((fabsf(est - gt) / gt) / err_max, 1.0f) * 255.0f)], else lut[256]
+ *   rgb       : (uint8) rintf(min(max(v, 0.0f), 1.0f) * 255.0f), NaN -> 0
+ * Returns 1 without a launch for: a NULL est, format outside 0..2, depth16 missing for a format, nothing asked for, more
+ * than 4 panels or an unknown kind, gt / rgb / lut / panels missing for a panel that needs them, near <= 0, far <= near,
+ * err_max <= 0, a stride smaller than an image, float pointers off 4 bytes or depth16 off 2.  Every output element is
+ * written; plain launch (capturable).  Additive entry point: ABI 6 unchanged. */
+int m4d_depth_export(const float* est, long long est_stride, const float* gt, long long gt_stride, const float* rgb,
+                     long long rgb_stride, int b, int h, int w, int format, uint16_t* depth16, int n_panels,
+                     const int* panel_kinds, const uint8_t* lut, float near, float far, float err_max, uint8_t* panels,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,210 @@
+"""Prediction export -- the back end of ``main.py --mode=predict --save_dir``, the mirror of the dataloaders' front end.
+
+The reference's predict loop hands ``d_est``, ``d_gt`` and ``i_rgb`` of every frame to the user (main.py:150-172); what users
+do with them is save a depth map and a colourised estimate beside the ground truth and the image.  Here one kernel per frame
+batch (``network_ops.depth_export``) writes the estimate in a dataset's own 16-bit encoding and as ready-to-save RGB8 panels,
+``PredictionWriter`` moves them through a ring of pinned buffers, and host threads do the PNG compression: the predict loop
+never waits for the host unless every slot of the ring is in flight, and host memory is ``slots`` frames however long the run.
+"""
+from __future__ import annotations
+
+import os
+import queue
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import network_ops as nops
+
+FORMATS = ("kitti16", "midair16")
+PANELS = ("rgb", "est", "gt", "err")
+
+# anchor colours of the table (position in 0..1, r, g, b): dark blue (far / no error) over green and yellow to dark red
+# (near / err_max), interpolated linearly per channel
+_ANCHORS = ((0.0, 24, 15, 92), (0.2, 35, 95, 180), (0.4, 30, 170, 160), (0.6, 120, 210, 70), (0.8, 250, 190, 40),
+            (1.0, 180, 20, 30))
+_INVALID = (0, 0, 0)
+
+
+def default_lut():
+    """[257,3] uint8 colour table: rows 0..255 interpolate the anchor colours, row 256 is the colour of invalid pixels."""
+    pos = np.array([a[0] for a in _ANCHORS], np.float64)
+    x = np.arange(256, dtype=np.float64) / 255.0
+    lut = np.empty((257, 3), np.uint8)
+    for c in range(3):
+        lut[:256, c] = np.rint(np.interp(x, pos, np.array([a[1 + c] for a in _ANCHORS], np.float64))).astype(np.uint8)
+    lut[256] = _INVALID
+    return lut
+
+
+class FrameNamer:
+    """Relative output paths ``s{slot:02d}_t{trajectory:04d}/{frame:06d}`` of the ``b`` samples of a step, from the step's
+    host-side ``new_traj``: a sample's trajectory counter advances where ``new_traj`` is set (and on its first frame), its
+    frame counter restarts there."""
+
+    def __init__(self, b):
+        self.traj = [-1] * int(b)
+        self.frame = [0] * int(b)
+
+    def __call__(self, new_traj):
+        flags = np.asarray(new_traj.cpu() if torch.is_tensor(new_traj) else new_traj, dtype=bool).reshape(-1)
+        if len(flags) != len(self.traj):
+            raise ValueError(f"new_traj has {len(flags)} samples, the namer {len(self.traj)}")
+        names = []
+        for s, new in enumerate(flags):
+            if new or self.traj[s] < 0:
+                self.traj[s] += 1
+                self.frame[s] = 0
+            else:
+                self.frame[s] += 1
+            names.append(f"s{s:02d}_t{self.traj[s]:04d}/{self.frame[s]:06d}")
+        return names
+
+
+def read_depth_png(path, fmt):
+    """A ``<name>_depth.png`` of ``PredictionWriter`` as float32 depth, with the arithmetic of the dataloaders: value / 256
+    (kitti16), 512 / float16(bits) (midair16; the invalid code 0x7C00 = +Inf reads as depth 0)."""
+    from PIL import Image
+    if fmt not in FORMATS:
+        raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
+    with Image.open(path) as im:
+        bits = np.asarray(im, dtype=np.uint16)
+    if fmt == "kitti16":
+        return bits.astype(np.float32) / np.float32(256.0)
+    with np.errstate(divide="ignore"):
+        return np.float32(512.0) / bits.view(np.float16).astype(np.float32)
+
+
+class _Slot:
+    def __init__(self, b, h, w, n_panels, dev):
+        self.depth_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
+        self.depth_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
+        self.panels_d = self.panels_h = None
+        if n_panels:
+            self.panels_d = torch.empty((b, n_panels * h, w, 3), dtype=torch.uint8, device=dev)
+            self.panels_h = torch.empty((b, n_panels * h, w, 3), dtype=torch.uint8).pin_memory()
+        self.event = torch.cuda.Event()
+        self.pending = 0
+
+
+class PredictionWriter:
+    """Writes ``<out_dir>/<name>_depth.png`` (16-bit greyscale, ``fmt``) and, with ``panels``, ``<name>_panels.png`` (RGB) for
+    every sample handed to ``submit``.  A ring of ``slots`` device + pinned host buffer pairs; ``submit`` launches the export
+    kernel and the device-to-host copies on the current stream, records an event and queues the files to ``threads`` worker
+    threads, which wait for the event, compress and free the slot.  ``submit`` blocks only while every slot is in flight.
+    ``close()`` (or leaving the ``with`` block) drains the ring and re-raises the first exception a worker hit.
+    ``encode=False`` does everything but the file encoding (for measuring the loop without the PNG encoder).  All submits
+    must come from one stream and have one geometry."""
+
+    def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
+                 encode=True):
+        if fmt not in FORMATS:
+            raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
+        panels = tuple(panels)
+        if len(panels) > 4 or any(p not in PANELS for p in panels):
+            raise ValueError(f"panels: up to four of {PANELS}, got {panels}")
+        if not (near > 0 and far > near and err_max > 0):
+            raise ValueError(f"need 0 < near < far and err_max > 0, got near {near}, far {far}, err_max {err_max}")
+        if slots < 1 or threads < 1:
+            raise ValueError("slots and threads must be >= 1")
+        self.out_dir, self.fmt, self.panels = str(out_dir), fmt, panels
+        self.near, self.far, self.err_max = float(near), float(far), float(err_max)
+        self.n_slots, self.compress_level, self.encode = int(slots), int(compress_level), bool(encode)
+        self.frames = 0                                    # samples submitted so far
+        self._pool = ThreadPoolExecutor(max_workers=int(threads), thread_name_prefix="m4d-export")
+        self._free = queue.Queue()
+        self._slots = None                                 # allocated at the first submit (the geometry is the frame's)
+        self._geometry = None
+        self._lut = None
+        self._lock = threading.Lock()
+        self._error = None
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:                                              # the body's exception wins; still leave nothing in flight
+            try:
+                self.close()
+            except Exception:
+                pass
+        return False
+
+    def _allocate(self, est):
+        b, h, w = est.shape[:3]
+        self._geometry = (b, h, w)
+        self._slots = [_Slot(b, h, w, len(self.panels), est.device) for _ in range(self.n_slots)]
+        if any(p != "rgb" for p in self.panels):
+            self._lut = torch.from_numpy(default_lut()).to(est.device)
+        for i in range(self.n_slots):
+            self._free.put(i)
+
+    def submit(self, est, names, gt=None, rgb=None):
+        """``est`` [b,h,w,1] (+ ``gt`` / ``rgb`` as the panels need) of one step; ``names``: b relative paths without suffix."""
+        if self._closed:
+            raise RuntimeError("PredictionWriter.submit after close()")
+        if self._slots is None:
+            self._allocate(est)
+        if tuple(est.shape[:3]) != self._geometry or len(names) != self._geometry[0]:
+            raise ValueError(f"submit: est {tuple(est.shape)} with {len(names)} names, the writer was sized for {self._geometry}")
+        index = self._free.get()                           # back-pressure: waits while every slot is in flight
+        slot = self._slots[index]
+        try:
+            nops.depth_export(est, self.fmt, self.panels, gt=gt, rgb=rgb, lut=self._lut, near=self.near, far=self.far,
+                              err_max=self.err_max, depth16=slot.depth_d, panels_out=slot.panels_d)
+            slot.depth_h.copy_(slot.depth_d, non_blocking=True)
+            if slot.panels_d is not None:
+                slot.panels_h.copy_(slot.panels_d, non_blocking=True)
+            slot.event.record()
+        except BaseException:
+            self._free.put(index)
+            raise
+        jobs = []
+        for s, name in enumerate(names):
+            jobs.append((name + "_depth.png", slot.depth_h, s))
+            if slot.panels_h is not None:
+                jobs.append((name + "_panels.png", slot.panels_h, s))
+        slot.pending = len(jobs)
+        self.frames += len(names)
+        for job in jobs:
+            self._pool.submit(self._work, index, *job)
+
+    def _work(self, index, rel_path, host, s):
+        slot = self._slots[index]
+        try:
+            slot.event.synchronize()
+            if self.encode:
+                from PIL import Image
+                path = os.path.join(self.out_dir, rel_path)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                arr = host[s].numpy()
+                if arr.dtype == np.int16:
+                    arr = arr.view(np.uint16)              # PIL mode I;16
+                Image.fromarray(arr).save(path, format="PNG", compress_level=self.compress_level)
+        except BaseException as e:                         # kept for close(); the slot is freed all the same
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+        finally:
+            with self._lock:
+                slot.pending -= 1
+                done = slot.pending == 0
+            if done:
+                self._free.put(index)
+
+    def close(self):
+        """Waits for every slot, stops the workers and re-raises the first worker exception."""
+        if self._closed:
+            return
+        self._closed = True
+        if self._slots is not None:
+            for _ in range(self.n_slots):
+                self._free.get()
+        self._pool.shutdown(wait=True)
+        if self._error is not None:
+            raise self._error

@@ -11,6 +11,8 @@ Flag names follow ``m4depth_options.py`` where the flag exists there.  Like the
 reference it writes the 7 metrics with ``%.18e`` (one per line, as np.savetxt does for the 1-D list) to
 ``<ckpt_dir>/perfs-<dataset>.txt`` (main.py:144-148).  With several ranks the batch
 is sharded (m4depth_amd.dist) and the metric accumulators are all-gathered over RCCL.
+``--mode=predict --save_dir DIR`` writes every frame's estimate as a 16-bit depth PNG in a dataset's own encoding (and, with
+``--save_panels``, a colour panel PNG) through ``m4depth_amd.export.PredictionWriter`` instead of collecting predictions.npy.
 ``--eval_streams B`` runs a dataset's streaming evaluation (no ``--db_seq_len``) with B whole trajectories side by side
 (m4depth_amd.stream_eval) and writes the same perfs file as the one-frame-at-a-time loop.
 """
@@ -65,6 +67,18 @@ def build_parser():
     p.add_argument("--host_input", action="store_true",
                    help="synthetic eval: hand every batch over from pinned HOST memory (the PCIe copy is part of the step) and "
                         "print the frames/s of the loop -- the PCIe-inclusive rate, next to bench.py's HBM-resident one")
+    p.add_argument("--save_dir", default=None, metavar="DIR",
+                   help="predict: write every frame to DIR/s<slot>_t<trajectory>/<frame>_depth.png (16-bit, --save_format), "
+                        "encoded on the GPU and compressed in host threads (m4depth_amd.export), instead of predictions.npy")
+    p.add_argument("--save_format", default=None, choices=["kitti16", "midair16"],
+                   help="--save_dir: uint16 = depth * 256 (kitti16, the default) or float16 bits of 512 / depth (midair16)")
+    p.add_argument("--save_panels", default=None, metavar="LIST",
+                   help="--save_dir: comma list of rgb,est,gt,err -- also write <frame>_panels.png with these panels stacked "
+                        "vertically (default: none)")
+    p.add_argument("--save_range", type=float, nargs=2, default=None, metavar=("NEAR", "FAR"),
+                   help="--save_panels: the depths the colour scale of est / gt spans, linear in inverse depth (default 1 80)")
+    p.add_argument("--save_err_max", type=float, default=None,
+                   help="--save_panels: the relative error the colour scale of err saturates at (default 0.5)")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--save_every", type=int, default=0, help="train: checkpoint every N steps (0 = at the end)")
     p.add_argument("--summary_interval", type=int, default=1200,
@@ -411,6 +425,45 @@ def _check_eval_streams(parser, args):
         parser.error("--eval_streams evaluates whole trajectories: it excludes --db_seq_len")
 
 
+def records_have_depth(args):
+    """Whether the trajectory files of ``--records_path`` name a ground-truth map (the loader's depth column): known on the
+    host before anything is loaded."""
+    import glob
+    from . import dataloaders as dl
+    col = dl.get_loader(args.dataset)._depth_column()
+    files = sorted(glob.glob(os.path.join(args.records_path, "**/*.csv"), recursive=True))
+    if not files:
+        return False
+    with open(files[0], newline="") as fh:
+        return col in fh.readline().rstrip("\r\n").split("\t")
+
+
+def check_save_args(parser, args):
+    """Refusals of the ``--save_*`` options; fills in their defaults and parses ``--save_panels`` into a tuple."""
+    from .export import PANELS
+    others = [f for f in ("save_format", "save_panels", "save_range", "save_err_max") if getattr(args, f) is not None]
+    if args.save_dir is None:
+        if others:
+            parser.error("--%s needs --save_dir" % others[0])
+        return
+    if args.mode != "predict":
+        parser.error("--save_dir is a --mode=predict option")
+    args.save_format = args.save_format or "kitti16"
+    panels = tuple(p for p in (args.save_panels or "").split(",") if p)
+    if len(panels) > 4 or any(p not in PANELS for p in panels):
+        parser.error("--save_panels: a comma list of up to four of %s, got %r" % (",".join(PANELS), args.save_panels))
+    args.save_panels = panels
+    args.save_range = tuple(args.save_range) if args.save_range is not None else (1.0, 80.0)
+    args.save_err_max = 0.5 if args.save_err_max is None else args.save_err_max
+    if not (0 < args.save_range[0] < args.save_range[1]):
+        parser.error("--save_range NEAR FAR needs 0 < NEAR < FAR")
+    if not args.save_err_max > 0:
+        parser.error("--save_err_max must be > 0")
+    if any(p in ("gt", "err") for p in panels) and args.dataset != "synthetic" and args.records_path is not None \
+            and not records_have_depth(args):
+        parser.error("--save_panels %s: the records of --records_path name no ground-truth map" % ",".join(panels))
+
+
 def eval_streams(args, model, dev):
     """Streaming evaluation with ``--eval_streams`` B slots (m4depth_amd.stream_eval): per step one ``stream_step`` (or a
     ``GraphedStream`` replay) and one per-sample metric launch into a preallocated [n_steps,B,7] / [n_steps,B] device log; no
@@ -457,6 +510,11 @@ def evaluate(args, model, rank, world, dev):
     ranks (numpy [7]), or None for predict (rank 0 has then written predictions.npy)."""
     runner = None
     preds = []
+    writer = namer = None
+    if args.mode == "predict" and args.save_dir is not None:
+        from .export import PredictionWriter
+        writer = PredictionWriter(args.save_dir, args.save_format, args.save_panels, near=args.save_range[0],
+                                  far=args.save_range[1], err_max=args.save_err_max)
     host_input = args.host_input and args.dataset == "synthetic" and args.mode != "predict"
     if args.eval_streams:
         eval_streams(args, model, dev)
@@ -481,6 +539,24 @@ def evaluate(args, model, rank, world, dev):
         return stream_runner[0](sf)["depth"]
 
     import time
+    t_save = None
+
+    def emit(frame):
+        """One predicted frame batch: to the writer (its export launch follows the forward -- or the graph replay -- on the
+        same stream; nothing is kept), or to the list predictions.npy is made of."""
+        nonlocal namer, t_save
+        est = predict(frame)
+        if writer is None:
+            preds.append(est.cpu().numpy())
+            return
+        if namer is None:
+            from .export import FrameNamer
+            namer = FrameNamer(est.shape[0])
+            t_save = time.perf_counter()
+        want_gt = any(p in ("gt", "err") for p in writer.panels)
+        writer.submit(est, namer(frame["new_traj"]), gt=frame.get("depth") if want_gt else None,
+                      rgb=frame["RGB_im"] if "rgb" in writer.panels else None)
+
     n_frames, t_loop = 0, None
     for batch_idx, data in enumerate(batches):
         if host_input:
@@ -491,7 +567,7 @@ def evaluate(args, model, rank, world, dev):
             n_frames += data["RGB_im"].shape[0] * data["RGB_im"].shape[1]
         if data["RGB_im"].dim() == 4:            # streaming frame of a real dataset (db_seq_len None)
             if args.mode == "predict":
-                preds.append(predict(data).cpu().numpy())
+                emit(data)
             else:
                 model.test_step(data)
             continue
@@ -499,7 +575,7 @@ def evaluate(args, model, rank, world, dev):
             for t in range(data["RGB_im"].shape[1]):
                 frame = {k: data[k][:, t] for k in ("depth", "RGB_im", "rot", "trans", "new_traj")}
                 frame["camera"] = data["camera"]
-                preds.append(predict(frame).cpu().numpy())
+                emit(frame)
             continue
         if args.graph:
             if runner is None:
@@ -510,6 +586,14 @@ def evaluate(args, model, rank, world, dev):
             model.graphed_test_step(data, runner)
         else:
             model.test_step(data)
+    if writer is not None:
+        writer.close()
+        if namer is not None:
+            dt = time.perf_counter() - t_save
+            print(f"predict: wrote {writer.frames} frames ({args.save_format}"
+                  + (", panels " + ",".join(writer.panels) if writer.panels else "")
+                  + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
+        return None
     if args.mode == "predict":
         if rank == 0:
             os.makedirs(args.ckpt_dir, exist_ok=True)
@@ -554,9 +638,12 @@ def main(argv=None):
         parser.error("--stream is a --mode=predict option")
     _check_eval_streams(parser, args)
     check_train_args(parser, args)
+    check_save_args(parser, args)
     rank, world, _, dev = D.init_from_env()
     if args.eval_streams and world > 1:
         raise SystemExit("streaming evaluation (--eval_streams) is sequential over the trajectories: run it on one rank")
+    if args.save_dir is not None and world > 1:
+        raise SystemExit("--save_dir writes one directory tree from one process: run it on one rank")
     if dev.type != "cuda":
         raise SystemExit("m4depth_amd.main needs a GPU: the hot path has no CPU fallback")
     ablation = ablation_from_args(args)

@@ -318,6 +318,65 @@ def depth_metrics_per_sample(gt, est, new_traj, active, max_d=80.0, rows=None, c
     return rows, counted
 
 
+EXPORT_FORMATS = {None: 0, "kitti16": 1, "midair16": 2}          # the `format` argument of m4d_depth_export
+EXPORT_PANELS = {"rgb": 0, "est": 1, "gt": 2, "err": 3}          # its panel kinds
+
+
+def depth_export(est, fmt, panels=(), gt=None, rgb=None, lut=None, near=1.0, far=80.0, err_max=0.5, depth16=None,
+                 panels_out=None):
+    """The estimate of a frame batch in its on-disk forms, one launch (m4d_depth_export): returns (depth16, panels).
+
+    ``est`` [b,h,w,1], ``gt`` [b,h,w,1], ``rgb`` [b,h,w,3]: float32 device tensors with dense images at a batch stride (a
+    frame slice of a sequence batch is read in place).  ``fmt`` 'kitti16' | 'midair16' | None -> ``depth16`` [b,h,w] int16
+    holding the uint16 bits (torch moves no uint16: ``.numpy().view(np.uint16)`` on the host), None without a format.
+    ``panels``: up to four of 'rgb', 'est', 'gt', 'err' -> [b, len(panels)*h, w, 3] uint8, None when empty; ``lut`` [257,3]
+    uint8 device tensor (export.default_lut), row 256 the invalid colour.  ``depth16`` / ``panels_out``: destinations to
+    write into (the slot buffers of export.PredictionWriter).  Nothing synchronises."""
+    if fmt not in EXPORT_FORMATS:
+        raise ValueError(f"fmt: expected one of {[k for k in EXPORT_FORMATS if k]} or None, got {fmt!r}")
+    panels = tuple(panels)
+    unknown = [p for p in panels if p not in EXPORT_PANELS]
+    if unknown or len(panels) > 4:
+        raise ValueError(f"panels: up to four of {list(EXPORT_PANELS)}, got {panels}")
+    if est.dim() != 4 or est.shape[3] != 1:
+        raise ValueError(f"est: expected [b,h,w,1], got {tuple(est.shape)}")
+    b, h, w = est.shape[:3]
+    dev = est.device
+    strides = {"est": _batch_stride(est, "est")}
+    for name, t, c, kinds in (("gt", gt, 1, ("gt", "err")), ("rgb", rgb, 3, ("rgb",))):
+        if t is None:
+            if any(p in kinds for p in panels):
+                raise ValueError(f"panels {panels} need {name}")
+            strides[name] = 0
+            continue
+        if tuple(t.shape[:3]) != (b, h, w) or t[0].numel() != h * w * c:
+            raise ValueError(f"{name} {tuple(t.shape)} does not belong to est {tuple(est.shape)}")
+        strides[name] = _batch_stride(t, name)
+    if any(p != "rgb" for p in panels):
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (257, 3):
+            raise ValueError("lut: expected a [257,3] uint8 device tensor (export.default_lut)")
+    else:
+        lut = None
+    if fmt is None:
+        depth16 = None
+    elif depth16 is None:
+        depth16 = torch.empty((b, h, w), dtype=torch.int16, device=dev)
+    elif tuple(depth16.shape) != (b, h, w):
+        raise ValueError(f"depth16: expected {(b, h, w)}, got {tuple(depth16.shape)}")
+    if not panels:
+        panels_out = None
+    elif panels_out is None:
+        panels_out = torch.empty((b, len(panels) * h, w, 3), dtype=torch.uint8, device=dev)
+    elif tuple(panels_out.shape) != (b, len(panels) * h, w, 3):
+        raise ValueError(f"panels_out: expected {(b, len(panels) * h, w, 3)}, got {tuple(panels_out.shape)}")
+    kinds = (ctypes.c_int * 4)(*[EXPORT_PANELS[p] for p in panels])
+    ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())          # noqa: E731  (views: checked above)
+    check(lib.m4d_depth_export(ptr(est), strides["est"], ptr(gt), strides["gt"], ptr(rgb), strides["rgb"], b, h, w,
+                               EXPORT_FORMATS[fmt], dptr(depth16, "depth16", torch.int16), len(panels), kinds,
+                               dptr(lut, "lut", torch.uint8), float(near), float(far), float(err_max),
+                               dptr(panels_out, "panels_out", torch.uint8), stream_ptr()), "m4d_depth_export")
+    return depth16, panels_out
+
 
 def train_log_step(loss, gt, est, log, counter, first_bad):
     """The step log of a training step (m4d_train_log_step): [loss, RMSE_log of the last frame] into row ``counter % rows`` of
