@@ -668,6 +668,30 @@ int m4d_depth_export(const float* est, long long est_stride, const float* gt, lo
                      const int* panel_kinds, const uint8_t* lut, float near, float far, float err_max, uint8_t* panels,
                      void* stream);
 
+/* ---- training summaries (main.py --mode=train --log_dir): float32 maps -> the uint8 images of a TensorBoard event -------- */
+
+/* Up to 16 float32 maps of different sizes -> uint8 images, in one launch.  src, stride, h, w, c, kind and out_offset are
+ * HOST arrays of n_maps entries (the descriptors travel to the kernel by value: no device-side table).  Map m is
+ * [b_m, h[m], w[m], c[m]] with c 1 or 3, image i at src[m] + i * stride[m] ELEMENTS (stride >= h*w*c: a frame slice of a
+ * [b,T,H,W,c] batch is read in place); only the first n images of every map are converted (tf.summary.image's max_outputs;
+ * every map must hold at least n).  The byte of map m, image i < n, pixel (y,x), channel ch is
+ *   out[out_offset[m] + ((i*h + y)*w + x)*c + ch]
+ * float32, one IEEE rounding per operation:
+ *   q(v)    : v NaN -> 0; t = v * 255.5f; t < 0 -> 0; t >= 255 -> 255 (+inf included); else (uint8) t, truncated.  This is
+ *             TensorFlow's convert_image_dtype(float32 -> uint8, saturate=True) -- scale by max + 0.5, saturate, truncating
+ *             cast -- which tf.summary.image applies.  Stated from TensorFlow's source as remembered: nothing in the build
+ *             environment can execute TensorFlow, so the rule is NOT checked against it.
+ *   kind 0  : colour or any map already in [0,1]: q(v)
+ *   kind 1  : log depth (m4depth_network.py:403,409,411-414):
+ *             q(logf(fminf(fmaxf(d, 1.0f), 200.0f)) / 5.29831737f), the constant the float32 nearest to ln 200; NaN, 0,
+ *             negative depths and velodyne holes give 0.
+ * Every output byte of the n images is written, nothing else.  Returns 1 without a launch for: n_maps outside 1..16, n < 1,
+ * a NULL array, source or out, c not 1 or 3, an unknown kind, h or w < 1, a stride smaller than an image, a float pointer off
+ * 4 bytes, a negative out_offset or overlapping output ranges.  Plain launch (capturable).  Additive entry point: ABI 6
+ * unchanged. */
+int m4d_summary_images(int n_maps, const float* const* src, const long long* stride, const int* h, const int* w, const int* c,
+                       const int* kind, const long long* out_offset, int n, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

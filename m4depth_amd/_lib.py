@@ -74,6 +74,9 @@ _SIGNATURES = {
                                 _c_fp, _c_fp],
     "m4d_depth_export": [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int, _c_int,
                          _c_int, _c_fp, _c_int, ctypes.POINTER(_c_int), _c_fp, _c_f, _c_f, _c_f, _c_fp, _c_fp],
+    "m4d_summary_images": [_c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(_c_int),
+                           ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
+                           ctypes.POINTER(ctypes.c_longlong), _c_int, _c_fp, _c_fp],
     "m4d_normalize_cuts": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
     "m4d_resize_bilinear_v1": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
     "m4d_resize_nearest": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],

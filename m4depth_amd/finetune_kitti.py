@@ -9,7 +9,7 @@
 * both repeat forever and every BATCH is drawn from one of the two with p = 0.5 (a generator seeded by ``--seed``);
 * an epoch is 2 x the KITTI length in steps, and the run lasts ``--finetune_steps // steps_per_epoch + 1`` epochs from the
   latest checkpoint of ``<ckpt_dir>/train`` on, with velodyne-type supervision;
-* checkpoints, TerminateOnNaN, ``--enable_validation`` and ``--graph`` behave as in ``m4depth_amd.main --mode=finetune``
+* checkpoints, TerminateOnNaN, ``--enable_validation``, ``--log_dir`` and ``--graph`` behave as in ``m4depth_amd.main --mode=finetune``
   (one captured step serves both datasets: they share the geometry).
 """
 from __future__ import annotations

@@ -13,6 +13,8 @@ reference it writes the 7 metrics with ``%.18e`` (one per line, as np.savetxt do
 is sharded (m4depth_amd.dist) and the metric accumulators are all-gathered over RCCL.
 ``--mode=predict --save_dir DIR`` writes every frame's estimate as a 16-bit depth PNG in a dataset's own encoding (and, with
 ``--save_panels``, a colour panel PNG) through ``m4depth_amd.export.PredictionWriter`` instead of collecting predictions.npy.
+``--mode=train --log_dir DIR`` writes the training summaries (loss, RMSE_log, the reference's summary images) as a TensorBoard
+event file through ``m4depth_amd.summaries.TrainSummaryWriter``.
 ``--eval_streams B`` runs a dataset's streaming evaluation (no ``--db_seq_len``) with B whole trajectories side by side
 (m4depth_amd.stream_eval) and writes the same perfs file as the one-frame-at-a-time loop.
 """
@@ -84,6 +86,11 @@ def build_parser():
     p.add_argument("--summary_interval", type=int, default=1200,
                    help="train --graph: read the device-side step log every N steps (m4depth_options.py:47-49); it is also "
                         "read at every epoch end and before every checkpoint")
+    p.add_argument("--log_dir", default=None, metavar="DIR",
+                   help="train: write a TensorBoard event file to DIR (m4depth_options.py:43; m4depth_amd.summaries): loss and "
+                        "RMSE_log of every step, and every --summary_interval steps the images of the reference's train_step "
+                        "(RGB_im, camera_prev_t_reproj, depth_gt, depth_lvl_i), converted on the GPU and compressed in host "
+                        "threads.  Rank 0 only")
     p.add_argument("--max_keep", type=int, default=0,
                    help="train: keep only the newest N checkpoints of <ckpt_dir>/train (0 = keep all)")
     p.add_argument("--enable_validation", action="store_true",
@@ -234,6 +241,19 @@ def default_epochs(args, rank, world, dev):
 
 
 def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
+    """``_train`` with the summary writer of ``--log_dir`` (rank 0; None without the option), closed on every way out."""
+    summary = None
+    if getattr(args, "log_dir", None) is not None and rank == 0:
+        from .summaries import TrainSummaryWriter
+        summary = TrainSummaryWriter(args.log_dir)
+    try:
+        return _train(args, ablation, rank, world, dev, epochs, depth_type, summary)
+    finally:
+        if summary is not None:
+            summary.close()
+
+
+def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summary=None):
     """main.py:73-109: Adam(1e-4), RMSE_log as the tracked metric, resume from the latest checkpoint.
     Several ranks = data parallel: the global batch is sharded and the gradients are averaged with
     one RCCL all-reduce per step (dist.all_reduce_gradients).
@@ -245,6 +265,11 @@ def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
 
     TerminateOnNaN (callbacks.py:69-132): a non-finite loss ends training with status 1; nothing of that epoch is saved (in
     graph mode the steps replayed after the bad one are discarded with it) and the checkpoints on disk stay as they are.
+
+    ``summary`` (a ``summaries.TrainSummaryWriter``): every reported step's loss and RMSE_log go to it as they are printed, and
+    at every step where ``(step - step0) % summary_interval == 0`` the step's images -- in graph mode right after that step's
+    replay (and the log read that tells whether it was finite), before the next batch is copied into the static buffers.
+    Nothing is written for a step with a non-finite loss or a later one.
 
     ``epochs`` = (count, epoch -> batches) (default: the dataset's, ``default_epochs``); ``depth_type`` defaults to the
     dataset's."""
@@ -288,6 +313,8 @@ def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
     def report(step, loss, rmse):
         if rank == 0:
             print(f"step {step}: loss {loss:.6f}  RMSE_log {rmse:.6f}")
+        if summary is not None:
+            summary.scalars(step, loss, rmse)
 
     step_log = runner = geometry = None
     logged = [step0]                                  # graph mode: the last step whose log row the host has read
@@ -303,6 +330,9 @@ def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
             report(logged[0] + i + 1, float(loss), float(rmse_log.result()))
         logged[0] += len(rows)
         return step0 + first_bad + 1 if first_bad >= 0 else None
+
+    def images_due(step):
+        return summary is not None and nan_step is None and (step - step0) % max(args.summary_interval, 1) == 0
 
     step, t0, n_timed, nan_step = step0, None, 0, None
     for epoch in range(n_epochs):
@@ -321,6 +351,8 @@ def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
                 step += 1
                 if (step - step0) % max(args.summary_interval, 1) == 0 or (args.save_every and step % args.save_every == 0):
                     nan_step = read_log()
+                if images_due(step):
+                    summary.images(step, runner.static, runner.pyramid, runner.camera)
             else:
                 out = model.train_step(data, grad_sync=sync)
                 step += 1
@@ -333,6 +365,8 @@ def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
                     nan_step = step
                 else:
                     report(step, loss, float(out["RMSE_log"]))
+                    if images_due(step):
+                        summary.images(step, data, model.last_pyramid, data["camera"])
             if nan_step is not None:
                 break
             if args.save_every and step % args.save_every == 0:
@@ -616,6 +650,8 @@ def check_train_args(parser, args, world=None):
         world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.summary_interval < 1:
         parser.error("--summary_interval must be >= 1")
+    if args.log_dir is not None and args.mode not in ("train", "finetune"):
+        parser.error("--log_dir is a --mode=train / --mode=finetune option")
     if args.max_keep < 0:
         parser.error("--max_keep must be >= 0")
     if args.keep_top_n < 1:

@@ -378,6 +378,55 @@ def depth_export(est, fmt, panels=(), gt=None, rgb=None, lut=None, near=1.0, far
     return depth16, panels_out
 
 
+SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                      # the `kind` argument of m4d_summary_images
+SUMMARY_MAX_MAPS = 16
+
+
+def summary_layout(shapes, n):
+    """(byte offsets, total bytes) of the images ``summary_images`` writes for maps of ``shapes`` [(h, w, c), ...]: map m's
+    [n,h,w,c] block starts at a multiple of 16 bytes."""
+    offsets, total = [], 0
+    for h, w, c in shapes:
+        offsets.append(total)
+        total += -(-(int(n) * h * w * c) // 16) * 16
+    return offsets, total
+
+
+def summary_images(maps, kinds, n, out=None):
+    """The first ``n`` images of every map as uint8, one launch for all of them (m4d_summary_images): returns a list of
+    [n,h,w,c] uint8 tensors, views of one buffer.
+
+    ``maps``: up to 16 float32 device tensors [b,h,w,c], c 1 or 3, b >= n, of any sizes, with dense images at a batch stride
+    (a frame slice such as ``data["RGB_im"][:, -1]`` is read in place).  ``kinds``: per map 'unit' (values in [0,1]: colour) or
+    'log_depth' (log(clip(d, 1, 200)) / log(200)).  ``out``: the flat uint8 device buffer to write into, at least
+    ``summary_layout(...)[1]`` bytes (a slot of summaries.TrainSummaryWriter); allocated when None.  Nothing synchronises."""
+    maps, kinds, n = list(maps), list(kinds), int(n)
+    if not 1 <= len(maps) <= SUMMARY_MAX_MAPS or len(kinds) != len(maps):
+        raise ValueError(f"summary_images: 1..{SUMMARY_MAX_MAPS} maps with one kind each, got {len(maps)} maps, {len(kinds)} kinds")
+    unknown = [k for k in kinds if k not in SUMMARY_KINDS]
+    if unknown:
+        raise ValueError(f"kinds: expected {list(SUMMARY_KINDS)}, got {unknown}")
+    strides = []
+    for i, t in enumerate(maps):
+        strides.append(_batch_stride(t, f"maps[{i}]"))
+        if t.dim() != 4 or t.shape[3] not in (1, 3) or t.shape[0] < n or n < 1:
+            raise ValueError(f"maps[{i}]: expected [b >= {n},h,w,1 or 3] with n >= 1, got {tuple(t.shape)}")
+    shapes = [tuple(t.shape[1:]) for t in maps]
+    offsets, total = summary_layout(shapes, n)
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=maps[0].device)
+    elif out.dim() != 1 or out.numel() < total:
+        raise ValueError(f"out: expected a flat uint8 buffer of at least {total} bytes, got {tuple(out.shape)}")
+    m = len(maps)
+    ints = lambda vals: (ctypes.c_int * m)(*vals)                                   # noqa: E731
+    longs = lambda vals: (ctypes.c_longlong * m)(*vals)                             # noqa: E731
+    check(lib.m4d_summary_images(m, (ctypes.c_void_p * m)(*[t.data_ptr() for t in maps]), longs(strides),
+                                 ints([s[0] for s in shapes]), ints([s[1] for s in shapes]), ints([s[2] for s in shapes]),
+                                 ints([SUMMARY_KINDS[k] for k in kinds]), longs(offsets), n, dptr(out, "out", torch.uint8),
+                                 stream_ptr()), "m4d_summary_images")
+    return [out[o:o + n * h * w * c].view(n, h, w, c) for o, (h, w, c) in zip(offsets, shapes)]
+
+
 def train_log_step(loss, gt, est, log, counter, first_bad):
     """The step log of a training step (m4d_train_log_step): [loss, RMSE_log of the last frame] into row ``counter % rows`` of
     ``log`` [rows, 2] float32, ``counter`` += 1, ``first_bad`` latched to the step index of the first non-finite loss -- all on

@@ -394,6 +394,7 @@ def train_step(model, data, optimizer, grad_sync=None):
         grad_sync([p for g in optimizer.param_groups for p in g["params"]])
     optimizer.step()
     model.step_counter += 1
+    model.last_pyramid = [lvl["depth"].detach() for lvl in preds[-1]]                # what :410-415 draw, finest first
     with torch.no_grad():                                                            # :418-427
         gt = gts[-1]["depth"]
         est = nops.resize_nearest(preds[-1][0]["depth"].detach().contiguous(), gt.shape[1], gt.shape[2])
@@ -417,6 +418,9 @@ class GraphedTrainStep:
     host synchronisation and fixed shapes, so it is captured once and replayed: the host then
     only copies the next batch into the static input buffers.
 
+    ``pyramid``: the last frame's depth estimate of every level, finest first (``est is pyramid[0]``), static tensors of the
+    capture like ``loss`` -- what ``summaries.TrainSummaryWriter.images`` draws as ``depth_lvl_i``.
+
     ``step_log`` (optional, a ``TrainStepLog``): every step, the warm-up steps included, ends with its device-side log
     entry, so the host reads losses and metrics only when it wants to.
 
@@ -435,15 +439,21 @@ class GraphedTrainStep:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
+            warm = None
             for _ in range(warmup):
-                self._step()
+                warm = self._step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         optimizer.zero_grad(set_to_none=True)
         self.graph = torch.cuda.CUDAGraph()
         from ._lib import framework_copies_in_capture
         with framework_copies_in_capture(), torch.cuda.graph(self.graph):      # the autograd graph's own nodes are framework kernels
-            self.loss, self.est = self._step()
+            self.loss, self.pyramid = self._step()
+        self.est = self.pyramid[0]
+        if warm is not None:                           # capturing ran nothing: until the first replay the static outputs hold the
+            self.loss.copy_(warm[0])                   # last warm-up step's, the step the caller has just taken
+            for dst, src in zip(self.pyramid, warm[1]):
+                dst.copy_(src)
 
     def _data(self):
         d = dict(self.static)
@@ -462,10 +472,10 @@ class GraphedTrainStep:
         if self.grad_sync is not None:
             self.grad_sync([p for g in self.optimizer.param_groups for p in g["params"]])
         self.optimizer.step()
-        loss, est = loss.detach(), preds[-1][0]["depth"].detach()
+        loss, pyramid = loss.detach(), [lvl["depth"].detach() for lvl in preds[-1]]
         if self.step_log is not None:                  # the last node of the step: warm-up steps are logged too
-            self.step_log.record(loss, self.static["depth"][:, -1], est)
-        return loss, est
+            self.step_log.record(loss, self.static["depth"][:, -1], pyramid[0])
+        return loss, pyramid
 
     def __call__(self, data=None):
         """Copies ``data`` into the static buffers, replays the step; returns (loss, finest depth
