@@ -668,6 +668,51 @@ int m4d_depth_export(const float* est, long long est_stride, const float* gt, lo
                      const int* panel_kinds, const uint8_t* lut, float near, float far, float err_max, uint8_t* panels,
                      void* stream);
 
+/* ---- point clouds (main.py --mode=predict --save_dir --save_cloud): the estimate as 3-D geometry ------------------------ */
+
+/* One camera-to-world pose per sample, kept on the device (the host never reads it): pose [b,7] float64 = qw qx qy qz tx ty tz,
+ * in / out.  rot [b,4] quaternion w,x,y,z, trans [b,3]: the frame-to-frame motion the network gets, in the convention
+ * reproject implies (utils/depth_operations.py:72-105): a point X of the current camera is R(rot) X + trans in the previous
+ * camera.  The world is the camera of the trajectory's first frame.  reset [b] uint8 device mask (may be NULL = nobody).
+ *   force_all || reset[s] : pose[s] = (1,0,0,0; 0,0,0); rot / trans of that sample are not read
+ *   otherwise             : q = rot[s] / |rot[s]|            (float64; |.| = sqrt(((w*w + x*x) + y*y) + z*z))
+ *                           tw <- R(qw_old) trans[s] + tw_old  (R as get_rot_mat writes it, in float64, rows summed left to right)
+ *                           qw <- (qw_old q) / |qw_old q|      (Hamilton product: R(qw) = R(qw_old) R(q))
+ * All of it float64, one rounding per operation.  Unlike get_rot_mat (utils/depth_operations.py:18-53), which uses the
+ * quaternion as it comes, both the incoming quaternion and the product are renormalised: the network sees one float32
+ * quaternion per frame, this state is the product of thousands of them, and without the renormalisation its norm drifts and
+ * R(qw) stops being a rotation (the cloud shears and scales).  Only rot_c = 4: a small-angle rot has no exact composition.
+ * A zero or non-finite quaternion makes the sample's pose NaN until its next reset.
+ * Returns 1 without a launch for: a NULL rot, trans or pose, b <= 0, rot / trans off 4 bytes, pose off 8.  One plain launch
+ * (capturable).  Additive entry point: ABI 6 unchanged. */
+int m4d_pose_accumulate(const unsigned char* reset, int force_all, const float* rot, const float* trans, int b, double* pose,
+                        void* stream);
+
+/* The depth maps of one step -> dense lists of coloured vertices.  depth [b,h,w,1], rgb [b,h,w,3] in 0..1: float32, image i at
+ * ptr + i * stride ELEMENTS (depth_stride >= h*w, rgb_stride >= 3*h*w: views are read in place); cam_f, cam_c [b,2];
+ * pose [b,7] float64 as m4d_pose_accumulate keeps it, or NULL = camera frame.
+ * A pixel (row, col) is kept when row % step == 0, col % step == 0, its depth d is finite and near <= d <= far.  Its vertex is
+ * 16 bytes: float32 x, y, z, then uint8 r, g, b, a:
+ *   x = (((col + 0.5f) - cx) / fx) * d,  y = (((row + 0.5f) - cy) / fy) * d,  z = d     (float32, get_coords_2d's operand order)
+ *   with pose: (x, y, z) <- (float) (R(q) (x, y, z) + t), R as get_rot_mat writes it and every operation in float64, rows
+ *              summed left to right, then t added: one rounding to float32 at the end
+ *   r, g, b = m4d_depth_export's rgb rule: (uint8) rintf(min(max(v, 0.0f), 1.0f) * 255.0f), NaN -> 0;  a = 255
+ * vertices [b, cap, 16 bytes] with cap = ceil(h/step) * ceil(w/step): the kept vertices of sample s are written densely from
+ * vertices[s][0] in raster order (deterministic: comparable byte for byte), one 16-byte store each; counts[s] int32 = their
+ * number; the tail beyond the count is left untouched.  workspace: m4d_depth_cloud_workspace_ints(b,h,w,step) int32.
+ * Two plain launches (capturable): a per-workgroup count, then the write pass, in which a workgroup sums the counts of the
+ * workgroups before it in its sample and places its vertices by wave64 ballots; no workgroup waits on another, no atomics.
+ * The write pass reads one count per earlier workgroup of the sample, so its cost grows with cap squared: cap > 2^24 (4096 x
+ * 4096 candidates) is refused.
+ * Returns 1 without a launch for: a NULL depth, rgb, cam_f, cam_c, vertices, counts or workspace, b <= 0 or > 65535, h or
+ * w <= 0, step < 1, cap > 2^24, far <= near (or a NaN bound), a stride smaller than an image, float / int pointers off 4 bytes, pose off
+ * 8, vertices off 16.  Additive entry points: ABI 6 unchanged. */
+int m4d_depth_cloud(const float* depth, long long depth_stride, const float* rgb, long long rgb_stride, const float* cam_f,
+                    const float* cam_c, const double* pose, int b, int h, int w, int step, float near, float far,
+                    void* vertices, int* counts, int* workspace, void* stream);
+/* int32 elements of m4d_depth_cloud's workspace (0 for a geometry it refuses). */
+long long m4d_depth_cloud_workspace_ints(int b, int h, int w, int step);
+
 /* ---- training summaries (main.py --mode=train --log_dir): float32 maps -> the uint8 images of a TensorBoard event -------- */
 
 /* Up to 16 float32 maps of different sizes -> uint8 images, in one launch.  src, stride, h, w, c, kind and out_offset are

@@ -5,6 +5,11 @@ do with them is save a depth map and a colourised estimate beside the ground tru
 batch (``network_ops.depth_export``) writes the estimate in a dataset's own 16-bit encoding and as ready-to-save RGB8 panels,
 ``PredictionWriter`` moves them through a ring of pinned buffers, and host threads do the PNG compression: the predict loop
 never waits for the host unless every slot of the ring is in flight, and host memory is ``slots`` frames however long the run.
+
+With ``cloud=True`` the writer also keeps one camera-to-world pose per sample on the device (``network_ops.pose_accumulate``),
+turns every estimate into a dense list of coloured vertices (``network_ops.depth_cloud``) and writes it as a binary PLY file
+beside the PNGs; the host never redoes the camera model or the pose chain, and never reads a vertex count before the slot's
+event has passed.
 """
 from __future__ import annotations
 
@@ -77,14 +82,67 @@ def read_depth_png(path, fmt):
         return np.float32(512.0) / bits.view(np.float16).astype(np.float32)
 
 
+PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")])
+_PLY_PROPERTIES = ["property float x", "property float y", "property float z", "property uchar red", "property uchar green",
+                   "property uchar blue", "property uchar alpha"]
+CLOUD_FRAMES = ("world", "camera")
+
+
+def write_cloud_ply(path, vertices, pose):
+    """``vertices``: [n,16] uint8 (or n ``PLY_VERTEX`` records) as ``network_ops.depth_cloud`` writes them, stored verbatim as
+    the body of a binary little-endian PLY file; ``pose``: the 7 float64 of the frame's camera-to-world pose, kept in a
+    comment line at full precision."""
+    body = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1, 16)
+    header = ["ply", "format binary_little_endian 1.0",
+              "comment pose " + " ".join("%.17g" % v for v in np.asarray(pose, np.float64).reshape(7)),
+              "element vertex %d" % len(body)] + _PLY_PROPERTIES + ["end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(body.data)
+
+
+def read_cloud_ply(path):
+    """A ``<name>_cloud.ply`` of ``PredictionWriter``: (xyz float32 [n,3], rgba uint8 [n,4], pose float64 [7])."""
+    with open(path, "rb") as fh:
+        lines = []
+        while not lines or lines[-1] != "end_header":
+            line = fh.readline()
+            if not line or len(lines) > 64:
+                raise ValueError(f"{path}: no PLY header")
+            lines.append(line.decode("ascii").rstrip("\r\n"))
+        body = fh.read()
+    poses = [l for l in lines if l.startswith("comment pose ")]
+    counts = [l for l in lines if l.startswith("element vertex ")]
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"] or len(poses) != 1 or len(counts) != 1 \
+            or [l for l in lines if l.startswith("property ")] != _PLY_PROPERTIES:
+        raise ValueError(f"{path}: not a point cloud of PredictionWriter")
+    n = int(counts[0].split()[2])
+    if len(body) != 16 * n:
+        raise ValueError(f"{path}: {n} vertices in the header, {len(body)} bytes in the body")
+    raw = np.frombuffer(body, np.uint8).reshape(n, 16)
+    pose = np.array([float(v) for v in poses[0].split()[2:]], np.float64)
+    if pose.shape != (7,):
+        raise ValueError(f"{path}: the pose comment holds {pose.size} numbers")
+    return raw[:, :12].copy().view(np.float32), raw[:, 12:].copy(), pose
+
+
 class _Slot:
-    def __init__(self, b, h, w, n_panels, dev):
+    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0):
         self.depth_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
         self.depth_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
         self.panels_d = self.panels_h = None
         if n_panels:
             self.panels_d = torch.empty((b, n_panels * h, w, 3), dtype=torch.uint8, device=dev)
             self.panels_h = torch.empty((b, n_panels * h, w, 3), dtype=torch.uint8).pin_memory()
+        self.cloud_d = None
+        if cloud_cap:
+            self.cloud_d = torch.empty((b, cloud_cap, 16), dtype=torch.uint8, device=dev)
+            self.cloud_h = torch.empty((b, cloud_cap, 16), dtype=torch.uint8).pin_memory()
+            self.counts_d = torch.empty(b, dtype=torch.int32, device=dev)
+            self.counts_h = torch.empty(b, dtype=torch.int32).pin_memory()
+            self.pose_h = torch.empty((b, 7), dtype=torch.float64).pin_memory()
+            self.reset_d = torch.empty(b, dtype=torch.uint8, device=dev)
+            self.reset_h = torch.empty(b, dtype=torch.uint8).pin_memory()
         self.event = torch.cuda.Event()
         self.pending = 0
 
@@ -96,10 +154,17 @@ class PredictionWriter:
     threads, which wait for the event, compress and free the slot.  ``submit`` blocks only while every slot is in flight.
     ``close()`` (or leaving the ``with`` block) drains the ring and re-raises the first exception a worker hit.
     ``encode=False`` does everything but the file encoding (for measuring the loop without the PNG encoder).  All submits
-    must come from one stream and have one geometry."""
+    must come from one stream and have one geometry.
+
+    ``cloud=True`` also writes ``<name>_cloud.ply``: every ``cloud_step``-th pixel of every ``cloud_step``-th row whose
+    estimate is finite and within [near, far], as float x, y, z + uchar red, green, blue, alpha, in the frame of the
+    trajectory's first camera (``cloud_frame="world"``) or of the frame's own camera (``"camera"``); the frame's
+    camera-to-world pose is in the header either way (``read_cloud_ply``).  Each slot then also owns a [b,cap,16] byte vertex
+    buffer with its pinned twin, the counts and a pinned copy of the poses; the whole ``cap`` region crosses PCIe every step
+    (the count is only known on the device), the worker writes the first ``counts[s]`` vertices."""
 
     def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
-                 encode=True):
+                 encode=True, cloud=False, cloud_step=2, cloud_frame="world"):
         if fmt not in FORMATS:
             raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
         panels = tuple(panels)
@@ -109,6 +174,10 @@ class PredictionWriter:
             raise ValueError(f"need 0 < near < far and err_max > 0, got near {near}, far {far}, err_max {err_max}")
         if slots < 1 or threads < 1:
             raise ValueError("slots and threads must be >= 1")
+        if int(cloud_step) < 1 or cloud_frame not in CLOUD_FRAMES:
+            raise ValueError(f"cloud_step must be >= 1 and cloud_frame one of {CLOUD_FRAMES}, got {cloud_step}, {cloud_frame!r}")
+        self.cloud, self.cloud_step, self.cloud_frame = bool(cloud), int(cloud_step), cloud_frame
+        self._pose = None                                  # [b,7] float64 device state of the cloud: camera-to-world poses
         self.out_dir, self.fmt, self.panels = str(out_dir), fmt, panels
         self.near, self.far, self.err_max = float(near), float(far), float(err_max)
         self.n_slots, self.compress_level, self.encode = int(slots), int(compress_level), bool(encode)
@@ -138,14 +207,48 @@ class PredictionWriter:
     def _allocate(self, est):
         b, h, w = est.shape[:3]
         self._geometry = (b, h, w)
-        self._slots = [_Slot(b, h, w, len(self.panels), est.device) for _ in range(self.n_slots)]
+        cap = nops.cloud_capacity(h, w, self.cloud_step) if self.cloud else 0
+        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap) for _ in range(self.n_slots)]
         if any(p != "rgb" for p in self.panels):
             self._lut = torch.from_numpy(default_lut()).to(est.device)
         for i in range(self.n_slots):
             self._free.put(i)
 
-    def submit(self, est, names, gt=None, rgb=None):
-        """``est`` [b,h,w,1] (+ ``gt`` / ``rgb`` as the panels need) of one step; ``names``: b relative paths without suffix."""
+    def _submit_cloud(self, slot, est, rgb, rot, trans, camera, reset):
+        """The cloud of one step into ``slot``, on the current stream: pose update, compaction, copies."""
+        if rgb is None or rot is None or trans is None or camera is None:
+            raise ValueError("a writer with cloud=True needs rgb, rot, trans and camera at every submit")
+        first = self._pose is None
+        if first:
+            self._pose = torch.empty((est.shape[0], 7), dtype=torch.float64, device=est.device)
+        # the first submit resets everybody (force_all), so its flags change nothing: host flags are checked and then not even
+        # uploaded, a device mask costs nothing to pass on and so still gets pose_accumulate's dtype and shape check
+        mask = None
+        if reset is not None:                              # checked at every submit, used from the second on
+            on_device = torch.is_tensor(reset) and reset.is_cuda
+            if not on_device:                              # host flags (the frame's new_traj)
+                reset = np.asarray(reset.numpy() if torch.is_tensor(reset) else reset, dtype=bool).reshape(-1)
+            n = reset.numel() if on_device else len(reset)
+            if n != slot.reset_h.shape[0]:
+                raise ValueError(f"reset has {n} samples, the writer {slot.reset_h.shape[0]}")
+            if on_device:
+                mask = reset                               # dtype and shape: pose_accumulate's check
+            elif not first:                                # through the slot's pinned bytes
+                slot.reset_h.numpy()[:] = reset
+                slot.reset_d.copy_(slot.reset_h, non_blocking=True)
+                mask = slot.reset_d
+        nops.pose_accumulate(rot, trans, self._pose, reset=mask, force_all=first)
+        nops.depth_cloud(est, rgb, camera["f"], camera["c"], step=self.cloud_step, near=self.near, far=self.far,
+                         pose=self._pose if self.cloud_frame == "world" else None, vertices=slot.cloud_d, counts=slot.counts_d)
+        slot.cloud_h.copy_(slot.cloud_d, non_blocking=True)
+        slot.counts_h.copy_(slot.counts_d, non_blocking=True)
+        slot.pose_h.copy_(self._pose, non_blocking=True)
+
+    def submit(self, est, names, gt=None, rgb=None, rot=None, trans=None, camera=None, reset=None):
+        """``est`` [b,h,w,1] (+ ``gt`` / ``rgb`` as the panels need) of one step; ``names``: b relative paths without suffix.
+        With ``cloud``: ``rgb``, the frame's motion ``rot`` [b,4] / ``trans`` [b,3], ``camera`` {f, c} [b,2] and ``reset`` --
+        which samples start a trajectory with this frame (host flags or a uint8 [b] device mask, None = nobody); the first
+        submit resets every sample."""
         if self._closed:
             raise RuntimeError("PredictionWriter.submit after close()")
         if self._slots is None:
@@ -160,6 +263,8 @@ class PredictionWriter:
             slot.depth_h.copy_(slot.depth_d, non_blocking=True)
             if slot.panels_d is not None:
                 slot.panels_h.copy_(slot.panels_d, non_blocking=True)
+            if self.cloud:
+                self._submit_cloud(slot, est, rgb, rot, trans, camera, reset)
             slot.event.record()
         except BaseException:
             self._free.put(index)
@@ -169,6 +274,8 @@ class PredictionWriter:
             jobs.append((name + "_depth.png", slot.depth_h, s))
             if slot.panels_h is not None:
                 jobs.append((name + "_panels.png", slot.panels_h, s))
+            if self.cloud:
+                jobs.append((name + "_cloud.ply", None, s))
         slot.pending = len(jobs)
         self.frames += len(names)
         for job in jobs:
@@ -179,13 +286,16 @@ class PredictionWriter:
         try:
             slot.event.synchronize()
             if self.encode:
-                from PIL import Image
                 path = os.path.join(self.out_dir, rel_path)
                 os.makedirs(os.path.dirname(path), exist_ok=True)
-                arr = host[s].numpy()
-                if arr.dtype == np.int16:
-                    arr = arr.view(np.uint16)              # PIL mode I;16
-                Image.fromarray(arr).save(path, format="PNG", compress_level=self.compress_level)
+                if host is None:                           # the cloud: the count is read here, after the event
+                    write_cloud_ply(path, slot.cloud_h[s, :int(slot.counts_h[s])].numpy(), slot.pose_h[s].numpy())
+                else:
+                    from PIL import Image
+                    arr = host[s].numpy()
+                    if arr.dtype == np.int16:
+                        arr = arr.view(np.uint16)          # PIL mode I;16
+                    Image.fromarray(arr).save(path, format="PNG", compress_level=self.compress_level)
         except BaseException as e:                         # kept for close(); the slot is freed all the same
             with self._lock:
                 if self._error is None:

@@ -12,7 +12,9 @@ reference it writes the 7 metrics with ``%.18e`` (one per line, as np.savetxt do
 ``<ckpt_dir>/perfs-<dataset>.txt`` (main.py:144-148).  With several ranks the batch
 is sharded (m4depth_amd.dist) and the metric accumulators are all-gathered over RCCL.
 ``--mode=predict --save_dir DIR`` writes every frame's estimate as a 16-bit depth PNG in a dataset's own encoding (and, with
-``--save_panels``, a colour panel PNG) through ``m4depth_amd.export.PredictionWriter`` instead of collecting predictions.npy.
+``--save_panels``, a colour panel PNG) through ``m4depth_amd.export.PredictionWriter`` instead of collecting predictions.npy;
+``--save_cloud`` adds a coloured point cloud per frame (binary PLY), compacted on the GPU, in the frame of the trajectory's first
+camera.
 ``--mode=train --log_dir DIR`` writes the training summaries (loss, RMSE_log, the reference's summary images) as a TensorBoard
 event file through ``m4depth_amd.summaries.TrainSummaryWriter``.
 ``--eval_streams B`` runs a dataset's streaming evaluation (no ``--db_seq_len``) with B whole trajectories side by side
@@ -81,6 +83,14 @@ def build_parser():
                    help="--save_panels: the depths the colour scale of est / gt spans, linear in inverse depth (default 1 80)")
     p.add_argument("--save_err_max", type=float, default=None,
                    help="--save_panels: the relative error the colour scale of err saturates at (default 0.5)")
+    p.add_argument("--save_cloud", action="store_true",
+                   help="--save_dir: also write <frame>_cloud.ply, the estimate as coloured 3-D points (depths within "
+                        "--save_range), back-projected, posed and compacted on the GPU")
+    p.add_argument("--cloud_stride", type=int, default=None, metavar="N",
+                   help="--save_cloud: keep every N-th pixel of every N-th row (default 2)")
+    p.add_argument("--cloud_frame", default=None, choices=["world", "camera"],
+                   help="--save_cloud: coordinates in the frame of the trajectory's first camera (world, the default; the "
+                        "frame-to-frame motions are chained on the GPU) or of each frame's own camera")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--save_every", type=int, default=0, help="train: checkpoint every N steps (0 = at the end)")
     p.add_argument("--summary_interval", type=int, default=1200,
@@ -476,6 +486,15 @@ def check_save_args(parser, args):
     """Refusals of the ``--save_*`` options; fills in their defaults and parses ``--save_panels`` into a tuple."""
     from .export import PANELS
     others = [f for f in ("save_format", "save_panels", "save_range", "save_err_max") if getattr(args, f) is not None]
+    others += [f for f in ("save_cloud",) if args.save_cloud]
+    cloud_others = [f for f in ("cloud_stride", "cloud_frame") if getattr(args, f) is not None]
+    if args.save_dir is not None and cloud_others and not args.save_cloud:
+        parser.error("--%s needs --save_cloud" % cloud_others[0])
+    others += cloud_others
+    if args.cloud_stride is not None and args.cloud_stride < 1:
+        parser.error("--cloud_stride must be >= 1")
+    args.cloud_stride = 2 if args.cloud_stride is None else args.cloud_stride
+    args.cloud_frame = args.cloud_frame or "world"
     if args.save_dir is None:
         if others:
             parser.error("--%s needs --save_dir" % others[0])
@@ -548,7 +567,8 @@ def evaluate(args, model, rank, world, dev):
     if args.mode == "predict" and args.save_dir is not None:
         from .export import PredictionWriter
         writer = PredictionWriter(args.save_dir, args.save_format, args.save_panels, near=args.save_range[0],
-                                  far=args.save_range[1], err_max=args.save_err_max)
+                                  far=args.save_range[1], err_max=args.save_err_max, cloud=args.save_cloud,
+                                  cloud_step=args.cloud_stride, cloud_frame=args.cloud_frame)
     host_input = args.host_input and args.dataset == "synthetic" and args.mode != "predict"
     if args.eval_streams:
         eval_streams(args, model, dev)
@@ -588,8 +608,11 @@ def evaluate(args, model, rank, world, dev):
             namer = FrameNamer(est.shape[0])
             t_save = time.perf_counter()
         want_gt = any(p in ("gt", "err") for p in writer.panels)
+        cloud = {}
+        if writer.cloud:                                       # the cloud launches follow the forward / the replay on its stream
+            cloud = dict(rot=frame["rot"], trans=frame["trans"], camera=frame["camera"], reset=frame["new_traj"])
         writer.submit(est, namer(frame["new_traj"]), gt=frame.get("depth") if want_gt else None,
-                      rgb=frame["RGB_im"] if "rgb" in writer.panels else None)
+                      rgb=frame["RGB_im"] if "rgb" in writer.panels or writer.cloud else None, **cloud)
 
     n_frames, t_loop = 0, None
     for batch_idx, data in enumerate(batches):
@@ -626,6 +649,7 @@ def evaluate(args, model, rank, world, dev):
             dt = time.perf_counter() - t_save
             print(f"predict: wrote {writer.frames} frames ({args.save_format}"
                   + (", panels " + ",".join(writer.panels) if writer.panels else "")
+                  + (f", clouds at stride {writer.cloud_step}" if writer.cloud else "")
                   + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
         return None
     if args.mode == "predict":

@@ -378,7 +378,76 @@ def depth_export(est, fmt, panels=(), gt=None, rgb=None, lut=None, near=1.0, far
     return depth16, panels_out
 
 
-SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                      # the `kind` argument of m4d_summary_images
+def pose_accumulate(rot, trans, pose, reset=None, force_all=False):
+    """One step of the per-sample camera-to-world pose kept on the device (m4d_pose_accumulate): ``pose`` [b,7] float64
+    (qw qx qy qz tx ty tz) is updated in place and returned.  ``rot`` [b,4] quaternions, ``trans`` [b,3]: the frame's motion
+    as the network gets it; a small-angle ``rot`` [b,3] is refused (it has no exact composition).  ``reset``: uint8 / bool [b]
+    device mask of the samples that start a trajectory (identity pose), ``force_all``: all of them.  Nothing synchronises."""
+    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or pose.dim() != 2 or pose.shape[1] != 7:
+        raise ValueError("pose: expected a [b,7] float64 device tensor")
+    b = pose.shape[0]
+    if tuple(rot.shape) == (b, 3):
+        raise ValueError("rot: small-angle rotations [b,3] cannot be accumulated into a pose; quaternions [b,4] only")
+    if tuple(rot.shape) != (b, 4) or tuple(trans.shape) != (b, 3):
+        raise ValueError(f"expected rot [{b},4] and trans [{b},3], got {tuple(rot.shape)} and {tuple(trans.shape)}")
+    if reset is not None:
+        if not isinstance(reset, torch.Tensor) or reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (b,):
+            raise ValueError(f"reset: expected a uint8 / bool [{b}] device tensor")
+        reset = reset.view(torch.uint8) if reset.dtype == torch.bool else reset
+    check(lib.m4d_pose_accumulate(dptr(reset, "reset", torch.uint8), int(bool(force_all)), dptr(as_f32(rot, "rot"), "rot"),
+                                  dptr(as_f32(trans, "trans"), "trans"), b, dptr(pose, "pose", torch.float64), stream_ptr()),
+          "m4d_pose_accumulate")
+    return pose
+
+
+def cloud_capacity(h, w, step):
+    """Vertices per sample a [h,w] map can give at ``step``: the size of ``depth_cloud``'s buffer."""
+    return -(-int(h) // int(step)) * -(-int(w) // int(step))
+
+
+def depth_cloud(depth, rgb, cam_f, cam_c, step=2, near=1.0, far=80.0, pose=None, vertices=None, counts=None):
+    """The depth maps of a frame batch as dense lists of coloured vertices (m4d_depth_cloud): returns (vertices
+    [b,cap,16] uint8, counts [b] int32), cap = ``cloud_capacity(h, w, step)``.  ``depth`` [b,h,w,1], ``rgb`` [b,h,w,3]: float32
+    device tensors with dense images at a batch stride; ``cam_f`` / ``cam_c`` [b,2]; ``pose`` [b,7] float64 as
+    ``pose_accumulate`` keeps it (world frame) or None (camera frame).  Every ``step``-th pixel of every ``step``-th row with
+    a finite depth in [near, far] gives a vertex -- float32 x, y, z and uint8 r, g, b, a -- written densely in raster order;
+    the bytes beyond ``counts[s]`` vertices of sample s are left as they were.  ``vertices`` / ``counts``: destinations (the
+    slot buffers of export.PredictionWriter).  Nothing synchronises."""
+    if depth.dim() != 4 or depth.shape[3] != 1:
+        raise ValueError(f"depth: expected [b,h,w,1], got {tuple(depth.shape)}")
+    b, h, w = depth.shape[:3]
+    step = int(step)
+    if step < 1:
+        raise ValueError(f"step must be >= 1, got {step}")
+    if not float(far) > float(near):
+        raise ValueError(f"need near < far, got {near}, {far}")
+    if tuple(rgb.shape) != (b, h, w, 3):
+        raise ValueError(f"rgb {tuple(rgb.shape)} does not belong to depth {tuple(depth.shape)}")
+    if tuple(cam_f.shape) != (b, 2) or tuple(cam_c.shape) != (b, 2):
+        raise ValueError(f"cam_f / cam_c: expected [{b},2], got {tuple(cam_f.shape)} and {tuple(cam_c.shape)}")
+    if pose is not None and (not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (b, 7)):
+        raise ValueError(f"pose: expected a [{b},7] float64 device tensor")
+    ds, rs = _batch_stride(depth, "depth"), _batch_stride(rgb, "rgb")
+    cap = cloud_capacity(h, w, step)
+    dev = depth.device
+    if vertices is None:
+        vertices = torch.empty((b, cap, 16), dtype=torch.uint8, device=dev)
+    elif tuple(vertices.shape) != (b, cap, 16):
+        raise ValueError(f"vertices: expected {(b, cap, 16)}, got {tuple(vertices.shape)}")
+    if counts is None:
+        counts = torch.empty(b, dtype=torch.int32, device=dev)
+    elif tuple(counts.shape) != (b,):
+        raise ValueError(f"counts: expected [{b}], got {tuple(counts.shape)}")
+    ws = _workspace("depth_cloud", 4 * int(lib.m4d_depth_cloud_workspace_ints(b, h, w, step)), dev).view(torch.int32)
+    check(lib.m4d_depth_cloud(ctypes.c_void_p(depth.data_ptr()), ds, ctypes.c_void_p(rgb.data_ptr()), rs,
+                              dptr(as_f32(cam_f, "cam_f"), "cam_f"), dptr(as_f32(cam_c, "cam_c"), "cam_c"),
+                              dptr(pose, "pose", torch.float64), b, h, w, step, float(near), float(far),
+                              dptr(vertices, "vertices", torch.uint8), dptr(counts, "counts", torch.int32),
+                              dptr(ws, "workspace", torch.int32), stream_ptr()), "m4d_depth_cloud")
+    return vertices, counts
+
+
+SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                     # the `kind` argument of m4d_summary_images
 SUMMARY_MAX_MAPS = 16
 
 
