@@ -209,7 +209,9 @@ __device__ __forceinline__ M4dPixel m4d_pixel_factors(const M4dMotion& m, int i,
 // One dimension of _interpolate_bilinear (utils/dense_image_warp.py:127-154):
 // floor clamped to [0,size-2], alpha clamped to [0,1].  fmaxf/fminf return the
 // non-NaN operand, so a NaN query (t = 0 is 0/0 in the reference) yields index 0
-// instead of an out-of-bounds read.
+// and weight 0 instead of an out-of-bounds read, +-Inf the nearest border: rule R1 of
+// DESIGN.md "Degenerate inputs".  Every index a kernel derives from a query comes
+// from here; tests/test_gpu_degenerate.py holds every such route to it.
 __device__ __forceinline__ void m4d_bilinear_axis(float q, int size, int& i0, float& a) {
   const float fl = fminf(fmaxf(0.0f, floorf(q)), (float)(size - 2));
   i0 = (int)fl;

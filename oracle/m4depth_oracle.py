@@ -14,6 +14,12 @@ follows, relative to the reference root) and from TF's documented op semantics;
 points where TF's internal arithmetic order is not derivable from the
 reference are marked [UNPINNED] and the choice made here is stated.
 
+Degenerate inputs (zero translation: 0/0 queries; an epipole pixel; all-zero feature cuts): what the reference does there
+is a platform matter (TF's NaN -> int32 cast, the NaN handling of its maximum / minimum) and unpinnable here; this module
+states the project's own rules (DESIGN.md "Degenerate inputs"): the clamps of ``interpolate_bilinear``, of the hypothesis
+parallax and of the level tail are ``np.fmax`` / ``np.fmin`` (a NaN drops to index 0 / weight 0 / the lower bound), everything
+else is plain IEEE arithmetic.  For inputs without NaN they are ``np.maximum`` / ``np.minimum``.
+
 Conventions: NHWC float32; ``i`` = column (x), ``j`` = row (y).  Every
 elementwise expression is evaluated with one rounding per operation (numpy
 float32, no FMA), in exactly the operand order written, so that a HIP kernel
@@ -214,10 +220,10 @@ def interpolate_bilinear(grid, query, return_index=False):
     for dim, size in ((0, H), (1, W)):
         q = query[..., dim]
         max_floor = F32(size - 2)
-        fl = np.minimum(np.maximum(F32(0.0), np.floor(q)), max_floor)     # :137-138
+        fl = np.fmin(np.fmax(F32(0.0), np.floor(q)), max_floor)           # :137-138; fmax / fmin: DESIGN.md "Degenerate inputs" R1
         floors.append(fl.astype(np.int32))                                  # :139
         a = q - fl                                                          # :146
-        a = np.minimum(np.maximum(F32(0.0), a), F32(1.0))                   # :149
+        a = np.fmin(np.fmax(F32(0.0), a), F32(1.0))                         # :149 (R1: a NaN query has weight 0)
         alphas.append(a[..., None])
     y0, x0 = floors
     y1, x1 = y0 + 1, x0 + 1
@@ -440,7 +446,7 @@ def get_parallax_sweeping_cv(c1, c2, disp_prev_t, disp, rot, trans, camera, sear
     idx = []
     for t in range(ncp):
         n = F32(t - r)
-        p = np.minimum(np.maximum(disp[..., 0] + n, F32(1e-6)), F32(1e6))  # :235-236
+        p = np.fmin(np.fmax(disp[..., 0] + n, F32(1e-6)), F32(1e6))        # :235-236 (R2: NaN -> 1e-6)
         divider = m["sqrt"] / p                                            # :262
         dxx = m["delta_x"] / divider                                       # :263
         dyy = m["delta_y"] / divider
@@ -710,7 +716,7 @@ class DepthEstimatorLevel:
         out = disp_refiner(f_input, self.weights, self.lvl_depth)              # :245
         para = out[..., :1]
         other = out[..., 1:]
-        para_curr = (np.exp(np.minimum(np.maximum(para, F32(-7.)), F32(7.))) / scale).astype(F32)   # :250
+        para_curr = (np.exp(np.fmin(np.fmax(para, F32(-7.)), F32(7.))) / scale).astype(F32)   # :250 (R2: NaN -> -7)
         depth = parallax2depth(para_curr, rot, trans, camera)                  # :251
         self.prev_f_maps = curr_f                                              # :258-260
         self.depth_prev_t = depth
