@@ -640,6 +640,52 @@ int m4d_decode_rgb8_resize(const uint8_t* images, int n, int ih, int iw, int oh,
 int m4d_decode_depth_resize(const void* raw, int kind, int n, int ih, int iw, int oh, int ow,
                             const float* rgb_resized, const int crop[4], float* out, void* stream);
 
+/* ---- a user's own recording (dataloaders/recording.py): lens undistortion fused into the decode ----------------- */
+
+/* The undistortion table of one recording: for every pixel of the pinhole OUTPUT camera the index coordinates (u, v) of its
+ * source in the distorted frame.  model 0 pinhole (dist may be NULL), 1 radtan (dist = k1 k2 p1 p2 k3: OpenCV / Kalibr),
+ * 2 equidistant (dist = k1 k2 k3 k4: OpenCV fisheye / Kalibr).  dist, src_cam = {fx, fy, cx, cy} of the recording and
+ * out_cam = {fx', fy', cx', cy'} of the output are HOST arrays (they travel to the kernel by value); principal points in the
+ * half-pixel convention of get_coords_2d (pixel centres at integer + 0.5).  map [oh,ow,2] float32 in device memory.
+ * Per output pixel (row, col), float32, one IEEE rounding per operation, in this order:
+ *   x = (((float)col + 0.5f) - cx') / fx',  y = (((float)row + 0.5f) - cy') / fy'
+ *   pinhole     : xd = x, yd = y
+ *   radtan      : r2  = x*x + y*y
+ *                 rad = 1.0f + r2 * (k1 + r2 * (k2 + r2 * k3))
+ *                 xd  = x * rad + ((((2.0f * p1) * x) * y) + p2 * (r2 + (2.0f * x) * x))
+ *                 yd  = y * rad + (p1 * (r2 + (2.0f * y) * y) + (((2.0f * p2) * x) * y))
+ *   equidistant : r = sqrtf(x*x + y*y), th = atanf(r), th2 = th * th
+ *                 thd = th * (1.0f + th2 * (k1 + th2 * (k2 + th2 * (k3 + th2 * k4))))
+ *                 s = r > 1e-8f ? thd / r : 1.0f;  xd = x * s, yd = y * s
+ *   u = (xd * fx + cx) - 0.5f,  v = (yd * fy + cy) - 0.5f
+ * The entry is (u, v) when -0.5f <= u <= (float)iw - 0.5f and -0.5f <= v <= (float)ih - 0.5f (inside the source image's pixel
+ * area); otherwise, and for any non-finite value, it is (-1, -1): no source.  The pinhole and radtan tables are bit-exact
+ * (+ - * / only, -ffp-contract=off); the equidistant one is as exact as the device's atanf.
+ * Known limit: a radtan polynomial with strongly negative k1 folds over at large radius; output pixels beyond the fold (a
+ * field of view widened far past the lens's) map back INTO the image and are not detected.
+ * Returns 1 without a launch for: a model outside 0..2, a NULL src_cam, out_cam or map, a NULL dist for models 1 and 2, a
+ * size <= 0, map off 8 bytes.  One plain launch (capturable).  Additive entry point: ABI 6 unchanged. */
+int m4d_undistort_map(int model, const float* dist, const float src_cam[4], const float out_cam[4], int ih, int iw, int oh,
+                      int ow, float* map, void* stream);
+/* RGB frames as the decoder leaves them, [n,ih,iw,3] uint8, looked up through map [oh,ow,2] (one table for all n frames)
+ * -> [n,oh,ow,3] float32.  Per output pixel, with (u, v) its entry:
+ *   an entry with u < -0.5f or v < -0.5f (the table's (-1, -1)), a NaN or an infinity: 0, 0, 0
+ *   otherwise, per axis as m4d_decode_rgb8_resize does from its source coordinate on: lo = clamp((int)floorf(u), 0, iw-1),
+ *   hi = clamp((int)ceilf(u), 0, iw-1), lerp = u - floorf(u); every tap is (float)byte / 255.0f first;
+ *   top = tl + (tr - tl) * xlerp, bot = bl + (br - bl) * xlerp, value = top + (bot - top) * ylerp.
+ * With the table ((o + 0.5f) * scale - 0.5f) the result equals m4d_decode_rgb8_resize bit for bit.  Indices are clamped: no
+ * table content reads outside the images (a finite coordinate past the image samples its border).  Returns 1 without a launch for: a NULL pointer, a size <= 0, map off 8 bytes,
+ * out off 4.  One plain launch (capturable).  Additive entry point: ABI 6 unchanged. */
+int m4d_decode_rgb8_remap(const uint8_t* images, const float* map, int n, int ih, int iw, int oh, int ow, float* out,
+                          void* stream);
+/* 16-bit depth maps registered to the colour camera, [n,ih,iw] uint16, through the same table -> [n,oh,ow,1] float32, nearest:
+ *   column = clamp((int)floorf(u + 0.5f), 0, iw-1), row likewise;  out = (float)value * inv_scale
+ * A source value of 0 (no measurement) and a no-source entry (as above: below -0.5, NaN or infinite) give exactly 0.  Returns 1 without a launch for: a NULL
+ * pointer, a size <= 0, raw off 2 bytes, map off 8, out off 4.  One plain launch (capturable).  Additive entry point: ABI 6
+ * unchanged. */
+int m4d_decode_depth16_remap(const uint16_t* raw, const float* map, float inv_scale, int n, int ih, int iw, int oh, int ow,
+                             float* out, void* stream);
+
 /* ---- prediction export (main.py --mode=predict --save_dir): the mirror of the decoders above ------------------ */
 
 /* The depth estimate of a frame batch -> what goes to disk, in one launch.  est [b,h,w,1], gt [b,h,w,1] (may be NULL),

@@ -72,6 +72,10 @@ _SIGNATURES = {
     "m4d_decode_rgb8_resize": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
     "m4d_decode_depth_resize": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, ctypes.POINTER(_c_int),
                                 _c_fp, _c_fp],
+    "m4d_undistort_map": [_c_int, ctypes.POINTER(_c_f), ctypes.POINTER(_c_f), ctypes.POINTER(_c_f), _c_int, _c_int, _c_int, _c_int,
+                          _c_fp, _c_fp],
+    "m4d_decode_rgb8_remap": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
+    "m4d_decode_depth16_remap": [_c_fp, _c_fp, _c_f, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
     "m4d_depth_export": [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int, _c_int,
                          _c_int, _c_fp, _c_int, ctypes.POINTER(_c_int), _c_fp, _c_f, _c_f, _c_f, _c_fp, _c_fp],
     "m4d_pose_accumulate": [_c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_fp, _c_fp],

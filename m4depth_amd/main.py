@@ -19,6 +19,9 @@ camera.
 event file through ``m4depth_amd.summaries.TrainSummaryWriter``.
 ``--eval_streams B`` runs a dataset's streaming evaluation (no ``--db_seq_len``) with B whole trajectories side by side
 (m4depth_amd.stream_eval) and writes the same perfs file as the one-frame-at-a-time loop.
+``--dataset=recording --records_path REC --height H --width W`` runs eval / predict on a user's own recording (frames, a
+TUM-style trajectory, a calibration with lens distortion: m4depth_amd.dataloaders.recording); the frames are undistorted and
+resized on the GPU.
 """
 from __future__ import annotations
 
@@ -39,10 +42,20 @@ from .network import M4Depth, M4depthAblationParameters, GraphedSequence
 def build_parser():
     p = argparse.ArgumentParser(description="M4Depth (MI355X native) train / eval / predict driver")
     p.add_argument("--mode", default="eval", choices=["train", "finetune", "eval", "validation", "predict"])
-    p.add_argument("--dataset", default="synthetic", choices=["synthetic", "midair", "tartanair", "kitti-raw"],
-                   help="a dataset of the reference (m4depth_options.py:11-14) or the seeded synthetic one")
+    p.add_argument("--dataset", default="synthetic", choices=["synthetic", "midair", "tartanair", "kitti-raw", "recording"],
+                   help="a dataset of the reference (m4depth_options.py:11-14), the seeded synthetic one, or your own recording "
+                        "(--records_path = a recording directory or a directory of them, dataloaders/recording.py; needs "
+                        "--height and --width, no --db_path_config)")
     p.add_argument("--db_path_config", default=None, help="json file with the dataset roots (m4depth_options.py:27-29)")
     p.add_argument("--records_path", default=None, help="directory of trajectory csv files (m4depth_options.py:33-35)")
+    p.add_argument("--rec_stride", type=int, default=None, metavar="N",
+                   help="--dataset=recording: take every N-th frame of a trajectory (default 1)")
+    p.add_argument("--rec_min_baseline", type=float, default=None, metavar="METRES",
+                   help="--dataset=recording: of those, keep a frame when the camera centre has moved at least this far since "
+                        "the last kept frame (default 0)")
+    p.add_argument("--rec_max_gap", type=float, default=None, metavar="SECONDS",
+                   help="--dataset=recording: drop a frame whose bracketing poses are further apart than this; the next kept "
+                        "frame starts a new trajectory (default 0.5)")
     p.add_argument("--no_augmentation", action="store_true")
     p.add_argument("--epochs", type=int, default=1, help="train on a real dataset: passes over the records")
     p.add_argument("--arch_depth", type=int, default=6, help="number of pyramid levels (m4depth_options.py:64)")
@@ -160,10 +173,16 @@ def dataset_batches(args, usecase, rank, world, dev):
     (``shard=(rank, world)``): every rank gets the same number of batches and reads / decodes only its own
     sequences.  Streaming evaluation is inherently sequential and stays single-rank."""
     from . import dataloaders as dl
-    if args.db_path_config is None or args.records_path is None:
-        raise SystemExit("--dataset %s needs --db_path_config and --records_path" % args.dataset)
-    roots = dataset_roots(args.db_path_config)
-    loader = dl.get_loader(args.dataset)
+    if args.dataset == "recording":
+        if args.records_path is None:
+            raise SystemExit("--dataset recording needs --records_path")
+        roots = dataset_roots(args.db_path_config) if args.db_path_config else {}
+        loader = recording_loader(args)
+    else:
+        if args.db_path_config is None or args.records_path is None:
+            raise SystemExit("--dataset %s needs --db_path_config and --records_path" % args.dataset)
+        roots = dataset_roots(args.db_path_config)
+        loader = dl.get_loader(args.dataset)
     settings = dl.DataloaderParameters(roots, args.records_path, args.db_seq_len, args.seq_len, not args.no_augmentation)
     if usecase == "eval_streams":
         kw = {"out_size": [args.height, args.width]} if args.height and args.width else {}
@@ -177,6 +196,46 @@ def dataset_batches(args, usecase, rank, world, dev):
     ds = loader.get_dataset(usecase, settings, batch_size=per_rank, device=dev, seed=args.seed,
                             shard=(0, 1) if streaming else (rank, world), **kw)
     return ds, loader.depth_type
+
+
+def recording_loader(args):
+    """The loader of ``--dataset=recording`` with the ``--rec_*`` options (their defaults where not given)."""
+    from . import dataloaders as dl
+    loader = dl.get_loader("recording")
+    loader.stride = 1 if args.rec_stride is None else args.rec_stride
+    loader.min_baseline = 0.0 if args.rec_min_baseline is None else args.rec_min_baseline
+    loader.max_gap = 0.5 if args.rec_max_gap is None else args.rec_max_gap
+    panels = getattr(args, "save_panels", None) or ()
+    panels = panels.split(",") if isinstance(panels, str) else panels
+    loader.require_depth = any(p in ("gt", "err") for p in panels)      # those panels need ground truth for every frame
+    return loader
+
+
+def check_recording_args(parser, args):
+    """Refusals around ``--dataset=recording``: its ``--rec_*`` options belong to it alone, and a recording has no default
+    network size."""
+    given = [f for f in ("rec_stride", "rec_min_baseline", "rec_max_gap") if getattr(args, f) is not None]
+    if args.dataset != "recording":
+        if given:
+            parser.error("--%s is a --dataset=recording option" % given[0])
+        return
+    if args.height is None or args.width is None:
+        parser.error("--dataset=recording needs --height and --width (the size the frames are undistorted and resized to)")
+    if args.records_path is not None:
+        from .dataloaders.recording import find_recordings
+        try:
+            find_recordings(args.records_path)
+        except ValueError as e:
+            parser.error("--records_path %s" % e)
+    unit = 2 ** args.arch_depth
+    if args.height < unit or args.width < unit or args.height % unit or args.width % unit:
+        parser.error("--dataset=recording: --height and --width must be positive multiples of 2**arch_depth = %d" % unit)
+    if args.rec_stride is not None and args.rec_stride < 1:
+        parser.error("--rec_stride must be >= 1")
+    if args.rec_min_baseline is not None and not args.rec_min_baseline >= 0:
+        parser.error("--rec_min_baseline must be >= 0")
+    if args.rec_max_gap is not None and not args.rec_max_gap > 0:
+        parser.error("--rec_max_gap must be > 0")
 
 
 def _train_dir(args):
@@ -464,7 +523,7 @@ def _check_eval_streams(parser, args):
     if args.mode not in ("eval", "validation"):
         parser.error("--eval_streams is a --mode=eval / --mode=validation option")
     if args.dataset == "synthetic":
-        parser.error("--eval_streams runs the trajectories of a real dataset (--dataset midair | tartanair | kitti-raw)")
+        parser.error("--eval_streams runs the trajectories of a real dataset (--dataset midair | tartanair | kitti-raw | recording)")
     if args.db_seq_len is not None:
         parser.error("--eval_streams evaluates whole trajectories: it excludes --db_seq_len")
 
@@ -474,6 +533,8 @@ def records_have_depth(args):
     host before anything is loaded."""
     import glob
     from . import dataloaders as dl
+    if args.dataset == "recording":
+        return dl.get_loader("recording").has_depth(args.records_path)
     col = dl.get_loader(args.dataset)._depth_column()
     files = sorted(glob.glob(os.path.join(args.records_path, "**/*.csv"), recursive=True))
     if not files:
@@ -698,6 +759,7 @@ def main(argv=None):
         parser.error("--stream is a --mode=predict option")
     _check_eval_streams(parser, args)
     check_train_args(parser, args)
+    check_recording_args(parser, args)
     check_save_args(parser, args)
     rank, world, _, dev = D.init_from_env()
     if args.eval_streams and world > 1:
