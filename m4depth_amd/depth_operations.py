@@ -141,15 +141,22 @@ def tile_in_batch(map, nbre_copies):
 _CV_ACCUM = {"fp32_round": 0, "fp16_seq": 1}
 
 
-def _dscv_forward(c1, c2, disp_prev_t, disp, rot, trans, f, c, r, nbre_cuts, cv_accum, return_index):
+def _dscv_forward(c1, c2, disp_prev_t, disp, rot, trans, f, c, r, nbre_cuts, cv_accum, return_index, into=None):
+    """``into`` = (address of the cost volume's first channel, row stride in floats, address of the time-recurrence feature or
+    None, its row stride, its log scale) inside a caller's strided rows (``network_ops.RefinerInput.dscv_into``): the cost
+    volume is written there, ``log(scale * prev_disp[centre])`` beside it, and nothing is allocated or returned."""
     b, h, w, C = c1.shape
     ncp = 2 * r + 1
-    cv = torch.empty((b, h, w, nbre_cuts * ncp), dtype=torch.float32, device=c1.device)
-    prev_disp = torch.empty((b, h, w, ncp), dtype=torch.float32, device=c1.device)
+    cv = prev_disp = None
+    if into is None:
+        cv = torch.empty((b, h, w, nbre_cuts * ncp), dtype=torch.float32, device=c1.device)
+        prev_disp = torch.empty((b, h, w, ncp), dtype=torch.float32, device=c1.device)
+        into = (dptr(cv), nbre_cuts * ncp, None, 0, 1.0)
+    cv_ptr, stride, log_ptr, log_stride, log_scale = into
     idx = torch.empty((b, h, w, ncp, 2), dtype=torch.int32, device=c1.device) if return_index else None
     check(lib.m4d_dscv_fwd(dptr(c1, "c1"), dptr(c2, "c2"), dptr(disp_prev_t), dptr(disp), dptr(rot, "rot"),
                            rot.shape[1], dptr(trans), dptr(f), dptr(c), b, h, w, C, r, nbre_cuts,
-                           _CV_ACCUM[cv_accum], dptr(cv), nbre_cuts * ncp, dptr(prev_disp), None, 0, 1.0,
+                           _CV_ACCUM[cv_accum], cv_ptr, stride, dptr(prev_disp), log_ptr, log_stride, log_scale,
                            dptr(idx, "index", torch.int32), stream_ptr()), "m4d_dscv_fwd")
     return cv, prev_disp, idx
 
@@ -211,12 +218,17 @@ def get_parallax_sweeping_cv(c1, c2, disp_prev_t, disp, rot, trans, camera, sear
     return (cv, prev_disp, idx) if return_index else (cv, prev_disp)
 
 
-def _sncv_forward(c1, c2, search_range, dilation_rate, nbre_cuts):
+def _sncv_forward(c1, c2, search_range, dilation_rate, nbre_cuts, into=None):
+    """``into`` = (address, row stride in floats) inside a caller's strided rows (``network_ops.RefinerInput.sncv_into``): the
+    cost volume is written there and nothing is allocated or returned."""
     b, h, w, C = c1.shape
     mo = 2 * search_range + 1
-    out = torch.empty((b, h, w, mo * mo * nbre_cuts), dtype=torch.float32, device=c1.device)
+    out = None
+    if into is None:
+        out = torch.empty((b, h, w, mo * mo * nbre_cuts), dtype=torch.float32, device=c1.device)
+        into = (dptr(out), mo * mo * nbre_cuts)
     check(lib.m4d_sncv_fwd(dptr(c1, "c1"), dptr(c2, "c2"), b, h, w, C, search_range, dilation_rate,
-                           nbre_cuts, dptr(out), mo * mo * nbre_cuts, stream_ptr()), "m4d_sncv_fwd")
+                           nbre_cuts, into[0], into[1], stream_ptr()), "m4d_sncv_fwd")
     return out
 
 

@@ -11,14 +11,14 @@ is involved.  Activations are NHWC float32 (``[b,h,w,c]``), exactly the referenc
 """
 from __future__ import annotations
 
-import ctypes
 from collections import namedtuple
 
 import numpy as np
 import torch
 
+from . import depth_operations as dops
 from . import network_ops as nops
-from ._lib import lib, dptr, stream_ptr, check, as_f32
+from ._lib import as_f32, lib                # noqa: F401  (lib: unused here -- tests and tools reach the library as ``network.lib``)
 from .synthetic import ENCODER_CHANNELS, REFINER_CHANNELS, f_input_channels, nbre_cuts_for
 
 # m4depth_network.py:21-22
@@ -26,8 +26,6 @@ M4depthAblationParameters = namedtuple('M4depthAblationParameters',
                                        ('DINL', 'SNCV', 'time_recurr', 'normalize_features',
                                         'subdivide_features', 'level_memory'),
                                        defaults=(True, True, True, True, True, True))
-
-_CV_ACCUM = {"fp32_round": 0, "fp16_seq": 1}
 
 import contextlib as _contextlib
 import os as _os
@@ -158,6 +156,9 @@ fused_front_min_pixels = int(_os.environ.get("M4D_FUSED_FRONT_MIN_PX", "0"))
 # most this many pixels (batch included: levels 4-6 at batch 1-3) the one-launch small-map cost-volume kernel stays -- a
 # handful of 8x8 tiles cannot fill the chip -- above it (batch >= 4) the fused front writes whole refiner-input rows.
 fused_front_coarse_min_pixels = int(_os.environ.get("M4D_FUSED_FRONT_COARSE_MIN_PX", "6000"))
+# Largest map (pixels, batch included) whose two cost volumes share one launch (m4d_dscv_sncv_fwd, m4d_level_front_small: one
+# workgroup per 8x8 tile); larger maps without a fused front run the DSCV and the SNCV as a launch each.
+_SMALL_CV_MAX_PIXELS = 6000
 
 # The last two refiner convolutions (32->16, 16->5) and the level tail in ONE kernel (csrc/m4d_tail.hip).  0 = three launches.
 fused_refiner_tail = _os.environ.get("M4D_FUSED_TAIL", "1") == "1"
@@ -227,6 +228,16 @@ def _to_device_f32(x, device):
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=torch.float32)
     return torch.as_tensor(np.asarray(x), dtype=torch.float32, device=device)
+
+
+def _starts_trajectory(new_traj):
+    """Does this ``new_traj`` (tensor, array or bool) start a trajectory?  "Sequences are synchronized over the batch"
+    (m4depth_network.py:207): the first sample speaks for all.  A device tensor costs a host read."""
+    if isinstance(new_traj, bool):
+        return new_traj
+    if isinstance(new_traj, torch.Tensor):
+        return bool(new_traj.reshape(-1)[0].item())
+    return bool(np.asarray(new_traj).reshape(-1)[0])
 
 
 def _stamp(*params):
@@ -459,6 +470,7 @@ class _Conv3x3SameTF(torch.nn.Module):
 
 
 ConvPlan = namedtuple("ConvPlan", ("kernel", "layout", "lat_config", "wino6_kernel", "stagger_us"))
+LevelPlan = namedtuple("LevelPlan", ("route", "normalize", "f_stride", "tail"))       # ``DepthEstimatorLevel.plan``
 
 # Packed weight layouts: pack function over the host HWIO kernel, whether the device copy is viewed as int16 (bf16 / fp16 bit
 # patterns), whether the pack function returns (weights, CoutPad).  ``_Conv3x3SameTF.can_use`` has each layout's condition.
@@ -687,7 +699,7 @@ class DepthEstimatorLevel(torch.nn.Module):
         if not isinstance(curr_f_maps, torch.Tensor) or not curr_f_maps.is_cuda or curr_f_maps.dim() != 4:
             return None
         b, h, w, c = curr_f_maps.shape
-        if not lib.m4d_pyramid_reset_supported(c, self.nbre_cuts):
+        if not nops.pyramid_reset_supported(c, self.nbre_cuts):
             return None
         self._ensure_state((b, h, w, c), curr_f_maps.device)
         return {"features": curr_f_maps, "cuts": self.nbre_cuts, "state_features": self._spare_f, "depth_state": self.depth_prev_t}
@@ -716,24 +728,58 @@ class DepthEstimatorLevel(torch.nn.Module):
             return out
         return f_map
 
+    def plan(self, b, h, w, c, gpu=True, own_state=True, reset=False, prenormalized=False):
+        """What ``forward`` does with a [b,h,w,c] map.  Pure: launches nothing, touches no tensor.  ``gpu``: the call is on the
+        GPU; ``own_state``: no explicit ``prev_f_maps`` / ``prev_t_depth``; ``reset``: the host knows the frame starts a trajectory (a
+        masked call never does: it resets per sample in its close); ``prenormalized``: normalised features of this shape came along.
+        ``route``: "reset" (:208-214) | "front" (``m4d_level_front_r``) | "front_small" (``m4d_level_front_small``) | "dscv_sncv"
+        (``level_pre``, then both cost volumes in one launch) | "dscv+sncv" (``level_pre``, DSCV, then the SNCV unless ablated).
+        ``normalize``, where the current features are normalised per cut: "in_front" | "prenormalized" (ahead of the level) |
+        "with_pre" (in ``level_pre``'s launch) | "separate" (a launch of its own; a copy when the features stay raw).
+        ``f_stride``: the refiner input's row stride.  ``tail``: "tail6" | "tail" (the fused close, bf16-split or fp32-MFMA) | "post"
+        (the unfused refiner, then ``level_post``); None on the reset route."""
+        ab, k, px = self.ablation, self.nbre_cuts, b * h * w
+        infer = gpu and not self.is_training
+        f_stride = _padded_refiner_width(self.f_in) if infer else self.f_in
+        # the one-launch fronts write complete refiner-input rows from the level's own state: a full inference step with every feature
+        whole_rows = (infer and own_state and not reset
+                      and ab.SNCV and ab.time_recurr and ab.normalize_features and ab.level_memory)
+        front_min_px = fused_front_min_pixels if k <= 2 else max(fused_front_min_pixels, fused_front_coarse_min_pixels)
+        if reset:
+            route = "reset"
+        elif (whole_rows and fused_front and px > front_min_px
+                and nops.level_front_supported(c, k, self.dscv_range, self.sncv_range, f_stride)):
+            route = "front"
+        elif (whole_rows and prenormalized and px <= _SMALL_CV_MAX_PIXELS and nops.pyramid_reset_supported(c, k)
+                and nops.level_front_small_supported(c, k, self.dscv_range, self.sncv_range)):
+            route = "front_small"                      # (pyramid_reset_supported: the widths ``normalize_levels`` covers)
+        elif ab.SNCV and gpu and px <= _SMALL_CV_MAX_PIXELS:
+            route = "dscv_sncv"
+        else:
+            route = "dscv+sncv"
+        if route in ("front", "front_small"):
+            normalize = "in_front" if route == "front" else "prenormalized"
+        elif ab.normalize_features and infer and own_state and c % k == 0:
+            normalize = "with_pre"                     # both open the level, neither depends on the other
+        else:
+            normalize = "separate"
+        if reset:
+            tail = None
+        elif fused_refiner_tail and gpu:
+            tail = "tail6" if tail_split and conv_arith in _SPLIT_ARITHS else "tail"
+        else:
+            tail = "post"
+        return LevelPlan(route, normalize, f_stride, tail)
+
     def _front_by_size(self, b, h, w, c):
-        """Does a [b,h,w,c] map of this level take the big-tile fused front (``m4d_level_front_r``)?  (size and shape part of
-        ``forward``'s decision)"""
-        k = self.nbre_cuts
-        F_st = _padded_refiner_width(self.f_in)
-        return (fused_front and b * h * w > (fused_front_min_pixels if k <= 2 else max(fused_front_min_pixels, fused_front_coarse_min_pixels))
-                and bool(lib.m4d_level_front_supported(c, k, self.dscv_range, self.sncv_range, F_st)))
+        """Does a full inference step of this level on a [b,h,w,c] map take the big-tile fused front (``m4d_level_front_r``)?"""
+        return self.plan(b, h, w, c).route == "front"
 
     def wants_prenormalized(self, b, h, w, c):
         """Would a full (non-reset) inference step of this level on a [b,h,w,c] map open with ``m4d_level_front_small`` -- i.e.
         should the caller hand it per-cut normalised features (``forward(..., curr_f_normalized=...)``,
         ``network_ops.normalize_levels``)?"""
-        ab = self.ablation
-        return (not self.is_training
-                and ab.SNCV and ab.time_recurr and ab.normalize_features and ab.level_memory
-                and b * h * w <= 6000 and not self._front_by_size(b, h, w, c)
-                and bool(lib.m4d_pyramid_reset_supported(c, self.nbre_cuts))
-                and bool(lib.m4d_level_front_small_supported(c, self.nbre_cuts, self.dscv_range, self.sncv_range)))
+        return self.plan(b, h, w, c, prenormalized=True).route == "front_small"
 
     def forward(self, curr_f_maps, prev_l_est, rot, trans, camera, new_traj, prev_f_maps=None, prev_t_depth=None,
                 curr_f_normalized=None, reset_mask=None, reset_parallax=None):
@@ -747,52 +793,33 @@ class DepthEstimatorLevel(torch.nn.Module):
         curr_f_maps = as_f32(curr_f_maps, "curr_f_maps")
         b, h, w, c = curr_f_maps.shape
         dev = curr_f_maps.device
-        k = self.nbre_cuts
         if reset_mask is not None and (self.is_training or prev_f_maps is not None or prev_t_depth is not None):
             raise RuntimeError("DepthEstimatorLevel: a reset mask is for inference on the level's own state (not training mode)")
-        use_state = (not self.is_training) and prev_f_maps is None and prev_t_depth is None    # :192
+        own_state = (not self.is_training) and prev_f_maps is None and prev_t_depth is None    # :192
         if not self.is_training:
             self._ensure_state((b, h, w, c), dev)
-        nt = new_traj
-        if reset_mask is not None:
-            nt = False                                 # per-sample resets happen in the masked close: no host read
-        elif isinstance(nt, torch.Tensor):
-            nt = bool(nt.reshape(-1)[0].item())       # "sequences are synchronized over the batch" (:207)
-        elif not isinstance(nt, bool):
-            nt = bool(np.asarray(nt).reshape(-1)[0])
-        ab = self.ablation
-        F_in = self.f_in
-        F_st = _padded_refiner_width(F_in) if (dev.type == "cuda" and not self.is_training) else F_in
-        # the fused level front: normalisation, upsampling, both cost volumes and the log features in one launch
-        use_front = (use_state and not nt and dev.type == "cuda" and self._spare_f is not None
-                     and ab.SNCV and ab.time_recurr and ab.normalize_features and ab.level_memory
-                     and self._front_by_size(b, h, w, c))
-        # a coarse level whose features arrive normalised: level_pre + DSCV + SNCV in one launch (m4d_level_front_small)
-        use_small = (curr_f_normalized is not None and not use_front and use_state and not nt and dev.type == "cuda"
-                     and self.wants_prenormalized(b, h, w, c)
-                     and tuple(curr_f_normalized.shape) == (b, h, w, c))
+        # (per-sample resets happen in the masked close: no host read; without a previous depth there is nothing to step from)
+        reset = (reset_mask is None and _starts_trajectory(new_traj)) or (not own_state and prev_t_depth is None)
+        p = self.plan(b, h, w, c, gpu=dev.type == "cuda", own_state=own_state, reset=reset,
+                      prenormalized=curr_f_normalized is not None and tuple(curr_f_normalized.shape) == (b, h, w, c))
         # normalised current features land in the spare state buffer: after the level
         # ran they ARE the new prev_f_maps (:211, :259) -- a pointer swap, not a copy.
-        # (inference, state mode) the normalisation shares a launch with level_pre below: both open the level, neither
-        # depends on the other
         norm_job = None
-        if use_front:
-            curr_f = self._spare_f
-        elif use_small:
+        if p.normalize == "prenormalized":
             curr_f = as_f32(curr_f_normalized, "curr_f_normalized")
-        elif (self.ablation.normalize_features and dev.type == "cuda" and not self.is_training
-                and prev_f_maps is None and self._spare_f is not None and c % self.nbre_cuts == 0):
-            curr_f = self._spare_f
-            norm_job = (curr_f_maps, self.nbre_cuts, curr_f)
-        else:
+        elif p.normalize == "separate":
             curr_f = self._vector_processing(curr_f_maps, out=self._spare_f if not self.is_training else None)
+        else:
+            curr_f = self._spare_f
+            if p.normalize == "with_pre":
+                norm_job = (curr_f_maps, self.nbre_cuts, curr_f)
         if prev_f_maps is not None:
             prev_f_maps = self._vector_processing(as_f32(prev_f_maps, "prev_f_maps"))
-        if use_state:
+        if own_state:
             prev_t_depth = self.depth_prev_t
             prev_f_maps = self.prev_f_maps
 
-        if prev_t_depth is None or nt:                                                 # :208-214
+        if p.route == "reset":                                                         # :208-214
             para_prev_l, depth_prev_l, other_prev_l, _ = _timed("pre", "reset", lambda: nops.level_pre(
                 prev_l_est, None, None, None, b, h, w, dev, normalize=norm_job,
                 depth_state_reset=None if self.is_training else self.depth_prev_t))         # :209, in the same launch
@@ -800,97 +827,67 @@ class DepthEstimatorLevel(torch.nn.Module):
                 self.prev_f_maps = curr_f                      # (curr_f is the spare buffer: the other one becomes the spare)
             return {"depth": depth_prev_l, "parallax": para_prev_l, "other": other_prev_l}
 
-        r = self.dscv_range
-        ncp = 2 * r + 1
-        if F_st != F_in:                              # channel stride of the refiner input buffer > its width: zero padding
-            f_buf = nops.zeroed_workspace(("f_input", self.lvl_depth), (b, h, w, F_st), dev)
-        else:
-            f_buf = torch.empty((b, h, w, F_in), dtype=torch.float32, device=dev)
-        f_input = f_buf
-        log_off = ncp * k
-        other_off = log_off + 1 if self.ablation.level_memory else -1
-        sncv_off = log_off + 1 + (4 if self.ablation.level_memory else 0)
+        ab, k, lvl = self.ablation, self.nbre_cuts, self.lvl_depth
         scale = float(2.0 ** self.lvl_mul)
-        # "preprocessor" (:216-242): upsample coarser estimate, prev_d2para, log / memory features
-        if not use_front and not use_small:
-            para_prev_l, depth_prev_l, other_prev_l, para_prev_t = _timed("pre", self.lvl_depth, lambda: nops.level_pre(
-                prev_l_est, as_f32(prev_t_depth, "prev_t_depth"), trans, camera, b, h, w, dev,
-                f_input=f_input, log_off=log_off, other_off=other_off, log_scale=scale, normalize=norm_job))
+        f_input = nops.RefinerInput.for_level(lvl, b, h, w, self.f_in, p.f_stride, (2 * self.dscv_range + 1) * k,
+                                              ab.level_memory, ab.time_recurr, dev)
+        # "preprocessor" (:216-242): upsample coarser estimate, prev_d2para, log / memory features -- inside the front kernels,
+        # or ahead of the cost volumes
+        para_prev_l = para_prev_t = None
+        if p.route in ("dscv_sncv", "dscv+sncv"):
+            para_prev_l, _, _, para_prev_t = _timed("pre", lvl, lambda: nops.level_pre(
+                prev_l_est, as_f32(prev_t_depth, "prev_t_depth"), trans, camera, b, h, w, dev, f_input=f_input, log_scale=scale,
+                normalize=norm_job))
         rot_t = as_f32(rot, "rot")
         tr = as_f32(trans, "trans").reshape(b, 3)
         cf = as_f32(camera["f"], "camera['f']").reshape(b, 2)
         cc = as_f32(camera["c"], "camera['c']").reshape(b, 2)
         if rot_t.dim() != 2 or rot_t.shape[1] not in (3, 4):
             raise ValueError('Rotation must be expressed as a small angle (x,y,z) or a quaternion (w,x,y,z)')
-        fin_ptr = f_input.data_ptr()
-        time_recurr = self.ablation.time_recurr
-        log_ptr = ctypes.c_void_p(fin_ptr + 4 * (F_in - 1)) if time_recurr else None      # channel F_in - 1 of a stride-F_st row
-        # DSCV (:220-221) -> f_input[..., 0:9k]; time-recurrence feature (:238) -> f_input[..., -1]
+        motion = (rot_t, tr, cf, cc)
         prev_f = as_f32(prev_f_maps, "prev_f_maps")
-        if use_front or use_small:                    # the coarser level's estimate: upsampled inside the front kernels
-            pp = po = None
-            ph = pw = 0
-            if prev_l_est is not None:
-                pp = as_f32(prev_l_est["parallax"], "prev_l_est['parallax']")
-                po = as_f32(prev_l_est["other"], "prev_l_est['other']")
-                ph, pw = pp.shape[1:3]
-        if use_front:
-            check(_timed("front", self.lvl_depth, lambda: lib.m4d_level_front_r(
-                dptr(curr_f_maps, "curr_f_maps"), dptr(curr_f), dptr(prev_f), dptr(as_f32(prev_t_depth, "prev_t_depth")),
-                dptr(pp), dptr(po), ph, pw, dptr(rot_t), rot_t.shape[1], dptr(tr), dptr(cf), dptr(cc),
-                b, h, w, c, k, self.dscv_range, self.sncv_range, _CV_ACCUM[self.cv_accum], ctypes.c_void_p(fin_ptr), F_st, scale,
-                stream_ptr())), "m4d_level_front_r")
-            para_prev_t = para_prev_l = None
-        elif use_small:
-            # (timed as "dscv_sncv" by bench.py: the launch that opens the level in the graph)
-            check(_timed("dscv_sncv", self.lvl_depth, lambda: lib.m4d_level_front_small(
-                dptr(curr_f), dptr(prev_f), dptr(as_f32(prev_t_depth, "prev_t_depth")), dptr(pp), dptr(po), ph, pw,
-                dptr(rot_t), rot_t.shape[1], dptr(tr), dptr(cf), dptr(cc), b, h, w, c, k, self.dscv_range, self.sncv_range,
-                _CV_ACCUM[self.cv_accum], ctypes.c_void_p(fin_ptr), F_st, scale, stream_ptr())), "m4d_level_front_small")
-            para_prev_t = para_prev_l = None
-        elif self.ablation.SNCV and dev.type == "cuda" and b * h * w <= 6000:
-            # small maps: both (independent) cost volumes in one launch (timed as "dscv_sncv" by bench.py: the launch the graph replays)
-            check(_timed("dscv_sncv", self.lvl_depth, lambda: lib.m4d_dscv_sncv_fwd(
-                dptr(curr_f), dptr(prev_f), dptr(para_prev_t), dptr(para_prev_l), dptr(rot_t), rot_t.shape[1],
-                dptr(tr), dptr(cf), dptr(cc), b, h, w, c, r, k, _CV_ACCUM[self.cv_accum], ctypes.c_void_p(fin_ptr),
-                F_st, None, log_ptr, F_st, scale, self.sncv_range, ctypes.c_void_p(fin_ptr + 4 * sncv_off), F_st,
-                stream_ptr())), "m4d_dscv_sncv_fwd")
-        else:
-            check(_timed("dscv", self.lvl_depth, lambda: lib.m4d_dscv_fwd(
-                dptr(curr_f), dptr(prev_f), dptr(para_prev_t), dptr(para_prev_l), dptr(rot_t), rot_t.shape[1],
-                dptr(tr), dptr(cf), dptr(cc), b, h, w, c, r, k, _CV_ACCUM[self.cv_accum], ctypes.c_void_p(fin_ptr),
-                F_st, None, log_ptr, F_st, scale, None, stream_ptr())), "m4d_dscv_fwd")
-            if self.ablation.SNCV:                                                     # :231-233
-                check(_timed("sncv", self.lvl_depth, lambda: lib.m4d_sncv_fwd(
-                    dptr(curr_f), dptr(curr_f), b, h, w, c, self.sncv_range, 1, k,
-                    ctypes.c_void_p(fin_ptr + 4 * sncv_off), F_st, stream_ptr())), "m4d_sncv_fwd")
-        self.last_f_input = f_input if F_st == F_in else f_input[..., :F_in]      # the reference-width view (inspection / tests)
+        # DSCV (:220-221) -> f_input[..., 0:9k]; time-recurrence feature (:238) -> f_input[..., -1]; SNCV (:231-233)
+        cv = (k, self.dscv_range, self.sncv_range, self.cv_accum, f_input, scale)
+        # route -> (the name bench.py times the launch under: "dscv_sncv" = the launch that opens a coarse level in the graph, launch)
+        timed_as, opening = {
+            "front": ("front", lambda: nops.level_front(
+                curr_f_maps, curr_f, prev_f, as_f32(prev_t_depth, "prev_t_depth"), prev_l_est, motion, *cv)),
+            "front_small": ("dscv_sncv", lambda: nops.level_front(
+                None, curr_f, prev_f, as_f32(prev_t_depth, "prev_t_depth"), prev_l_est, motion, *cv)),
+            "dscv_sncv": ("dscv_sncv", lambda: nops.dscv_sncv(curr_f, prev_f, para_prev_t, para_prev_l, motion, *cv)),
+            "dscv+sncv": ("dscv", lambda: dops._dscv_forward(
+                curr_f, prev_f, para_prev_t, para_prev_l, *motion, self.dscv_range, k, self.cv_accum, False,
+                into=f_input.dscv_into(scale))),
+        }[p.route]
+        _timed(timed_as, lvl, opening)
+        if p.route == "dscv+sncv" and ab.SNCV:
+            _timed("sncv", lvl, lambda: dops._sncv_forward(curr_f, curr_f, self.sncv_range, 1, k, into=f_input.sncv_into()))
+        self.last_f_input = f_input.rows()
         self.last_cv_inputs = (curr_f, prev_f, para_prev_t, para_prev_l, rot_t, tr, cf, cc)   # for tools/bench_kernels.py
         self.last_front_inputs = (curr_f_maps, prev_l_est, prev_t_depth)
         if debug_tap is not None:
-            debug_tap("encoder_map", self.lvl_depth, curr_f_maps)
-            debug_tap("f_input", self.lvl_depth, self.last_f_input)
+            debug_tap("encoder_map", lvl, curr_f_maps)
+            debug_tap("f_input", lvl, self.last_f_input)
         # "depth_estimator" (:244-260)
-        mask_kw = {} if reset_mask is None else {"reset": reset_mask, "reset_parallax": float(reset_parallax)}
-        convs = list(self.disp_refiner.prep_conv_layers) + list(self.disp_refiner.est_d_conv_layers)
-        if (fused_refiner_tail and dev.type == "cuda" and len(convs) == 7 and convs[5].weight is not None
-                and tuple(convs[5].weight.shape[:2]) == (16, 32) and tuple(convs[6].weight.shape[:2]) == (5, 16)):
-            x = f_input
+        close_kw = {"depth_state": None if self.is_training else self.depth_prev_t}
+        if reset_mask is not None:
+            close_kw.update(reset=reset_mask, reset_parallax=float(reset_parallax))
+        camera_t = {"f": cf, "c": cc}
+        if p.tail == "post":
+            prev_out = self.disp_refiner(f_input.buf)
+            para_curr_l, depth, other = _timed("post", lvl, lambda: nops.level_post(
+                prev_out[0], rot_t, tr, camera_t, scale, **close_kw))
+        else:
+            convs = list(self.disp_refiner.prep_conv_layers) + list(self.disp_refiner.est_d_conv_layers)
+            x = f_input.buf
             for ci, conv in enumerate(convs[:5]):
                 x = conv(x, slope=0.1, final=(ci == 4))                   # the fused tail reads a finished tensor
                 if debug_tap is not None:
-                    debug_tap(f"refiner_conv{ci + 1}", self.lvl_depth, x.dense() if isinstance(x, nops.PartialAct) else x)
-            split = tail_split and conv_arith in _SPLIT_ARITHS
-            w6p, w7p = self._tail_weights(convs, split)
-            tail_fn = nops.refiner_tail6 if split else nops.refiner_tail
-            para_curr_l, depth, other = _timed("tail", self.lvl_depth, lambda: tail_fn(
-                x, w6p, convs[5].bias, w7p, convs[6].bias, rot_t, tr, {"f": cf, "c": cc}, scale,
-                depth_state=self.depth_prev_t if not self.is_training else None, **mask_kw))
-        else:
-            prev_out = self.disp_refiner(f_input)
-            para_curr_l, depth, other = _timed("post", self.lvl_depth, lambda: nops.level_post(
-                prev_out[0], rot_t, tr, {"f": cf, "c": cc}, scale, depth_state=self.depth_prev_t if not self.is_training else None,
-                **mask_kw))
+                    debug_tap(f"refiner_conv{ci + 1}", lvl, x.dense() if isinstance(x, nops.PartialAct) else x)
+            w6p, w7p = self._tail_weights(convs, p.tail == "tail6")
+            tail_fn = {"tail6": nops.refiner_tail6, "tail": nops.refiner_tail}[p.tail]
+            para_curr_l, depth, other = _timed("tail", lvl, lambda: tail_fn(
+                x, w6p, convs[5].bias, w7p, convs[6].bias, rot_t, tr, camera_t, scale, **close_kw))
         if not self.is_training:
             # the normalised features ARE the new prev_f_maps (:211, :259): the level's spare buffer, or -- the one-launch opening of
             # a coarse level -- the caller's tensor, borrowed and only read (the level's own two buffers stay its own: _spare_f)
@@ -925,15 +922,20 @@ class DepthEstimatorPyramid(torch.nn.Module):
         behind the encoder: the normalisation does not depend on the decoder's state, so it leaves the levels' latency chains."""
         if self.is_training or pyr is None or not isinstance(pyr[0], torch.Tensor) or not pyr[0].is_cuda:
             return None
-        jobs = [(lvl, t) for lvl, t in enumerate(pyr[:len(self.levels)])
-                if t.dim() == 4 and self.levels[lvl].wants_prenormalized(bsz, t.shape[1], t.shape[2], t.shape[3])]
+        jobs = self._prenormalized_levels(pyr, bsz)
         if not jobs:
             return None
-        outs = _timed("norm", "levels", lambda: nops.normalize_levels([(t, self.levels[lvl].nbre_cuts) for lvl, t in jobs]))
+        outs = _timed("norm", "levels", lambda: nops.normalize_levels([(pyr[lvl], self.levels[lvl].nbre_cuts) for lvl in jobs]))
         res = [None] * len(pyr)
-        for (lvl, _), o in zip(jobs, outs):
+        for lvl, o in zip(jobs, outs):
             res[lvl] = o
         return res
+
+    def _prenormalized_levels(self, pyr, bsz):
+        """The levels (indices) that want per-cut normalised maps ahead of a full step (``wants_prenormalized``) on the feature
+        pyramid ``pyr`` of a batch-``bsz`` sequence."""
+        return [lvl for lvl, t in enumerate(pyr[:len(self.levels)])
+                if t.dim() == 4 and self.levels[lvl].wants_prenormalized(bsz, t.shape[1], t.shape[2], t.shape[3])]
 
     @staticmethod
     def _frame_slice(npyr, j, bsz):
@@ -972,7 +974,6 @@ class DepthEstimatorPyramid(torch.nn.Module):
         for seq_i, (f_pyr_curr, sample) in enumerate(zip(f_maps_pyrs, traj_samples)):
             rot = sample['rot']
             trans = sample['trans']
-            cnter = float(n_lvls)
             d_est_curr = None
             fused = self._reset_all_levels(f_pyr_curr, sample["new_traj"])
             if fused is not None:
@@ -994,7 +995,6 @@ class DepthEstimatorPyramid(torch.nn.Module):
                 est = level(f_maps_curr, d_est, rot, trans, local_camera, sample["new_traj"],
                             prev_f_maps=f_maps_prev, prev_t_depth=d_est_prev, curr_f_normalized=n_curr)
                 d_est_curr = [est] if d_est_curr is None else d_est_curr + [est]
-                cnter -= 1.
             d_est_seq.append(d_est_curr[::-1])
         return d_est_seq
 
@@ -1003,12 +1003,7 @@ class DepthEstimatorPyramid(torch.nn.Module):
         frame is not a reset frame or a level cannot take part (then the per-level loop runs)."""
         if not fused_pyramid_reset or self.is_training:
             return None
-        nt = new_traj
-        if isinstance(nt, torch.Tensor):
-            nt = bool(nt.reshape(-1)[0].item())
-        elif not isinstance(nt, bool):
-            nt = bool(np.asarray(nt).reshape(-1)[0])
-        if not nt or not isinstance(f_pyr[0], torch.Tensor) or not f_pyr[0].is_cuda:
+        if not _starts_trajectory(new_traj) or not isinstance(f_pyr[0], torch.Tensor) or not f_pyr[0].is_cuda:
             return None
         order = list(range(len(self.levels) - 1, -1, -1))                             # coarse -> fine
         jobs = [self.levels[lvl].reset_job(as_f32(f_pyr[lvl], "curr_f_maps")) for lvl in order]
@@ -1041,8 +1036,7 @@ class DepthEstimatorPyramid(torch.nn.Module):
         n_lvls = len(self.levels)
         self.ensure_stream_state(f_pyr)
         bsz = f_pyr[0].shape[0]
-        jobs = [lvl for lvl in range(n_lvls)
-                if self.levels[lvl].wants_prenormalized(bsz, f_pyr[lvl].shape[1], f_pyr[lvl].shape[2], f_pyr[lvl].shape[3])]
+        jobs = self._prenormalized_levels(f_pyr, bsz)
         n_curr = [None] * n_lvls
         if jobs:
             outs = _timed("norm", "levels", lambda: nops.normalize_levels(
@@ -1077,8 +1071,7 @@ class DepthEstimatorPyramid(torch.nn.Module):
         n_fr = len(traj_samples)
 
         def is_reset(f):
-            nt = traj_samples[f]["new_traj"]
-            return bool(nt.reshape(-1)[0].item()) if isinstance(nt, torch.Tensor) else bool(np.asarray(nt).reshape(-1)[0])
+            return _starts_trajectory(traj_samples[f]["new_traj"])
         # frame -> stream: one per frame, but a reset frame (new_traj: six state-seeding launches of a few microseconds) rides on
         # the stream of the frame that follows it: the first full frame's coarse-to-fine chain then has no cross-stream wait in
         # front of every level (each such wait is a ~4.7 us gap in the executor's queue, profiles/r05_queue_trace_b1_graph.txt, on
@@ -1470,8 +1463,7 @@ class M4Depth(torch.nn.Module):
             preds = self([[data], data["camera"]], training=False)
             gt = data["depth"]
             est = preds["depth"]
-            nt = data["new_traj"]
-            new_traj = bool(nt.reshape(-1)[0].item()) if isinstance(nt, torch.Tensor) else bool(np.asarray(nt).reshape(-1)[0])
+            new_traj = _starts_trajectory(data["new_traj"])
         if not new_traj:                                                               # :465-470
             self._update_metrics(gt, est, 80.)
         return self._metric_results()

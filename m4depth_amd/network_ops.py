@@ -8,6 +8,7 @@ import ctypes
 import torch
 
 from ._lib import lib, dptr, stream_ptr, check, as_f32
+from .depth_operations import _CV_ACCUM
 
 
 def normalize_cuts(x, nbre_cuts, out=None):
@@ -47,11 +48,11 @@ def resize_nearest(x, out_h, out_w, out=None):
     return out
 
 
-def level_pre(prev_l_est, depth_prev_t, trans, camera, b, h, w, device, f_input=None, log_off=0,
-              other_off=-1, log_scale=1.0, normalize=None, depth_state_reset=None):
+def level_pre(prev_l_est, depth_prev_t, trans, camera, b, h, w, device, f_input=None, log_scale=1.0, normalize=None,
+              depth_state_reset=None):
     """Fused upsample of the coarser level's estimate (+ prev_d2para of the
     temporal depth state, + the log-parallax / level-memory features written
-    straight into ``f_input``).  Returns (para_prev_l, depth_prev_l,
+    straight into ``f_input``, a ``RefinerInput``, at its ``log_off`` / ``other_off``).  Returns (para_prev_l, depth_prev_l,
     other_prev_l, para_prev_t or None).  ``normalize`` = (raw features [b,h,w,C], cuts, out): the per-cut
     normalisation of the level's current features rides in the same launch (m4d_level_pre_normalize).
     ``depth_state_reset`` [b,h,w,1] (reset branch, m4depth_network.py:209) is set to 1000 in the same pass."""
@@ -72,21 +73,103 @@ def level_pre(prev_l_est, depth_prev_t, trans, camera, b, h, w, device, f_input=
         tr = as_f32(trans, "trans").reshape(b, 3)
         f = as_f32(camera["f"], "camera['f']").reshape(b, 2)
         c = as_f32(camera["c"], "camera['c']").reshape(b, 2)
-    f_stride = f_input.shape[-1] if f_input is not None else 0
+    fin_buf, f_stride, log_off, other_off = (None, 0, 0, -1) if f_input is None else (
+        f_input.buf, f_input.f_stride, f_input.log_off, f_input.other_off)
     if normalize is not None:
         raw, cuts, nout = normalize
         raw = as_f32(raw, "curr_f_maps")
         check(lib.m4d_level_pre_normalize(dptr(pd), dptr(pp), dptr(po), ph, pw, dptr(depth_prev_t, "depth_prev_t"), dptr(tr),
                                           dptr(f), dptr(c), b, h, w, dptr(para), dptr(depth), dptr(other), dptr(para_t),
-                                          dptr(f_input, "f_input"), f_stride, int(log_off), int(other_off), float(log_scale),
+                                          dptr(fin_buf, "f_input"), f_stride, int(log_off), int(other_off), float(log_scale),
                                           dptr(depth_state_reset, "depth_state_reset"), dptr(raw, "curr_f_maps"), int(raw.shape[-1]), int(cuts), dptr(nout, "normalised features"),
                                           stream_ptr()), "m4d_level_pre_normalize")
         return para, depth, other, para_t
     check(lib.m4d_level_pre(dptr(pd), dptr(pp), dptr(po), ph, pw, dptr(depth_prev_t, "depth_prev_t"), dptr(tr),
                             dptr(f), dptr(c), b, h, w, dptr(para), dptr(depth), dptr(other), dptr(para_t),
-                            dptr(f_input, "f_input"), f_stride, int(log_off), int(other_off), float(log_scale),
+                            dptr(fin_buf, "f_input"), f_stride, int(log_off), int(other_off), float(log_scale),
                             dptr(depth_state_reset, "depth_state_reset"), stream_ptr()), "m4d_level_pre")
     return para, depth, other, para_t
+
+
+class RefinerInput:
+    """The refiner-input rows of one level call and the only place that does address arithmetic on them: ``buf``
+    [b,h,w,f_stride] (``f_stride`` >= ``f_in``, the width the refiner was built for) and the channel offsets of the log-parallax
+    feature, the level-memory features, the SNCV and the time-recurrence feature (-1 = the level has none)."""
+
+    def __init__(self, buf, f_in, log_off=0, other_off=-1, sncv_off=-1, recurr_off=-1):
+        self.buf, self.f_in, self.f_stride = buf, f_in, buf.shape[-1]
+        self.log_off, self.other_off, self.sncv_off, self.recurr_off = log_off, other_off, sncv_off, recurr_off
+
+    @classmethod
+    def for_level(cls, key, b, h, w, f_in, f_stride, dscv_channels, level_memory, time_recurr, device):
+        """The rows of m4depth_network.py:224-242 (DSCV | log parallax | memory | SNCV | time recurrence).  ``f_stride`` > ``f_in``:
+        the persistent zeroed workspace of ``key``, whose padding channels nothing ever writes."""
+        if f_stride > f_in:
+            buf = zeroed_workspace(("f_input", key), (b, h, w, f_stride), device)
+        else:
+            buf = torch.empty((b, h, w, f_in), dtype=torch.float32, device=device)
+        mem = 4 if level_memory else 0
+        return cls(buf, f_in, dscv_channels, dscv_channels + 1 if level_memory else -1, dscv_channels + 1 + mem,
+                   f_in - 1 if time_recurr else -1)
+
+    def at(self, channel):
+        """Address of ``channel`` of the first row; None (NULL) for a channel the level does not have."""
+        return None if channel < 0 else ctypes.c_void_p(self.buf.data_ptr() + 4 * channel)
+
+    def dscv_into(self, log_scale):
+        return self.at(0), self.f_stride, self.at(self.recurr_off), self.f_stride, log_scale
+
+    def sncv_into(self):
+        return self.at(self.sncv_off), self.f_stride
+
+    def rows(self):
+        """The reference-width view (inspection / tests)."""
+        return self.buf if self.f_stride == self.f_in else self.buf[..., :self.f_in]
+
+
+def level_front_supported(c, cuts, dscv_range, sncv_range, f_stride):
+    return bool(lib.m4d_level_front_supported(c, cuts, dscv_range, sncv_range, f_stride))
+
+
+def level_front_small_supported(c, cuts, dscv_range, sncv_range):
+    return bool(lib.m4d_level_front_small_supported(c, cuts, dscv_range, sncv_range))
+
+
+def pyramid_reset_supported(c, cuts):
+    return bool(lib.m4d_pyramid_reset_supported(c, cuts))
+
+
+def _coarser_estimate(prev_l_est):
+    """(parallax, other, their height, width) of the coarser level's estimate, which the front kernels upsample themselves; NULL
+    at the coarsest level."""
+    if prev_l_est is None:
+        return None, None, 0, 0
+    pp = as_f32(prev_l_est["parallax"], "prev_l_est['parallax']")
+    return pp, as_f32(prev_l_est["other"], "prev_l_est['other']"), pp.shape[1], pp.shape[2]
+
+
+def level_front(raw, curr_f, prev_f, depth_prev_t, prev_l_est, motion, cuts, dscv_range, sncv_range, cv_accum, f_input, scale):
+    """The whole level front in one launch: ``level_pre``, DSCV and SNCV -> complete rows of ``f_input`` (a ``RefinerInput``), with
+    the per-cut normalisation of ``raw`` into ``curr_f`` (m4d_level_front_r) or, ``raw`` None, on a ``curr_f`` normalised ahead of
+    the level (m4d_level_front_small).  ``motion`` = (rot, trans [b,3], f [b,2], c [b,2])."""
+    rot, tr, cf, cc = motion
+    pp, po, ph, pw = _coarser_estimate(prev_l_est)
+    b, h, w, c = curr_f.shape
+    name, head = ("m4d_level_front_small", ()) if raw is None else ("m4d_level_front_r", (dptr(raw, "curr_f_maps"),))
+    check(getattr(lib, name)(*head, dptr(curr_f), dptr(prev_f), dptr(depth_prev_t, "prev_t_depth"), dptr(pp), dptr(po), ph, pw,
+                             dptr(rot), rot.shape[1], dptr(tr), dptr(cf), dptr(cc), b, h, w, c, cuts, dscv_range, sncv_range,
+                             _CV_ACCUM[cv_accum], f_input.at(0), f_input.f_stride, scale, stream_ptr()), name)
+
+
+def dscv_sncv(curr_f, prev_f, para_prev_t, para_prev_l, motion, cuts, dscv_range, sncv_range, cv_accum, f_input, scale):
+    """Both cost volumes of a small map in one launch (m4d_dscv_sncv_fwd), into the rows of ``f_input``."""
+    rot, tr, cf, cc = motion
+    b, h, w, c = curr_f.shape
+    cv, stride, log, log_stride, log_scale = f_input.dscv_into(scale)
+    sncv, sncv_stride = f_input.sncv_into()
+    check(lib.m4d_dscv_sncv_fwd(dptr(curr_f), dptr(prev_f), dptr(para_prev_t), dptr(para_prev_l), dptr(rot), rot.shape[1],
+                                dptr(tr), dptr(cf), dptr(cc), b, h, w, c, dscv_range, cuts, _CV_ACCUM[cv_accum], cv, stride, None,
+                                log, log_stride, log_scale, sncv_range, sncv, sncv_stride, stream_ptr()), "m4d_dscv_sncv_fwd")
 
 
 def pyramid_reset(levels, b):

@@ -189,8 +189,8 @@ def test_level_pre_post_kernels(M, dev):
     dprev = (1 + 50 * rng.random([b, h, w, 1])).astype(F)
     f_in = torch.full((b, h, w, 12), -7.0, device=dev)
     para, depth, other, para_t = nops.level_pre(to_dev(prev, dev), to_dev(dprev, dev), to_dev(trans, dev),
-                                                to_dev(cam, dev), b, h, w, dev, f_input=f_in, log_off=3,
-                                                other_off=4, log_scale=0.25)
+                                                to_dev(cam, dev), b, h, w, dev,
+                                                f_input=nops.RefinerInput(f_in, 12, log_off=3, other_off=4), log_scale=0.25)
     op = O.resize_bilinear_v1(prev["parallax"], h, w) * F(2.)
     assert_bits_equal(npy(para), op, "para_prev_l")
     assert_bits_equal(npy(depth), O.resize_bilinear_v1(prev["depth"], h, w), "depth_prev_l")
