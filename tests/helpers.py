@@ -9,6 +9,49 @@ def camera_np(b, h, w):
             "c": np.tile(np.array([[0.5 * w, 0.5 * h]], F), [b, 1])}
 
 
+# (fx/w, fy/h, cx/w, cy/h): KITTI-like (the ratios make_fake_dataset writes for kitti-raw); the Mid-Air focal rule with a shifted
+# principal point; a recording whose undistortion left the principal point far off centre.  Within a row all four numbers
+# differ and no two rows share a number.
+CAMERA_RATIOS = ((0.58, 1.92, 0.49, 0.51),
+                 (0.50, 0.50, 0.53, 0.46),
+                 (0.83, 1.11, 0.31, 0.66))
+
+
+def cameras_np(b, h, w):
+    """Per-sample, off-centre intrinsics: sample s takes row s % 3 of CAMERA_RATIOS, f times 1.0137 and c times 0.9971 (so
+    that no value is dyadic), rounded to float32.  Unlike ``camera_np``: f != c, every sample has its own camera, and the
+    default-looking camera is not sample 0."""
+    r = np.array([CAMERA_RATIOS[s % 3] for s in range(b)], np.float64)
+    return {"f": (r[:, 0:2] * np.array([w, h]) * 1.0137).astype(F),
+            "c": (r[:, 2:4] * np.array([w, h]) * 0.9971).astype(F)}
+
+
+def stream_camera_np(t, b, h, w):
+    """The camera of frame t of a stream whose intrinsics change every frame: cameras_np rows shifted by t, times 1 + 0.01 t."""
+    cam = cameras_np(b + t, h, w)
+    return {k: (v[t:t + b] * F(1.0 + 0.01 * t)).astype(F) for k, v in cam.items()}
+
+
+CAMERA_MODEL_CASE = (3, 3, 3, 64, 96, 4321)      # levels, batch, frames, height, width, seed
+
+
+def camera_model_case():
+    """(weights, samples, camera): synthetic.well_conditioned_case(3, 3, 3, 64, 96, 4321) with cameras_np(3, 64, 96)."""
+    from m4depth_amd import synthetic
+    W, samples, _ = synthetic.well_conditioned_case(*CAMERA_MODEL_CASE)
+    return W, samples, cameras_np(CAMERA_MODEL_CASE[1], CAMERA_MODEL_CASE[3], CAMERA_MODEL_CASE[4])
+
+
+def take(x, rows):
+    """The batch rows ``rows`` (an index, a slice or a list of indices) of arrays, dicts of arrays and lists of sample dicts;
+    an index gives a batch of one."""
+    if isinstance(x, dict):
+        return {k: take(v, rows) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [take(v, rows) for v in x]
+    return x[rows:rows + 1] if isinstance(rows, (int, np.integer)) else x[rows]
+
+
 def motion_np(rng, b, quat=True, t_scale=(1.0, 1.0, 1.0)):
     aa = rng.normal(0.0, 0.02, [b, 3])
     if quat:

@@ -16,7 +16,7 @@ import torch
 
 from oracle import m4depth_oracle as O
 from oracle import m4depth_oracle_train as OT
-from helpers import F, camera_np, motion_np, to_dev, npy, hbm_pressure
+from helpers import F, camera_np, cameras_np, motion_np, to_dev, npy, hbm_pressure
 from grad_cases import CONV_BACKWARD_RECIPE_CASES, CV_RECIPE_LEVELS, conv_case_id
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +40,14 @@ def test_dscv_backward(M, dev, C, k, r, h, w):
     _dscv_backward_case(M, dev, 2, C, k, r, h, w, seed=C + k)
 
 
-def _dscv_backward_case(M, dev, b, C, k, r, h, w, seed, t_scale=(1.0, 1.0, 1.0), disp_hi=6.0):
+@pytest.mark.parametrize("C,k,r,h,w", [(32, 2, 4, 12, 20), (192, 8, 4, 6, 10)])
+def test_dscv_backward_per_sample_cameras(M, dev, C, k, r, h, w):
+    """m4d_dscv_bwd at batch 3 with another, off-centre camera per sample (helpers.cameras_np; test_camera_cases.py checks that
+    the restatement reads the camera per sample); the 4e-3 bar of the other cases."""
+    _dscv_backward_case(M, dev, 3, C, k, r, h, w, seed=300 + C + k, cam_fn=cameras_np)
+
+
+def _dscv_backward_case(M, dev, b, C, k, r, h, w, seed, t_scale=(1.0, 1.0, 1.0), disp_hi=6.0, cam_fn=camera_np):
     """Gradients of the DSCV on the device vs autodiff of the restatement; returns the forward's (y0, x0) grid."""
     rng = np.random.default_rng(seed)
     c1 = O.normalize_cuts(rng.normal(size=[b, h, w, C]).astype(F), k)
@@ -48,7 +55,7 @@ def _dscv_backward_case(M, dev, b, C, k, r, h, w, seed, t_scale=(1.0, 1.0, 1.0),
     disp = rng.uniform(0.5, disp_hi, [b, h, w, 1]).astype(F)
     dpt = rng.uniform(0.5, 6.0, [b, h, w, 1]).astype(F)
     rot, trans = motion_np(rng, b, t_scale=t_scale)
-    cam = camera_np(b, h, w)
+    cam = cam_fn(b, h, w)
     ncp = 2 * r + 1
     g_cv = rng.normal(size=[b, h, w, k * ncp]).astype(F)
     g_pd = rng.normal(size=[b, h, w, ncp]).astype(F)
@@ -231,12 +238,12 @@ def _normalize_cuts_case(dev, rng, b, h, w, C, k):
     _close(npy(dx.grad), tx.grad.numpy(), 1e-5, f"normalize_cuts backward {b}x{h}x{w}x{C} k={k}")
 
 
-def _level_post_case(dev, rng, b, h, w):
+def _level_post_case(dev, rng, b, h, w, cam_fn=camera_np):
     from m4depth_amd import training as TR
     ro = rng.normal(0, 3.0, size=[b, h, w, 5]).astype(F)
     ro[0, 0, 0, 0] = 9.0                                   # outside the clip: no gradient
     rot, trans = motion_np(rng, b)
-    cam = camera_np(b, h, w)
+    cam = cam_fn(b, h, w)
     gs = [rng.normal(size=[b, h, w, n]).astype(F) for n in (1, 1, 4)]
     tro = torch.from_numpy(ro).requires_grad_(True)
     para = torch.exp(torch.clamp(tro[..., :1], -7., 7.)) / 0.5
@@ -281,6 +288,11 @@ def test_glue_backward_kernels_match_autodiff_of_the_restatement(M, dev):
     _normalize_cuts_case(dev, rng, b, h, w, 32, 2)         # per-cut normalisation
     _level_post_case(dev, rng, b, h, w)                    # level tail
     _loss_level_case(dev, rng, b, h, w, 4)                 # loss term of one level, both ground-truth kinds
+
+
+def test_level_post_backward_per_sample_cameras(M, dev):
+    """m4d_level_post_bwd at 3 x 6 x 9 with another, off-centre camera per sample (helpers.cameras_np); the 1e-5 bar."""
+    _level_post_case(dev, np.random.default_rng(41), 3, 6, 9, cam_fn=cameras_np)
 
 
 def test_glue_backward_kernels_at_recipe_geometries(M, dev):

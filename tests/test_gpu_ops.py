@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from oracle import m4depth_oracle as O
-from helpers import F, camera_np, motion_np, to_dev, npy, assert_bits_equal, rel_err
+from helpers import F, camera_np, cameras_np, motion_np, to_dev, npy, assert_bits_equal, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -1093,6 +1093,17 @@ def test_fused_level_front_is_bitwise_the_separate_kernels(M, dev, depth, b, h, 
 
 
 @pytest.mark.parametrize("depth,b,h,w,quat,cv_accum", [
+    (1, 3, 37, 45, True, "fp32_round"),
+    (3, 3, 19, 33, True, "fp32_round"),
+    (6, 3, 13, 11, False, "fp32_round"),
+])
+def test_fused_level_front_per_sample_cameras(M, dev, depth, b, h, w, quat, cv_accum):
+    """The same comparison at batch 3 with another, off-centre camera per sample (helpers.cameras_np); test_gpu_camera.py holds
+    the separate kernels to the oracle with these cameras."""
+    _fused_front_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, 4, 3, cam_fn=cameras_np)
+
+
+@pytest.mark.parametrize("depth,b,h,w,quat,cv_accum", [
     (1, 1, 21, 37, True, "fp32_round"),      # 16x8 tiles, ragged both ways; 13 hypotheses over 4 lanes per pixel
     (1, 2, 8, 16, False, "fp16_seq"),        # exactly one tile
     (2, 1, 19, 20, True, "fp32_round"),      # C = 32, 2 cuts: 8x8 tiles, refiner-input rows of 370 (stride 376)
@@ -1112,6 +1123,15 @@ def test_fused_level_front_large_windows_is_bitwise_the_separate_kernels(M, dev,
 
 
 @pytest.mark.parametrize("depth,b,h,w,quat,cv_accum", [
+    (2, 3, 19, 20, True, "fp32_round"),
+    (4, 3, 13, 18, True, "fp32_round"),
+])
+def test_fused_level_front_large_windows_per_sample_cameras(M, dev, depth, b, h, w, quat, cv_accum):
+    """m4d_level_front_r's (6, 6) instantiations at batch 3 with another, off-centre camera per sample."""
+    _fused_front_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, 6, 6, cam_fn=cameras_np)
+
+
+@pytest.mark.parametrize("depth,b,h,w,quat,cv_accum", [
     (4, 1, 24, 80, True, "fp32_round"),      # levels 4-6 of the 384x1280 pyramid at batch 1: what the bench path launches
     (5, 1, 12, 40, True, "fp32_round"),
     (6, 1, 6, 20, True, "fp32_round"),
@@ -1127,6 +1147,20 @@ def test_level_front_small_is_bitwise_the_separate_launches(M, dev, depth, b, h,
     two dependent launches it replaces: refiner input (padding channels included), feature state, depth state and outputs bit
     for bit over four frames (reset, two full frames with a per-pixel depth memory and coarser estimate, one without a coarser
     level = the coarsest level's form of the call)."""
+    _front_small_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, monkeypatch)
+
+
+@pytest.mark.parametrize("depth,b,h,w,quat,cv_accum", [
+    (2, 3, 17, 23, False, "fp32_round"),
+    (4, 3, 21, 19, False, "fp16_seq"),
+    (6, 3, 13, 11, True, "fp16_seq"),
+])
+def test_level_front_small_per_sample_cameras(M, dev, depth, b, h, w, quat, cv_accum, monkeypatch):
+    """m4d_level_front_small at batch 3 with another, off-centre camera per sample."""
+    _front_small_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, monkeypatch, cam_fn=cameras_np)
+
+
+def _front_small_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, monkeypatch, cam_fn=camera_np):
     from m4depth_amd import network as net, network_ops as nops, synthetic as S
     rng = np.random.default_rng(900 + depth * 10 + h)
     C = S_ENC[depth - 1]
@@ -1142,7 +1176,7 @@ def test_level_front_small_is_bitwise_the_separate_launches(M, dev, depth, b, h,
             cv.load_hwio(W[f"lvl.{depth}.conv.{i}.kernel"], W[f"lvl.{depth}.conv.{i}.bias"], dev)
         levels.append(gl)
     assert levels[0].wants_prenormalized(b, h, w, C)
-    cam = to_dev(camera_np(b, h, w), dev)
+    cam = to_dev(cam_fn(b, h, w), dev)
     launches = []
     for step in range(4):
         rot, trans = motion_np(rng, b, quat=quat, t_scale=(3.0, 3.0, 1.0))
@@ -1171,7 +1205,7 @@ def test_level_front_small_is_bitwise_the_separate_launches(M, dev, depth, b, h,
             assert torch.isfinite(fins[0]).all()
 
 
-def _fused_front_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, rd, rs):
+def _fused_front_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, rd, rs, cam_fn=camera_np):
     from m4depth_amd import network as net
     rng = np.random.default_rng(500 + depth * 10 + h)
     C = S_ENC[depth - 1]
@@ -1186,7 +1220,7 @@ def _fused_front_vs_separate(M, dev, depth, b, h, w, quat, cv_accum, rd, rs):
         for i, cv in enumerate(convs):
             cv.load_hwio(W[f"lvl.{depth}.conv.{i}.kernel"], W[f"lvl.{depth}.conv.{i}.bias"], dev)
         levels.append(gl)
-    cam = to_dev(camera_np(b, h, w), dev)
+    cam = to_dev(cam_fn(b, h, w), dev)
     old = (net.fused_front, net.fused_front_min_pixels, net.fused_front_coarse_min_pixels)
     net.fused_front_coarse_min_pixels = 0            # levels 4-6: take the fused front on these small maps too
     f_row = (2 * rd + 1 + (2 * rs + 1) ** 2) * 2 ** (depth // 2) + 6

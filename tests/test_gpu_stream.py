@@ -16,7 +16,7 @@ import torch
 
 from oracle import m4depth_oracle as O
 from m4depth_amd import synthetic as S
-from helpers import npy, assert_bits_equal, rel_err
+from helpers import npy, assert_bits_equal, rel_err, cameras_np, motion_np
 
 pytestmark = pytest.mark.gpu
 
@@ -167,9 +167,28 @@ def test_reset_constants_and_state(dev):
 def test_masked_close_kernels_guard_bands(dev, kernel):
     """The three masked closes on odd map sizes (partial tiles), outputs inside guard bands: masked samples get the reset
     constants, unmasked samples the bits of the unmasked entry point, and not one word outside the outputs changes."""
+    b = 3
+    rot = np.tile(np.array([[1.0, 0.01, -0.02, 0.005]], np.float32), (b, 1))
+    trans = np.tile(np.array([[0.3, 0.1, 0.02]], np.float32), (b, 1))
+    cam = {"f": np.full((b, 2), 20.0, np.float32), "c": np.full((b, 2), 10.0, np.float32)}
+    _masked_close_case(dev, kernel, [1, 0, 1], rot, trans, cam)
+
+
+@pytest.mark.parametrize("mask", [[1, 0, 1], [0, 1, 0]])
+@pytest.mark.parametrize("kernel", ["tail6", "tail", "post"])
+def test_masked_close_kernels_per_sample_cameras(dev, kernel, mask):
+    """The same with another pose and another, off-centre camera per sample (helpers.cameras_np), every sample once the live
+    one; the depth of every live sample is also held to the oracle: parallax2depth of the kernel's own parallax, bit for bit."""
+    b, h, w = 3, 13, 29
+    rot, trans = motion_np(np.random.default_rng(15), b)
+    _masked_close_case(dev, kernel, mask, rot, trans, cameras_np(b, h, w), oracle=True)
+
+
+def _masked_close_case(dev, kernel, mask, rot, trans, cam, oracle=False):
     from m4depth_amd import network as net, network_ops as nops
     from m4depth_amd._lib import lib
     b, h, w = 3, 13, 29
+    rot_np, trans_np, cam_np = rot, trans, cam
     W = S.init_weights(2, seed=14)
     model = _model(dev, W, levels=2)
     lvl = model.d_estimator.levels[0]
@@ -177,11 +196,11 @@ def test_masked_close_kernels_guard_bands(dev, kernel):
     g = torch.Generator(device="cpu").manual_seed(3)
     x32 = torch.randn((b, h, w, 32), generator=g).to(dev)
     ro = torch.randn((b, h, w, 5), generator=g).to(dev)
-    rot = torch.from_numpy(np.tile(np.array([[1.0, 0.01, -0.02, 0.005]], np.float32), (b, 1))).to(dev)
-    trans = torch.from_numpy(np.tile(np.array([[0.3, 0.1, 0.02]], np.float32), (b, 1))).to(dev)
-    cf = torch.full((b, 2), 20.0, device=dev)
-    cc = torch.full((b, 2), 10.0, device=dev)
-    mask = torch.tensor([1, 0, 1], dtype=torch.uint8, device=dev)
+    rot = torch.from_numpy(rot_np).to(dev)
+    trans = torch.from_numpy(trans_np).to(dev)
+    cf = torch.from_numpy(cam_np["f"]).to(dev)
+    cc = torch.from_numpy(cam_np["c"]).to(dev)
+    mask = torch.tensor(mask, dtype=torch.uint8, device=dev)
     G = 256
     sentinel = -12345.5
 
@@ -227,6 +246,12 @@ def test_masked_close_kernels_guard_bands(dev, kernel):
             assert_bits_equal(depth[s], rd[s, ..., 0], f"{kernel} depth")
             assert_bits_equal(dst[s], rd[s, ..., 0], f"{kernel} depth state")
             assert_bits_equal(oth[s], ro_[s], f"{kernel} other")
+            if oracle:
+                want = O.parallax2depth(para[s:s + 1, ..., None], rot_np[s:s + 1], trans_np[s:s + 1],
+                                        {k: v[s:s + 1] for k, v in cam_np.items()})
+                assert_bits_equal(depth[s], want[0, ..., 0], f"{kernel} sample {s}: depth = parallax2depth(parallax)")
+    if oracle:                                                                    # ... and the unmasked entry, every sample
+        assert_bits_equal(rd, O.parallax2depth(rp, rot_np, trans_np, cam_np), f"unmasked {kernel}: depth = parallax2depth(parallax)")
 
 
 def test_staggered_resets_against_the_oracle(dev):

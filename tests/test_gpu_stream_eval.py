@@ -148,16 +148,16 @@ def midair_set(tmp_path_factory):
 _runs = {}
 
 
-def _perfs(midair_set, *extra):
-    """perfs-midair.txt of one main.py run (cached per flag set): (the file's bytes, the 7 values)."""
+def _perfs(dataset_set, *extra, dataset="midair", arch=None):
+    """perfs-<dataset>.txt of one main.py run (cached per dataset and flag set): (the file's bytes, the 7 values)."""
     from m4depth_amd import main as MAIN
-    key = tuple(extra)
+    key = (dataset,) + tuple(extra)
     if key not in _runs:
-        cfg, rec, root = midair_set
+        cfg, rec, root = dataset_set
         ck = os.path.join(root, "ckpt_" + str(len(_runs)))
-        argv = ["--mode", "eval", "--dataset", "midair", "--db_path_config", cfg, "--records_path", rec, "--ckpt_dir", ck]
-        assert MAIN.main(argv + COMMON_ARCH + list(extra)) == 0
-        path = os.path.join(ck, "perfs-midair.txt")
+        argv = ["--mode", "eval", "--dataset", dataset, "--db_path_config", cfg, "--records_path", rec, "--ckpt_dir", ck]
+        assert MAIN.main(argv + (COMMON_ARCH if arch is None else arch) + list(extra)) == 0
+        path = os.path.join(ck, "perfs-" + dataset + ".txt")
         _runs[key] = (open(path, "rb").read(), np.loadtxt(path).astype(np.float32))
     return _runs[key]
 
@@ -207,6 +207,58 @@ def test_batched_close_to_sequential(dev, midair_set, slots):
     print(f"[stream_eval] {slots} slots vs 1: relative {rel} (AbsRel..RMSE_log), Delta {dd}")
     assert (rel <= BATCHED_REL_TOL).all(), (got, one)
     assert (dd <= BATCHED_DELTA_TOL).all(), (got, one)
+
+
+# ---- per-trajectory intrinsics: a slot must carry its own trajectory's camera into the network ------------------------------
+KITTI_LENGTHS = [5, 2, 4, 3, 2]            # more trajectories than slots: a slot takes a second trajectory, with another camera
+KITTI_SIZE = (48, 80)                      # the smallest 4-level size (multiples of 16) the Garg crop leaves rows and columns of
+KITTI_ARCH = ["--arch_depth", "4", "--height", str(KITTI_SIZE[0]), "--width", str(KITTI_SIZE[1])]
+# fx fy cx cy (normalised by the image size) of each trajectory: all different, f != c, off centre
+KITTI_CAMERAS = [(0.58, 1.92, 0.49, 0.51), (0.71, 1.55, 0.53, 0.46), (0.83, 1.11, 0.31, 0.66), (0.64, 1.73, 0.44, 0.57),
+                 (0.92, 1.31, 0.61, 0.38)]
+
+
+@pytest.fixture(scope="module")
+def kitti_set(tmp_path_factory):
+    root = str(tmp_path_factory.mktemp("stream_eval_kitti"))
+    db, rec = make_fake_dataset(root, "kitti-raw", n_traj=len(KITTI_LENGTHS), n_frames=max(KITTI_LENGTHS), size=KITTI_SIZE, seed=23)
+    for t, n in enumerate(KITTI_LENGTHS):           # unequal lengths, another camera per trajectory
+        path = os.path.join(rec, f"set_{t}", f"traj_{t:04d}.csv")
+        lines = open(path).read().splitlines()
+        out = [lines[0]]
+        for ln in lines[1:1 + n]:
+            v = ln.split("\t")
+            v[-4:] = [repr(x) for x in KITTI_CAMERAS[t]]
+            out.append("\t".join(v))
+        with open(path, "w") as fh:
+            fh.write("\n".join(out) + "\n")
+    cfg = os.path.join(root, "datasets_location.json")
+    with open(cfg, "w") as fh:
+        json.dump({"kitti-raw": db}, fh)
+    return cfg, rec, root
+
+
+def _kitti_perfs(kitti_set, *extra):
+    return _perfs(kitti_set, *extra, dataset="kitti-raw", arch=KITTI_ARCH)
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_one_slot_equals_sequential_with_per_trajectory_cameras(dev, kitti_set, graph):
+    """KITTI format, another camera per trajectory: --eval_streams 1 writes the sequential run's perfs file, byte for byte, eager
+    and from the hipGraph (whose static camera buffers must follow the trajectory in the slot)."""
+    seq_bytes, seq = _kitti_perfs(kitti_set)
+    got_bytes, got = _kitti_perfs(kitti_set, "--eval_streams", "1", *(["--graph"] if graph else []))
+    assert np.isfinite(seq).all() and seq[0] > 0
+    assert got_bytes == seq_bytes, f"1 slot {'graph' if graph else 'eager'}: {got} vs sequential {seq}"
+
+
+def test_schedule_independence_with_per_trajectory_cameras(dev, kitti_set):
+    """4 slots, longest-first against csv-order dealing: the trajectories run in other slots, so a slot that carried another
+    trajectory's camera into the network would change these bytes (the Mid-Air set, one camera for all, cannot show that)."""
+    a = _kitti_perfs(kitti_set, "--eval_streams", "4", "--eval_streams_policy", "lpt")
+    b = _kitti_perfs(kitti_set, "--eval_streams", "4", "--eval_streams_policy", "arrival")
+    assert np.isfinite(a[1]).all() and a[1][0] > 0
+    assert a[0] == b[0], f"lpt {a[1]} vs arrival {b[1]}"
 
 
 # ---- the slot loader against the batch-1 streaming plan -----------------------------------------------------------------
