@@ -490,6 +490,12 @@ int m4d_conv3x3s_bias_act_ws(const float* x, const float* wp, const float* bias,
 int m4d_conv3x3_bias_act_ws(const float* x, const float* wp, const float* bias, int b, int h, int w,
                             int Cin, int Cout, int CoutPad, float slope, float* out, float* workspace,
                             long long workspace_floats, void* stream);
+/* m4d_conv3x3s_bias_act_ws with the split-K factor -- which sets the summation order -- decided for a launch on split_batch
+ * images instead of this launch's b: the same layer launched on one frame or on several stacked frames of a batch-split_batch
+ * sequence gives the same bits per image.  split_batch == b is m4d_conv3x3s_bias_act_ws. */
+int m4d_conv3x3s_bias_act_wsb(const float* x, const float* wp, const float* bias, int b, int split_batch, int h, int w,
+                              int Cin, int Cout, int CoutPad, int stride, float slope, float* out,
+                              float* workspace, long long workspace_floats, void* stream);
 /* Latency-first form of the same stride-1 layer for SMALL maps at batch 1 (round 5, csrc/m4d_convlat.hip; the DispRefiner
  * convolutions of the coarse pyramid levels, m4depth_network.py:116-135): every wave requests everything it needs -- its weight
  * fragments of at most two 16-channel chunks straight into MFMA operand registers, then the workgroup's halo -- in ONE memory

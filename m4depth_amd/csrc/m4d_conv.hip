@@ -791,10 +791,24 @@ extern "C" int m4d_conv3x3s2_dinl_bias_act(const float* x_raw, const float* mean
   return M4D_LAUNCH_RESULT();
 }
 
+extern "C" int m4d_conv3x3s_bias_act_wsb(const float* x, const float* wp, const float* bias, int b, int split_batch, int h,
+                                         int w, int Cin, int Cout, int CoutPad, int stride, float slope, float* out,
+                                         float* workspace, long long workspace_floats, void* stream);
+
 extern "C" int m4d_conv3x3s_bias_act_ws(const float* x, const float* wp, const float* bias, int b, int h, int w,
                                         int Cin, int Cout, int CoutPad, int stride, float slope, float* out,
                                         float* workspace, long long workspace_floats, void* stream) {
-  M4D_CHECK_ARG(x && wp && bias && out && b > 0 && h > 0 && w > 0 && Cin > 0 && Cout > 0);
+  return m4d_conv3x3s_bias_act_wsb(x, wp, bias, b, b, h, w, Cin, Cout, CoutPad, stride, slope, out, workspace,
+                                   workspace_floats, stream);
+}
+
+// ... with the split-K factor decided for a batch of ``split_batch`` images instead of the ``b`` of this launch.  The factor sets
+// the summation order: a caller that launches the same layer on different numbers of stacked images (the encoder: one frame of
+// a stream, two or more frames of a sequence) passes the same ``split_batch`` every time and gets the same bits per image.
+extern "C" int m4d_conv3x3s_bias_act_wsb(const float* x, const float* wp, const float* bias, int b, int split_batch, int h,
+                                         int w, int Cin, int Cout, int CoutPad, int stride, float slope, float* out,
+                                         float* workspace, long long workspace_floats, void* stream) {
+  M4D_CHECK_ARG(x && wp && bias && out && b > 0 && split_batch > 0 && h > 0 && w > 0 && Cin > 0 && Cout > 0);
   M4D_CHECK_ARG((stride == 1 || stride == 2) && CoutPad % 32 == 0 && CoutPad >= Cout);
   M4D_CHECK_ARG(((((uintptr_t)x) & (Cin % 2 == 0 ? 7u : 3u)) == 0) && ((((uintptr_t)wp) & 15u) == 0));
   ConvArgs a;
@@ -812,12 +826,17 @@ extern "C" int m4d_conv3x3s_bias_act_ws(const float* x, const float* wp, const f
   const long long tiles = (long long)a.tiles_x * a.tiles_y;
   const int n32 = CoutPad / 32;
   // N-tiles per workgroup: as wide as possible (A reuse) while the launch still fills the chip
-  int nt = n32 >= 4 && n32 % 4 == 0 ? 4 : (n32 % 3 == 0 ? 3 : (n32 % 2 == 0 ? 2 : 1));
-  while (nt > 1 && tiles * b * (n32 / nt) < 512) nt = (nt == 4 || nt == 2) ? nt / 2 : 1;
+  auto n_tiles_for = [&](int images) {
+    int nt = n32 >= 4 && n32 % 4 == 0 ? 4 : (n32 % 3 == 0 ? 3 : (n32 % 2 == 0 ? 2 : 1));
+    while (nt > 1 && tiles * images * (n32 / nt) < 512) nt = (nt == 4 || nt == 2) ? nt / 2 : 1;
+    return nt;
+  };
+  const int nt = n_tiles_for(b);
   // split-K when even the narrowest N split leaves most of the chip idle (coarse pyramid levels):
   // every split keeps >= 2 chunks, partial sums go through the caller's workspace.  (One chunk per split / up to 32 splits
   // measured +0.1-0.5 % end to end, tools/ab_bench.sh -- not worth moving the rounding of every coarse-level layer.)
-  const long long blocks = tiles * b * (n32 / nt);
+  // (from the grid a launch on ``split_batch`` images would have: the same factor however many images this launch carries)
+  const long long blocks = tiles * split_batch * (n32 / n_tiles_for(split_batch));
   int ksplit = 1;
   static int sk_target = -1, sk_min_chunks = -1, sk_max = -1;     // tuning knobs (profiling): M4D_CONV_SPLITK_TARGET / _MIN_CHUNKS / _MAX
   if (sk_target < 0) { const char* e = getenv("M4D_CONV_SPLITK_TARGET"); sk_target = e ? atoi(e) : 256; }

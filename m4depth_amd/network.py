@@ -196,6 +196,11 @@ fused_encoder_level0 = _os.environ.get("M4D_FUSED_ENC0", "1") == "1"
 # Encoder in two batches: frames [0, split) before the decoder, frames [split, T) on frame `split`'s stream.  (Encoding every
 # frame on its own stream instead was measured slower, 633 vs 643 frames/s at batch 1: a batched pass has 4x fewer launches.)
 pipeline_encoder_split = int(_os.environ.get("M4D_PIPELINE_ENCODER_SPLIT", "2"))
+# Frames per encoder launch the direct kernel's split-K factor is decided for, whatever a launch stacks (``splitk_batch``): the
+# stack of the split above, the launches the factor was tuned on.  A streamed frame, the odd last frame of a 3-frame sequence and
+# a batch of two frames then sum every output in the same order (before, the launcher decided from its own batch: at 256x768
+# and 384x512 a stream and the sequence call differed in the last bits from encoder level 3 on).
+encoder_splitk_frames = 2
 # With the split: level 0's DINL statistics of every frame are taken in the first batch's launches (per-image arithmetic, same bits).
 encoder_stats_up_front = _os.environ.get("M4D_ENC_STATS_UP_FRONT", "1") == "1"
 
@@ -397,6 +402,13 @@ class _Conv3x3SameTF(torch.nn.Module):
         eff_b = self.dispatch_batch if self.per_image_dispatch else b
         return eff_b * h * w <= lat_conv_max_pixels
 
+    def splitk_batch(self):
+        """The batch the direct kernel's split-K factor is decided for (None: the launch's own).  The factor sets the summation
+        order, so an encoder layer -- launched on one frame of a stream, on two stacked frames or on the odd last frame of a
+        sequence -- takes it from the sequence batch x ``encoder_splitk_frames``, like its kernel choice: the same in every
+        launch mode."""
+        return self.dispatch_batch * encoder_splitk_frames if self.per_image_dispatch else None
+
     def same_pads(self, h, w):
         """TF 'SAME' (before, after) pads for rows and columns at this stride."""
         s = self.stride
@@ -504,7 +516,7 @@ _CONV_LAUNCH = {
     "small": ("conv3x3_small_bias_act", lambda c, x, w, act, p: nops.conv3x3_small_bias_act(
         x, w[0], c.bias, c.out_channels, w[1], act, stride=c.stride)),
     "direct": ("conv3x3_bias_act", lambda c, x, w, act, p: nops.conv3x3_bias_act(
-        x, w[0], c.bias, c.out_channels, w[1], act, stride=c.stride)),
+        x, w[0], c.bias, c.out_channels, w[1], act, stride=c.stride, split_batch=c.splitk_batch())),
 }
 
 

@@ -623,20 +623,28 @@ def pack_conv_weights(kernel_hwio):
     return np.ascontiguousarray(w.transpose(1, 0, 3, 2)), cpad    # [chunk][tap][n][16p]
 
 
-def conv3x3_bias_act(x, wp, bias, cout, cout_pad, slope=0.1, stride=1):
-    """3x3 TF-'SAME' convolution (stride 1 or 2) + bias + leaky_relu(slope) on the matrix cores."""
+def conv3x3_bias_act(x, wp, bias, cout, cout_pad, slope=0.1, stride=1, split_batch=None):
+    """3x3 TF-'SAME' convolution (stride 1 or 2) + bias + leaky_relu(slope) on the matrix cores.  ``split_batch``: the batch the
+    split-K factor (= the summation order) is decided for, when it is not the batch of this launch: the encoder runs a layer on
+    one frame or on several stacked frames and must get the same bits per image either way."""
     x = as_f32(x, "x")
     b, h, w, cin = x.shape
+    split_b = b if split_batch is None else int(split_batch)
     oh, ow = -(-h // stride), -(-w // stride)
     out = torch.empty((b, oh, ow, cout), dtype=torch.float32, device=x.device)
     ws = None
     ws_floats = 0
-    if b * oh * ow <= 16384:                             # coarse levels: allow split-K through a workspace
+    if split_b * oh * ow <= 16384:                       # coarse levels: allow split-K through a workspace
         ws_floats = int(lib.m4d_conv3x3_workspace_floats(b, oh, ow, int(cout_pad)))
         ws = _workspace("conv_splitk", 4 * ws_floats, x.device)
-    check(lib.m4d_conv3x3s_bias_act_ws(dptr(x, "x"), dptr(wp, "wp"), dptr(bias, "bias"), b, h, w, cin, int(cout),
-                                       int(cout_pad), int(stride), float(slope), dptr(out), dptr(ws), ws_floats,
-                                       stream_ptr()), "m4d_conv3x3s_bias_act_ws")
+    if split_batch is None:
+        check(lib.m4d_conv3x3s_bias_act_ws(dptr(x, "x"), dptr(wp, "wp"), dptr(bias, "bias"), b, h, w, cin, int(cout),
+                                           int(cout_pad), int(stride), float(slope), dptr(out), dptr(ws), ws_floats,
+                                           stream_ptr()), "m4d_conv3x3s_bias_act_ws")
+    else:
+        check(lib.m4d_conv3x3s_bias_act_wsb(dptr(x, "x"), dptr(wp, "wp"), dptr(bias, "bias"), b, split_b, h, w, cin, int(cout),
+                                            int(cout_pad), int(stride), float(slope), dptr(out), dptr(ws), ws_floats,
+                                            stream_ptr()), "m4d_conv3x3s_bias_act_wsb")
     return out
 
 

@@ -60,12 +60,18 @@ def test_level_step_teacher_forced(dev, depth, h, w, coarse_front, monkeypatch):
     front instantiations of their geometries (the default from batch >= 4 at 384x1280); ``"small"`` = the one-launch opening of a
     coarse level on features normalised ahead of it (m4d_normalize_levels + m4d_level_front_small: what the batch-1 bench path
     runs on levels 4-6 since round 6), against the oracle directly."""
+    level_step_teacher_forced(dev, depth, 2, h, w, coarse_front, monkeypatch)
+
+
+def level_step_teacher_forced(dev, depth, b, h, w, coarse_front, monkeypatch, seed=None, one_launch_convs=True):
+    """The body of ``test_level_step_teacher_forced`` at batch ``b`` (tests/test_gpu_datasets.py runs it on the datasets' maps).
+    ``one_launch_convs``: the level's five convolutions are one launch each (the latency-first kernels), so that the "small"
+    form can be held to its launch count."""
     import m4depth_amd as M
     from m4depth_amd import network as net, network_ops as nops
     if coarse_front is True:
         monkeypatch.setattr(net, "fused_front_coarse_min_pixels", 0)
-    rng = np.random.default_rng(200 + depth)
-    b = 2
+    rng = np.random.default_rng(200 + depth if seed is None else seed)
     C = S.ENCODER_CHANNELS[depth - 1]
     W = S.init_weights(6, seed=3)
     ol = O.DepthEstimatorLevel(W, depth)
@@ -91,7 +97,7 @@ def test_level_step_teacher_forced(dev, depth, h, w, coarse_front, monkeypatch):
             nf = nops.normalize_levels([(to_dev(f, dev), gl.nbre_cuts)])[0]
         n0 = int(net.lib.m4d_launch_count())
         eg = gl(to_dev(f, dev), to_dev(prev, dev), to_dev(rot, dev), to_dev(trans, dev), to_dev(cam, dev), nt, curr_f_normalized=nf)
-        if coarse_front == "small" and step > 0:
+        if coarse_front == "small" and step > 0 and one_launch_convs:
             assert int(net.lib.m4d_launch_count()) - n0 == 7, "a coarse level = front + 5 convolutions + tail"
         assert_bits_equal(npy(gl.prev_f_maps), ol.prev_f_maps, "state: normalised features")
         if step == 0:
@@ -107,7 +113,7 @@ def test_level_step_teacher_forced(dev, depth, h, w, coarse_front, monkeypatch):
         assert np.max(rel_err(fg[..., [log_a, log_b]], fo[..., [log_a, log_b]], 1e-3)) < 2e-6
         # convolutions differ in summation order: compare outputs with the north-star tolerance
         check_depth_and_parallax(npy(eg["depth"]), npy(eg["parallax"]), eo["depth"], eo["parallax"], rot, trans, cam,
-                                 f"level {depth} step {step}")
+                                 f"level {depth} batch {b} {h}x{w} step {step}")
         # hand the oracle's state to the GPU level so that the next step is teacher-forced again
         gl.depth_prev_t.copy_(to_dev(ol.depth_prev_t, dev))
 

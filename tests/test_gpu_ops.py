@@ -93,8 +93,12 @@ LEVEL_GEOM = [(1, 48, 80, 16, 1), (2, 24, 40, 32, 2), (3, 24, 40, 64, 2), (4, 12
 @pytest.mark.parametrize("lvl,h,w,C,k", LEVEL_GEOM)
 def test_dscv_sncv_level_geometries(M, dev, lvl, h, w, C, k):
     """Every (C, cuts) pair of the 6-level pyramid, batch 2, DSCV r=4 / SNCV r=3."""
-    rng = np.random.default_rng(100 + lvl)
-    b = 2
+    dscv_sncv_vs_oracle(M, dev, 2, h, w, C, k, 100 + lvl)
+
+
+def dscv_sncv_vs_oracle(M, dev, b, h, w, C, k, seed):
+    """DSCV (r = 4: volume, reprojected parallax, index grid) and SNCV (r = 3, c1 against itself) bit for bit against the oracle."""
+    rng = np.random.default_rng(seed)
     cam = camera_np(b, h, w)
     rot, trans = motion_np(rng, b, t_scale=(3.0, 3.0, 1.0))
     c1 = O.normalize_cuts(rng.standard_normal([b, h, w, C]).astype(F), k)
@@ -1042,9 +1046,13 @@ def test_small_map_conv(M, dev, b, h, w, cin, cout, slope):
 def test_merged_cost_volume_launch(M, dev, b, h, w, C, k):
     """m4d_dscv_sncv_fwd (one launch for both volumes on small maps, the two entries in sequence above 6000 pixels) gives the
     bits of m4d_dscv_fwd + m4d_sncv_fwd."""
+    merged_cost_volume_vs_separate(dev, b, h, w, C, k, C + k)
+
+
+def merged_cost_volume_vs_separate(dev, b, h, w, C, k, seed):
     import ctypes
     from m4depth_amd._lib import lib, check, dptr, stream_ptr
-    rng = np.random.default_rng(C + k)
+    rng = np.random.default_rng(seed)
     cam = camera_np(b, h, w)
     rot, trans = motion_np(rng, b, t_scale=(3.0, 3.0, 1.0))
     c1 = O.normalize_cuts(rng.standard_normal([b, h, w, C]).astype(F), k)
