@@ -33,8 +33,8 @@ int m4d_tape_end(void);
 int m4d_tape_length(int tape);
 int m4d_tape_replay(int tape, void* stream);
 int m4d_tape_free(int tape);
-/* Entry points that enqueue a hipMemsetAsync beside their kernels (m4d_backproject_bwd, m4d_dscv_bwd, ...) return
- * hipErrorNotSupported while the calling thread records: a memset is not a kernel launch and would be lost from the replay. */
+/* The scatter backwards (m4d_backproject_bwd, m4d_dscv_bwd) zero their outputs with a kernel launch (m4d_zero_f32), which
+ * is recorded like any other launch. */
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,19 @@ inline void m4d_launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t l
   hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<KArgs>(args)...);
 }
 
+// ---- zero-fill of a buffer that atomic adds then scatter into: a KERNEL, not hipMemsetAsync ---------------------------------
+// Inside a captured training step (training.GraphedTrainStep) a memset node was not reliably ordered against the kernel nodes
+// around it on replay: the scatter's sums came out with stale or missing terms in some replays.
+static __global__ void __launch_bounds__(256) m4d_zero_f32_kernel(float* __restrict__ p, long long n) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = 0.f;
+}
+
+static inline void m4d_zero_f32(float* p, long long n, hipStream_t stream) {
+  const long long blocks = (n + 255) / 256;
+  m4d_launch(m4d_zero_f32_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks))), dim3(256), 0, stream, p, n);
+}
+
 // ---- the > 64 KB dynamic-LDS opt-in of a kernel: per FUNCTION and per DEVICE, from any host thread --------------------------
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the current device only, and a process may drive several GPUs from
 // several threads (round 5 kept `static bool attr_set` flags: one device, unsynchronised -- ADVICE r5).  `done` = one bit per

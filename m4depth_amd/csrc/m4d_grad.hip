@@ -314,16 +314,8 @@ extern "C" int m4d_dscv_bwd(const float* c1, const float* c2, const float* disp_
   M4D_CHECK_ARG(g_cv_stride >= nbre_cuts * (2 * search_range + 1));
   M4D_CHECK_ARG(((((uintptr_t)c1 | (uintptr_t)c2 | (uintptr_t)g_c1 | (uintptr_t)g_c2)) & 15u) == 0);
   hipStream_t s = (hipStream_t)stream;
-  const size_t fbytes = (size_t)b * h * w * C * sizeof(float);
-#if M4D_EXPERIMENTS
-  if (m4d_tape_recording()) return (int)hipErrorNotSupported;      // a memset is not a kernel launch: it would be lost from the replay
-#endif
-  hipError_t e = hipMemsetAsync(g_c2, 0, fbytes, s);
-  if (e != hipSuccess) return (int)e;
-  if (g_disp_prev_t) {
-    e = hipMemsetAsync(g_disp_prev_t, 0, (size_t)b * h * w * sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
-  }
+  m4d_zero_f32(g_c2, (long long)b * h * w * C, s);
+  if (g_disp_prev_t) m4d_zero_f32(g_disp_prev_t, (long long)b * h * w, s);
   DscvBwdArgs a;
   a.c1 = c1; a.c2 = c2; a.disp_prev_t = disp_prev_t; a.disp = disp; a.rot = rot; a.rot_c = rot_c;
   a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c; a.h = h; a.w = w; a.C = C; a.r = search_range;

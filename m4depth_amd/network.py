@@ -54,7 +54,8 @@ _WINO2_MIN_WORKGROUPS = 60
 # products, float32 accumulation (csrc/m4d_wino6.hip: float32 accuracy -- error against float64 0.8x that of the fp32
 # MFMA kernels, tools/bench_wino6.py -- at 2.67x less matrix-core time); "f16x2" (default) = the same layers with float32
 # operands scaled by powers of two (per Winograd tile / per output channel) and split into two fp16 terms, three fp16 MFMA
-# products (csrc/m4d_wino_f16.hip: error against float64 at the bf16x3 level), and the stride-1
+# products (csrc/m4d_wino_f16.hip: error against float64 at the bf16x3 level, DESIGN.md section 6, also on the trained
+# encoder's weights (tests/test_gpu_trained.py)), and the stride-1
 # latency-first layers likewise (csrc/m4d_convlat_f16.hip) -- every other kernel (small-map, fused tail,
 # training) keeps its bf16x3 form under "f16x2"; "f32" = the fp32-MFMA kernels everywhere.
 conv_arith = _os.environ.get("M4D_CONV_ARITH", "f16x2")

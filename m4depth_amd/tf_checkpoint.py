@@ -15,8 +15,8 @@ Pinning: TensorFlow cannot run here, so the formats are restated from TensorFlow
 core/lib/io/format.cc, block.cc (table), core/util/tensor_bundle (entries, string tensors),
 core/protobuf/tensor_bundle.proto and trackable_object_graph.proto.  The table / bundle-entry / tensor-data
 layers ARE pinned against files written by TensorFlow itself: the reference ships the bundles of its legacy
-model (.legacy/trained_weights/M4Depth-d6), whose index files and the head of one data file are committed
-under tests/golden/tf_legacy/; every block trailer and every tensor carries a masked crc32c written by
+model (.legacy/trained_weights/M4Depth-d6), whose index files and one data file (its head, and the rest as byte ranges
+beside it: tests/trained_cases.py) are committed under tests/golden/tf_legacy/; every block trailer and every tensor carries a masked crc32c written by
 TensorFlow, and the reader verifies them (tests/test_tf_checkpoint.py).  Those bundles are name-based
 (tf.train.Saver), so the object-graph walk (``lookup``) remains UNPINNED: it is tested against a writer that
 follows the same description (tests/tf_bundle_writer.py).  Block compression is rejected loudly (the bundle

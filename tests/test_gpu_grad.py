@@ -99,13 +99,13 @@ def _sncv_backward_case(M, dev, b, h, w, C, k, r, same, seed):
 
 
 # ---- the cost volumes at the recipe's geometries: batch 3, the six levels of a 384 x 384 crop, level 1 of a KITTI frame ----
-DSCV_WINDOW_FLOATS = 48 * 256          # the default LDS budget of m4d_dscv_bwd (csrc/m4d_grad.hip:341-342)
+DSCV_WINDOW_FLOATS = 48 * 256          # the default LDS budget of m4d_dscv_bwd (csrc/m4d_grad.hip:333-334)
 
 
 def dscv_window_mix(idx, C):
     """(private, direct): how many pixel blocks of dscv_bwd_kernel keep their g_c2 window in LDS and how many scatter
     straight to memory, from the forward's (y0, x0) grid [b, h, w, 2r+1, 2] and the block shape of the launcher
-    (csrc/m4d_grad.hip:332-340), with the window test of the kernel (:128-130)."""
+    (csrc/m4d_grad.hip:324-332), with the window test of the kernel (:128-130)."""
     b, h, w = idx.shape[:3]
     ppw = 64 // (C // 4)
     p2 = 0

@@ -833,13 +833,10 @@ def test_fused_refiner_tail(M, dev, b, h, w, quat, kernel):
 
 
 def _trained_legacy_encoder_weights():
-    """The trained first two encoder levels of the reference's legacy model, read from the TensorFlow-written bundle
-    head in tests/golden/tf_legacy (same layer shapes as FeaturePyramid, m4depth_network.py:59-74)."""
-    import os
-    from m4depth_amd import tf_checkpoint as TC
-    d = os.path.join(os.path.dirname(__file__), "golden", "tf_legacy")
-    r = TC.CheckpointReader(os.path.join(d, "features"), data_path=os.path.join(d, "features.data-%05d-of-%05d"))
-    return {(l, c, p): r.tensor(f"feature_pyramid/layer_{l}/conv2d_{c}/{p}") for l in (1, 2) for c in (1, 2) for p in ("kernel", "bias")}
+    """The trained encoder of the reference's legacy model, read from the TensorFlow-written bundle in tests/golden/tf_legacy
+    (same layer shapes as FeaturePyramid, m4depth_network.py:59-74): tests/trained_cases.py."""
+    from trained_cases import trained_encoder_weights
+    return trained_encoder_weights()
 
 
 @pytest.mark.parametrize("weights", ["random", "trained"])

@@ -127,3 +127,15 @@ def test_integration_doc_lists_exactly_the_switches_the_package_reads():
         if line.startswith("| `M4D_"):
             in_table |= set(re.findall(r"\bM4D_[A-Z0-9_]+", line.split("|")[1]))
     assert in_table == in_code, (sorted(in_code - in_table), sorted(in_table - in_code))
+
+
+def test_library_sources_enqueue_no_memset():
+    """Every zero-fill of the library is a kernel launch (m4d_zero_f32, csrc/m4d_common.h).  A hipMemsetAsync captured into the
+    training graph becomes a memset node, and those were not reliably ordered against the kernel nodes around them on replay:
+    the scatter backwards summed onto stale or half-cleared buffers in some replays."""
+    src = os.path.join(ROOT, "m4depth_amd", "csrc")
+    names = [n for n in sorted(os.listdir(src)) if n.endswith((".hip", ".h", ".cpp"))]
+    assert "m4d_grad.hip" in names and "m4d_warp.hip" in names
+    for n in names:
+        code = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(src, n)).read(), flags=re.S)
+        assert not re.search(r"\bhipMemset\w*\s*\(", code), f"csrc/{n} enqueues a memset"
