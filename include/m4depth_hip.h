@@ -337,6 +337,45 @@ int m4d_train_log_step(const float* loss, const float* gt, long long gt_stride, 
                        int h, int w, float* log, int log_rows, long long* counter, long long* first_bad,
                        void* workspace, void* stream);
 
+/* ---- Photometric reprojection loss: training without ground-truth depth (csrc/m4d_photo.hip) ----------
+ * Standard self-supervised depth training (Godard et al., "Digging into self-supervised monocular depth estimation",
+ * ICCV 2019, eq. 2-5: SSIM + L1 photometric error, auto-masking, edge-aware smoothness), one term per pyramid level, with the
+ * exact relative pose of the data instead of a pose network.  Per level (map h x w) and frame t >= 1, with cur / prev the
+ * level images of frames t / t-1 and dc = clip(depth, 0.01, 200):
+ *   warped = reproject(prev, dc, rot, trans, camera)[0], bit for bit (the query and the bilinear sample of m4d_reproject_flow
+ *            + m4d_dense_image_warp); valid = Pz > 0 and 0 <= qx <= w-1 and 0 <= qy <= h-1 and depth finite;
+ *            dwarp = d warped / d dc, analytic: dq/ddc = (A Pz - Px C) / Pz^2 per axis, d warped/dqx = (1-ay)(tr-tl) + ay(br-bl),
+ *            d warped/dqy = (1-ax)(bl-tl) + ax(br-tr), 0 on an axis whose alpha was clamped;
+ *   pe(a,b) = 0.85 (1 - SSIM(a,b)) / 2 + 0.15 |a - b|, mean over the 3 channels, at interior pixels (1 <= y <= h-2,
+ *            1 <= x <= w-2); SSIM over the 3x3 window, sigma^2 = mean(x^2) - mu^2, sigma_xy = mean(xy) - mu_x mu_y,
+ *            C1 = 0.01^2, C2 = 0.03^2, no clipping;
+ *   M(p)   = p interior and all 9 window pixels valid and (automask != 0: pe(warped,cur)(p) < pe(prev,cur)(p)); N = sum M;
+ *   photo  = sum M pe(warped,cur) / max(N,1);
+ *   smooth = [sum_{x<w-1} |ld(y,x+1) - ld(y,x)| exp(-mean_c |cur(y,x+1) - cur(y,x)|) + the same along y] / (b h w), ld = log dc;
+ *   out4   = (photo + lambda smooth, photo, smooth, N).
+ * Backward (a gather, no atomics): g_depth(q) = g_out * inside(q) * [ sum_c dwarp_c(q) sum_{p in 3x3(q)} M(p)
+ *   d pe_c(p) / d warped_c(q) / max(N,1) + lambda d smooth / d dc(q) ], inside = (0.01 <= depth <= 200), with the mask and N
+ *   of the forward.  Images are [b,h,w,3], depth / valid / mask [b,h,w,1] (valid, mask: one byte per pixel, 0 or 1); cameras
+ *   are per sample and level-local; h, w >= 3, b h w <= 2^24.  Deterministic: block partials in double, fixed-order finish.
+ *
+ * Image pyramid (data, no gradient): level 0 = the 2x2 mean of image [n,H,W,3], ((a + b) + (c + d)) * 0.25 with a, b on the
+ * upper row; level i = the same of level i-1.  Level i ([n, H >> (i+1), W >> (i+1), 3]) starts at float offset
+ * sum_{k<i} n * 3 * (H >> (k+1)) * (W >> (k+1)) of `out`, which holds m4d_image_pyramid_floats floats (-1: H or W is no
+ * multiple of 2^levels). */
+long long m4d_image_pyramid_floats(int n, int H, int W, int levels);
+int m4d_image_pyramid_box(const float* image, int n, int H, int W, int levels, float* out, void* stream);
+int m4d_photo_warp_fwd(const float* depth, const float* rot, int rot_c, const float* trans, const float* cam_f,
+                       const float* cam_c, const float* prev, int b, int h, int w, float* warped, float* dwarp,
+                       unsigned char* valid, void* stream);
+/* workspace of m4d_photo_loss_fwd in bytes (8-byte aligned); -1 for sizes the loss refuses */
+long long m4d_photo_workspace_bytes(int b, int h, int w);
+int m4d_photo_loss_fwd(const float* depth, const float* warped, const unsigned char* valid, const float* cur,
+                       const float* prev, int b, int h, int w, float lambda, int automask, void* workspace,
+                       float* out4, unsigned char* mask, void* stream);
+int m4d_photo_loss_bwd(const float* depth, const float* warped, const float* dwarp, const float* cur,
+                       const unsigned char* mask, const float* out4, const float* g_out, int b, int h, int w,
+                       float lambda, float* g_depth, void* stream);
+
 /* ---- m4depth_network.py: DepthEstimatorLevel glue -------------------------------- */
 
 /* Per-cut L2 normalisation (:179-189, tf.linalg.normalize, no epsilon). */

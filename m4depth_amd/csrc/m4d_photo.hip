@@ -1,0 +1,389 @@
+// Photometric reprojection loss: training without ground-truth depth ("Photometric loss").
+//
+// Per pyramid level and frame t >= 1 the previous frame's image is warped into the current one with the PREDICTED depth
+// (the query of depth_operations.reproject: reproject_flow_kernel + interp_bilinear_kernel, same device functions, same
+// operation order, so `warped` carries reproject's bits) and compared with the current image:
+//   pe(a, b)   = 0.85 (1 - SSIM(a, b)) / 2 + 0.15 |a - b|, mean over the 3 channels, SSIM over the 3x3 window with
+//                sigma^2 = mean(x^2) - mu^2, sigma_xy = mean(xy) - mu_x mu_y, C1 = 0.01^2, C2 = 0.03^2, no clipping;
+//   M(p)       = p interior (1 <= y <= h-2, 1 <= x <= w-2), all 9 window pixels valid, and (auto-masking, optional)
+//                pe(warped, cur)(p) < pe(prev, cur)(p);   valid = Pz > 0, query inside [0, w-1] x [0, h-1], depth finite;
+//   photo      = sum M pe(warped, cur) / max(N, 1), N = sum M;
+//   smooth     = [sum_{x<w-1} |ld(y,x+1) - ld(y,x)| exp(-mean_c |cur(y,x+1) - cur(y,x)|) + the same along y] / (b h w),
+//                ld = log(clip(depth, 0.01, 200));
+//   term       = photo + lambda smooth            (Monodepth2: Godard et al., ICCV 2019, eq. 2-5, single source frame).
+// The backward is a pure gather: every pixel q sums the derivative of the (at most 9) masked windows it lies in, times
+// dwarp = d warped / d clip(depth) of the forward, plus the smoothness term; the mask and N are the forward's.
+//
+// Structure: 16x16-pixel tiles, 256 threads, `warped`, `cur`, validity / mask and log depth of the tile plus its halo in LDS
+// (1 pixel forward, 2 pixels backward: the windows of the 3x3 neighbours), window statistics and sums in double (the maps are
+// small; float32's cancellation in mean(x^2) - mu^2 against C2 = 9e-4 would otherwise be the largest error of the loss).
+// No atomics, no memset: block partials in double, wave64 shuffles, one fixed-order finish -- the same bits every run.
+#include "m4d_common.h"
+#include "../../include/m4depth_hip.h"
+
+namespace {
+
+constexpr int kTile = 16;
+constexpr double kC1 = 0.01 * 0.01, kC2 = 0.03 * 0.03;
+
+// ---- image pyramid: 2x2 mean, ((a + b) + (c + d)) * 0.25 with a, b on the upper row ---------------------------------------
+__global__ void __launch_bounds__(256)
+pyramid_box_kernel(const float* __restrict__ in, int oh, int ow, long long total, float* __restrict__ out) {
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(idx % 3);
+    long long r = idx / 3;
+    const int x = (int)(r % ow); r /= ow;
+    const int y = (int)(r % oh);
+    const long long ni = r / oh;
+    const long long iw3 = 2LL * ow * 3;
+    const float* p = in + (ni * 2 * oh + 2 * y) * iw3 + 2LL * x * 3 + c;
+    out[idx] = ((p[0] + p[3]) + (p[iw3] + p[iw3 + 3])) * 0.25f;
+  }
+}
+
+// ---- warp: reproject's query, the bilinear sample, its derivative w.r.t. the clipped depth, validity ----------------------
+__global__ void __launch_bounds__(256)
+photo_warp_fwd_kernel(const float* __restrict__ depth, const float* __restrict__ rot, int rot_c, const float* __restrict__ trans,
+                      const float* __restrict__ cam_f, const float* __restrict__ cam_c, const float* __restrict__ prev, int h, int w,
+                      float* __restrict__ warped, float* __restrict__ dwarp, unsigned char* __restrict__ valid) {
+  const int bi = blockIdx.y;
+  const M4dMotion m = m4d_load_motion(rot, rot_c, trans, cam_f, cam_c, bi);
+  // combined_mat = diag(fx,fy,1) @ [R|t] as in reproject_flow_kernel (m4d_geometry.hip): the same sequential dot products
+  const float T[3][4] = {{m.r00, m.r01, m.r02, m.tx}, {m.r10, m.r11, m.r12, m.ty}, {m.r20, m.r21, m.r22, m.tz}};
+  const float P[3][3] = {{m.fx, 0.f, 0.f}, {0.f, m.fy, 0.f}, {0.f, 0.f, 1.f}};
+  float M[3][4];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float acc = P[r][0] * T[0][c];
+      acc = acc + P[r][1] * T[1][c];
+      acc = acc + P[r][2] * T[2][c];
+      M[r][c] = acc;
+    }
+  const int hw = h * w;
+  const float* img = prev + (long long)bi * hw * 3;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += gridDim.x * blockDim.x) {
+    const int i = p % w, j = p / w;
+    const long long o = (long long)bi * hw + p;
+    const float draw = depth[o];
+    const float d = fminf(fmaxf(draw, 0.01f), 200.0f);
+    const float mx = ((float)i + 0.5f) - m.cx;
+    const float my = ((float)j + 0.5f) - m.cy;
+    const float ux = mx / m.fx, uy = my / m.fy;
+    const float pos0 = ux * d, pos1 = uy * d, pos2 = 1.0f * d;
+    float pr[3], dpr[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      float acc = M[r][0] * pos0;
+      acc = acc + M[r][1] * pos1;
+      acc = acc + M[r][2] * pos2;
+      pr[r] = acc + M[r][3] * 1.0f;
+      dpr[r] = (M[r][0] * ux + M[r][1] * uy) + M[r][2];        // d pr[r] / d d
+    }
+    const float px = pr[0] / pr[2], py = pr[1] / pr[2];
+    const float qy = (float)j + (py - my);                     // dense_image_warp.py:244 on reproject's flow
+    const float qx = (float)i + (px - mx);
+    int y0, x0;
+    float ay, ax;
+    m4d_bilinear_axis(qy, h, y0, ay);
+    m4d_bilinear_axis(qx, w, x0, ax);
+    // an axis whose alpha was clamped carries no gradient (the gradient of clip outside its bounds; NaN: none)
+    const float ry = qy - (float)y0, rx = qx - (float)x0;
+    const bool gy_on = ry >= 0.0f && ry <= 1.0f, gx_on = rx >= 0.0f && rx <= 1.0f;
+    const float pz2 = pr[2] * pr[2];
+    const float dqx = (dpr[0] * pr[2] - pr[0] * dpr[2]) / pz2;
+    const float dqy = (dpr[1] * pr[2] - pr[1] * dpr[2]) / pz2;
+    const bool ok = pr[2] > 0.0f && qx >= 0.0f && qx <= (float)(w - 1) && qy >= 0.0f && qy <= (float)(h - 1) && isfinite(draw);
+    const float* s = img + ((long long)y0 * w + x0) * 3;
+    const long long rs = (long long)w * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float tl = s[c], tr = s[3 + c], bl = s[rs + c], br = s[rs + 3 + c];
+      warped[o * 3 + c] = m4d_lerp2(tl, tr, bl, br, ax, ay);
+      const float dwx = gx_on ? (1.0f - ay) * (tr - tl) + ay * (br - bl) : 0.0f;
+      const float dwy = gy_on ? (1.0f - ax) * (bl - tl) + ax * (br - tr) : 0.0f;
+      dwarp[o * 3 + c] = ok ? dwx * dqx + dwy * dqy : 0.0f;    // never read where invalid (no masked window holds the pixel)
+    }
+    valid[o] = ok ? 1 : 0;
+  }
+}
+
+// ---- shared pieces of the loss kernels -----------------------------------------------------------------------------------
+__device__ __forceinline__ float clip_depth(float d) { return fminf(fmaxf(d, 0.01f), 200.0f); }
+
+// window sums of one channel at LDS position `at` (row pitch S pixels, 3 floats per pixel)
+struct WinStats { double mx, my, n1, n2, d1, d2; };
+template <int S>
+__device__ __forceinline__ WinStats win_stats(const float* __restrict__ x, const float* __restrict__ y, int at, int c) {
+  double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int k = (at + dy * S + dx) * 3 + c;
+      const double a = (double)x[k], b = (double)y[k];
+      sx += a; sy += b; sxx += a * a; syy += b * b; sxy += a * b;
+    }
+  WinStats s;
+  s.mx = sx / 9.0; s.my = sy / 9.0;
+  const double vx = sxx / 9.0 - s.mx * s.mx, vy = syy / 9.0 - s.my * s.my, cxy = sxy / 9.0 - s.mx * s.my;
+  s.n1 = 2.0 * s.mx * s.my + kC1; s.n2 = 2.0 * cxy + kC2;
+  s.d1 = s.mx * s.mx + s.my * s.my + kC1; s.d2 = vx + vy + kC2;
+  return s;
+}
+
+template <int S>
+__device__ __forceinline__ double photo_error(const float* __restrict__ x, const float* __restrict__ y, int at) {
+  double pe = 0.0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const WinStats s = win_stats<S>(x, y, at, c);
+    const double ssim = (s.n1 * s.n2) / (s.d1 * s.d2);
+    pe += 0.85 * (1.0 - ssim) / 2.0 + 0.15 * fabs((double)x[at * 3 + c] - (double)y[at * 3 + c]);
+  }
+  return pe / 3.0;
+}
+
+__device__ __forceinline__ double edge_weight(const float* __restrict__ cur, int a, int b) {
+  const double d = (fabs((double)cur[b * 3] - (double)cur[a * 3]) + fabs((double)cur[b * 3 + 1] - (double)cur[a * 3 + 1]))
+                   + fabs((double)cur[b * 3 + 2] - (double)cur[a * 3 + 2]);
+  return exp(-(d / 3.0));
+}
+
+// ---- forward: per-pixel error, mask, block partials (sum M pe, N, sum smooth) ----------------------------------------------
+__global__ void __launch_bounds__(256)
+photo_loss_fwd_kernel(const float* __restrict__ depth, const float* __restrict__ warped, const unsigned char* __restrict__ valid,
+                      const float* __restrict__ cur, const float* __restrict__ prev, int h, int w, int automask,
+                      unsigned char* __restrict__ mask, double* __restrict__ partial) {
+  constexpr int HALO = 1, S = kTile + 2 * HALO;
+  __shared__ float s_w[S * S * 3], s_c[S * S * 3], s_p[S * S * 3];
+  __shared__ double s_ld[S * S];
+  __shared__ unsigned char s_v[S * S];
+  __shared__ double red[3][4];
+  const int bi = blockIdx.z, x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
+  const long long base = (long long)bi * h * w;
+  for (int k = threadIdx.x; k < S * S; k += 256) {
+    const int gy = y0 - HALO + k / S, gx = x0 - HALO + k % S;
+    const bool in = gy >= 0 && gy < h && gx >= 0 && gx < w;
+    const long long o = base + (long long)gy * w + gx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      s_w[k * 3 + c] = in ? warped[o * 3 + c] : 0.f;
+      s_c[k * 3 + c] = in ? cur[o * 3 + c] : 0.f;
+      s_p[k * 3 + c] = in ? prev[o * 3 + c] : 0.f;
+    }
+    s_v[k] = in ? valid[o] : 0;
+    s_ld[k] = in ? log((double)clip_depth(depth[o])) : 0.0;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x % kTile, ty = threadIdx.x / kTile;
+  const int gx = x0 + tx, gy = y0 + ty;
+  const int at = (ty + HALO) * S + (tx + HALO);
+  double s_pe = 0.0, s_n = 0.0, s_sm = 0.0;
+  if (gx < w && gy < h) {
+    bool on = gx >= 1 && gx <= w - 2 && gy >= 1 && gy <= h - 2;
+    if (on) {
+#pragma unroll
+      for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) on = on && s_v[at + dy * S + dx] != 0;
+    }
+    if (on) {
+      const double pe_w = photo_error<S>(s_w, s_c, at);
+      if (automask) on = pe_w < photo_error<S>(s_p, s_c, at);
+      if (on) { s_pe = pe_w; s_n = 1.0; }
+    }
+    mask[base + (long long)gy * w + gx] = on ? 1 : 0;
+    if (gx < w - 1) s_sm += fabs(s_ld[at + 1] - s_ld[at]) * edge_weight(s_c, at, at + 1);
+    if (gy < h - 1) s_sm += fabs(s_ld[at + S] - s_ld[at]) * edge_weight(s_c, at, at + S);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s_pe += __shfl_down(s_pe, o); s_n += __shfl_down(s_n, o); s_sm += __shfl_down(s_sm, o); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_pe; red[1][threadIdx.x >> 6] = s_n; red[2][threadIdx.x >> 6] = s_sm; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    partial[3 * blk + threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+  }
+}
+
+// one workgroup: lane t sums partials t, t + 256, ... in index order, then a fixed halving tree; out = (term, photo, smooth, N)
+__global__ void __launch_bounds__(256)
+photo_loss_finish_kernel(const double* __restrict__ partial, long long nblk, double pixels, float lambda, float* __restrict__ out) {
+  __shared__ double sh[3][256];
+  double s[3] = {0.0, 0.0, 0.0};
+  for (long long k = threadIdx.x; k < nblk; k += 256) { s[0] += partial[3 * k]; s[1] += partial[3 * k + 1]; s[2] += partial[3 * k + 2]; }
+  sh[0][threadIdx.x] = s[0]; sh[1][threadIdx.x] = s[1]; sh[2][threadIdx.x] = s[2];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off)
+      for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double n = sh[1][0];
+    const double photo = sh[0][0] / (n > 1.0 ? n : 1.0);
+    const double smooth = sh[2][0] / pixels;
+    out[0] = (float)(photo + (double)lambda * smooth);
+    out[1] = (float)photo;
+    out[2] = (float)smooth;
+    out[3] = (float)n;
+  }
+}
+
+// ---- backward: gather over the masked windows a pixel lies in ---------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+photo_loss_bwd_kernel(const float* __restrict__ depth, const float* __restrict__ warped, const float* __restrict__ dwarp,
+                      const float* __restrict__ cur, const unsigned char* __restrict__ mask, const float* __restrict__ out4,
+                      const float* __restrict__ g_out, int h, int w, float lambda, double pixels, float* __restrict__ g_depth) {
+  constexpr int HALO = 2, S = kTile + 2 * HALO, S1 = kTile + 2;
+  __shared__ float s_w[S * S * 3], s_c[S * S * 3];
+  __shared__ double s_ld[S * S];
+  __shared__ unsigned char s_m[S * S];
+  __shared__ double s_st[S1 * S1 * 3 * 6];         // (mu_x, mu_y, n1, n2, 1/d1, 1/d2) per channel of every window centre
+  const int bi = blockIdx.z, x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
+  const long long base = (long long)bi * h * w;
+  for (int k = threadIdx.x; k < S * S; k += 256) {
+    const int gy = y0 - HALO + k / S, gx = x0 - HALO + k % S;
+    const bool in = gy >= 0 && gy < h && gx >= 0 && gx < w;
+    const long long o = base + (long long)gy * w + gx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      s_w[k * 3 + c] = in ? warped[o * 3 + c] : 0.f;
+      s_c[k * 3 + c] = in ? cur[o * 3 + c] : 0.f;
+    }
+    s_m[k] = in ? mask[o] : 0;
+    s_ld[k] = in ? log((double)clip_depth(depth[o])) : 0.0;
+  }
+  __syncthreads();
+  // a masked pixel is interior, so its window lies inside the image and inside the 2-pixel halo
+  for (int k = threadIdx.x; k < S1 * S1; k += 256) {
+    const int at = (k / S1 + 1) * S + (k % S1 + 1);
+    if (s_m[at]) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const WinStats s = win_stats<S>(s_w, s_c, at, c);
+        double* st = s_st + (k * 3 + c) * 6;
+        st[0] = s.mx; st[1] = s.my; st[2] = s.n1; st[3] = s.n2; st[4] = 1.0 / s.d1; st[5] = 1.0 / s.d2;
+      }
+    }
+  }
+  __syncthreads();
+  const int tx = threadIdx.x % kTile, ty = threadIdx.x / kTile;
+  const int gx = x0 + tx, gy = y0 + ty;
+  if (gx >= w || gy >= h) return;
+  const int at = (ty + HALO) * S + (tx + HALO);
+  const long long o = base + (long long)gy * w + gx;
+  double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int p = at + dy * S + dx;
+      if (!s_m[p]) continue;
+      const int k = (ty + 1 + dy) * S1 + (tx + 1 + dx);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double* st = s_st + (k * 3 + c) * 6;
+        const double xq = (double)s_w[at * 3 + c], yq = (double)s_c[at * 3 + c];
+        const double inv = st[4] * st[5];
+        const double ssim = st[2] * st[3] * inv;
+        const double dssim = (2.0 / 9.0) * ((st[1] * st[3] + st[2] * (yq - st[1])) * inv
+                                            - ssim * (st[0] * st[4] + (xq - st[0]) * st[5]));
+        double d = -0.425 * dssim;
+        if (dy == 0 && dx == 0) {
+          const double e = xq - yq;
+          d += 0.15 * (e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0));
+        }
+        acc[c] += d;
+      }
+    }
+  const double n = (double)out4[3];
+  double g = ((acc[0] * (double)dwarp[o * 3] + acc[1] * (double)dwarp[o * 3 + 1]) + acc[2] * (double)dwarp[o * 3 + 2])
+             / (3.0 * (n > 1.0 ? n : 1.0));
+  // smoothness: the (up to) four differences the pixel's log depth enters
+  double sm = 0.0;
+  const double ld = s_ld[at];
+  if (gx < w - 1) { const double e = s_ld[at + 1] - ld; sm -= (e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0)) * edge_weight(s_c, at, at + 1); }
+  if (gx > 0)     { const double e = ld - s_ld[at - 1]; sm += (e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0)) * edge_weight(s_c, at - 1, at); }
+  if (gy < h - 1) { const double e = s_ld[at + S] - ld; sm -= (e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0)) * edge_weight(s_c, at, at + S); }
+  if (gy > 0)     { const double e = ld - s_ld[at - S]; sm += (e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0)) * edge_weight(s_c, at - S, at); }
+  const float draw = depth[o];
+  const bool inside = draw >= 0.01f && draw <= 200.0f;         // clip passes inside its bounds (m4d_loss_level_bwd)
+  g += (double)lambda * sm / (pixels * (double)clip_depth(draw));
+  g_depth[o] = inside ? (float)((double)g_out[0] * g) : 0.0f;
+}
+
+inline bool photo_dims_ok(int b, int h, int w) {
+  return b > 0 && h >= 3 && w >= 3 && (long long)b * h * w <= (1LL << 24);     // N travels as a float: exact up to 2^24
+}
+inline long long photo_blocks(int b, int h, int w) {
+  return (long long)b * ((h + kTile - 1) / kTile) * ((w + kTile - 1) / kTile);
+}
+
+}  // namespace
+
+extern "C" long long m4d_image_pyramid_floats(int n, int H, int W, int levels) {
+  if (n <= 0 || H <= 0 || W <= 0 || levels < 1 || levels > 16 || H % (1 << levels) != 0 || W % (1 << levels) != 0) return -1;
+  long long total = 0;
+  for (int i = 1; i <= levels; ++i) total += (long long)n * (H >> i) * (W >> i) * 3;
+  return total;
+}
+
+extern "C" int m4d_image_pyramid_box(const float* image, int n, int H, int W, int levels, float* out, void* stream) {
+  M4D_CHECK_ARG(image && out && m4d_image_pyramid_floats(n, H, W, levels) > 0);
+  const float* src = image;
+  float* dst = out;
+  for (int i = 1; i <= levels; ++i) {
+    const int oh = H >> i, ow = W >> i;
+    const long long total = (long long)n * oh * ow * 3;
+    long long g = (total + 255) / 256;
+    m4d_launch(pyramid_box_kernel, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, (hipStream_t)stream, src, oh, ow, total, dst);
+    src = dst;
+    dst += total;
+  }
+  return M4D_LAUNCH_RESULT();
+}
+
+extern "C" int m4d_photo_warp_fwd(const float* depth, const float* rot, int rot_c, const float* trans, const float* cam_f,
+                                  const float* cam_c, const float* prev, int b, int h, int w, float* warped, float* dwarp,
+                                  unsigned char* valid, void* stream) {
+  M4D_CHECK_ARG(depth && rot && trans && cam_f && cam_c && prev && warped && dwarp && valid);
+  M4D_CHECK_ARG(photo_dims_ok(b, h, w) && (rot_c == 3 || rot_c == 4));
+  int gx = m4d_blocks((long long)h * w, 256);
+  if (gx > 4096) gx = 4096;
+  m4d_launch(photo_warp_fwd_kernel, dim3(gx, b), dim3(256), 0, (hipStream_t)stream, depth, rot, rot_c, trans, cam_f, cam_c, prev,
+             h, w, warped, dwarp, valid);
+  return M4D_LAUNCH_RESULT();
+}
+
+extern "C" long long m4d_photo_workspace_bytes(int b, int h, int w) {
+  if (!photo_dims_ok(b, h, w)) return -1;
+  return photo_blocks(b, h, w) * 3 * (long long)sizeof(double);
+}
+
+extern "C" int m4d_photo_loss_fwd(const float* depth, const float* warped, const unsigned char* valid, const float* cur,
+                                  const float* prev, int b, int h, int w, float lambda, int automask, void* workspace,
+                                  float* out4, unsigned char* mask, void* stream) {
+  M4D_CHECK_ARG(depth && warped && valid && cur && prev && workspace && out4 && mask);
+  M4D_CHECK_ARG(photo_dims_ok(b, h, w) && (((uintptr_t)workspace) & 7u) == 0);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile, b);
+  m4d_launch(photo_loss_fwd_kernel, grid, dim3(256), 0, s, depth, warped, valid, cur, prev, h, w, automask, mask,
+             (double*)workspace);
+  m4d_launch(photo_loss_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, photo_blocks(b, h, w),
+             (double)b * h * w, lambda, out4);
+  return M4D_LAUNCH_RESULT();
+}
+
+extern "C" int m4d_photo_loss_bwd(const float* depth, const float* warped, const float* dwarp, const float* cur,
+                                  const unsigned char* mask, const float* out4, const float* g_out, int b, int h, int w,
+                                  float lambda, float* g_depth, void* stream) {
+  M4D_CHECK_ARG(depth && warped && dwarp && cur && mask && out4 && g_out && g_depth);
+  M4D_CHECK_ARG(photo_dims_ok(b, h, w));
+  const dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile, b);
+  m4d_launch(photo_loss_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, depth, warped, dwarp, cur, mask, out4, g_out, h, w,
+             lambda, (double)b * h * w, g_depth);
+  return M4D_LAUNCH_RESULT();
+}

@@ -308,13 +308,15 @@ class DataLoaderRecording(DataLoaderGeneric):
     cannot be scored, so every use case but predict -- and predict when ``require_depth`` is set (ground-truth panels) -- refuses
     a recording without depth.txt and leaves out the frames no depth file is associated with (``select_frames``): there every
     frame carries a map.  In a plain predict run ground truth is decoded where it exists; in a sequence batch that mixes
-    frames with and without it the latter get an all-zero map."""
+    frames with and without it the latter get an all-zero map.  ``allow_missing_depth`` (train only: the photometric loss needs
+    no ground truth) lifts the refusal for the 'train' use case in the same way: such frames get the all-zero map."""
 
     def __init__(self, stride=1, min_baseline=0.0, max_gap=0.5):
         super().__init__("recording")
         self.depth_type = "map"
         self.stride, self.min_baseline, self.max_gap = stride, min_baseline, max_gap
         self.require_depth = False                                  # predict: ground truth needed for every frame (gt / err panels)
+        self.allow_missing_depth = False                            # train: a recording without depth.txt is accepted
         self.recordings, self._tables = None, {}
 
     def _set_output_size(self, out_size=None):
@@ -335,6 +337,8 @@ class DataLoaderRecording(DataLoaderGeneric):
     def _get_trajectories(self):
         self.recordings = [read_recording(r) for r in find_recordings(self.records_path)]
         need_depth = self.usecase != "predict" or self.require_depth
+        if self.usecase == "train" and self.allow_missing_depth:
+            need_depth = False
         if need_depth:
             for rec in self.recordings:
                 if rec.depth is None:
@@ -413,7 +417,7 @@ class DataLoaderRecording(DataLoaderGeneric):
         any_depth = any(r["depth"] is not None for r in raws)
         all_depth = all(r["depth"] is not None for r in raws)
         dep_out = None
-        if any_depth:
+        if any_depth or (self.usecase == "train" and self.allow_missing_depth):      # a training batch always carries a map
             dep_out = (torch.empty if all_depth else torch.zeros)((T, oh, ow, 1), dtype=torch.float32, device=self.device)
         for ri, idx in groups.items():
             cam = self.recordings[ri].camera

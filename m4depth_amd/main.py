@@ -105,6 +105,15 @@ def build_parser():
                    help="--save_cloud: coordinates in the frame of the trajectory's first camera (world, the default; the "
                         "frame-to-frame motions are chained on the GPU) or of each frame's own camera")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
+    p.add_argument("--loss", default="supervised", choices=["supervised", "photometric"],
+                   help="train: supervised = the reference's log-depth L1 against ground truth; photometric = the reprojection "
+                        "loss between neighbouring frames (SSIM + L1, auto-masking, edge-aware smoothness), which needs poses "
+                        "but no ground-truth depth -- the way to finetune on a --dataset=recording without depth.txt")
+    p.add_argument("--photo_smooth", type=float, default=None,
+                   help="--loss=photometric: weight of the edge-aware smoothness term (default 1e-3, Monodepth2's value; not "
+                        "tuned for this network)")
+    p.add_argument("--no_photo_automask", action="store_true",
+                   help="--loss=photometric: keep the pixels whose unwarped previous frame already matches better (auto-masking off)")
     p.add_argument("--save_every", type=int, default=0, help="train: checkpoint every N steps (0 = at the end)")
     p.add_argument("--summary_interval", type=int, default=1200,
                    help="train --graph: read the device-side step log every N steps (m4depth_options.py:47-49); it is also "
@@ -120,7 +129,7 @@ def build_parser():
                    help="train: checkpoint at every epoch end and validate that checkpoint in-process (--mode=validation on "
                         "--val_dataset / --val_records_path, seq_len 4 / db_seq_len 4), keeping the best-N in <ckpt_dir>/best")
     p.add_argument("--val_records_path", default=None, help="--enable_validation: trajectory csv files of the validation set")
-    p.add_argument("--val_dataset", default="kitti-raw", choices=["midair", "tartanair", "kitti-raw"],
+    p.add_argument("--val_dataset", default="kitti-raw", choices=["midair", "tartanair", "kitti-raw", "recording"],
                    help="--enable_validation: the validation set's dataset")
     p.add_argument("--keep_top_n", type=int, default=1,
                    help="validation: how many best checkpoints <ckpt_dir>/best keeps (callbacks.py:173-240)")
@@ -208,6 +217,7 @@ def recording_loader(args):
     panels = getattr(args, "save_panels", None) or ()
     panels = panels.split(",") if isinstance(panels, str) else panels
     loader.require_depth = any(p in ("gt", "err") for p in panels)      # those panels need ground truth for every frame
+    loader.allow_missing_depth = getattr(args, "loss", "supervised") == "photometric"      # train: that loss reads no ground truth
     return loader
 
 
@@ -309,6 +319,11 @@ def default_epochs(args, rank, world, dev):
     return args.epochs, lambda epoch: dataset_batches(args, args.mode, rank, world, dev)[0]
 
 
+def format_step(step, loss, rmse=None):
+    """The line a reported training step prints; ``rmse`` None = the batch has no ground truth (nothing to score against)."""
+    return f"step {step}: loss {loss:.6f}" + ("" if rmse is None else f"  RMSE_log {rmse:.6f}")
+
+
 def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
     """``_train`` with the summary writer of ``--log_dir`` (rank 0; None without the option), closed on every way out."""
     summary = None
@@ -356,6 +371,12 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
                            capturable=args.graph)
     rmse_log = RootMeanSquaredLogError()
     model.compile(optimizer=opt, metrics=[rmse_log])
+    model.train_loss = getattr(args, "loss", "supervised")
+    model.photo_smooth = 1e-3 if getattr(args, "photo_smooth", None) is None else args.photo_smooth
+    model.photo_automask = not getattr(args, "no_photo_automask", False)
+    # a batch without ground truth (a recording without depth.txt under --loss=photometric): RMSE_log is a 0/0 masked mean,
+    # so it is neither printed nor logged, and the loss alone decides whether a step was bad
+    has_gt = args.dataset == "synthetic" or args.records_path is None or records_have_depth(args)
     ck = latest_checkpoint(args)
     step0 = 0
     if ck is not None:
@@ -381,9 +402,9 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
 
     def report(step, loss, rmse):
         if rank == 0:
-            print(f"step {step}: loss {loss:.6f}  RMSE_log {rmse:.6f}")
+            print(format_step(step, loss, rmse if has_gt else None))
         if summary is not None:
-            summary.scalars(step, loss, rmse)
+            summary.scalars(step, loss, rmse if has_gt else None)
 
     step_log = runner = geometry = None
     logged = [step0]                                  # graph mode: the last step whose log row the host has read
@@ -395,7 +416,8 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
         for i, (loss, rmse) in enumerate(rows):
             if first_bad >= 0 and i + logged[0] - step0 >= first_bad:
                 break                                 # the steps after the bad one are discarded
-            rmse_log._update(torch.tensor(rmse))
+            if has_gt:
+                rmse_log._update(torch.tensor(rmse))
             report(logged[0] + i + 1, float(loss), float(rmse_log.result()))
         logged[0] += len(rows)
         return step0 + first_bad + 1 if first_bad >= 0 else None
@@ -411,7 +433,8 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
                 if runner is None:
                     geometry = _geometry(data)
                     step_log = TR.TrainStepLog(max(args.summary_interval, 1) + 1, dev)
-                    runner = TR.GraphedTrainStep(model, data, opt, warmup=1, grad_sync=sync, step_log=step_log)
+                    runner = TR.GraphedTrainStep(model, data, opt, warmup=1, grad_sync=sync, step_log=step_log,
+                                                 loss=model.train_loss)
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
                 else:
@@ -421,7 +444,7 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
                 if (step - step0) % max(args.summary_interval, 1) == 0 or (args.save_every and step % args.save_every == 0):
                     nan_step = read_log()
                 if images_due(step):
-                    summary.images(step, runner.static, runner.pyramid, runner.camera)
+                    summary.images(step, runner.static, runner.pyramid, runner.camera, has_gt=has_gt)
             else:
                 out = model.train_step(data, grad_sync=sync)
                 step += 1
@@ -435,7 +458,7 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
                 else:
                     report(step, loss, float(out["RMSE_log"]))
                     if images_due(step):
-                        summary.images(step, data, model.last_pyramid, data["camera"])
+                        summary.images(step, data, model.last_pyramid, data["camera"], has_gt=has_gt)
             if nan_step is not None:
                 break
             if args.save_every and step % args.save_every == 0:
@@ -748,6 +771,29 @@ def check_train_args(parser, args, world=None):
             parser.error("--enable_validation needs --db_path_config (the validation set's dataset root)")
         if world > 1:
             parser.error("--enable_validation runs in-process on one GPU: it is refused with several ranks")
+    photo_opts = [f for f, on in (("photo_smooth", args.photo_smooth is not None), ("no_photo_automask", args.no_photo_automask)) if on]
+    if args.loss != "supervised" and args.mode != "train":
+        parser.error("--loss=%s is a --mode=train option" % args.loss)
+    if photo_opts and args.loss != "photometric":
+        parser.error("--%s needs --loss=photometric" % photo_opts[0])
+    if args.photo_smooth is not None and not args.photo_smooth >= 0:
+        parser.error("--photo_smooth must be >= 0")
+    if args.mode == "train" and args.loss == "supervised" and args.dataset == "recording" and args.records_path is not None:
+        try:
+            if not records_have_depth(args):
+                parser.error("--mode=train on a recording without depth.txt needs --loss=photometric (the supervised loss reads "
+                             "ground-truth depth)")
+        except ValueError:
+            pass                                   # a malformed --records_path: check_recording_args reports it
+    if args.enable_validation and args.val_dataset == "recording" and args.val_records_path is not None:
+        from . import dataloaders as dl
+        try:
+            scored = dl.get_loader("recording").has_depth(args.val_records_path)
+        except ValueError as e:
+            parser.error("--val_records_path %s" % e)
+        if not scored:
+            parser.error("--enable_validation: a recording of --val_records_path has no depth.txt -- validation scores against "
+                         "ground truth, which such a recording does not have")
     if args.graph and args.mode in ("train", "finetune") and world > 1:
         parser.error("--graph training is refused with several ranks (RCCL inside a captured training step is not supported)")
 

@@ -1399,11 +1399,13 @@ class M4Depth(torch.nn.Module):
 
     def train_step(self, data, grad_sync=None):
         """m4depth_network.py:371-431; needs ``compile(optimizer=...)`` and trainable parameters
-        (``training.set_trainable``)."""
+        (``training.set_trainable``).  ``self.train_loss`` (a per-model setting, default ``supervised``) names the loss:
+        ``photometric`` trains without ground-truth depth (``training.photometric_loss`` with ``self.photo_smooth`` and
+        ``self.photo_automask``)."""
         from . import training as TR
         if getattr(self, "optimizer", None) is None:
             raise RuntimeError("train_step: compile the model with an optimizer first")
-        return TR.train_step(self, data, self.optimizer, grad_sync)
+        return TR.train_step(self, data, self.optimizer, grad_sync, loss=getattr(self, "train_loss", "supervised"))
 
     def _update_metrics(self, gt_raw, est_raw, max_d=80.):
         """compiled_metrics.update_state on the clipped maps (:465-470).  With the default

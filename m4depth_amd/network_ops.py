@@ -1239,3 +1239,86 @@ def stream_prepare(new_traj, force_all, rot, trans):
                                  dptr(tr, "trans"), b, dptr(reset, "reset", torch.uint8), dptr(rot_out), dptr(tr_out), stream_ptr()),
           "m4d_stream_prepare")
     return reset, rot_out, tr_out
+
+
+# ---- photometric reprojection loss (csrc/m4d_photo.hip; the definition: include/m4depth_hip.h) ------------------------------
+def image_pyramid_box(images, levels):
+    """The image pyramid of the photometric loss (m4d_image_pyramid_box): ``images`` [n,H,W,3] in [0,1] -> list of ``levels``
+    maps, level i = [n, H >> (i+1), W >> (i+1), 3], each the 2x2 mean of the one before -- views of one buffer, one call."""
+    images = as_f32(images, "images")
+    if images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError(f"images: expected [n,H,W,3], got {tuple(images.shape)}")
+    n, H, W, _ = images.shape
+    total = int(lib.m4d_image_pyramid_floats(n, H, W, int(levels)))
+    if total < 0:
+        raise ValueError(f"image_pyramid_box: {H}x{W} is no multiple of 2^{levels}")
+    buf = torch.empty(total, dtype=torch.float32, device=images.device)
+    check(lib.m4d_image_pyramid_box(dptr(images, "images"), n, H, W, int(levels), dptr(buf), stream_ptr()), "m4d_image_pyramid_box")
+    out, off = [], 0
+    for i in range(1, int(levels) + 1):
+        h, w = H >> i, W >> i
+        out.append(buf[off:off + n * h * w * 3].view(n, h, w, 3))
+        off += n * h * w * 3
+    return out
+
+
+def _photo_motion(depth, rot, trans, f, c):
+    depth = as_f32(depth, "depth")
+    if depth.dim() != 4 or depth.shape[3] != 1:
+        raise ValueError(f"depth: expected [b,h,w,1], got {tuple(depth.shape)}")
+    b = depth.shape[0]
+    rot = as_f32(rot, "rot")
+    if rot.dim() != 2 or rot.shape[0] != b or rot.shape[1] not in (3, 4):
+        raise ValueError('Rotation must be expressed as a small angle (x,y,z) or a quaternion (w,x,y,z)')
+    return depth, rot, as_f32(trans, "trans").reshape(b, 3), as_f32(f, "f").reshape(b, 2), as_f32(c, "c").reshape(b, 2)
+
+
+def _photo_image(img, name, b, h, w):
+    img = as_f32(img, name)
+    if tuple(img.shape) != (b, h, w, 3):
+        raise ValueError(f"{name}: expected {(b, h, w, 3)}, got {tuple(img.shape)}")
+    return img
+
+
+def photo_warp_fwd(depth, rot, trans, f, c, prev):
+    """m4d_photo_warp_fwd: (warped [b,h,w,3] = reproject(prev, clip(depth), ...)[0] bit for bit, dwarp [b,h,w,3] = d warped /
+    d clip(depth), valid [b,h,w,1] uint8); ``f`` / ``c`` are the per-sample level cameras [b,2]."""
+    depth, rot, trans, f, c = _photo_motion(depth, rot, trans, f, c)
+    b, h, w, _ = depth.shape
+    prev = _photo_image(prev, "prev", b, h, w)
+    warped = torch.empty_like(prev)
+    dwarp = torch.empty_like(prev)
+    valid = torch.empty((b, h, w, 1), dtype=torch.uint8, device=depth.device)
+    check(lib.m4d_photo_warp_fwd(dptr(depth, "depth"), dptr(rot, "rot"), rot.shape[1], dptr(trans), dptr(f), dptr(c), dptr(prev), b, h, w,
+                                 dptr(warped), dptr(dwarp), dptr(valid, "valid", torch.uint8), stream_ptr()), "m4d_photo_warp_fwd")
+    return warped, dwarp, valid
+
+
+def photo_loss_fwd(depth, warped, valid, cur, prev, smooth, automask):
+    """m4d_photo_loss_fwd: (out4 = (term, photo, smooth, N) float32 [4], mask [b,h,w,1] uint8)."""
+    depth = as_f32(depth, "depth")
+    b, h, w, _ = depth.shape
+    warped, cur, prev = (_photo_image(t, n, b, h, w) for t, n in ((warped, "warped"), (cur, "cur"), (prev, "prev")))
+    nbytes = int(lib.m4d_photo_workspace_bytes(b, h, w))
+    if nbytes < 0:
+        raise ValueError(f"photometric loss: a {b}x{h}x{w} map is refused (h, w >= 3 and b*h*w <= 2^24)")
+    ws = _workspace("photo", nbytes + 8, depth.device)
+    ws_ptr = ctypes.c_void_p((ws.data_ptr() + 7) // 8 * 8)
+    out4 = torch.empty(4, dtype=torch.float32, device=depth.device)
+    mask = torch.empty((b, h, w, 1), dtype=torch.uint8, device=depth.device)
+    check(lib.m4d_photo_loss_fwd(dptr(depth, "depth"), dptr(warped), dptr(valid, "valid", torch.uint8), dptr(cur), dptr(prev), b, h, w,
+                                 float(smooth), int(bool(automask)), ws_ptr, dptr(out4), dptr(mask, "mask", torch.uint8), stream_ptr()),
+          "m4d_photo_loss_fwd")
+    return out4, mask
+
+
+def photo_loss_bwd(depth, warped, dwarp, cur, mask, out4, g_out, smooth):
+    """m4d_photo_loss_bwd: g_depth [b,h,w,1] from the scalar gradient ``g_out`` (device, [1]) with the forward's mask and out4."""
+    depth = as_f32(depth, "depth")
+    b, h, w, _ = depth.shape
+    warped, dwarp, cur = (_photo_image(t, n, b, h, w) for t, n in ((warped, "warped"), (dwarp, "dwarp"), (cur, "cur")))
+    g_depth = torch.empty_like(depth)
+    check(lib.m4d_photo_loss_bwd(dptr(depth, "depth"), dptr(warped), dptr(dwarp), dptr(cur), dptr(mask, "mask", torch.uint8),
+                                 dptr(out4, "out4"), dptr(as_f32(g_out, "g_out").reshape(1)), b, h, w, float(smooth), dptr(g_depth),
+                                 stream_ptr()), "m4d_photo_loss_bwd")
+    return g_depth

@@ -245,27 +245,36 @@ class TrainSummaryWriter:
                 if ready is not None:
                     self.events.add_record(ready)
 
-    def scalars(self, step, loss, rmse_log):
-        self._emit(self._ticket(), encode_event(time.time(), step=int(step), values=[scalar_value("loss", loss),
-                                                                                      scalar_value("RMSE_log", rmse_log)]))
+    def scalars(self, step, loss, rmse_log=None):
+        """``rmse_log`` None: the batch has no ground truth, only the loss is written."""
+        values = [scalar_value("loss", loss)] + ([] if rmse_log is None else [scalar_value("RMSE_log", rmse_log)])
+        self._emit(self._ticket(), encode_event(time.time(), step=int(step), values=values))
 
     # -- the device side: replaced by stand-ins in the host tests
     def _make_slot(self, nbytes, dev):
         return _Slot(nbytes, dev)
 
     @staticmethod
-    def _geometry(data, pyramid):
-        """(tags, [(h, w, c), ...]) of the step's maps."""
+    def _geometry(data, pyramid, has_gt=True):
+        """(tags, [(h, w, c), ...]) of the step's maps; without ground truth the two images made of it are left out."""
         H, W = data["RGB_im"].shape[2:4]
-        tags = ["RGB_im", "camera_prev_t_reproj", "depth_gt"] + [f"depth_lvl_{i}" for i in range(len(pyramid))]
-        return tags, [(H, W, 3), (H, W, 3), (H, W, 1)] + [tuple(p.shape[1:]) for p in pyramid]
+        gt_tags, gt_shapes = (["camera_prev_t_reproj", "depth_gt"], [(H, W, 3), (H, W, 1)]) if has_gt else ([], [])
+        tags = ["RGB_im"] + gt_tags + [f"depth_lvl_{i}" for i in range(len(pyramid))]
+        return tags, [(H, W, 3)] + gt_shapes + [tuple(p.shape[1:]) for p in pyramid]
 
-    def _render(self, slot, data, pyramid, camera, n):
+    def _render(self, slot, data, pyramid, camera, n, has_gt=True):
         """Enqueues the step's images into ``slot`` on the current stream and records its event; returns the host views
         [n,h,w,c] uint8 of the maps, valid once the event has completed."""
         from . import network_ops as nops
         from .depth_operations import reproject
         rgb, depth = data["RGB_im"], data["depth"]
+        if not has_gt:
+            maps = [rgb[:, -1]] + list(pyramid)
+            nops.summary_images(maps, ["unit"] + ["log_depth"] * len(pyramid), n, out=slot.dev)
+            slot.host.copy_(slot.dev, non_blocking=True)
+            slot.event.record()
+            offsets, _ = nops.summary_layout([tuple(m.shape[1:]) for m in maps], n)
+            return [slot.host[o:o + n * m[0].numel()].view(n, *m.shape[1:]) for o, m in zip(offsets, maps)]
         reproj, _ = reproject(rgb[:n, -2], depth[:n, -1], data["rot"][:n, -1], data["trans"][:n, -1],
                               {k: v[:n] for k, v in camera.items()})                 # m4depth_network.py:405-406
         maps = [rgb[:, -1], reproj, depth[:, -1]] + list(pyramid)
@@ -275,14 +284,15 @@ class TrainSummaryWriter:
         offsets, _ = nops.summary_layout([tuple(m.shape[1:]) for m in maps], n)
         return [slot.host[o:o + n * m[0].numel()].view(n, *m.shape[1:]) for o, m in zip(offsets, maps)]
 
-    def images(self, step, data, pyramid, camera):
+    def images(self, step, data, pyramid, camera, has_gt=True):
         """``data``: the step's [b,T,...] device batch (``RGB_im``, ``depth``, ``rot``, ``trans``), T >= 2; ``pyramid``: the last
-        frame's depth estimates [b,h_i,w_i,1], finest first; ``camera``: {'f', 'c'} [b,2]."""
+        frame's depth estimates [b,h_i,w_i,1], finest first; ``camera``: {'f', 'c'} [b,2].  ``has_gt`` False (a batch without
+        ground truth): ``RGB_im`` and ``depth_lvl_i`` only -- ``camera_prev_t_reproj`` and ``depth_gt`` are made of it."""
         shape = tuple(data["RGB_im"].shape)
         if len(shape) != 5 or shape[1] < 2 or not 1 <= len(pyramid) <= 13:
             raise ValueError(f"images: expected a [b,T>=2,H,W,3] batch and 1..13 levels, got RGB_im {shape}, {len(pyramid)} levels")
         n = min(self.max_outputs, shape[0])
-        tags, shapes = self._geometry(data, pyramid)
+        tags, shapes = self._geometry(data, pyramid, has_gt)
         if self._slots is None:
             from .network_ops import summary_layout
             nbytes = summary_layout(shapes, n)[1]
@@ -295,7 +305,8 @@ class TrainSummaryWriter:
         ticket = self._ticket()
         index = self._free.get()                           # back-pressure: waits while every slot is in flight
         try:
-            views = self._render(self._slots[index], data, pyramid, camera, n)
+            # (the sixth argument only when it is not the default: stand-ins of _render keep the five-argument form)
+            views = self._render(self._slots[index], data, pyramid, camera, n, *(() if has_gt else (False,)))
         except BaseException:
             self._free.put(index)
             self._emit(ticket, None)

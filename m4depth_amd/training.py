@@ -243,6 +243,25 @@ class _LevelL1(torch.autograd.Function):
         return g_pred, None, None
 
 
+class _LevelPhoto(torch.autograd.Function):
+    """One level's unweighted term of the photometric reprojection loss (include/m4depth_hip.h, "Photometric reprojection
+    loss"): photo + smooth * smoothness of the predicted depth of frame t against the level images of frames t and t-1.
+    The images are data; the gradient goes through the warp into the depth (m4d_photo_loss_bwd, a gather)."""
+
+    @staticmethod
+    def forward(ctx, depth, rot, trans, f, c, cur, prev, smooth, automask):
+        warped, dwarp, valid = nops.photo_warp_fwd(depth, rot, trans, f, c, prev)
+        out4, mask = nops.photo_loss_fwd(depth, warped, valid, cur, prev, smooth, automask)
+        ctx.save_for_backward(depth, warped, dwarp, cur, mask, out4)
+        ctx.smooth = smooth
+        return out4[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        depth, warped, dwarp, cur, mask, out4 = ctx.saved_tensors
+        return (nops.photo_loss_bwd(depth, warped, dwarp, cur, mask, out4, g, ctx.smooth),) + (None,) * 8
+
+
 def level_forward_train(level, curr_f_maps, prev_l_est, rot, trans, camera, prev_f_maps, prev_t_depth, cache):
     """DepthEstimatorLevel.call with is_training=True (m4depth_network.py:167-262)."""
     b, h, w, c = curr_f_maps.shape
@@ -357,6 +376,44 @@ def m4depth_loss(gts, preds, depth_type="map"):
     return l1_loss
 
 
+LOSSES = ("supervised", "photometric")
+
+
+def photometric_loss(samples, preds, camera, smooth=1e-3, automask=True):
+    """Training without ground-truth depth: the photometric reprojection loss (SSIM + L1 error between frame t and frame t-1
+    warped with the PREDICTED depth and the data's exact relative pose, validity mask, auto-masking, edge-aware smoothness:
+    Godard et al., ICCV 2019; the definition is in include/m4depth_hip.h).  One term per level of every frame but the first,
+    with the level weights of ``m4depth_loss``.  ``samples[t]`` = {"RGB_im" [b,H,W,3] in [0,1], "rot", "trans"}, ``preds`` as
+    ``model_forward_train`` returns them, ``camera`` the full-resolution intrinsics.  The image pyramid of every frame is built
+    once, by one call."""
+    T = len(samples)
+    L = len(preds[-1])
+    b = samples[0]["RGB_im"].shape[0]
+    frames = torch.stack([as_f32(s["RGB_im"], "RGB_im") for s in samples], dim=0)               # [T,b,H,W,3]
+    with torch.no_grad():
+        pyr = [lvl.view(T, b, *lvl.shape[1:]) for lvl in nops.image_pyramid_box(frames.view(T * b, *frames.shape[2:]), L)]
+    f, c = as_f32(camera["f"], "f").reshape(b, 2), as_f32(camera["c"], "c").reshape(b, 2)
+    cams = [(f / 2. ** (i + 1), c / 2. ** (i + 1)) for i in range(L)]
+    loss = 0.
+    for t in range(1, T):
+        rot, trans = as_f32(samples[t]["rot"], "rot"), as_f32(samples[t]["trans"], "trans").reshape(b, 3)
+        for i, pred in enumerate(preds[t]):
+            term = _LevelPhoto.apply(as_f32(pred["depth"], "pred depth"), rot, trans, cams[i][0], cams[i][1], pyr[i][t], pyr[i][t - 1],
+                                     float(smooth), bool(automask))
+            loss = loss + term * ((0.64 / (2. ** (i - 1))) / float(T - 1))
+    return loss
+
+
+def _loss_of(model, loss, gts, samples, preds, camera):
+    """The training loss ``loss`` names: ``supervised`` = m4depth_loss against ground truth, ``photometric`` = photometric_loss
+    (its two settings are per-model: ``model.photo_smooth``, ``model.photo_automask``)."""
+    if loss == "supervised":
+        return m4depth_loss(gts, preds, model.depth_type)
+    if loss == "photometric":
+        return photometric_loss(samples, preds, camera, getattr(model, "photo_smooth", 1e-3), getattr(model, "photo_automask", True))
+    raise ValueError(f"loss: expected one of {LOSSES}, got {loss!r}")
+
+
 def unstack_sequence(data):
     """The sample re-arrangement at the top of train_step / test_step (m4depth_network.py:377-385)."""
     T = data["depth"].shape[1]
@@ -375,19 +432,23 @@ def set_trainable(model, flag=True):
     return model
 
 
-def train_step(model, data, optimizer, grad_sync=None):
+def train_step(model, data, optimizer, grad_sync=None, loss="supervised"):
     """M4Depth.train_step (m4depth_network.py:371-431): loss, gradients, optimizer update, metrics
     of the last frame.  ``data`` holds [b,T,...] device tensors (+ data['camera']).  ``grad_sync``
     (optional) runs between backward and the update -- dist.all_reduce_gradients for data-parallel
-    training over RCCL."""
+    training over RCCL.  ``loss``: ``supervised`` (m4depth_loss, the reference's) or ``photometric`` (photometric_loss: the
+    ground truth is then read by the metric only)."""
     from .metrics import RootMeanSquaredLogError
+    if loss not in LOSSES:
+        raise ValueError(f"loss: expected one of {LOSSES}, got {loss!r}")
+    loss_name = loss
     traj_samples = unstack_sequence(data)
     with torch.no_grad():
         gts = [{"depth": s["depth"], "parallax": depth2parallax(s["depth"], s["rot"], s["trans"], data["camera"])}
                for s in traj_samples]
     with torch.enable_grad():
         preds = model_forward_train(model, traj_samples, data["camera"])
-        loss = m4depth_loss(gts, preds, model.depth_type)
+        loss = _loss_of(model, loss_name, gts, traj_samples, preds, data["camera"])
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     if grad_sync is not None:
@@ -421,6 +482,9 @@ class GraphedTrainStep:
     ``pyramid``: the last frame's depth estimate of every level, finest first (``est is pyramid[0]``), static tensors of the
     capture like ``loss`` -- what ``summaries.TrainSummaryWriter.images`` draws as ``depth_lvl_i``.
 
+    ``loss``: as in ``train_step``; the photometric loss's pyramid and loss launches are nodes of the capture like the rest (no
+    host synchronisation: the mask count N stays on the device).
+
     ``step_log`` (optional, a ``TrainStepLog``): every step, the warm-up steps included, ends with its device-side log
     entry, so the host reads losses and metrics only when it wants to.
 
@@ -429,7 +493,10 @@ class GraphedTrainStep:
     host-side control flow baked into the capture).  The eager warm-up steps (packed-weight and
     workspace allocation) are REAL optimizer steps on ``example``."""
 
-    def __init__(self, model, example, optimizer, warmup=3, grad_sync=None, step_log=None):
+    def __init__(self, model, example, optimizer, warmup=3, grad_sync=None, step_log=None, loss="supervised"):
+        if loss not in LOSSES:
+            raise ValueError(f"loss: expected one of {LOSSES}, got {loss!r}")
+        self.loss_name = loss
         self.model, self.optimizer = model, optimizer
         self.step_log = step_log
         self.static = {k: example[k].clone() for k in ("depth", "RGB_im", "rot", "trans")}
@@ -466,7 +533,7 @@ class GraphedTrainStep:
         samples = unstack_sequence(data)
         gts = [{"depth": s["depth"]} for s in samples]
         preds = model_forward_train(self.model, samples, self.camera)
-        loss = m4depth_loss(gts, preds, self.model.depth_type)
+        loss = _loss_of(self.model, self.loss_name, gts, samples, preds, self.camera)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         if self.grad_sync is not None:
