@@ -324,6 +324,10 @@ def format_step(step, loss, rmse=None):
     return f"step {step}: loss {loss:.6f}" + ("" if rmse is None else f"  RMSE_log {rmse:.6f}")
 
 
+class _NonFiniteParameters(Exception):
+    """Raised where a checkpoint would be written from non-finite parameters; carries the step."""
+
+
 def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
     """``_train`` with the summary writer of ``--log_dir`` (rank 0; None without the option), closed on every way out."""
     summary = None
@@ -332,6 +336,9 @@ def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
         summary = TrainSummaryWriter(args.log_dir)
     try:
         return _train(args, ablation, rank, world, dev, epochs, depth_type, summary)
+    except _NonFiniteParameters as e:
+        print(f"step {e.args[0]}: non-finite parameters, training stopped: no checkpoint of this state is written")
+        return 1
     finally:
         if summary is not None:
             summary.close()
@@ -349,6 +356,7 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
 
     TerminateOnNaN (callbacks.py:69-132): a non-finite loss ends training with status 1; nothing of that epoch is saved (in
     graph mode the steps replayed after the bad one are discarded with it) and the checkpoints on disk stay as they are.
+    Non-finite parameters behind a finite loss are caught where a checkpoint is due (``save``): status 1, nothing written.
 
     ``summary`` (a ``summaries.TrainSummaryWriter``): every reported step's loss and RMSE_log go to it as they are printed, and
     at every step where ``(step - step0) % summary_interval == 0`` the step's images -- in graph mode right after that step's
@@ -386,9 +394,17 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
             opt.load_state_dict(torch.load(opt_path, map_location=dev))
             _set_capturable(opt, args.graph, dev)
     sync = D.all_reduce_gradients if world > 1 else None
-    saved = set()
+    saved, checked = set(), set()
 
     def save(step):
+        # A step whose gradients are non-finite while its loss is finite (a stationary sample: DESIGN.md "Degenerate inputs",
+        # R6) leaves non-finite weights behind that TerminateOnNaN only sees one step later: look at the parameters where they
+        # are written -- once per save, reduced on the device, one host read, on every rank (the replicas hold the same
+        # weights, so all ranks stop together) -- never in the step itself.
+        if step not in checked:
+            checked.add(step)
+            if not bool(torch.stack([torch.isfinite(p.detach()).all() for p in model.parameters()]).all()):
+                raise _NonFiniteParameters(step)
         if rank != 0 or step in saved:
             return None
         saved.add(step)

@@ -4,7 +4,9 @@ The reference differentiates its Python/TensorFlow graph with ``tf.GradientTape`
 (train_step, m4depth_network.py:371-399).  TensorFlow cannot run here (PARITY UNPINNED,
 see m4depth_oracle.py), so this module restates the same graph op for op with
 torch **CPU** tensors and lets torch's autodiff play the role of TF's: gathers become
-scatter-adds, ``floor`` has no gradient, ``clip_by_value`` passes inside its bounds, the
+scatter-adds, ``floor`` has no gradient, ``clip_by_value`` passes inside its bounds (``_clip``:
+the rules R1, R2 and R5 of DESIGN.md "Degenerate inputs", so the graph can be evaluated and
+differentiated on a stationary camera, an epipole pixel or NaN features), the
 float16 product / mean of the DSCV (utils/depth_operations.py:276-277) are differentiated in
 float16, ``prev_d2para`` ends in ``stop_gradient`` (:215).  The forward values are checked
 against the strict-float32 numpy oracle in tests/test_oracle_train.py.
@@ -24,6 +26,39 @@ REFINER_CHANNELS = [128, 128, 96, 64, 32, 16, 5]       # m4depth_network.py:103,
 
 def _t(x, dtype=torch.float32):
     return x.to(dtype) if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=dtype)
+
+
+# --------------------------------------------------------------------------
+# the clamps of DESIGN.md "Degenerate inputs" (R1, R2 forward; R5 backward)
+# --------------------------------------------------------------------------
+class _Clip(torch.autograd.Function):
+    """tf.clip_by_value as the rules state it.  Forward: min(max(x, lo), hi) with the NaN-DROPPING pair (fmax / fmin, what
+    fmaxf / fminf do on the device): a NaN becomes ``lo`` (R1, R2).  Backward: a SELECT -- the incoming gradient inside
+    [lo, hi], exactly 0 outside whatever arrives, a NaN input counting as outside (R5).  torch.fmax / torch.fmin would multiply
+    the gradient by a 0/1 mask (0 * NaN = NaN), which is not the rule.  On inputs without NaN this is torch.clamp, bit for bit,
+    forward and backward."""
+
+    @staticmethod
+    def forward(ctx, x, lo, hi):
+        ctx.save_for_backward(x)
+        ctx.lo, ctx.hi = lo, hi
+        return torch.fmin(torch.fmax(x, torch.tensor(lo, dtype=x.dtype)), torch.tensor(hi, dtype=x.dtype))
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        return torch.where((x >= ctx.lo) & (x <= ctx.hi), g, torch.zeros((), dtype=g.dtype)), None, None
+
+
+def _clip(x, lo, hi):
+    return _Clip.apply(x, float(lo), float(hi))
+
+
+def _floor_index(q, size):
+    """min(max(0, floor(q)), size - 2) of dense_image_warp.py:138-141 as a float, NaN-dropping (R1: a NaN query gives index 0,
+    +-Inf the last / first cell); floor has no gradient (R6)."""
+    fl = torch.fmin(torch.fmax(torch.zeros((), dtype=q.dtype), torch.floor(q)), torch.tensor(float(size - 2), dtype=q.dtype))
+    return fl.detach()
 
 
 # --------------------------------------------------------------------------
@@ -114,13 +149,11 @@ def interpolate_bilinear(grid, query):
     alphas, floors, ceils = [], [], []
     for dim, size in ((0, H), (1, W)):
         q = query[..., dim]
-        fl = torch.minimum(torch.maximum(torch.zeros((), dtype=q.dtype), torch.floor(q)),
-                           torch.tensor(float(size - 2), dtype=q.dtype))         # :138-141 (floor: no gradient)
-        fl = fl.detach()
+        fl = _floor_index(q, size)                                                # :138-141 (floor: no gradient)
         i0 = fl.to(torch.int64)
         floors.append(i0)
         ceils.append(i0 + 1)
-        alphas.append(torch.clamp(q - fl, 0.0, 1.0).unsqueeze(-1))              # :147-154
+        alphas.append(_clip(q - fl, 0.0, 1.0).unsqueeze(-1))                    # :147-154
     flat = grid.reshape(B, H * W, C)
 
     def gather(yc, xc):
@@ -153,7 +186,7 @@ def get_parallax_sweeping_cv(c1, c2, disp_prev_t, disp, rot, trans, camera, sear
     cvs = [[None] * ncp for _ in range(k)]
     prev = []
     for t in range(ncp):
-        p = torch.clamp(disp[..., 0] + float(t - r), 1e-6, 1e6)                  # :235-236
+        p = _clip(disp[..., 0] + float(t - r), 1e-6, 1e6)                        # :235-236
         divider = m["sqrt"] / p                                                  # :262
         dxx = m["delta_x"] / divider
         dyy = m["delta_y"] / divider
@@ -317,7 +350,7 @@ def level_train(weights, lvl_depth, curr_f_maps, prev_l_est, rot, trans, camera,
     f_input = torch.cat(feats, dim=3)
     out = disp_refiner(f_input, weights, lvl_depth)
     para, other = out[..., :1], out[..., 1:]
-    para_curr = torch.exp(torch.clamp(para, -7., 7.)) / scale                    # :250
+    para_curr = torch.exp(_clip(para, -7., 7.)) / scale                          # :250
     depth = parallax2depth(para_curr, rot, trans, camera)
     return {"other": other, "depth": depth, "parallax": para_curr}
 
@@ -353,7 +386,7 @@ def model_train(weights, traj_samples, camera, nbre_levels, ablation=None, dscv_
 def m4depth_loss(gts, preds, depth_type="map"):
     """M4Depth.m4depth_loss, m4depth_network.py:491-536."""
     def preprocess(x):
-        return torch.log(torch.clamp(x, 0.01, 200.))
+        return torch.log(_clip(x, 0.01, 200.))
 
     def masked_reduce_mean(array, mask, dims=None):
         if dims is None:

@@ -15,6 +15,13 @@ changes another sample's bits) is checked by the same comparison -- on one of th
                   -10 so that hypotheses sit on both clamps of         underflows to 0, so s = 0 and delta / (s / p) = +-Inf
                   clip(disp + n, 1e-6, 1e6): queries 1e6 pixels away   on every pixel
   "prev_d2para"   moving; depth_prev_t == tz on planted pixels: prev_d2para's denominator is 0 there (both samples)
+
+Backward only (BACKWARD_CASES = CASES + these; the forward tests keep their table):
+  "clamped_corner" identity rotation, motion up and to the left (tz = 0): every hypothesis of pixel (0, 0) leaves the map over
+                  BOTH edges, so both alphas are clamped and the query gradient is selected to 0 (R5) -- while the four cells
+                  it reads hold a NaN feature cut (sample 0: cut 0 of f2[0, 0, 0] is all zero) or an infinite warped parallax
+                  (sample 1: depth_prev_t[1, 0, 0] == tz).  The alpha gradients are NaN / Inf there, g_disp is exactly 0: the
+                  one place where a clamp gradient written as a PRODUCT with a 0/1 mask gives another answer (NaN).
 """
 from collections import namedtuple
 
@@ -54,8 +61,12 @@ def case_id(c):
     return f"{c.kind}-{c.geom}"
 
 
+BACKWARD_ONLY_KINDS = ("clamped_corner",)
+BACKWARD_CASES = CASES + [Case("clamped_corner", "13x21"), Case("clamped_corner", "37x45")]
+
+
 def _seed(case):
-    return 7000 + 100 * KINDS.index(case.kind) + sorted(GEOMS).index(case.geom)
+    return 7000 + 100 * (KINDS + BACKWARD_ONLY_KINDS).index(case.kind) + sorted(GEOMS).index(case.geom)
 
 
 def far_plant(h, w):
@@ -110,6 +121,11 @@ def make(case):
     elif case.kind == "prev_d2para":
         for (j, i) in d2para_plant(h, w):
             depth_prev_t[:, j, i, 0] = trans[:, 2]
+    elif case.kind == "clamped_corner":
+        rot = np.tile(np.array([[1.0, 0.0, 0.0, 0.0]], F), [B, 1])
+        trans = np.array([[-0.3, -0.2, 0.0], [-0.25, -0.35, 0.0]], F)
+        f2[0, 0, 0, :nc] = 0.0
+        depth_prev_t[1, 0, 0, 0] = trans[1, 2]
     else:
         raise ValueError(case.kind)
     return dict(f1=f1, f2=f2, disp=disp, depth_prev_t=depth_prev_t, rot=rot, trans=trans, cam=cam, h=h, w=w, C=C, k=k)
@@ -187,6 +203,96 @@ def reference(case):
     r["inputs"] = d
     _REFERENCE[case] = r
     return r
+
+
+# ---- the backward on the same cases (rules R5, R6): fixed upstream gradients and autodiff of the rule-bearing restatement
+BACKWARD_TENSORS = ("dscv_g_c1", "dscv_g_c2", "dscv_g_disp_prev_t", "dscv_g_disp", "sncv_auto_g_c1", "sncv_g_c1", "sncv_g_c2", "norm_g_f1")
+# the tensors whose graph has no float16 step: their non-finite masks are the same in float32 and float64
+NO_HALF_TENSORS = ("dscv_g_disp_prev_t", "sncv_auto_g_c1", "sncv_g_c1", "sncv_g_c2", "norm_g_f1")
+
+
+def backward_upstream(case):
+    """The upstream gradients of a case (finite, drawn once per case): of cv, of the warped parallax, of the SNCV output and of
+    the normalised features."""
+    g = GEOMS[case.geom]
+    rng = np.random.default_rng(50000 + _seed(case))
+    ncp, mo2 = 2 * DSCV_RANGE + 1, (2 * SNCV_RANGE + 1) ** 2
+    return dict(g_cv=rng.standard_normal([B, g.h, g.w, g.k * ncp]).astype(F),
+                g_prev_disp=rng.standard_normal([B, g.h, g.w, ncp]).astype(F),
+                g_sncv=rng.standard_normal([B, g.h, g.w, mo2 * g.k]).astype(F),
+                g_feat=rng.standard_normal([B, g.h, g.w, g.C]).astype(F))
+
+
+_BACKWARD = {}
+
+
+def backward_reference(case, double=False):
+    """Autodiff of oracle/m4depth_oracle_train.py on ``case``, evaluated once per process and shared read-only: the gradients
+    BACKWARD_TENSORS and the forward outputs (cv, prev_disp, sncv_auto, sncv, c1n) they were taken through.  The cost volumes
+    take the numpy oracle's normalised features and prev_d2para as their leaves (what the kernels are handed); the normalisation
+    takes the raw f1.  ``double``: the float32 inputs evaluated in float64, the DSCV correlation without its float16 step."""
+    key = (case, double)
+    if key in _BACKWARD:
+        return _BACKWARD[key]
+    import torch
+    from oracle import m4depth_oracle_train as OT
+    r = reference(case)
+    d, u = r["inputs"], backward_upstream(case)
+    k = d["k"]
+    dt = torch.float64 if double else torch.float32
+    T = lambda a: torch.from_numpy(np.array(a)).to(dt)
+    leaf = lambda a: T(a).requires_grad_(True)
+    cam = {n: np.asarray(v, np.float64 if double else F) for n, v in d["cam"].items()}
+    out = {}
+    c1, c2, dpt, disp = leaf(r["c1"]), leaf(r["c2"]), leaf(r["pd2p"]), leaf(d["disp"])
+    cv, pd = OT.get_parallax_sweeping_cv(c1, c2, dpt, disp, T(d["rot"]), T(d["trans"]), cam, DSCV_RANGE, nbre_cuts=k, half=not double)
+    ((cv * T(u["g_cv"])).sum() + (pd * T(u["g_prev_disp"])).sum()).backward()
+    out.update(cv=cv, prev_disp=pd, dscv_g_c1=c1.grad, dscv_g_c2=c2.grad, dscv_g_disp_prev_t=dpt.grad, dscv_g_disp=disp.grad)
+    a = leaf(r["c1"])
+    sn = OT.cost_volume(a, a, SNCV_RANGE, nbre_cuts=k)
+    (sn * T(u["g_sncv"])).sum().backward()
+    out.update(sncv_auto=sn, sncv_auto_g_c1=a.grad)
+    a, b_ = leaf(r["c1"]), leaf(r["c2"])
+    sn = OT.cost_volume(a, b_, SNCV_RANGE, nbre_cuts=k)
+    (sn * T(u["g_sncv"])).sum().backward()
+    out.update(sncv=sn, sncv_g_c1=a.grad, sncv_g_c2=b_.grad)
+    f1 = leaf(d["f1"])
+    c1n = OT.normalize_cuts(f1, k)
+    (c1n * T(u["g_feat"])).sum().backward()
+    out.update(c1n=c1n, norm_g_f1=f1.grad)
+    out = {n: v.detach().numpy() for n, v in out.items()}
+    for v in out.values():
+        v.setflags(write=False)
+    _BACKWARD[key] = out
+    return out
+
+
+DSCV_BWD_WINDOW_FLOATS = 48 * 256    # the default LDS budget of m4d_dscv_bwd (csrc/m4d_grad.hip, the launcher)
+
+
+def dscv_bwd_blocks(idx, C):
+    """(private [b, blocks_y, blocks_x] bool, block height, block width): which pixel blocks of dscv_bwd_kernel keep their g_c2
+    window in LDS, from the forward's (y0, x0) grid [b, h, w, 2r+1, 2] -- the block shape of the launcher and the window
+    test of the kernel, per block (tests/test_gpu_grad.py::dscv_window_mix gives the two totals)."""
+    b, h, w = idx.shape[:3]
+    ppw = 64 // (C // 4)
+    p2 = 0
+    while (2 << p2) <= 4 * ppw:
+        p2 += 1
+    bh, bw = 1 << (p2 // 2), 1 << (p2 - p2 // 2)
+    ph, pw = -(-h // bh) * bh, -(-w // bw) * bw
+    pad = np.pad(idx, ((0, 0), (0, ph - h), (0, pw - w), (0, 0), (0, 0)), mode="edge")
+    blk = pad.reshape(b, ph // bh, bh, pw // bw, bw, -1, 2)
+    lo, hi = blk.min(axis=(2, 4, 5)), blk.max(axis=(2, 4, 5))
+    cells = (hi[..., 0] - lo[..., 0] + 2).astype(np.int64) * (hi[..., 1] - lo[..., 1] + 2)
+    return cells * C <= DSCV_BWD_WINDOW_FLOATS, bh, bw
+
+
+def blocks_with(pixels, bh, bw):
+    """[b, blocks_y, blocks_x] bool: the blocks holding a True pixel of ``pixels`` [b, h, w]."""
+    b, h, w = pixels.shape
+    ph, pw = -(-h // bh) * bh, -(-w // bw) * bw
+    return np.pad(pixels, ((0, 0), (0, ph - h), (0, pw - w))).reshape(b, ph // bh, bh, pw // bw, bw).any(axis=(2, 4))
 
 
 PARITY_OUTPUTS = ("p2d", "d2p", "pd2p", "recompute", "reproject", "cv_fp32_round", "cv_fp16_seq", "prev_disp", "sncv_auto", "sncv",

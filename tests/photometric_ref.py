@@ -274,6 +274,48 @@ def hostile_depth_case():
     return case
 
 
+def stationary_case(h=13, w=21):
+    """make_case('13x21-quat') with sample 0 STATIONARY -- identity rotation, zero translation, the case of a hovering drone --
+    beside the moving sample 1.  Sample 0's camera is dyadic (f = (16, 8), c = (10.25, 6.75)) and its depths are powers of two
+    (2^(1 + (j + 2 i) mod 4): no two neighbours equal, so the smoothness term sits on no kink), which makes its projection
+    EXACT in float32 and float64 alike: every query is the pixel's own centre, every pixel is valid, d query / d depth is exactly
+    0, and ``warped`` is ``prev`` bit for bit except in the last row and column (read with weight 1 from the cell before:
+    a * (r - l) + l is r to an ulp).  Without that the validity of the border pixels (q >= 0 against q = 0 -+ one
+    ulp) is decided by last-bit noise and no two evaluations agree on the mask.  The weight of the bilinear cell is 0 / 1 on a
+    cell border everywhere (the ``cell`` margin is 0), but with d query / d depth = 0 the choice of cell carries no gradient:
+    ``stationary_well`` leaves the cell margin out for sample 0."""
+    case = make_case("13x21-quat")
+    jj, ii = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    case["depth"][0, ..., 0] = 2.0 ** (1 + (jj + 2 * ii) % 4)
+    case["rot"][0] = [1.0, 0.0, 0.0, 0.0]
+    case["trans"][0] = 0.0
+    case["f"], case["c"] = case["f"].copy(), case["c"].copy()
+    case["f"][0], case["c"][0] = [16.0, 8.0], [10.25, 6.75]
+    case["name"] = "stationary"
+    return case
+
+
+def stationary_well(margins):
+    """``well_conditioned`` for stationary_case: sample 0 without the cell margin (see there)."""
+    well = well_conditioned(margins)
+    well[0] = ((margins["absdiff"] >= MARGIN) & (margins["smooth"] >= MARGIN) & (margins["clip"] >= MARGIN))[0]
+    return well
+
+
+@functools.lru_cache(maxsize=None)
+def stationary_yardstick():
+    """``yardstick`` for stationary_case with ``automask=False`` (with the auto-mask sample 0's mask compares pe(warped, cur)
+    with pe(prev, cur) where warped == prev: nothing to compare it with)."""
+    case = stationary_case()
+    r64, g64 = term_and_grad(case, torch.float64, automask=False)
+    r32, g32 = term_and_grad(case, torch.float32, automask=False)
+    well = stationary_well(r64["margins"])
+    out = {"case": case, "ref": (r64, g64, well), "r32": r32}
+    out["loss"] = max(abs(r32[k].item() - r64[k].item()) / abs(r64[k].item()) for k in ("term", "photo", "smooth"))
+    out["grad"] = ((g32.double() - g64).abs()[..., 0][well].max() / g64.abs().max()).item()
+    return out
+
+
 def learn_case(b=2, h=24, w=40):
     """The optimisation setup: prev a smooth sinusoid texture, cur = prev warped with a sloped plane (6 + 0.08 x + 0.05 y,
     second sample x 1.3), translation about 0.35 sideways, start 1.25 x the true depth."""

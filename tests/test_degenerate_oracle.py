@@ -165,3 +165,134 @@ def test_oracle_model_recovers_one_frame_after_motion_resumes():
             finite.append(all(np.isfinite(e["other"]).all() for e in est[-1]))
     assert not finite[D.STATIONARY_FRAME], "the stationary frame was meant to put NaN into the refiner"
     assert D.first_recovered(finite) == D.ORACLE_K == 1
+
+
+# ------------------------------------------------------------------------------------------------ the backward (R5, R6)
+BACKWARD_CASES = pytest.mark.parametrize("case", D.BACKWARD_CASES, ids=D.case_id)
+
+def _masks(a):
+    return np.isnan(a), np.isposinf(a), np.isneginf(a)
+
+
+@BACKWARD_CASES
+def test_restatement_forward_masks_equal_the_numpy_oracle(case):
+    """The rule-bearing training restatement (oracle/m4depth_oracle_train.py, fmax / fmin clamps) can be evaluated on every
+    case, and its forward NaN / +Inf / -Inf masks are the numpy oracle's."""
+    r, t = D.reference(case), D.backward_reference(case)
+    for name, ref in (("cv", "cv_fp32_round"), ("prev_disp", "prev_disp"), ("sncv_auto", "sncv_auto"), ("sncv", "sncv"), ("c1n", "c1")):
+        for kind, a, b in zip(("NaN", "+Inf", "-Inf"), _masks(t[name]), _masks(r[ref])):
+            assert np.array_equal(a, b), f"{case}: {kind} mask of {name}: {int(a.sum())} entries vs {int(b.sum())}"
+
+
+@BACKWARD_CASES
+def test_case_sits_on_its_edge_in_the_backward(case):
+    """Autodiff of the restatement under R5 / R6 with the case's fixed upstream gradients (``D.backward_upstream``): the pattern
+    each kind is in the table for.  Share of FINITE entries, sample 0 / sample 1, in per cent (13x21; the other geometries
+    give the same pattern, the zero-cut shares depend on the map size):
+
+      kind          g_c1         g_c2         g_disp_prev_t  g_disp        SNCV g_c1 (c1, c1)  SNCV g_c1 / g_c2 (c1, c2)  normalize g_f1
+      stationary    100 / 100    100 / 100    100 / 100      0 / 100       100 / 100           100 / 100, 100 / 100       100 / 100
+      epipole       100 / 100    100 / 100    100 / 100      99.6 / 99.6   100 / 100           100 / 100, 100 / 100       100 / 100
+      zero_cut      75.3 / 99.3  97.1 / 100   100 / 100      51.3 / 99.6   91.0 / 100          86.8 / 94.1, 91.0 / 100    99.8 / 100
+      far_query     100 / 100    100 / 100    100 / 100      100 / 1.5     100 / 100           100 / 100, 100 / 100       100 / 100
+      prev_d2para   100 / 100    100 / 100    100 / 100      84.6 / 86.8   100 / 100           100 / 100, 100 / 100       100 / 100
+
+    stationary: 0 * NaN on the way from the (selected-to-zero, R5) query gradient to g_disp (R6) -- every g_disp of sample 0
+    is NaN, nothing else is, and the neighbour is wholly finite.  epipole: the same on the one pixel with s = 0.  zero_cut:
+    NaN features reach g_c1 (through the warped c2), g_c2 (through c1) and g_disp.  far_query: sample 1's queries are +-Inf,
+    delta / (0 / p) = +-Inf meets a zero query gradient; the finite rest is exactly 0 (every hypothesis on a clamp of the
+    parallax: R5).  prev_d2para: the warped parallax interpolates Inf, its alpha gradient is Inf - Inf.  clamped_corner
+    (backward only): see tests/degenerate_cases.py; g_disp of pixel (0, 0) is exactly 0 beside NaN / Inf alpha gradients."""
+    t = D.backward_reference(case)
+    d = D.reference(case)["inputs"]
+    h, w = d["h"], d["w"]
+    fin = {n: np.isfinite(t[n]) for n in D.BACKWARD_TENSORS}
+    print(D.case_id(case), {n: [round(100 * float(f[s].mean()), 1) for s in range(D.B)] for n, f in fin.items()})
+    g_disp = t["dscv_g_disp"][..., 0]
+    if case.kind == "stationary":
+        assert np.isnan(g_disp[0]).all(), f"{case}: g_disp of the stationary sample"
+        for n in D.BACKWARD_TENSORS:
+            assert fin[n][1].all(), f"{case}: {n} of the neighbour sample is not finite"
+            assert n == "dscv_g_disp" or fin[n][0].all(), f"{case}: {n} of the stationary sample"
+    elif case.kind == "epipole":
+        want = np.zeros([D.B, h, w], bool)
+        want[:, h // 2, w // 2] = True
+        assert np.array_equal(np.isnan(g_disp), want), f"{case}: NaN g_disp off the epipole pixel"
+        assert all(fin[n].all() for n in D.BACKWARD_TENSORS if n != "dscv_g_disp")
+    elif case.kind == "zero_cut":
+        for n in ("dscv_g_disp", "dscv_g_c1", "dscv_g_c2", "sncv_auto_g_c1", "sncv_g_c1", "sncv_g_c2", "norm_g_f1"):
+            assert np.isnan(t[n][0]).any(), f"{case}: no NaN in {n} of sample 0"
+        assert fin["dscv_g_disp_prev_t"].all()
+    elif case.kind == "far_query":
+        nan1 = np.isnan(g_disp[1])
+        assert nan1.mean() > 0.9, f"{case}: {100 * nan1.mean():.1f} % of sample 1's g_disp is NaN"
+        assert (~nan1).any() and (g_disp[1][~nan1] == 0).all(), f"{case}: the finite rest is where every hypothesis is clamped"
+        assert fin["dscv_g_disp"][0].all() and (g_disp[0] == 0).any() and (g_disp[0] != 0).any()
+        assert all(fin[n].all() for n in D.BACKWARD_TENSORS if n != "dscv_g_disp")
+    elif case.kind == "clamped_corner":
+        r = D.reference(case)
+        q00 = r["queries"][:, 0, 0]                                     # [b, 2r+1, 2]
+        assert (q00 < 0).all(), f"{case}: a hypothesis of pixel (0, 0) stays inside the map"
+        assert (r["idx"][:, 0, 0] == 0).all() and np.isnan(r["c2"][0, 0, 0]).any() and np.isposinf(r["pd2p"][1, 0, 0, 0])
+        assert_bits_equal(np.abs(g_disp[:, 0, 0]), np.zeros(D.B, F), f"{case}: g_disp of pixel (0, 0) is selected to 0 (R5)")
+        assert np.isnan(t["dscv_g_c1"][0, 0, 0]).any() and not np.isfinite(t["prev_disp"][1, 0, 0]).all()
+        # the same graph with the clamp gradient written as a product with a 0/1 mask is NaN there: the case tells the two apart
+        import torch
+        from oracle import m4depth_oracle_train as OT
+
+        class ProductClip(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, lo, hi):
+                ctx.save_for_backward(((x >= lo) & (x <= hi)).to(x.dtype))
+                return torch.fmin(torch.fmax(x, torch.tensor(lo, dtype=x.dtype)), torch.tensor(hi, dtype=x.dtype))
+
+            @staticmethod
+            def backward(ctx, g):
+                return g * ctx.saved_tensors[0], None, None
+
+        old_clip = OT._clip
+        OT._clip = lambda x, lo, hi: ProductClip.apply(x, float(lo), float(hi))
+        try:
+            u = D.backward_upstream(case)
+            leaves = [torch.from_numpy(np.array(a)).requires_grad_(True) for a in (r["c1"], r["c2"], r["pd2p"], d["disp"])]
+            cv, pd = OT.get_parallax_sweeping_cv(*leaves, d["rot"], d["trans"], d["cam"], D.DSCV_RANGE, nbre_cuts=d["k"])
+            ((cv * torch.from_numpy(u["g_cv"])).sum() + (pd * torch.from_numpy(u["g_prev_disp"])).sum()).backward()
+        finally:
+            OT._clip = old_clip
+        assert np.isnan(leaves[3].grad.numpy()[:, 0, 0, 0]).all(), f"{case}: a mask-multiplying clamp gradient gives the same answer"
+    elif case.kind == "prev_d2para":
+        assert np.isinf(t["prev_disp"]).any() and not fin["dscv_g_disp"].all(), f"{case}: the infinite parallax reaches no gradient"
+        assert all(fin[n].all() for n in D.BACKWARD_TENSORS if n != "dscv_g_disp")
+
+
+@BACKWARD_CASES
+def test_float32_and_float64_restatements_agree_on_the_non_finite_masks(case):
+    """What lets the GPU tests ask for equal masks on 100 % of the entries: the reference's own masks do not depend on its
+    precision.  Demanded of every tensor whose graph has no float16 step (``D.NO_HALF_TENSORS``); it also holds for the three
+    DSCV gradients behind the float16 product, with one exception that is a property of the forward input, not of the
+    gradient: sample 1 of far_query moves by 1e-30, delta^2 underflows to s = 0 in float32 only, so its queries are +-Inf in
+    float32 and finite (1e30 pixels away) in float64, and g_disp is NaN against 0."""
+    a, b = D.backward_reference(case), D.backward_reference(case, double=True)
+    for n in D.BACKWARD_TENSORS:
+        if case.kind == "far_query" and n == "dscv_g_disp":
+            assert all(np.array_equal(x[0], y[0]) for x, y in zip(_masks(a[n]), _masks(b[n]))), f"{case}: {n}, sample 0"
+            continue
+        for kind, x, y in zip(("NaN", "+Inf", "-Inf"), _masks(a[n]), _masks(b[n])):
+            assert np.array_equal(x, y), f"{case}: {kind} mask of {n}: {int(x.sum())} entries in float32, {int(y.sum())} in float64"
+
+
+def test_r5_clamp_gradient_is_a_select():
+    """R5: outside the bounds, and on a NaN input, the gradient is exactly 0 even when NaN or Inf arrives; inside it is the
+    incoming gradient.  Forward: a NaN drops to the lower bound (R1, R2)."""
+    import torch
+    from oracle import m4depth_oracle_train as OT
+    nan, inf = float("nan"), float("inf")
+    x = torch.tensor([nan, -inf, -8.0, -7.0, 0.5, 7.0, 8.0, inf], requires_grad=True)
+    y = OT._clip(x, -7.0, 7.0)
+    assert y.tolist() == [-7.0, -7.0, -7.0, -7.0, 0.5, 7.0, 7.0, 7.0]
+    y.backward(torch.tensor([nan, nan, inf, 2.0, nan, 3.0, -inf, nan]))
+    g = x.grad.numpy()
+    assert_bits_equal(g[[0, 1, 2, 6, 7]], np.zeros(5, F), "outside or NaN: +0")
+    assert g[3] == 2.0 and np.isnan(g[4]) and g[5] == 3.0
+    q = torch.tensor([nan, inf, -inf, 2.75])
+    assert OT._floor_index(q, 7).tolist() == [0.0, 5.0, 0.0, 2.0]

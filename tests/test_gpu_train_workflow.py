@@ -166,6 +166,42 @@ def test_nan_stops_training_and_saves_nothing_of_its_epoch(dev, tmp_path, capsys
         assert all(np.isfinite(z[k]).all() for k in z.files)
 
 
+def _stationary_epochs(dev, epochs=2, per_epoch=2):
+    """epoch -> device batches of synthetic data; in the LAST batch of the first epoch sample 0 does not move on the last
+    frame (a hovering drone, a car at a traffic light).  Every input is finite."""
+    def epoch(e):
+        for i in range(per_epoch):
+            d = to_dev(_data(60 + e * per_epoch + i), dev)
+            if (e, i) == (0, per_epoch - 1):
+                d["trans"][0, -1] = 0.0
+            yield d
+    return epochs, epoch
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_a_stationary_frame_never_reaches_a_checkpoint(dev, tmp_path, capsys, monkeypatch, graph):
+    """A stationary sample leaves the loss finite (DESIGN.md "Degenerate inputs", R2) and the gradients NaN (R6), so the
+    optimizer step makes the weights NaN and only the NEXT step's loss shows it.  Here the poisoning step is the last of an
+    epoch and a checkpoint is due right after it (--save_every 2): the driver checks the parameters where it saves, writes
+    nothing and exits with status 1; no file with a non-finite value is ever on disk."""
+    from m4depth_amd import main as MAIN
+    monkeypatch.setattr(MAIN, "default_epochs", lambda args, rank, world, dev_: _stationary_epochs(dev))
+    ck = str(tmp_path / "ck")
+    argv = ["--mode", "train", "--ckpt_dir", ck, "--save_every", "2"] + SYN + (["--graph"] if graph else [])
+    assert MAIN.main(argv) == 1
+    out = capsys.readouterr().out
+    steps = _losses(out)
+    assert [s for s, _ in steps] == [1, 2] and all(np.isfinite(l) for _, l in steps), out    # the poisoning step's loss is finite
+    assert "step 2: non-finite parameters" in out and "saved" not in out
+    train = os.path.join(ck, "train")
+    written = sorted(os.listdir(train)) if os.path.isdir(train) else []
+    for name in written:
+        if name.endswith(".npz"):
+            with np.load(os.path.join(train, name)) as z:
+                assert all(np.isfinite(z[k]).all() for k in z.files), name
+    assert written == [], written
+
+
 def _tree(tmp_path):
     """Fake Mid-Air (training) and KITTI (finetuning and validation) sets with one datasets_location.json, and the records
     tree finetune_kitti reads (<records>/kitti-raw-filtered/train_data, <records>/midair/train_data)."""

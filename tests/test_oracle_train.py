@@ -92,3 +92,55 @@ def test_loss_value_and_gradients_exist():
         preds = [[{"depth": torch.full((1, H // 2, W // 2, 1), 10.0)}, {"depth": torch.full((1, H // 4, W // 4, 1), 10.0)}]] * T
         val = OT.m4depth_loss(gts, preds, mode).item()
         assert np.isfinite(val) and val > 0
+
+
+def test_rule_bearing_clamps_move_no_bit_on_healthy_inputs(monkeypatch):
+    """The restatement's clamps state the rules R1, R2, R5 of DESIGN.md "Degenerate inputs" (``OT._clip`` / ``OT._floor_index``:
+    fmax / fmin forward, a select backward).  On inputs without NaN or Inf that changes nothing: the outputs, the loss and every
+    gradient of the cases above are, bit for bit, those of the clamp lines the restatement had before (kept here)."""
+    def old_floor_index(q, size):
+        fl = torch.minimum(torch.maximum(torch.zeros((), dtype=q.dtype), torch.floor(q)),
+                           torch.tensor(float(size - 2), dtype=q.dtype))
+        return fl.detach()
+
+    def old_clip(x, lo, hi):
+        return torch.clamp(x, lo, hi)
+
+    def bits(t):
+        return t.detach().contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+
+    def dscv_case(dtype):
+        rng = np.random.default_rng(5)
+        b, h, w, C, k = 2, 12, 20, 16, 2
+        ts = [torch.from_numpy(a).to(dtype).requires_grad_(True) for a in
+              (_unit(rng, [b, h, w, C], k), _unit(rng, [b, h, w, C], k), rng.uniform(0.5, 6.0, [b, h, w, 1]).astype(F),
+               rng.uniform(-2.0, 6.0, [b, h, w, 1]).astype(F))]
+        rot, trans = motion_np(rng, b, t_scale=(3.0, 3.0, 1.0))      # queries leave the map: every clamp has both sides
+        cv, pd = OT.get_parallax_sweeping_cv(ts[0], ts[1], ts[3], ts[2], rot, trans, camera_np(b, h, w), 4, nbre_cuts=k,
+                                             half=dtype == torch.float32)
+        g = torch.from_numpy(rng.normal(size=cv.shape)).to(dtype)
+        ((cv * g).sum() + pd.sum()).backward()
+        return [cv, pd] + [t.grad for t in ts]
+
+    def loss_case():
+        L, H, W, T = 2, 32, 48, 2
+        wts = synthetic.init_weights(nbre_levels=L, seed=3, dscv_range=2, sncv_range=2, bias_std=0.05)
+        samples, cam = synthetic.make_sequence(1, T, H, W, seed=12)
+        tw = {k: torch.from_numpy(v).requires_grad_(True) for k, v in wts.items()}
+        data = {k: torch.from_numpy(np.stack([s[k] for s in samples], axis=1)) for k in ("RGB_im", "depth", "rot", "trans")}
+        data["new_traj"] = np.stack([s["new_traj"] for s in samples], axis=1)
+        data["camera"] = cam
+        loss, preds = OT.train_loss(tw, data, L, dscv_range=2, sncv_range=2)
+        loss.backward()
+        return [loss.reshape(1)] + [p["parallax"] for p in preds[1]] + [tw[k].grad for k in sorted(tw) if tw[k].grad is not None]
+
+    new = dscv_case(torch.float32) + dscv_case(torch.float64) + loss_case()
+    monkeypatch.setattr(OT, "_clip", old_clip)
+    monkeypatch.setattr(OT, "_floor_index", old_floor_index)
+    old = dscv_case(torch.float32) + dscv_case(torch.float64) + loss_case()
+    assert len(new) == len(old) > 20
+    for n, (a, b) in enumerate(zip(new, old)):
+        assert torch.isfinite(a).all(), n
+        assert torch.equal(bits(a), bits(b)), f"tensor {n}: {int((bits(a) != bits(b)).sum())} of {a.numel()} entries moved"
+    disp_grad = new[5]
+    assert bool((disp_grad == 0).any()) and bool((disp_grad != 0).any()), "the parallax clamp was meant to be reached"

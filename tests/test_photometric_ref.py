@@ -125,3 +125,27 @@ def test_restatement_learns():
     print(f"median relative depth error {start:.2%} -> {med:.4%} (p90 {p90:.4%})")
     assert start == pytest.approx(0.25, abs=1e-6)
     assert med <= 0.01
+
+
+def test_stationary_case_is_exact_in_both_precisions():
+    """R.stationary_case (a stationary sample beside a moving one): sample 0's queries are the pixel centres exactly, in float32
+    and float64 alike, so both agree on ``valid`` (all of sample 0), on the mask without the auto-mask and on N; ``warped`` is
+    ``prev`` off the last row / column and within an ulp there; the depth gradient of sample 0 is the smoothness term's alone.
+    With the auto-mask, sample 0's mask compares pe(warped, cur) with pe(prev, cur) of the same image: last-bit noise decides,
+    and the two precisions need not agree (they do not: N = 58 against 61)."""
+    y = R.stationary_yardstick()
+    r64, g64, well = y["ref"]
+    r32, case = y["r32"], y["case"]
+    prev = torch.from_numpy(case["prev"])
+    for r in (r32, r64):
+        assert bool(r["valid"][0].all()) and not bool(r["valid"][1].all())
+        assert torch.equal(r["warped"][0, :-1, :-1].detach().float(), prev[0, :-1, :-1])
+        assert float((r["warped"][0].detach().float() - prev[0]).abs().max()) <= 2.0 ** -23
+    assert torch.equal(r32["mask"], r64["mask"]) and r32["n"].item() == r64["n"].item() > 11 * 19
+    assert bool(r64["mask"][0, 1:-1, 1:-1].all())
+    assert float(well.double().mean()) >= 0.99 and bool(well[0].all())
+    assert (r64["margins"]["cell"][0] == 0).all()
+    assert 0 < float(g64[0].abs().max()) < 0.05 * float(g64[1].abs().max())
+    print(f"stationary: float32 restatement's error: loss {y['loss']:.2e}, g_depth {y['grad']:.2e} of max |g|")
+    a64, _ = R.term_and_grad(case, torch.float64, automask=True)
+    assert a64["n"].item() <= r64["n"].item() and not bool(a64["mask"][0].any())
