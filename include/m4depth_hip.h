@@ -376,6 +376,50 @@ int m4d_photo_loss_bwd(const float* depth, const float* warped, const float* dwa
                        const unsigned char* mask, const float* out4, const float* g_out, int b, int h, int w,
                        float lambda, float* g_depth, void* stream);
 
+/* Full-resolution terms and the minimum over two sources (the two options of the loss; with scale = level and one source the
+ * definition above, unchanged).  Frame t >= 1, level i, level depth d [b,h,w,1]:
+ * Scale.  level: D = d, images and camera those of the level.  full: D = U_s(d), s = 2^(i+1), [b, h s, w s, 1]; the images
+ *   are the input frames themselves (no pyramid), the camera the full-resolution one.  U_s = bilinear upsampling with
+ *   half-pixel centres and edge clamp (PyTorch's interpolate(mode="bilinear", align_corners=False)); per axis, output index Y:
+ *     src = max((Y + 0.5) / s - 0.5, 0), y0 = min(floor(src), h-1), y1 = min(y0 + 1, h-1), a = src - y0,
+ *   value = m4d_lerp2(tl, tr, bl, br, ax, ay) in that operation order (s a power of two: src and a are exact in float32, the
+ *   result is bit-reproducible).  The RAW depth is upsampled; the clip to [0.01, 200], `valid` and `inside` apply to D as
+ *   they apply to `depth` above; smoothness is that of D against the full-resolution current image, divided by the number of
+ *   elements of D.
+ * Sources.  Source 0 = frame t-1 with the motion of frame t.  With two sources and t < T-1, source 1 = frame t+1 with the
+ *   inverse of the motion of frame t+1: rot' = (w, -x, -y, -z), trans' = -(R(rot') trans); quaternions only (I + [r]x has no
+ *   exact inverse of that form).  The last frame of a sequence has source 0 only.
+ * Per source s: warped_s, dwarp_s, valid_s = m4d_photo_warp_fwd on D.  Per pixel p: pe_s(p) = pe(warped_s, cur)(p);
+ *   ok_s(p) = p interior and all 9 window pixels valid for s; m(p), sel(p): walk the sources in order, source s replaces the
+ *   choice when ok_s(p) and (nothing chosen yet or pe_s(p) < m(p)) -- a tie keeps the previous frame, no ok source selects
+ *   nothing; id(p) = min over the present sources of pe(image_s, cur)(p) (independent of D: the same for every level of a
+ *   frame at scale full); M(p) = sel(p) != none and (auto-masking off or m(p) < id(p)); N = sum M;
+ *   photo = sum_M m / max(N,1); term and out4 as above.
+ * Backward (a gather, no atomics): g_D(q) = g [ sum_s dwarp_s(q) sum_{p in 3x3(q), M(p), sel(p)=s} d pe_s(p)/d warped_s(q)
+ *   / max(N,1) + lambda d smooth/dD(q) ] inside(q);  g_d = U_s^T g_D, the exact adjoint of U_s including the clamped border
+ *   rows and columns, itself a gather: a coarse pixel collects from the at most 2s x 2s fine pixels whose stencil holds it, in
+ *   a fixed order (s <= 4: one thread, row-major; s >= 8: one wave, lane l the values l, l+64, ..., double, shuffle tree).
+ *
+ * m4d_upsample_hp_*: x / g_x [b,h,w], out / g_out [b, h s, w s]; s in {2,4,8,16,32,64}, h, w >= 1, b (h s)(w s) <= 2^24,
+ *   anything else: invalid argument, no launch.
+ * m4d_photo_identity_fwd: pe_id [b,h,w] float32 = id above (src1 NULL: one source); non-interior pixels are written as 0 and
+ *   never read.
+ * m4d_photo_min_fwd: warped1 / valid1 NULL (both or neither) = one source; pe_id NULL = auto-masking off; sel [b,h,w] bytes,
+ *   0 = not in M, 1 = previous, 2 = next; workspace of m4d_photo_min_workspace_bytes bytes, 8-byte aligned.
+ * m4d_photo_min_bwd: one gather over both sources with the forward's sel and out4 (warped1 / dwarp1 NULL: one source, a sel
+ *   byte of 2 then selects nothing). */
+int m4d_upsample_hp_fwd(const float* x, int b, int h, int w, int s, float* out, void* stream);
+int m4d_upsample_hp_bwd(const float* g_out, int b, int h, int w, int s, float* g_x, void* stream);
+int m4d_photo_identity_fwd(const float* cur, const float* src0, const float* src1_or_null, int b, int h, int w, float* pe_id,
+                           void* stream);
+long long m4d_photo_min_workspace_bytes(int b, int h, int w);
+int m4d_photo_min_fwd(const float* depth, const float* warped0, const unsigned char* valid0, const float* warped1,
+                      const unsigned char* valid1, const float* cur, const float* pe_id, int b, int h, int w, float lambda,
+                      void* workspace, float* out4, unsigned char* sel, void* stream);
+int m4d_photo_min_bwd(const float* depth, const float* warped0, const float* dwarp0, const float* warped1, const float* dwarp1,
+                      const float* cur, const unsigned char* sel, const float* out4, const float* g_out, int b, int h, int w,
+                      float lambda, float* g_depth, void* stream);
+
 /* ---- m4depth_network.py: DepthEstimatorLevel glue -------------------------------- */
 
 /* Per-cut L2 normalisation (:179-189, tf.linalg.normalize, no epsilon). */

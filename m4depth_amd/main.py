@@ -114,6 +114,12 @@ def build_parser():
                         "tuned for this network)")
     p.add_argument("--no_photo_automask", action="store_true",
                    help="--loss=photometric: keep the pixels whose unwarped previous frame already matches better (auto-masking off)")
+    p.add_argument("--photo_scale", default=None, choices=["level", "full"],
+                   help="--loss=photometric: level (default) = each term at its level's resolution against the image pyramid; "
+                        "full = every level's depth upsampled to the input resolution and compared there (Monodepth2's form)")
+    p.add_argument("--photo_sources", default=None, choices=["prev", "both"],
+                   help="--loss=photometric: prev (default) = frame t-1 only; both = the per-pixel minimum over frame t-1 and frame "
+                        "t+1, which drops pixels one neighbour does not see (needs quaternion rotations)")
     p.add_argument("--save_every", type=int, default=0, help="train: checkpoint every N steps (0 = at the end)")
     p.add_argument("--summary_interval", type=int, default=1200,
                    help="train --graph: read the device-side step log every N steps (m4depth_options.py:47-49); it is also "
@@ -382,6 +388,8 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
     model.train_loss = getattr(args, "loss", "supervised")
     model.photo_smooth = 1e-3 if getattr(args, "photo_smooth", None) is None else args.photo_smooth
     model.photo_automask = not getattr(args, "no_photo_automask", False)
+    model.photo_scale = getattr(args, "photo_scale", None) or "level"
+    model.photo_sources = getattr(args, "photo_sources", None) or "prev"
     # a batch without ground truth (a recording without depth.txt under --loss=photometric): RMSE_log is a 0/0 masked mean,
     # so it is neither printed nor logged, and the loss alone decides whether a step was bad
     has_gt = args.dataset == "synthetic" or args.records_path is None or records_have_depth(args)
@@ -787,7 +795,8 @@ def check_train_args(parser, args, world=None):
             parser.error("--enable_validation needs --db_path_config (the validation set's dataset root)")
         if world > 1:
             parser.error("--enable_validation runs in-process on one GPU: it is refused with several ranks")
-    photo_opts = [f for f, on in (("photo_smooth", args.photo_smooth is not None), ("no_photo_automask", args.no_photo_automask)) if on]
+    photo_opts = [f for f, on in (("photo_smooth", args.photo_smooth is not None), ("no_photo_automask", args.no_photo_automask),
+                                      ("photo_scale", args.photo_scale is not None), ("photo_sources", args.photo_sources is not None)) if on]
     if args.loss != "supervised" and args.mode != "train":
         parser.error("--loss=%s is a --mode=train option" % args.loss)
     if photo_opts and args.loss != "photometric":

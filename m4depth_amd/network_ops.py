@@ -1322,3 +1322,119 @@ def photo_loss_bwd(depth, warped, dwarp, cur, mask, out4, g_out, smooth):
                                  dptr(out4, "out4"), dptr(as_f32(g_out, "g_out").reshape(1)), b, h, w, float(smooth), dptr(g_depth),
                                  stream_ptr()), "m4d_photo_loss_bwd")
     return g_depth
+
+
+# ---- full-resolution terms, minimum over two sources (include/m4depth_hip.h, "Full-resolution terms ...") -------------------
+UPSAMPLE_HP_SCALES = (2, 4, 8, 16, 32, 64)
+
+
+def _hp_map(x, name):
+    x = as_f32(x, name)
+    if x.dim() != 4 or x.shape[3] != 1:
+        raise ValueError(f"{name}: expected [b,h,w,1], got {tuple(x.shape)}")
+    return x
+
+
+def upsample_hp(x, s):
+    """m4d_upsample_hp_fwd: ``x`` [b,h,w,1] -> [b, h s, w s, 1], bilinear with half-pixel centres and edge clamp (the bits of
+    the header's definition; ``interpolate(mode="bilinear", align_corners=False)`` to rounding)."""
+    x = _hp_map(x, "x")
+    b, h, w, _ = x.shape
+    s = int(s)
+    if s not in UPSAMPLE_HP_SCALES or b * h * s * w * s > 1 << 24:
+        raise ValueError(f"upsample_hp: scale {s} of a {b}x{h}x{w} map is refused (s in {UPSAMPLE_HP_SCALES}, b (h s)(w s) <= 2^24)")
+    out = torch.empty((b, h * s, w * s, 1), dtype=torch.float32, device=x.device)
+    check(lib.m4d_upsample_hp_fwd(dptr(x, "x"), b, h, w, s, dptr(out), stream_ptr()), "m4d_upsample_hp_fwd")
+    return out
+
+
+def upsample_hp_bwd(g_out, s):
+    """m4d_upsample_hp_bwd: the exact adjoint of ``upsample_hp``: ``g_out`` [b, h s, w s, 1] -> [b,h,w,1]; the same bits
+    every run."""
+    g_out = _hp_map(g_out, "g_out")
+    b, H, W, _ = g_out.shape
+    s = int(s)
+    if s not in UPSAMPLE_HP_SCALES or H % s or W % s or b * H * W > 1 << 24 or H == 0 or W == 0:
+        raise ValueError(f"upsample_hp_bwd: scale {s} of a {b}x{H}x{W} gradient is refused (s in {UPSAMPLE_HP_SCALES}, H and W "
+                         "multiples of s, b H W <= 2^24)")
+    g_x = torch.empty((b, H // s, W // s, 1), dtype=torch.float32, device=g_out.device)
+    check(lib.m4d_upsample_hp_bwd(dptr(g_out, "g_out"), b, H // s, W // s, s, dptr(g_x), stream_ptr()), "m4d_upsample_hp_bwd")
+    return g_x
+
+
+def _photo_cur(cur):
+    cur = as_f32(cur, "cur")
+    if cur.dim() != 4 or cur.shape[3] != 3:
+        raise ValueError(f"cur: expected [b,h,w,3], got {tuple(cur.shape)}")
+    return cur
+
+
+def photo_identity(cur, src0, src1=None):
+    """m4d_photo_identity_fwd: pe_id [b,h,w] float32 = min over the given sources of pe(source, cur) at the interior pixels
+    (0 elsewhere): the right-hand side of the auto-mask, independent of the depth."""
+    cur = _photo_cur(cur)
+    b, h, w, _ = cur.shape
+    src0 = _photo_image(src0, "src0", b, h, w)
+    src1 = None if src1 is None else _photo_image(src1, "src1", b, h, w)
+    if int(lib.m4d_photo_min_workspace_bytes(b, h, w)) < 0:
+        raise ValueError(f"photometric loss: a {b}x{h}x{w} map is refused (h, w >= 3 and b*h*w <= 2^24)")
+    pe_id = torch.empty((b, h, w), dtype=torch.float32, device=cur.device)
+    check(lib.m4d_photo_identity_fwd(dptr(cur, "cur"), dptr(src0), dptr(src1), b, h, w, dptr(pe_id), stream_ptr()),
+          "m4d_photo_identity_fwd")
+    return pe_id
+
+
+def _photo_source(warped, valid, names, b, h, w):
+    """One source's pair (warped [b,h,w,3], valid [b,h,w,1] uint8), both or neither."""
+    if (warped is None) != (valid is None):
+        raise ValueError(f"{names[0]} and {names[1]}: give both or neither")
+    if warped is None:
+        return None, None
+    if tuple(valid.shape) != (b, h, w, 1):
+        raise ValueError(f"{names[1]}: expected {(b, h, w, 1)}, got {tuple(valid.shape)}")
+    return _photo_image(warped, names[0], b, h, w), valid
+
+
+def photo_min_fwd(depth, warped0, valid0, warped1, valid1, cur, pe_id, smooth):
+    """m4d_photo_min_fwd: (out4 = (term, photo, smooth, N) float32 [4], sel [b,h,w,1] uint8: 0 = not in the mask, 1 = source
+    0, 2 = source 1).  ``warped1`` / ``valid1`` None = one source; ``pe_id`` (photo_identity) None = auto-masking off."""
+    depth = _hp_map(depth, "depth")
+    b, h, w, _ = depth.shape
+    cur = _photo_image(cur, "cur", b, h, w)
+    warped0, valid0 = _photo_source(warped0, valid0, ("warped0", "valid0"), b, h, w)
+    if warped0 is None:
+        raise ValueError("warped0 and valid0: source 0 is required")
+    warped1, valid1 = _photo_source(warped1, valid1, ("warped1", "valid1"), b, h, w)
+    if pe_id is not None and tuple(pe_id.shape) != (b, h, w):
+        raise ValueError(f"pe_id: expected {(b, h, w)}, got {tuple(pe_id.shape)}")
+    nbytes = int(lib.m4d_photo_min_workspace_bytes(b, h, w))
+    if nbytes < 0:
+        raise ValueError(f"photometric loss: a {b}x{h}x{w} map is refused (h, w >= 3 and b*h*w <= 2^24)")
+    ws = _workspace("photo", nbytes + 8, depth.device)
+    ws_ptr = ctypes.c_void_p((ws.data_ptr() + 7) // 8 * 8)
+    out4 = torch.empty(4, dtype=torch.float32, device=depth.device)
+    sel = torch.empty((b, h, w, 1), dtype=torch.uint8, device=depth.device)
+    check(lib.m4d_photo_min_fwd(dptr(depth, "depth"), dptr(warped0), dptr(valid0, "valid0", torch.uint8), dptr(warped1),
+                                dptr(valid1, "valid1", torch.uint8), dptr(cur), dptr(pe_id, "pe_id"), b, h, w, float(smooth), ws_ptr,
+                                dptr(out4), dptr(sel, "sel", torch.uint8), stream_ptr()), "m4d_photo_min_fwd")
+    return out4, sel
+
+
+def photo_min_bwd(depth, warped0, dwarp0, warped1, dwarp1, cur, sel, out4, g_out, smooth):
+    """m4d_photo_min_bwd: g_depth [b,h,w,1] from the scalar gradient ``g_out`` (device, [1]) with the forward's sel and out4,
+    one gather over both sources."""
+    depth = _hp_map(depth, "depth")
+    b, h, w, _ = depth.shape
+    cur = _photo_image(cur, "cur", b, h, w)
+    warped0, dwarp0 = _photo_image(warped0, "warped0", b, h, w), _photo_image(dwarp0, "dwarp0", b, h, w)
+    if (warped1 is None) != (dwarp1 is None):
+        raise ValueError("warped1 and dwarp1: give both or neither")
+    if warped1 is not None:
+        warped1, dwarp1 = _photo_image(warped1, "warped1", b, h, w), _photo_image(dwarp1, "dwarp1", b, h, w)
+    if tuple(sel.shape) != (b, h, w, 1):
+        raise ValueError(f"sel: expected {(b, h, w, 1)}, got {tuple(sel.shape)}")
+    g_depth = torch.empty_like(depth)
+    check(lib.m4d_photo_min_bwd(dptr(depth, "depth"), dptr(warped0), dptr(dwarp0), dptr(warped1), dptr(dwarp1), dptr(cur),
+                                dptr(sel, "sel", torch.uint8), dptr(out4, "out4"), dptr(as_f32(g_out, "g_out").reshape(1)), b, h, w,
+                                float(smooth), dptr(g_depth), stream_ptr()), "m4d_photo_min_bwd")
+    return g_depth

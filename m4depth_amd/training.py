@@ -262,6 +262,50 @@ class _LevelPhoto(torch.autograd.Function):
         return (nops.photo_loss_bwd(depth, warped, dwarp, cur, mask, out4, g, ctx.smooth),) + (None,) * 8
 
 
+class _MultiPhoto(torch.autograd.Function):
+    """One level's unweighted term with the loss's options (include/m4depth_hip.h, "Full-resolution terms and the minimum over
+    two sources"): ``s`` > 1 upsamples the level depth to the images' resolution first (U_s, m4d_upsample_hp_fwd), ``src1`` adds
+    the next frame, warped with the inverse motion ``rot1`` / ``trans1``; ``pe_id`` (nops.photo_identity, None = auto-masking
+    off) is shared by the levels of a frame at scale full.  The backward is two gathers: m4d_photo_min_bwd, then U_s^T."""
+
+    @staticmethod
+    def forward(ctx, depth, rot0, trans0, rot1, trans1, f, c, cur, src0, src1, pe_id, s, smooth):
+        D = nops.upsample_hp(depth, s) if s > 1 else depth
+        warped0, dwarp0, valid0 = nops.photo_warp_fwd(D, rot0, trans0, f, c, src0)
+        warped1 = dwarp1 = valid1 = None
+        if src1 is not None:
+            warped1, dwarp1, valid1 = nops.photo_warp_fwd(D, rot1, trans1, f, c, src1)
+        out4, sel = nops.photo_min_fwd(D, warped0, valid0, warped1, valid1, cur, pe_id, smooth)
+        ctx.save_for_backward(D, warped0, dwarp0, warped1, dwarp1, cur, sel, out4)
+        ctx.smooth, ctx.s = smooth, s
+        return out4[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        D, warped0, dwarp0, warped1, dwarp1, cur, sel, out4 = ctx.saved_tensors
+        g_D = nops.photo_min_bwd(D, warped0, dwarp0, warped1, dwarp1, cur, sel, out4, g, ctx.smooth)
+        return (nops.upsample_hp_bwd(g_D, ctx.s) if ctx.s > 1 else g_D,) + (None,) * 12
+
+
+def motion_inverse(rot, trans):
+    """The inverse of a quaternion motion x -> R(rot) x + trans: rot' = (w, -x, -y, -z), trans' = -(R(rot') trans), with
+    m4d_load_motion's rotation matrix.  Torch ops on the device (7 numbers per sample), capturable."""
+    if rot.shape[-1] != 4:
+        raise ValueError("photometric loss, sources='both': the inverse motion needs quaternion rotations (w,x,y,z); a small-angle "
+                         "rotation I + [r]x has no exact inverse of that form")
+    inv = torch.cat([rot[..., :1], -rot[..., 1:]], dim=-1)           # no host constant: the capture takes no copy from the host
+    w, x, y, z = inv.unbind(-1)
+    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    t0, t1, t2 = trans.unbind(-1)
+    out = torch.stack([((1.0 - (tyy + tzz)) * t0 + (txy - twz) * t1) + (txz + twy) * t2,
+                       ((txy + twz) * t0 + (1.0 - (txx + tzz)) * t1) + (tyz - twx) * t2,
+                       ((txz - twy) * t0 + (tyz + twx) * t1) + (1.0 - (txx + tyy)) * t2], dim=-1)
+    return inv.contiguous(), (-out).contiguous()
+
+
 def level_forward_train(level, curr_f_maps, prev_l_est, rot, trans, camera, prev_f_maps, prev_t_depth, cache):
     """DepthEstimatorLevel.call with is_training=True (m4depth_network.py:167-262)."""
     b, h, w, c = curr_f_maps.shape
@@ -377,15 +421,28 @@ def m4depth_loss(gts, preds, depth_type="map"):
 
 
 LOSSES = ("supervised", "photometric")
+PHOTO_SCALES = ("level", "full")
+PHOTO_SOURCES = ("prev", "both")
 
 
-def photometric_loss(samples, preds, camera, smooth=1e-3, automask=True):
+def photometric_loss(samples, preds, camera, smooth=1e-3, automask=True, scale="level", sources="prev"):
     """Training without ground-truth depth: the photometric reprojection loss (SSIM + L1 error between frame t and frame t-1
     warped with the PREDICTED depth and the data's exact relative pose, validity mask, auto-masking, edge-aware smoothness:
     Godard et al., ICCV 2019; the definition is in include/m4depth_hip.h).  One term per level of every frame but the first,
     with the level weights of ``m4depth_loss``.  ``samples[t]`` = {"RGB_im" [b,H,W,3] in [0,1], "rot", "trans"}, ``preds`` as
     ``model_forward_train`` returns them, ``camera`` the full-resolution intrinsics.  The image pyramid of every frame is built
-    once, by one call."""
+    once, by one call.
+
+    ``scale``: ``level`` = each term at its level's resolution against the image pyramid; ``full`` = the level depth upsampled to
+    the input resolution (half-pixel bilinear) and compared there against the frames themselves (Monodepth2's form).
+    ``sources``: ``prev`` = frame t-1 only; ``both`` = the per-pixel minimum over frame t-1 and frame t+1 (the last frame has
+    the previous one only), which needs quaternion rotations.  The defaults take ``_LevelPhoto``; anything else ``_MultiPhoto``."""
+    if scale not in PHOTO_SCALES:
+        raise ValueError(f"scale: expected one of {PHOTO_SCALES}, got {scale!r}")
+    if sources not in PHOTO_SOURCES:
+        raise ValueError(f"sources: expected one of {PHOTO_SOURCES}, got {sources!r}")
+    if scale != "level" or sources != "prev":
+        return _photometric_loss_multi(samples, preds, camera, float(smooth), bool(automask), scale, sources)
     T = len(samples)
     L = len(preds[-1])
     b = samples[0]["RGB_im"].shape[0]
@@ -404,13 +461,58 @@ def photometric_loss(samples, preds, camera, smooth=1e-3, automask=True):
     return loss
 
 
+def _photometric_loss_multi(samples, preds, camera, smooth, automask, scale, sources):
+    """photometric_loss with ``scale`` / ``sources`` other than the defaults."""
+    T = len(samples)
+    L = len(preds[-1])
+    b = samples[0]["RGB_im"].shape[0]
+    both = sources == "both"
+    if both and any(s["rot"].shape[-1] != 4 for s in samples):
+        raise ValueError("photometric loss, sources='both': the inverse motion needs quaternion rotations (w,x,y,z); a small-angle "
+                         "rotation I + [r]x has no exact inverse of that form")
+    images = [as_f32(s["RGB_im"], "RGB_im") for s in samples]
+    f, c = as_f32(camera["f"], "f").reshape(b, 2), as_f32(camera["c"], "c").reshape(b, 2)
+    if scale == "full":
+        H, W = images[0].shape[1:3]
+        if H % (1 << L) or W % (1 << L):
+            raise ValueError(f"photometric loss, scale='full': {H}x{W} is no multiple of 2^{L}")
+        level_images = [images] * L                                   # level i, frame t: the frames themselves
+        cams = [(f, c)] * L
+    else:
+        with torch.no_grad():
+            frames = torch.stack(images, dim=0)
+            pyr = [lvl.view(T, b, *lvl.shape[1:]) for lvl in nops.image_pyramid_box(frames.view(T * b, *frames.shape[2:]), L)]
+        level_images = [[pyr[i][t] for t in range(T)] for i in range(L)]
+        cams = [(f / 2. ** (i + 1), c / 2. ** (i + 1)) for i in range(L)]
+    loss = 0.
+    for t in range(1, T):
+        rot0, trans0 = as_f32(samples[t]["rot"], "rot"), as_f32(samples[t]["trans"], "trans").reshape(b, 3)
+        nxt = both and t < T - 1
+        rot1 = trans1 = None
+        if nxt:
+            with torch.no_grad():
+                rot1, trans1 = motion_inverse(as_f32(samples[t + 1]["rot"], "rot"), as_f32(samples[t + 1]["trans"], "trans").reshape(b, 3))
+        pe_id = None
+        for i, pred in enumerate(preds[t]):
+            img = level_images[i]
+            src1 = img[t + 1] if nxt else None
+            if automask and (pe_id is None or scale == "level"):       # at scale full one identity error serves every level
+                with torch.no_grad():
+                    pe_id = nops.photo_identity(img[t], img[t - 1], src1)
+            term = _MultiPhoto.apply(as_f32(pred["depth"], "pred depth"), rot0, trans0, rot1, trans1, cams[i][0], cams[i][1], img[t],
+                                     img[t - 1], src1, pe_id, 2 ** (i + 1) if scale == "full" else 1, smooth)
+            loss = loss + term * ((0.64 / (2. ** (i - 1))) / float(T - 1))
+    return loss
+
+
 def _loss_of(model, loss, gts, samples, preds, camera):
     """The training loss ``loss`` names: ``supervised`` = m4depth_loss against ground truth, ``photometric`` = photometric_loss
-    (its two settings are per-model: ``model.photo_smooth``, ``model.photo_automask``)."""
+    (its settings are per-model: ``model.photo_smooth``, ``model.photo_automask``, ``model.photo_scale``, ``model.photo_sources``)."""
     if loss == "supervised":
         return m4depth_loss(gts, preds, model.depth_type)
     if loss == "photometric":
-        return photometric_loss(samples, preds, camera, getattr(model, "photo_smooth", 1e-3), getattr(model, "photo_automask", True))
+        return photometric_loss(samples, preds, camera, getattr(model, "photo_smooth", 1e-3), getattr(model, "photo_automask", True),
+                                getattr(model, "photo_scale", "level"), getattr(model, "photo_sources", "prev"))
     raise ValueError(f"loss: expected one of {LOSSES}, got {loss!r}")
 
 

@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture of the step")
     ap.add_argument("--loss", default="supervised", choices=["supervised", "photometric"], help="training.LOSSES")
+    ap.add_argument("--photo_scale", default="level", choices=["level", "full"], help="--loss photometric: training.PHOTO_SCALES")
+    ap.add_argument("--photo_sources", default="prev", choices=["prev", "both"], help="--loss photometric: training.PHOTO_SOURCES")
     args = ap.parse_args()
     import m4depth_amd as M
     from m4depth_amd import synthetic as S, training as TR
@@ -33,6 +35,7 @@ def main():
     opt = torch.optim.Adam(model.parameters(), lr=1e-4, eps=1e-7, capturable=not args.eager)
     model.compile(optimizer=opt, metrics=[RootMeanSquaredLogError()])
     model.train_loss = args.loss
+    model.photo_scale, model.photo_sources = args.photo_scale, args.photo_sources
     samples, cam = S.make_sequence(args.batch, args.seq_len, args.height, args.width, seed=1)
     data = {k: torch.from_numpy(np.stack([s[k] for s in samples], axis=1)).to(dev) for k in ("depth", "RGB_im", "rot", "trans")}
     data["new_traj"] = np.stack([s["new_traj"] for s in samples], axis=1)
@@ -55,7 +58,7 @@ def main():
     print(json.dumps({"metric": "train sequences/s", "value": round(args.batch / dt, 2), "ms_per_step": round(dt * 1e3, 2),
                       "frames_per_s": round(args.batch * args.seq_len / dt, 1),
                       "config": f"{args.height}x{args.width} L={args.levels} batch {args.batch} seq_len {args.seq_len}",
-                      "loss": args.loss, "loss_first": losses[0], "loss_last": losses[-1],
+                      "loss": args.loss, "photo_scale": args.photo_scale, "photo_sources": args.photo_sources, "loss_first": losses[0], "loss_last": losses[-1],
                       "launch": "eager" if args.eager else "hipGraph replay of the whole step", "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}))
 
 
