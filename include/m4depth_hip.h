@@ -420,6 +420,39 @@ int m4d_photo_min_bwd(const float* depth, const float* warped0, const float* dwa
                       const float* cur, const unsigned char* sel, const float* out4, const float* g_out, int b, int h, int w,
                       float lambda, float* g_depth, void* stream);
 
+/* ---- Reprojection consistency: a label-free score of the full-resolution estimate (csrc/m4d_consistency.hip) ----------
+ * Scores the depth map a trajectory's frame was given against the previous frame of the same trajectory, without ground truth
+ * (main.py --consistency).  Per sample s of a batch, at the input resolution H x W:
+ *   D [H,W,1] the raw estimate of the current frame, Dp that of the previous frame; cur, prev [H,W,3] the two images;
+ *   rot (rot_c 3 or 4), trans the current frame's motion (a point X of the current camera is R X + t in the previous one);
+ *   cam_f, cam_c the sample's own full-resolution camera.
+ * Warp.  (warped, valid, qx, qy, Pz) = the query of m4d_photo_warp_fwd on D, clip to [0.01, 200] and `valid` included: the
+ *   same device functions in the same operation order (csrc/m4d_photo_common.h), the same bits; dwarp is not computed.
+ * Photometric part.  M(p) = p interior and all 9 window pixels valid (no auto-mask); pe_w = pe(warped, cur)(p),
+ *   pe_id = pe(prev, cur)(p) with pe and its double-precision window statistics as above; N = sum M.
+ * Geometric part (the depth-consistency term of Bian et al., NeurIPS 2019).  G(p) = valid(p) and the four bilinear taps of Dp
+ *   at the query are finite and > 0; Dq = m4d_lerp2 of those taps with the cell and alphas of the image sample;
+ *   g(p) = |Pz - Dq| / (Pz + Dq) in double from the float32 Pz and Dq; Ng = sum G.
+ * Row, six float32 values, each rounded once from double:
+ *   photo = sum_M pe_w / N;  photo_id = sum_M pe_id / N;  better = #{p in M: pe_w < pe_id} / N;  geo = sum_G g / Ng;
+ *   cover = N / ((H-2)(W-2));  geo_cover = Ng / (H W).
+ * counted[s] = active[s] && !reset[s] && N > 0 && Ng > 0, decided on the device; a sample that is not counted gets a row of
+ *   six zeros.  A sample with !active[s] || reset[s] has none of its images or depth maps read (its previous-frame buffers may
+ *   hold another trajectory or nothing): its blocks leave after reading the masks.
+ * Deterministic: block partials in double, wave64 shuffles, a fixed-order finish per sample, no atomics, no zero-fill (every
+ *   block writes its own partial); row s of a batch launch equals the row of a launch on sample s alone bit for bit.
+ * Layout: batch strides in floats (>= the dense image, H W or 3 H W), images dense: a frame slice of a [B,T,...] tensor is read
+ *   in place.  reset, active: uint8 [b] device masks; rows6 [b][6] floats, counted [b] bytes; workspace of
+ *   m4d_consistency_workspace_bytes(b, h, w) bytes, 8-byte aligned (-1: a size the call refuses).  Invalid argument, no launch:
+ *   a NULL pointer, b outside [1, 65535], h or w < 3, h w > 2^24, rot_c not in {3,4}, a stride below the dense image, a
+ *   workspace off 8 bytes.  Two plain launches (capturable).  Additive entry points: ABI 6 unchanged. */
+long long m4d_consistency_workspace_bytes(int b, int h, int w);
+int m4d_consistency_per_sample(const float* est, long long est_stride, const float* est_prev, long long est_prev_stride,
+                               const float* cur, long long cur_stride, const float* prev, long long prev_stride,
+                               const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,
+                               const unsigned char* reset, const unsigned char* active, int b, int h, int w, void* workspace,
+                               float* rows6, unsigned char* counted, void* stream);
+
 /* ---- m4depth_network.py: DepthEstimatorLevel glue -------------------------------- */
 
 /* Per-cut L2 normalisation (:179-189, tf.linalg.normalize, no epsilon). */

@@ -175,6 +175,9 @@ _SIGNATURES = {
     "m4d_photo_identity_fwd": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
     "m4d_photo_min_fwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp, _c_fp, _c_fp],
     "m4d_photo_min_bwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
+    "m4d_consistency_per_sample": [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp,
+                                   ctypes.c_longlong, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int,
+                                   _c_fp, _c_fp, _c_fp, _c_fp],
 }
 
 # include/m4depth_hip_experiments.h: present only in a `make EXPERIMENTS=1` build of the library (the launch tape and the
@@ -190,6 +193,7 @@ _LL_SIGNATURES = {"m4d_launch_count": [], "m4d_wino6_persistent_min_units": [], 
                   "m4d_bias_act_bwd_workspace_floats": [ctypes.c_longlong, _c_int], "m4d_loss_workspace_floats": [],
                   "m4d_train_log_workspace_bytes": [], "m4d_image_pyramid_floats": [_c_int, _c_int, _c_int, _c_int],
                   "m4d_photo_workspace_bytes": [_c_int, _c_int, _c_int], "m4d_photo_min_workspace_bytes": [_c_int, _c_int, _c_int],
+                  "m4d_consistency_workspace_bytes": [_c_int, _c_int, _c_int],
                   "m4d_depth_cloud_workspace_ints": [_c_int, _c_int, _c_int, _c_int],
                   "m4d_conv3x3_wgrad_workspace_floats": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]}
 _VOID_SIGNATURES = {"m4d_dscv_set_variant": [_c_int], "m4d_dscv_set_fallback_counter": [_c_fp],

@@ -6,6 +6,7 @@ A checkpoint is ``ckpt-<step>.npz`` (the network) plus ``ckpt-<step>.opt.pt`` (t
 """
 from __future__ import annotations
 
+import collections
 import csv
 import os
 import shutil
@@ -14,6 +15,22 @@ import shutil
 METRIC_COLUMNS = ("abs_rel", "sq_rel", "rmse", "rmsel", "a1", "a2", "a3")
 _LOWER_IS_BETTER = ("rmse", "rmsel", "abs_rel", "sq_rel")
 _HIGHER_IS_BETTER = ("a1", "a2", "a3")
+
+# What the best-N manager judges on: the table's columns and which of them are lower-is-better (the rest: higher is better).
+# A candidate beats a row when it wins strictly on a majority -- more than half -- of the columns.
+Criterion = collections.namedtuple("Criterion", ("columns", "lower"))
+DEFAULT_CRITERION = Criterion(METRIC_COLUMNS, _LOWER_IS_BETTER)            # today's seven: a majority is more than 3 of 7
+# a validation set without ground truth (main.py --val_consistency): the photometric part of the reprojection-consistency score
+PHOTO_CRITERION = Criterion(("photo",), ("photo",))
+
+
+def criterion_wins(criterion, candidate, row):
+    """How many of the criterion's columns ``candidate`` beats ``row`` on (strictly)."""
+    wins = 0
+    for m in criterion.columns:
+        c, r = float(candidate[m]), float(row[m])
+        wins += (r > c) if m in criterion.lower else (r < c)
+    return wins
 
 
 def checkpoint_steps(d):
@@ -73,9 +90,10 @@ def format_validation_line(metrics):
     return "".join(format(float(v), ".4f") + "\t\t" for v in metrics) + "\n"
 
 
-def append_validation_perfs(ckpt_dir, metrics):
+def append_validation_perfs(ckpt_dir, metrics, name="validation-perfs.txt"):
+    """One more line of ``<ckpt_dir>/<name>`` (validation-consistency.txt: the six means of main.py --val_consistency)."""
     os.makedirs(ckpt_dir, exist_ok=True)
-    with open(os.path.join(ckpt_dir, "validation-perfs.txt"), "a") as fh:
+    with open(os.path.join(ckpt_dir, name), "a") as fh:
         fh.write(format_validation_line(metrics))
 
 
@@ -96,10 +114,14 @@ class BestCheckpointManager:
       * while the table has fewer than ``keep_top_n`` rows, the checkpoint is backed up without comparison;
       * otherwise the rows are scanned in file order and the FIRST row the candidate beats on a majority (> 3 of 7) counts:
         the candidate is appended, and if the table then holds more than ``keep_top_n`` rows, that row and its files go.
-        No row beaten: nothing changes."""
+        No row beaten: nothing changes.
 
-    def __init__(self, train_dir, best_dir, keep_top_n=1):
+    ``criterion`` (default: the seven metrics) names the columns and their direction; a majority is more than half of them.  A
+    ``best_dir`` whose table has other columns than the criterion is refused (ValueError), never mixed."""
+
+    def __init__(self, train_dir, best_dir, keep_top_n=1, criterion=DEFAULT_CRITERION):
         self.train_dir, self.backup_dir, self.max_keep = train_dir, best_dir, int(keep_top_n)
+        self.criterion = criterion
         os.makedirs(self.backup_dir, exist_ok=True)
         self.perfs_file_name = os.path.join(self.backup_dir, "validation_perfs.csv")
 
@@ -107,14 +129,21 @@ class BestCheckpointManager:
         if not os.path.isfile(self.perfs_file_name):
             return []
         with open(self.perfs_file_name, newline="") as fh:
-            return list(csv.DictReader(fh))
+            rd = csv.DictReader(fh)
+            rows = list(rd)
+        want = list(self.criterion.columns) + ["ckpt_name"]
+        if list(rd.fieldnames or []) != want:
+            raise ValueError(f"{self.perfs_file_name} has the columns {rd.fieldnames}, this run judges on {want}: the best "
+                             "directory was made with another criterion -- use another --ckpt_dir or remove it")
+        return rows
 
     def _write_table(self, rows):
         with open(self.perfs_file_name, "w", newline="") as fh:
-            wr = csv.DictWriter(fh, fieldnames=list(METRIC_COLUMNS) + ["ckpt_name"])
+            names = list(self.criterion.columns) + ["ckpt_name"]
+            wr = csv.DictWriter(fh, fieldnames=names)
             wr.writeheader()
             for r in rows:
-                wr.writerow({k: r[k] for k in list(METRIC_COLUMNS) + ["ckpt_name"]})
+                wr.writerow({k: r[k] for k in names})
 
     def backup_last_ckpt(self):
         """Copies the latest checkpoint of the training directory (network and optimizer state); returns its file name."""
@@ -130,11 +159,12 @@ class BestCheckpointManager:
             fh.write('model_checkpoint_path: "%s"\nall_model_checkpoint_paths: "%s"\n' % (name, name))
 
     def update_backup(self, perfs):
-        """``perfs``: {column: value} of the 7 metrics (or their list in METRIC_COLUMNS order).  Returns True when the latest
-        checkpoint was backed up."""
+        """``perfs``: {column: value} of the criterion's columns (or their list in that order; default: the 7 metrics in
+        METRIC_COLUMNS order).  Returns True when the latest checkpoint was backed up."""
+        columns = self.criterion.columns
         if not isinstance(perfs, dict):
-            perfs = dict(zip(METRIC_COLUMNS, perfs))
-        cand = {m: float(perfs[m]) for m in METRIC_COLUMNS}
+            perfs = dict(zip(columns, perfs))
+        cand = {m: float(perfs[m]) for m in columns}
         rows = self.read_table()
         if len(rows) < self.max_keep:
             cand["ckpt_name"] = self.backup_last_ckpt()
@@ -142,7 +172,7 @@ class BestCheckpointManager:
             self._name_latest(cand["ckpt_name"])
             return True
         for i, row in enumerate(rows):
-            if majority_wins(cand, row) > 3:
+            if 2 * criterion_wins(self.criterion, cand, row) > len(columns):
                 cand["ckpt_name"] = self.backup_last_ckpt()
                 rows = rows + [cand]
                 if len(rows) > self.max_keep:

@@ -19,12 +19,12 @@
 // small; float32's cancellation in mean(x^2) - mu^2 against C2 = 9e-4 would otherwise be the largest error of the loss).
 // No atomics, no memset: block partials in double, wave64 shuffles, one fixed-order finish -- the same bits every run.
 #include "m4d_common.h"
+#include "m4d_photo_common.h"
 #include "../../include/m4depth_hip.h"
 
 namespace {
 
-constexpr int kTile = 16;
-constexpr double kC1 = 0.01 * 0.01, kC2 = 0.03 * 0.03;
+constexpr int kTile = kPhotoTile;
 
 // ---- image pyramid: 2x2 mean, ((a + b) + (c + d)) * 0.25 with a, b on the upper row ---------------------------------------
 __global__ void __launch_bounds__(256)
@@ -48,53 +48,28 @@ photo_warp_fwd_kernel(const float* __restrict__ depth, const float* __restrict__
                       float* __restrict__ warped, float* __restrict__ dwarp, unsigned char* __restrict__ valid) {
   const int bi = blockIdx.y;
   const M4dMotion m = m4d_load_motion(rot, rot_c, trans, cam_f, cam_c, bi);
-  // combined_mat = diag(fx,fy,1) @ [R|t] as in reproject_flow_kernel (m4d_geometry.hip): the same sequential dot products
-  const float T[3][4] = {{m.r00, m.r01, m.r02, m.tx}, {m.r10, m.r11, m.r12, m.ty}, {m.r20, m.r21, m.r22, m.tz}};
-  const float P[3][3] = {{m.fx, 0.f, 0.f}, {0.f, m.fy, 0.f}, {0.f, 0.f, 1.f}};
   float M[3][4];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float acc = P[r][0] * T[0][c];
-      acc = acc + P[r][1] * T[1][c];
-      acc = acc + P[r][2] * T[2][c];
-      M[r][c] = acc;
-    }
+  m4d_photo_matrix(m, M);
   const int hw = h * w;
   const float* img = prev + (long long)bi * hw * 3;
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += gridDim.x * blockDim.x) {
     const int i = p % w, j = p / w;
     const long long o = (long long)bi * hw + p;
     const float draw = depth[o];
-    const float d = fminf(fmaxf(draw, 0.01f), 200.0f);
-    const float mx = ((float)i + 0.5f) - m.cx;
-    const float my = ((float)j + 0.5f) - m.cy;
-    const float ux = mx / m.fx, uy = my / m.fy;
-    const float pos0 = ux * d, pos1 = uy * d, pos2 = 1.0f * d;
-    float pr[3], dpr[3];
+    const M4dPhotoQuery q = m4d_photo_query(m, M, i, j, draw, h, w);
+    const float ux = q.ux, uy = q.uy, qx = q.qx, qy = q.qy, ax = q.ax, ay = q.ay;
+    const float* pr = q.pr;
+    const int x0 = q.x0, y0 = q.y0;
+    float dpr[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      float acc = M[r][0] * pos0;
-      acc = acc + M[r][1] * pos1;
-      acc = acc + M[r][2] * pos2;
-      pr[r] = acc + M[r][3] * 1.0f;
-      dpr[r] = (M[r][0] * ux + M[r][1] * uy) + M[r][2];        // d pr[r] / d d
-    }
-    const float px = pr[0] / pr[2], py = pr[1] / pr[2];
-    const float qy = (float)j + (py - my);                     // dense_image_warp.py:244 on reproject's flow
-    const float qx = (float)i + (px - mx);
-    int y0, x0;
-    float ay, ax;
-    m4d_bilinear_axis(qy, h, y0, ay);
-    m4d_bilinear_axis(qx, w, x0, ax);
+    for (int r = 0; r < 3; ++r) dpr[r] = (M[r][0] * ux + M[r][1] * uy) + M[r][2];        // d pr[r] / d d
     // an axis whose alpha was clamped carries no gradient (the gradient of clip outside its bounds; NaN: none)
     const float ry = qy - (float)y0, rx = qx - (float)x0;
     const bool gy_on = ry >= 0.0f && ry <= 1.0f, gx_on = rx >= 0.0f && rx <= 1.0f;
     const float pz2 = pr[2] * pr[2];
     const float dqx = (dpr[0] * pr[2] - pr[0] * dpr[2]) / pz2;
     const float dqy = (dpr[1] * pr[2] - pr[1] * dpr[2]) / pz2;
-    const bool ok = pr[2] > 0.0f && qx >= 0.0f && qx <= (float)(w - 1) && qy >= 0.0f && qy <= (float)(h - 1) && isfinite(draw);
+    const bool ok = q.ok;
     const float* s = img + ((long long)y0 * w + x0) * 3;
     const long long rs = (long long)w * 3;
 #pragma unroll
@@ -112,39 +87,7 @@ photo_warp_fwd_kernel(const float* __restrict__ depth, const float* __restrict__
 // ---- shared pieces of the loss kernels -----------------------------------------------------------------------------------
 __device__ __forceinline__ float clip_depth(float d) { return fminf(fmaxf(d, 0.01f), 200.0f); }
 
-// window sums of one channel at LDS position `at` (row pitch S pixels, 3 floats per pixel)
-struct WinStats { double mx, my, n1, n2, d1, d2; };
-template <int S>
-__device__ __forceinline__ WinStats win_stats(const float* __restrict__ x, const float* __restrict__ y, int at, int c) {
-  double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      const int k = (at + dy * S + dx) * 3 + c;
-      const double a = (double)x[k], b = (double)y[k];
-      sx += a; sy += b; sxx += a * a; syy += b * b; sxy += a * b;
-    }
-  WinStats s;
-  s.mx = sx / 9.0; s.my = sy / 9.0;
-  const double vx = sxx / 9.0 - s.mx * s.mx, vy = syy / 9.0 - s.my * s.my, cxy = sxy / 9.0 - s.mx * s.my;
-  s.n1 = 2.0 * s.mx * s.my + kC1; s.n2 = 2.0 * cxy + kC2;
-  s.d1 = s.mx * s.mx + s.my * s.my + kC1; s.d2 = vx + vy + kC2;
-  return s;
-}
-
-template <int S>
-__device__ __forceinline__ double photo_error(const float* __restrict__ x, const float* __restrict__ y, int at) {
-  double pe = 0.0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const WinStats s = win_stats<S>(x, y, at, c);
-    const double ssim = (s.n1 * s.n2) / (s.d1 * s.d2);
-    pe += 0.85 * (1.0 - ssim) / 2.0 + 0.15 * fabs((double)x[at * 3 + c] - (double)y[at * 3 + c]);
-  }
-  return pe / 3.0;
-}
-
+// win_stats / photo_error: m4d_photo_common.h
 __device__ __forceinline__ double edge_weight(const float* __restrict__ cur, int a, int b) {
   const double d = (fabs((double)cur[b * 3] - (double)cur[a * 3]) + fabs((double)cur[b * 3 + 1] - (double)cur[a * 3 + 1]))
                    + fabs((double)cur[b * 3 + 2] - (double)cur[a * 3 + 2]);

@@ -309,7 +309,9 @@ class DataLoaderRecording(DataLoaderGeneric):
     a recording without depth.txt and leaves out the frames no depth file is associated with (``select_frames``): there every
     frame carries a map.  In a plain predict run ground truth is decoded where it exists; in a sequence batch that mixes
     frames with and without it the latter get an all-zero map.  ``allow_missing_depth`` (train only: the photometric loss needs
-    no ground truth) lifts the refusal for the 'train' use case in the same way: such frames get the all-zero map."""
+    no ground truth) lifts the refusal for the 'train' use case in the same way: such frames get the all-zero map.
+    ``allow_missing_depth_streams`` lifts it for the 'eval_streams' use case (main.py --consistency, which scores without ground
+    truth): every frame is kept, and a step without any ground truth carries no ``depth``."""
 
     def __init__(self, stride=1, min_baseline=0.0, max_gap=0.5):
         super().__init__("recording")
@@ -317,6 +319,7 @@ class DataLoaderRecording(DataLoaderGeneric):
         self.stride, self.min_baseline, self.max_gap = stride, min_baseline, max_gap
         self.require_depth = False                                  # predict: ground truth needed for every frame (gt / err panels)
         self.allow_missing_depth = False                            # train: a recording without depth.txt is accepted
+        self.allow_missing_depth_streams = False                    # eval_streams: the same (main.py --consistency), every frame kept
         self.recordings, self._tables = None, {}
 
     def _set_output_size(self, out_size=None):
@@ -339,6 +342,9 @@ class DataLoaderRecording(DataLoaderGeneric):
         need_depth = self.usecase != "predict" or self.require_depth
         if self.usecase == "train" and self.allow_missing_depth:
             need_depth = False
+        no_gt = self.usecase == "eval_streams" and self.allow_missing_depth_streams
+        if no_gt:
+            need_depth = False
         if need_depth:
             for rec in self.recordings:
                 if rec.depth is None:
@@ -354,7 +360,9 @@ class DataLoaderRecording(DataLoaderGeneric):
                 motions = relative_motions(np.stack([fr["T_wc"] for fr in frames])) if frames else []
                 rows = []
                 for i, (fr, m) in enumerate(zip(frames, motions)):
-                    row = {"id": i, "camera_l": fr["path"], "depth": fr["depth"] or "", "rec": ri, "timestamp": fr["t"]}
+                    # no_gt: the set is scored without ground truth, so none is read (not even where a recording has some)
+                    row = {"id": i, "camera_l": fr["path"], "depth": "" if no_gt else fr["depth"] or "", "rec": ri,
+                           "timestamp": fr["t"]}
                     row.update(zip(("qw", "qx", "qy", "qz", "tx", "ty", "tz"), (float(v) for v in m)))
                     rows.append(row)
                 if rows:

@@ -18,7 +18,10 @@ camera.
 ``--mode=train --log_dir DIR`` writes the training summaries (loss, RMSE_log, the reference's summary images) as a TensorBoard
 event file through ``m4depth_amd.summaries.TrainSummaryWriter``.
 ``--eval_streams B`` runs a dataset's streaming evaluation (no ``--db_seq_len``) with B whole trajectories side by side
-(m4depth_amd.stream_eval) and writes the same perfs file as the one-frame-at-a-time loop.
+(m4depth_amd.stream_eval) and writes the same perfs file as the one-frame-at-a-time loop.  ``--consistency`` adds a score that
+needs no ground truth (m4depth_amd.consistency: every frame's estimate against the previous frame, photometric and geometric)
+and its two files; ``--enable_validation --val_consistency`` validates a training run that way, best-N on ``photo`` where the
+validation set has no depth.
 ``--dataset=recording --records_path REC --height H --width W`` runs eval / predict on a user's own recording (frames, a
 TUM-style trajectory, a calibration with lens distortion: m4depth_amd.dataloaders.recording); the frames are undistorted and
 resized on the GPU.
@@ -81,6 +84,12 @@ def build_parser():
                         "one-frame-at-a-time loop.  0 = that loop")
     p.add_argument("--eval_streams_policy", default="lpt", choices=["lpt", "arrival"],
                    help="--eval_streams: the order trajectories are dealt to free slots (lpt = longest first, arrival = csv order)")
+    p.add_argument("--consistency", action="store_true",
+                   help="--eval_streams: also score every frame without ground truth -- the previous frame reprojected with the "
+                        "estimated depth against the current one (photo: SSIM + L1, the criterion) and the estimate against the "
+                        "previous frame's (geo, a diagnostic); m4depth_amd.consistency.  Writes perfs-consistency-<dataset>.txt "
+                        "and consistency-frames-<dataset>.txt; a set without ground truth (a recording without depth.txt) is then "
+                        "accepted and the seven metrics are skipped")
     p.add_argument("--host_input", action="store_true",
                    help="synthetic eval: hand every batch over from pinned HOST memory (the PCIe copy is part of the step) and "
                         "print the frames/s of the loop -- the PCIe-inclusive rate, next to bench.py's HBM-resident one")
@@ -137,6 +146,10 @@ def build_parser():
     p.add_argument("--val_records_path", default=None, help="--enable_validation: trajectory csv files of the validation set")
     p.add_argument("--val_dataset", default="kitti-raw", choices=["midair", "tartanair", "kitti-raw", "recording"],
                    help="--enable_validation: the validation set's dataset")
+    p.add_argument("--val_consistency", action="store_true",
+                   help="--enable_validation: validate as --eval_streams <batch_size> --consistency on whole trajectories instead "
+                        "of the 4-frame sequence batches, appending a line to validation-consistency.txt; required for a "
+                        "validation set without ground truth, where best-N is then judged on photo alone (lower is better)")
     p.add_argument("--keep_top_n", type=int, default=1,
                    help="validation: how many best checkpoints <ckpt_dir>/best keeps (callbacks.py:173-240)")
     # ablation flags, spelled as in m4depth_options.py:67-84
@@ -224,6 +237,9 @@ def recording_loader(args):
     panels = panels.split(",") if isinstance(panels, str) else panels
     loader.require_depth = any(p in ("gt", "err") for p in panels)      # those panels need ground truth for every frame
     loader.allow_missing_depth = getattr(args, "loss", "supervised") == "photometric"      # train: that loss reads no ground truth
+    # eval_streams under --consistency: a recording without depth.txt is scored without ground truth, every frame kept
+    loader.allow_missing_depth_streams = bool(getattr(args, "consistency", False)) and args.records_path is not None \
+        and not loader.has_depth(args.records_path)
     return loader
 
 
@@ -516,6 +532,9 @@ def validation_args(args):
     v.mode, v.dataset, v.records_path = "validation", args.val_dataset, args.val_records_path
     v.seq_len = v.db_seq_len = 4
     v.eval_streams, v.graph, v.stream, v.host_input, v.tf_checkpoint = 0, False, False, False, None
+    v.consistency = False
+    if args.val_consistency:          # whole trajectories, batch_size side by side, scored with and without ground truth
+        v.eval_streams, v.eval_streams_policy, v.db_seq_len, v.consistency = args.batch_size, "lpt", None, True
     return v
 
 
@@ -531,10 +550,11 @@ def validate_checkpoint(args, ablation, dev, path):
         model.load_numpy_weights(read_weights(path), dev)
         model.compile(metrics=default_metrics())
         metrics = evaluate(vargs, model, 0, 1, dev)
-        write_perfs(vargs, model, metrics)
+        if metrics is not None:
+            write_perfs(vargs, model, metrics)
         del model
         torch.cuda.synchronize()
-    write_validation(vargs, metrics)
+    write_validation(vargs, metrics, getattr(vargs, "consistency_means", None))
     return metrics
 
 
@@ -547,11 +567,20 @@ def write_perfs(args, model, metrics):
     print("wrote", path)
 
 
-def write_validation(args, metrics):
-    """main.py:132-142: the best-N manager judges the latest training checkpoint, and one line goes to validation-perfs.txt."""
-    CK.BestCheckpointManager(_train_dir(args), os.path.join(args.ckpt_dir, "best"), keep_top_n=args.keep_top_n) \
-        .update_backup(dict(zip(CK.METRIC_COLUMNS, metrics)))
-    CK.append_validation_perfs(args.ckpt_dir, metrics)
+def write_validation(args, metrics, consistency=None):
+    """main.py:132-142: the best-N manager judges the latest training checkpoint, and one line goes to validation-perfs.txt.
+    ``consistency`` (the six means of --consistency, or None) adds a line to validation-consistency.txt; where there are no
+    seven metrics (a validation set without ground truth) best-N is judged on its ``photo`` alone, lower is better."""
+    best = os.path.join(args.ckpt_dir, "best")
+    if metrics is not None:
+        CK.BestCheckpointManager(_train_dir(args), best, keep_top_n=args.keep_top_n) \
+            .update_backup(dict(zip(CK.METRIC_COLUMNS, metrics)))
+        CK.append_validation_perfs(args.ckpt_dir, metrics)
+    elif consistency is not None:
+        CK.BestCheckpointManager(_train_dir(args), best, keep_top_n=args.keep_top_n, criterion=CK.PHOTO_CRITERION) \
+            .update_backup({"photo": float(consistency[0])})
+    if consistency is not None:
+        CK.append_validation_perfs(args.ckpt_dir, consistency, "validation-consistency.txt")
 
 
 def _stream_frame(frame, dev):
@@ -565,6 +594,9 @@ def _stream_frame(frame, dev):
 def _check_eval_streams(parser, args):
     if args.eval_streams < 0:
         parser.error("--eval_streams must be >= 0")
+    if args.consistency and (not args.eval_streams or args.mode not in ("eval", "validation")):
+        parser.error("--consistency needs --eval_streams B (with or without --graph) in --mode=eval / --mode=validation: it scores "
+                     "whole trajectories, each frame against the one before it")
     if not args.eval_streams:
         return
     if args.mode not in ("eval", "validation"):
@@ -629,15 +661,29 @@ def eval_streams(args, model, dev):
     """Streaming evaluation with ``--eval_streams`` B slots (m4depth_amd.stream_eval): per step one ``stream_step`` (or a
     ``GraphedStream`` replay) and one per-sample metric launch into a preallocated [n_steps,B,7] / [n_steps,B] device log; no
     host read of any mask.  After the last step: one copy of the log to the host, the fold in the sequential order, and the
-    folded (total, count) loaded into the compiled metrics for the writer."""
+    folded (total, count) loaded into the compiled metrics for the writer.
+
+    ``--consistency`` adds one launch pair per step (``consistency.ConsistencyScorer``) into an [n_steps,B,6] / [n_steps,B] log
+    of its own and, after the last step, ``perfs-consistency-<dataset>.txt`` and ``consistency-frames-<dataset>.txt``; the means
+    are left in ``args.consistency_means``.  With ground truth the seven metrics are computed exactly as without the flag;
+    without it (a recording without depth.txt, csv files without a depth column) they are skipped.  Returns whether the seven
+    were computed."""
     import time
     from . import network_ops as nops
     from . import stream_eval as SE
+    has_gt = records_have_depth(args) if args.consistency else True    # without --consistency the loader refuses or the step fails
     ds, _ = dataset_batches(args, "eval_streams", 0, 1, dev)
     sched = ds.schedule
     n_steps, B = sched.cells.shape[:2]
-    rows = torch.empty((n_steps, B, 7), dtype=torch.float32, device=dev)
-    counted = torch.empty((n_steps, B), dtype=torch.uint8, device=dev)
+    if has_gt:
+        rows = torch.empty((n_steps, B, 7), dtype=torch.float32, device=dev)
+        counted = torch.empty((n_steps, B), dtype=torch.uint8, device=dev)
+    scorer = None
+    if args.consistency:                                           # one more launch pair per step into a log of its own
+        from . import consistency as CS
+        scorer = CS.ConsistencyScorer(copy_estimate=args.graph)    # GraphedStream's output buffer is overwritten by the next replay
+        c_rows = torch.empty((n_steps, B, len(CS.COLUMNS)), dtype=torch.float32, device=dev)
+        c_counted = torch.empty((n_steps, B), dtype=torch.uint8, device=dev)
     active = (sched.cells[..., 0] >= 0).sum(axis=1)                # the schedule's, known on the host without a device read
     runner, t0 = None, None
     for step, batch in enumerate(ds):
@@ -653,17 +699,37 @@ def eval_streams(args, model, dev):
             est = runner(frame)["depth"]
         else:
             est = model.stream_step(frame)["depth"]
-        nops.depth_metrics_per_sample(batch["depth"], est, batch["new_traj"], batch["active"], 80., rows=rows[step],
-                                      counted=counted[step])
-    rows_h, counted_h = rows.cpu().numpy(), counted.cpu().numpy()
+        if has_gt:
+            nops.depth_metrics_per_sample(batch["depth"], est, batch["new_traj"], batch["active"], 80., rows=rows[step],
+                                          counted=counted[step])
+        if scorer is not None:
+            scorer.step(frame, est, batch["reset"], batch["active"], c_rows[step], c_counted[step])
+    if has_gt:
+        rows_h, counted_h = rows.cpu().numpy(), counted.cpu().numpy()
+    if scorer is not None:
+        c_rows_h, c_counted_h = c_rows.cpu().numpy(), c_counted.cpu().numpy()
     if t0 is not None:
         dt = time.perf_counter() - t0
         n = int(active[1:].sum())
-        print(f"eval_streams {B} slots ({args.eval_streams_policy}, {'graph' if args.graph else 'eager'}): {n / dt:.1f} "
+        print(f"eval_streams {B} slots ({args.eval_streams_policy}, {'graph' if args.graph else 'eager'}"
+              f"{', consistency' if scorer is not None else ''}): {n / dt:.1f} "
               f"sample-frames/s over {n} active sample-frames of {n_steps - 1} steps (the first step excluded)")
-    total, count = SE.fold(rows_h, counted_h, sched.cells)
-    for i, m in enumerate(model.compiled_metrics):
-        m.load_state(torch.tensor(total[i], dtype=torch.float32, device=dev), count)
+    if has_gt:
+        total, count = SE.fold(rows_h, counted_h, sched.cells)
+        for i, m in enumerate(model.compiled_metrics):
+            m.load_state(torch.tensor(total[i], dtype=torch.float32, device=dev), count)
+    args.consistency_means = None
+    if scorer is not None:
+        c_total, c_count, frames = SE.fold_consistency(c_rows_h, c_counted_h, sched.cells)
+        args.consistency_means = SE.fold_result(c_total, c_count)
+        os.makedirs(args.ckpt_dir, exist_ok=True)
+        CS.write_perfs(CS.perfs_path(args.ckpt_dir, args.dataset), args.consistency_means)
+        CS.write_frames(CS.frames_path(args.ckpt_dir, args.dataset), frames)
+        for name, v in zip(CS.COLUMNS, args.consistency_means):
+            print(f"consistency {name}: {v:.6f}")
+        print(f"wrote {CS.perfs_path(args.ckpt_dir, args.dataset)} and {CS.frames_path(args.ckpt_dir, args.dataset)} "
+              f"({c_count} counted frames)")
+    return has_gt
 
 
 def evaluate(args, model, rank, world, dev):
@@ -679,7 +745,8 @@ def evaluate(args, model, rank, world, dev):
                                   cloud_step=args.cloud_stride, cloud_frame=args.cloud_frame)
     host_input = args.host_input and args.dataset == "synthetic" and args.mode != "predict"
     if args.eval_streams:
-        eval_streams(args, model, dev)
+        if not eval_streams(args, model, dev):
+            return None                                # no ground truth (--consistency): there are no seven metrics
         batches = ()
     elif args.dataset == "synthetic":
         batches = synthetic_batches(args, rank, world, dev, on_host=host_input)
@@ -795,6 +862,8 @@ def check_train_args(parser, args, world=None):
             parser.error("--enable_validation needs --db_path_config (the validation set's dataset root)")
         if world > 1:
             parser.error("--enable_validation runs in-process on one GPU: it is refused with several ranks")
+    elif args.val_consistency:
+        parser.error("--val_consistency needs --enable_validation (it chooses how that validation scores)")
     photo_opts = [f for f, on in (("photo_smooth", args.photo_smooth is not None), ("no_photo_automask", args.no_photo_automask),
                                       ("photo_scale", args.photo_scale is not None), ("photo_sources", args.photo_sources is not None)) if on]
     if args.loss != "supervised" and args.mode != "train":
@@ -816,7 +885,7 @@ def check_train_args(parser, args, world=None):
             scored = dl.get_loader("recording").has_depth(args.val_records_path)
         except ValueError as e:
             parser.error("--val_records_path %s" % e)
-        if not scored:
+        if not scored and not args.val_consistency:
             parser.error("--enable_validation: a recording of --val_records_path has no depth.txt -- validation scores against "
                          "ground truth, which such a recording does not have")
     if args.graph and args.mode in ("train", "finetune") and world > 1:
@@ -848,8 +917,8 @@ def main(argv=None):
     metrics = evaluate(args, model, rank, world, dev)
     if metrics is not None and rank == 0:
         write_perfs(args, model, metrics)
-        if args.mode == "validation":
-            write_validation(args, metrics)
+    if args.mode == "validation" and rank == 0:
+        write_validation(args, metrics, getattr(args, "consistency_means", None))
     return 0
 
 if __name__ == "__main__":

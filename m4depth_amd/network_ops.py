@@ -401,6 +401,53 @@ def depth_metrics_per_sample(gt, est, new_traj, active, max_d=80.0, rows=None, c
     return rows, counted
 
 
+def consistency_per_sample(est, est_prev, cur, prev, rot, trans, f, c, reset, active, rows=None, counted=None):
+    """The reprojection-consistency score (include/m4depth_hip.h, "Reprojection consistency") of every sample of a batch in one
+    launch pair: returns (rows [b,6] float32 = photo, photo_id, better, geo, cover, geo_cover; counted [b] uint8), device tensors.
+    ``est`` / ``est_prev`` [b,H,W,1] are the estimates of the current and the previous frame, ``cur`` / ``prev`` [b,H,W,3] the two
+    images (dense images at a batch stride: a frame slice of a [B,T,...] tensor is read in place), ``rot`` [b,3|4] / ``trans``
+    [b,3] the current frame's motion, ``f`` / ``c`` [b,2] the per-sample full-resolution cameras.  ``counted[s]`` = active[s] and
+    not reset[s] and N > 0 and Ng > 0, decided on the device (uint8 / bool [b] masks, never read by the host); an uncounted row is
+    six zeros and a masked-off sample's images and maps are not read.  Nothing synchronises.  ``rows`` / ``counted`` may be views
+    into a preallocated log (one step's row of an [n_steps,b,6] / [n_steps,b] tensor)."""
+    if est.dim() != 4 or est.shape[3] != 1:
+        raise ValueError(f"est: expected [b,H,W,1], got {tuple(est.shape)}")
+    b, h, w, _ = est.shape
+    if tuple(est_prev.shape) != (b, h, w, 1):
+        raise ValueError(f"est_prev: expected {(b, h, w, 1)}, got {tuple(est_prev.shape)}")
+    for name, t in (("cur", cur), ("prev", prev)):
+        if tuple(t.shape) != (b, h, w, 3):
+            raise ValueError(f"{name}: expected {(b, h, w, 3)}, got {tuple(t.shape)}")
+    for name, m in (("reset", reset), ("active", active)):
+        if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != (b,):
+            raise ValueError(f"{name}: expected a uint8 / bool [{b}] device tensor")
+    reset = reset.view(torch.uint8) if reset.dtype == torch.bool else reset
+    active = active.view(torch.uint8) if active.dtype == torch.bool else active
+    rot = as_f32(rot, "rot")
+    if rot.dim() != 2 or rot.shape[0] != b or rot.shape[1] not in (3, 4):
+        raise ValueError('Rotation must be expressed as a small angle (x,y,z) or a quaternion (w,x,y,z)')
+    trans, f, c = as_f32(trans, "trans").reshape(b, 3), as_f32(f, "f").reshape(b, 2), as_f32(c, "c").reshape(b, 2)
+    strides = [_batch_stride(t, n) for t, n in ((est, "est"), (est_prev, "est_prev"), (cur, "cur"), (prev, "prev"))]
+    if rows is None:
+        rows = torch.empty((b, 6), dtype=torch.float32, device=est.device)
+    if counted is None:
+        counted = torch.empty(b, dtype=torch.uint8, device=est.device)
+    if tuple(rows.shape) != (b, 6) or tuple(counted.shape) != (b,):
+        raise ValueError(f"rows must be [{b},6] and counted [{b}], got {tuple(rows.shape)} and {tuple(counted.shape)}")
+    nbytes = int(lib.m4d_consistency_workspace_bytes(b, h, w))
+    if nbytes < 0:
+        raise ValueError(f"consistency: a {b}x{h}x{w} batch is refused (h, w >= 3, h*w <= 2^24, b <= 65535)")
+    ws = _workspace("consistency", nbytes + 8, est.device)
+    ws_ptr = ctypes.c_void_p((ws.data_ptr() + 7) // 8 * 8)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(lib.m4d_consistency_per_sample(vp(est), strides[0], vp(est_prev), strides[1], vp(cur), strides[2], vp(prev), strides[3],
+                                         dptr(rot, "rot"), rot.shape[1], dptr(trans, "trans"), dptr(f, "f"), dptr(c, "c"),
+                                         dptr(reset, "reset", torch.uint8), dptr(active, "active", torch.uint8), b, h, w, ws_ptr,
+                                         dptr(rows, "rows"), dptr(counted, "counted", torch.uint8), stream_ptr()),
+          "m4d_consistency_per_sample")
+    return rows, counted
+
+
 EXPORT_FORMATS = {None: 0, "kitti16": 1, "midair16": 2}          # the `format` argument of m4d_depth_export
 EXPORT_PANELS = {"rgb": 0, "est": 1, "gt": 2, "err": 3}          # its panel kinds
 

@@ -108,6 +108,36 @@ def fold(rows, counted, cells, traj_order=None):
     return total, count
 
 
+def fold_consistency(rows, counted, cells, traj_order=None):
+    """``fold`` for the 6-column log of ``consistency.ConsistencyScorer`` (``consistency.COLUMNS``): the same sequential walk
+    (trajectory in ``traj_order``, default ascending = csv order; frame in order), the counted rows summed as ``total =
+    float32(total + v)``.  Returns (total float32 [6], count, frames) with ``frames`` the counted (trajectory, frame, row)
+    triples in the walk's order -- the per-frame file of ``main.py --consistency``."""
+    rows = np.asarray(rows, np.float32)
+    counted = np.asarray(counted)
+    cells = np.asarray(cells)
+    if rows.shape[:2] != cells.shape[:2] or counted.shape != cells.shape[:2] or rows.shape[2:] != (6,):
+        raise ValueError(f"fold: rows {rows.shape}, counted {counted.shape} and cells {cells.shape} disagree")
+    live = cells[..., 0] >= 0
+    st, sl = np.nonzero(live)
+    tr, fr = cells[st, sl, 0], cells[st, sl, 1]
+    if traj_order is None:
+        rank = tr
+    else:
+        pos = {int(t): i for i, t in enumerate(traj_order)}
+        rank = np.array([pos[int(t)] for t in tr], np.int64)
+    walk = np.lexsort((fr, rank))                    # trajectory, then frame
+    total = np.zeros(6, np.float32)
+    count = 0
+    frames = []
+    for k in walk:
+        if counted[st[k], sl[k]]:
+            total = (total + rows[st[k], sl[k]]).astype(np.float32)
+            count += 1
+            frames.append((int(tr[k]), int(fr[k]), rows[st[k], sl[k]].copy()))
+    return total, count, frames
+
+
 def fold_result(total, count):
     """``float32(total) / float32(count)`` (count 0 -> the totals themselves, as the writer's clamp to 1 gives)."""
     return (np.asarray(total, np.float32) / np.float32(max(int(count), 1))).astype(np.float32)
