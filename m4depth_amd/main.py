@@ -28,9 +28,9 @@ resized on the GPU.
 """
 from __future__ import annotations
 
-import argparse
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -39,129 +39,9 @@ from . import checkpoints as CK
 from . import dist as D
 from . import synthetic as S
 from .metrics import default_metrics
-from .network import M4Depth, M4depthAblationParameters, GraphedSequence
-
-
-def build_parser():
-    p = argparse.ArgumentParser(description="M4Depth (MI355X native) train / eval / predict driver")
-    p.add_argument("--mode", default="eval", choices=["train", "finetune", "eval", "validation", "predict"])
-    p.add_argument("--dataset", default="synthetic", choices=["synthetic", "midair", "tartanair", "kitti-raw", "recording"],
-                   help="a dataset of the reference (m4depth_options.py:11-14), the seeded synthetic one, or your own recording "
-                        "(--records_path = a recording directory or a directory of them, dataloaders/recording.py; needs "
-                        "--height and --width, no --db_path_config)")
-    p.add_argument("--db_path_config", default=None, help="json file with the dataset roots (m4depth_options.py:27-29)")
-    p.add_argument("--records_path", default=None, help="directory of trajectory csv files (m4depth_options.py:33-35)")
-    p.add_argument("--rec_stride", type=int, default=None, metavar="N",
-                   help="--dataset=recording: take every N-th frame of a trajectory (default 1)")
-    p.add_argument("--rec_min_baseline", type=float, default=None, metavar="METRES",
-                   help="--dataset=recording: of those, keep a frame when the camera centre has moved at least this far since "
-                        "the last kept frame (default 0)")
-    p.add_argument("--rec_max_gap", type=float, default=None, metavar="SECONDS",
-                   help="--dataset=recording: drop a frame whose bracketing poses are further apart than this; the next kept "
-                        "frame starts a new trajectory (default 0.5)")
-    p.add_argument("--no_augmentation", action="store_true")
-    p.add_argument("--epochs", type=int, default=1, help="train on a real dataset: passes over the records")
-    p.add_argument("--arch_depth", type=int, default=6, help="number of pyramid levels (m4depth_options.py:64)")
-    p.add_argument("--seq_len", type=int, default=4)
-    p.add_argument("--db_seq_len", type=int, default=None)
-    p.add_argument("--batch_size", type=int, default=1, help="GLOBAL batch (sharded over ranks)")
-    p.add_argument("--n_batches", type=int, default=2, help="synthetic dataset: batches to generate")
-    p.add_argument("--height", type=int, default=None, help="frame height (default: 384 synthetic, else the dataset's)")
-    p.add_argument("--width", type=int, default=None)
-    p.add_argument("--ckpt_dir", default="ckpt")
-    p.add_argument("--tf_checkpoint", default=None,
-                   help="TensorFlow checkpoint of the reference model (prefix, or a directory holding a 'checkpoint' state "
-                        "file, e.g. pretrained_weights/midair): used instead of <ckpt_dir>/train for the initial weights")
-    p.add_argument("--seed", type=int, default=1234)
-    p.add_argument("--graph", action="store_true", help="replay the sequence forward from a hipGraph")
-    p.add_argument("--stream", action="store_true",
-                   help="predict: run the frames as B independent streams with per-sample trajectory resets (M4Depth.stream_step; "
-                        "with --graph replayed from network.GraphedStream)")
-    p.add_argument("--eval_streams", type=int, default=0, metavar="N",
-                   help="eval / validation on a dataset's whole trajectories (no --db_seq_len): run N trajectories side by side "
-                        "as the samples of M4Depth.stream_step (with --graph replayed from network.GraphedStream), score each "
-                        "sample on the device and fold the scores in the sequential run's order -- the same perfs file as the "
-                        "one-frame-at-a-time loop.  0 = that loop")
-    p.add_argument("--eval_streams_policy", default="lpt", choices=["lpt", "arrival"],
-                   help="--eval_streams: the order trajectories are dealt to free slots (lpt = longest first, arrival = csv order)")
-    p.add_argument("--consistency", action="store_true",
-                   help="--eval_streams: also score every frame without ground truth -- the previous frame reprojected with the "
-                        "estimated depth against the current one (photo: SSIM + L1, the criterion) and the estimate against the "
-                        "previous frame's (geo, a diagnostic); m4depth_amd.consistency.  Writes perfs-consistency-<dataset>.txt "
-                        "and consistency-frames-<dataset>.txt; a set without ground truth (a recording without depth.txt) is then "
-                        "accepted and the seven metrics are skipped")
-    p.add_argument("--host_input", action="store_true",
-                   help="synthetic eval: hand every batch over from pinned HOST memory (the PCIe copy is part of the step) and "
-                        "print the frames/s of the loop -- the PCIe-inclusive rate, next to bench.py's HBM-resident one")
-    p.add_argument("--save_dir", default=None, metavar="DIR",
-                   help="predict: write every frame to DIR/s<slot>_t<trajectory>/<frame>_depth.png (16-bit, --save_format), "
-                        "encoded on the GPU and compressed in host threads (m4depth_amd.export), instead of predictions.npy")
-    p.add_argument("--save_format", default=None, choices=["kitti16", "midair16"],
-                   help="--save_dir: uint16 = depth * 256 (kitti16, the default) or float16 bits of 512 / depth (midair16)")
-    p.add_argument("--save_panels", default=None, metavar="LIST",
-                   help="--save_dir: comma list of rgb,est,gt,err -- also write <frame>_panels.png with these panels stacked "
-                        "vertically (default: none)")
-    p.add_argument("--save_range", type=float, nargs=2, default=None, metavar=("NEAR", "FAR"),
-                   help="--save_panels: the depths the colour scale of est / gt spans, linear in inverse depth (default 1 80)")
-    p.add_argument("--save_err_max", type=float, default=None,
-                   help="--save_panels: the relative error the colour scale of err saturates at (default 0.5)")
-    p.add_argument("--save_cloud", action="store_true",
-                   help="--save_dir: also write <frame>_cloud.ply, the estimate as coloured 3-D points (depths within "
-                        "--save_range), back-projected, posed and compacted on the GPU")
-    p.add_argument("--cloud_stride", type=int, default=None, metavar="N",
-                   help="--save_cloud: keep every N-th pixel of every N-th row (default 2)")
-    p.add_argument("--cloud_frame", default=None, choices=["world", "camera"],
-                   help="--save_cloud: coordinates in the frame of the trajectory's first camera (world, the default; the "
-                        "frame-to-frame motions are chained on the GPU) or of each frame's own camera")
-    p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
-    p.add_argument("--loss", default="supervised", choices=["supervised", "photometric"],
-                   help="train: supervised = the reference's log-depth L1 against ground truth; photometric = the reprojection "
-                        "loss between neighbouring frames (SSIM + L1, auto-masking, edge-aware smoothness), which needs poses "
-                        "but no ground-truth depth -- the way to finetune on a --dataset=recording without depth.txt")
-    p.add_argument("--photo_smooth", type=float, default=None,
-                   help="--loss=photometric: weight of the edge-aware smoothness term (default 1e-3, Monodepth2's value; not "
-                        "tuned for this network)")
-    p.add_argument("--no_photo_automask", action="store_true",
-                   help="--loss=photometric: keep the pixels whose unwarped previous frame already matches better (auto-masking off)")
-    p.add_argument("--photo_scale", default=None, choices=["level", "full"],
-                   help="--loss=photometric: level (default) = each term at its level's resolution against the image pyramid; "
-                        "full = every level's depth upsampled to the input resolution and compared there (Monodepth2's form)")
-    p.add_argument("--photo_sources", default=None, choices=["prev", "both"],
-                   help="--loss=photometric: prev (default) = frame t-1 only; both = the per-pixel minimum over frame t-1 and frame "
-                        "t+1, which drops pixels one neighbour does not see (needs quaternion rotations)")
-    p.add_argument("--save_every", type=int, default=0, help="train: checkpoint every N steps (0 = at the end)")
-    p.add_argument("--summary_interval", type=int, default=1200,
-                   help="train --graph: read the device-side step log every N steps (m4depth_options.py:47-49); it is also "
-                        "read at every epoch end and before every checkpoint")
-    p.add_argument("--log_dir", default=None, metavar="DIR",
-                   help="train: write a TensorBoard event file to DIR (m4depth_options.py:43; m4depth_amd.summaries): loss and "
-                        "RMSE_log of every step, and every --summary_interval steps the images of the reference's train_step "
-                        "(RGB_im, camera_prev_t_reproj, depth_gt, depth_lvl_i), converted on the GPU and compressed in host "
-                        "threads.  Rank 0 only")
-    p.add_argument("--max_keep", type=int, default=0,
-                   help="train: keep only the newest N checkpoints of <ckpt_dir>/train (0 = keep all)")
-    p.add_argument("--enable_validation", action="store_true",
-                   help="train: checkpoint at every epoch end and validate that checkpoint in-process (--mode=validation on "
-                        "--val_dataset / --val_records_path, seq_len 4 / db_seq_len 4), keeping the best-N in <ckpt_dir>/best")
-    p.add_argument("--val_records_path", default=None, help="--enable_validation: trajectory csv files of the validation set")
-    p.add_argument("--val_dataset", default="kitti-raw", choices=["midair", "tartanair", "kitti-raw", "recording"],
-                   help="--enable_validation: the validation set's dataset")
-    p.add_argument("--val_consistency", action="store_true",
-                   help="--enable_validation: validate as --eval_streams <batch_size> --consistency on whole trajectories instead "
-                        "of the 4-frame sequence batches, appending a line to validation-consistency.txt; required for a "
-                        "validation set without ground truth, where best-N is then judged on photo alone (lower is better)")
-    p.add_argument("--keep_top_n", type=int, default=1,
-                   help="validation: how many best checkpoints <ckpt_dir>/best keeps (callbacks.py:173-240)")
-    # ablation flags, spelled as in m4depth_options.py:67-84
-    for flag in ("DINL", "SNCV", "time_recurr", "feature_normalization", "feature_subdivision", "level_memory"):
-        p.add_argument(f"--no_{flag}", action="store_true")
-    return p
-
-
-def ablation_from_args(args):
-    return M4depthAblationParameters(not args.no_DINL, not args.no_SNCV, not args.no_time_recurr,
-                                     not args.no_feature_normalization, not args.no_feature_subdivision,
-                                     not args.no_level_memory)                  # m4depth_options.py:96-98
+from .network import M4Depth, GraphedSequence, GraphedStream
+from .options import (build_parser, ablation_from_args, check_args, check_recording_args, check_save_args,  # noqa: F401
+                      check_stream_args, check_train_args, _check_eval_streams, records_have_depth)
 
 
 def synthetic_batches(args, rank, world, dev, on_host=False):
@@ -212,18 +92,24 @@ def dataset_batches(args, usecase, rank, world, dev):
         roots = dataset_roots(args.db_path_config)
         loader = dl.get_loader(args.dataset)
     settings = dl.DataloaderParameters(roots, args.records_path, args.db_seq_len, args.seq_len, not args.no_augmentation)
+    kw = {"out_size": [args.height, args.width]} if args.height and args.width else {}
     if usecase == "eval_streams":
-        kw = {"out_size": [args.height, args.width]} if args.height and args.width else {}
         return loader.get_dataset(usecase, settings, batch_size=args.eval_streams, device=dev, seed=args.seed,
                                   slot_policy=args.eval_streams_policy, **kw), loader.depth_type
     streaming = usecase in ("eval", "predict") and args.db_seq_len is None
     if streaming and world > 1:
         raise SystemExit("streaming evaluation (no --db_seq_len) is sequential: run it on one rank")
-    per_rank = 1 if streaming else D.shard_range(args.batch_size, rank, world)[1] - D.shard_range(args.batch_size, rank, world)[0]
-    kw = {"out_size": [args.height, args.width]} if args.height and args.width else {}
-    ds = loader.get_dataset(usecase, settings, batch_size=per_rank, device=dev, seed=args.seed,
+    lo, hi = (0, 1) if streaming else D.shard_range(args.batch_size, rank, world)
+    ds = loader.get_dataset(usecase, settings, batch_size=hi - lo, device=dev, seed=args.seed,
                             shard=(0, 1) if streaming else (rank, world), **kw)
     return ds, loader.depth_type
+
+
+def input_batches(args, usecase, rank, world, dev, on_host=False):
+    """The batches ``--mode=eval|validation|predict`` runs over: the seeded synthetic ones or the dataset's."""
+    if args.dataset == "synthetic":
+        return synthetic_batches(args, rank, world, dev, on_host=on_host)
+    return dataset_batches(args, usecase, rank, world, dev)[0]
 
 
 def recording_loader(args):
@@ -233,41 +119,14 @@ def recording_loader(args):
     loader.stride = 1 if args.rec_stride is None else args.rec_stride
     loader.min_baseline = 0.0 if args.rec_min_baseline is None else args.rec_min_baseline
     loader.max_gap = 0.5 if args.rec_max_gap is None else args.rec_max_gap
-    panels = getattr(args, "save_panels", None) or ()
+    panels = args.save_panels or ()
     panels = panels.split(",") if isinstance(panels, str) else panels
     loader.require_depth = any(p in ("gt", "err") for p in panels)      # those panels need ground truth for every frame
-    loader.allow_missing_depth = getattr(args, "loss", "supervised") == "photometric"      # train: that loss reads no ground truth
+    loader.allow_missing_depth = args.loss == "photometric"             # train: that loss reads no ground truth
     # eval_streams under --consistency: a recording without depth.txt is scored without ground truth, every frame kept
-    loader.allow_missing_depth_streams = bool(getattr(args, "consistency", False)) and args.records_path is not None \
+    loader.allow_missing_depth_streams = args.consistency and args.records_path is not None \
         and not loader.has_depth(args.records_path)
     return loader
-
-
-def check_recording_args(parser, args):
-    """Refusals around ``--dataset=recording``: its ``--rec_*`` options belong to it alone, and a recording has no default
-    network size."""
-    given = [f for f in ("rec_stride", "rec_min_baseline", "rec_max_gap") if getattr(args, f) is not None]
-    if args.dataset != "recording":
-        if given:
-            parser.error("--%s is a --dataset=recording option" % given[0])
-        return
-    if args.height is None or args.width is None:
-        parser.error("--dataset=recording needs --height and --width (the size the frames are undistorted and resized to)")
-    if args.records_path is not None:
-        from .dataloaders.recording import find_recordings
-        try:
-            find_recordings(args.records_path)
-        except ValueError as e:
-            parser.error("--records_path %s" % e)
-    unit = 2 ** args.arch_depth
-    if args.height < unit or args.width < unit or args.height % unit or args.width % unit:
-        parser.error("--dataset=recording: --height and --width must be positive multiples of 2**arch_depth = %d" % unit)
-    if args.rec_stride is not None and args.rec_stride < 1:
-        parser.error("--rec_stride must be >= 1")
-    if args.rec_min_baseline is not None and not args.rec_min_baseline >= 0:
-        parser.error("--rec_min_baseline must be >= 0")
-    if args.rec_max_gap is not None and not args.rec_max_gap > 0:
-        parser.error("--rec_max_gap must be > 0")
 
 
 def _train_dir(args):
@@ -350,50 +209,194 @@ class _NonFiniteParameters(Exception):
     """Raised where a checkpoint would be written from non-finite parameters; carries the step."""
 
 
-def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
-    """``_train`` with the summary writer of ``--log_dir`` (rank 0; None without the option), closed on every way out."""
-    summary = None
-    if getattr(args, "log_dir", None) is not None and rank == 0:
-        from .summaries import TrainSummaryWriter
-        summary = TrainSummaryWriter(args.log_dir)
+class CheckpointWriter:
+    """The checkpoints of a training run, ``<ckpt_dir>/train/ckpt-<step>.npz`` with the optimizer state next to it: a step is
+    written once (rank 0) and the oldest files are pruned to ``--max_keep``."""
+
+    def __init__(self, args, model, opt, rank):
+        self.dir, self.max_keep, self.model, self.opt, self.rank = _train_dir(args), args.max_keep, model, opt, rank
+        self.saved, self.checked = set(), set()        # the steps written / the steps whose parameters were looked at
+
+    def path(self, step):
+        return os.path.join(self.dir, f"ckpt-{step}.npz")
+
+    def save(self, step):
+        """Writes the checkpoint of ``step``; returns its path, or None where nothing was written (rank != 0, or the step is
+        on disk already).  Raises ``_NonFiniteParameters`` instead of writing non-finite weights."""
+        # A step whose gradients are non-finite while its loss is finite (a stationary sample: DESIGN.md "Degenerate inputs",
+        # R6) leaves non-finite weights behind that TerminateOnNaN only sees one step later: look at the parameters where they
+        # are written -- once per save, reduced on the device, one host read, on every rank (the replicas hold the same
+        # weights, so all ranks stop together) -- never in the step itself.
+        if step not in self.checked:
+            self.checked.add(step)
+            if not bool(torch.stack([torch.isfinite(p.detach()).all() for p in self.model.parameters()]).all()):
+                raise _NonFiniteParameters(step)
+        if self.rank != 0 or step in self.saved:
+            return None
+        self.saved.add(step)
+        os.makedirs(self.dir, exist_ok=True)
+        path = self.path(step)
+        np.savez(path, **self.model.numpy_weights())
+        torch.save(self.opt.state_dict(), path[:-4] + ".opt.pt")
+        print("saved", path)
+        CK.prune_checkpoints(self.dir, self.max_keep)
+        return path
+
+
+class _Stepper:
+    """What ``train_loop`` asks of a training step.  ``step(data)`` takes one and returns the rows ``(step, loss, rmse)`` the
+    host knows right away, ``read()`` those it has to fetch; ``bad`` is the step of the first non-finite loss once its row
+    was seen (that row and the later ones are never returned); ``images(summary, step)`` draws the step just taken;
+    ``n_timed`` / ``rate()`` clock the steps after the first.  ``rmse`` is None where the batches have no ground truth:
+    RMSE_log is then a 0/0 masked mean, and the loss alone decides whether a step was bad."""
+
+    def __init__(self, model, rmse_log, step0, has_gt, grad_sync):
+        self.model, self.rmse_log, self.has_gt, self.grad_sync = model, rmse_log, has_gt, grad_sync
+        self.step0 = self.taken = step0
+        self.bad, self.t0, self.n_timed = None, None, 0
+
+    def read(self):
+        return []
+
+    def rate(self):
+        torch.cuda.synchronize()
+        return self.n_timed / (time.perf_counter() - self.t0)
+
+
+class EagerStepper(_Stepper):
+    """``model.train_step``: every step's loss is read as it is taken."""
+    mode = "eager"
+
+    def step(self, data):
+        out = self.model.train_step(data, grad_sync=self.grad_sync)
+        self.taken, self.data = self.taken + 1, data
+        loss = float(out["loss"])
+        if self.t0 is None:
+            self.t0 = time.perf_counter()
+        else:
+            self.n_timed += 1
+        if not np.isfinite(loss):
+            self.bad = self.taken
+            return []
+        rmse = float(out["RMSE_log"])
+        return [(self.taken, loss, rmse if self.has_gt else None)]
+
+    def images(self, summary, step):
+        summary.images(step, self.data, self.model.last_pyramid, self.data["camera"], has_gt=self.has_gt)
+
+
+class GraphStepper(_Stepper):
+    """``training.GraphedTrainStep``: the first batch runs its eager warm-up step (a real step: the same trajectory as the
+    eager loop) and the step is captured once; every later batch is copied into its static buffers and replayed.  Each step
+    ends with the device-side step log (``training.TrainStepLog``, ``log_rows`` rows), so ``step`` returns nothing and the
+    host reads only at ``read()``; the rows from the first non-finite loss on are discarded, the replayed steps after it
+    included."""
+    mode = "graph"
+
+    def __init__(self, model, rmse_log, step0, has_gt, grad_sync, opt, log_rows, dev):
+        super().__init__(model, rmse_log, step0, has_gt, grad_sync)
+        self.opt, self.log_rows, self.dev = opt, log_rows, dev
+        self.runner = self.step_log = self.geometry = None
+        self.logged = step0                            # the last step whose log row the host has read
+
+    def step(self, data):
+        from . import training as TR
+        check_graph_batch(data, self.geometry)
+        if self.runner is None:
+            self.geometry = _geometry(data)
+            self.step_log = TR.TrainStepLog(self.log_rows, self.dev)
+            self.runner = TR.GraphedTrainStep(self.model, data, self.opt, warmup=1, grad_sync=self.grad_sync,
+                                              step_log=self.step_log, loss=self.model.train_loss)
+            torch.cuda.synchronize()
+            self.t0 = time.perf_counter()
+        else:
+            self.runner(data)
+            self.n_timed += 1
+        self.taken += 1
+        return []
+
+    def read(self):
+        if self.runner is None or self.bad is not None:
+            return []
+        rows, first_bad = self.step_log.read()
+        out = []
+        for i, (loss, rmse) in enumerate(rows):
+            if first_bad >= 0 and i + self.logged - self.step0 >= first_bad:
+                break
+            if self.has_gt:
+                self.rmse_log._update(torch.tensor(rmse))                       # the compiled RMSE_log Mean
+            rmse = float(self.rmse_log.result())
+            out.append((self.logged + i + 1, float(loss), rmse if self.has_gt else None))
+        self.logged += len(rows)
+        if first_bad >= 0:
+            self.bad = self.step0 + first_bad + 1
+        return out
+
+    def images(self, summary, step):
+        summary.images(step, self.runner.static, self.runner.pyramid, self.runner.camera, has_gt=self.has_gt)
+
+
+def train_loop(args, stepper, ckpts, summary, epochs, step0=0, rank=0, validate=None):
+    """The training loop over ``epochs`` = (count, epoch -> batches); steps are numbered from ``step0``.  Returns the status.
+
+    The rows a step returns are reported at once (printed by rank 0 and handed to ``summary``, a TrainSummaryWriter or None);
+    the stepper is asked to ``read`` every ``--summary_interval`` steps counted from ``step0``, where ``--save_every`` divides
+    the step (no checkpoint is written from unread rows) and at every epoch end.  The images of a ``--summary_interval``-th
+    step are drawn after its rows are in (they tell whether it was finite) and before the next batch is handed over.
+    TerminateOnNaN (callbacks.py:69-132): a non-finite loss ends training with status 1 before any image or save; nothing of
+    that epoch is saved.  Non-finite parameters behind a finite loss are caught where a checkpoint is due (``ckpts.save``
+    raises): status 1, nothing written.  ``validate`` (``--enable_validation``): every epoch ends with its checkpoint, which
+    rank 0 hands to ``validate(path)``."""
+    def report(rows):
+        for step, loss, rmse in rows:
+            if rank == 0:
+                print(format_step(step, loss, rmse))
+            if summary is not None:
+                summary.scalars(step, loss, rmse)
+
+    n_epochs, epoch_batches = epochs
+    step = step0
     try:
-        return _train(args, ablation, rank, world, dev, epochs, depth_type, summary)
+        for epoch in range(n_epochs):
+            for data in epoch_batches(epoch):
+                rows = stepper.step(data)
+                step += 1
+                summary_due = (step - step0) % args.summary_interval == 0
+                save_due = args.save_every and step % args.save_every == 0
+                report(rows + stepper.read() if summary_due or save_due else rows)
+                if stepper.bad is not None:
+                    break
+                if summary_due and summary is not None:
+                    stepper.images(summary, step)
+                if save_due:
+                    ckpts.save(step)
+            report(stepper.read())
+            if stepper.bad is not None:
+                print(f"step {stepper.bad}: non-finite loss, training stopped (TerminateOnNaN): nothing of epoch {epoch + 1} "
+                      "is saved")
+                return 1
+            if validate is not None:
+                path = ckpts.save(step) or ckpts.path(step)
+                if rank == 0:
+                    validate(path)
+        if stepper.n_timed and rank == 0:
+            print(f"train ({stepper.mode}): {stepper.rate():.2f} steps/s over {stepper.n_timed} steps (the first step excluded)")
+        if not args.save_every or step % args.save_every != 0:
+            ckpts.save(step)
+        return 0
     except _NonFiniteParameters as e:
         print(f"step {e.args[0]}: non-finite parameters, training stopped: no checkpoint of this state is written")
         return 1
-    finally:
-        if summary is not None:
-            summary.close()
 
 
-def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summary=None):
-    """main.py:73-109: Adam(1e-4), RMSE_log as the tracked metric, resume from the latest checkpoint.
-    Several ranks = data parallel: the global batch is sharded and the gradients are averaged with
-    one RCCL all-reduce per step (dist.all_reduce_gradients).
-
-    ``--graph``: the first batch runs the eager warm-up step of ``training.GraphedTrainStep`` (a real step: the same
-    trajectory as the eager loop), the step is captured once, and every later batch is copied into its static buffers and
-    replayed; each step ends with the device-side step log (``training.TrainStepLog``), read every ``--summary_interval``
-    steps, before a checkpoint and at every epoch end -- the host reads nothing per step.
-
-    TerminateOnNaN (callbacks.py:69-132): a non-finite loss ends training with status 1; nothing of that epoch is saved (in
-    graph mode the steps replayed after the bad one are discarded with it) and the checkpoints on disk stay as they are.
-    Non-finite parameters behind a finite loss are caught where a checkpoint is due (``save``): status 1, nothing written.
-
-    ``summary`` (a ``summaries.TrainSummaryWriter``): every reported step's loss and RMSE_log go to it as they are printed, and
-    at every step where ``(step - step0) % summary_interval == 0`` the step's images -- in graph mode right after that step's
-    replay (and the log read that tells whether it was finite), before the next batch is copied into the static buffers.
-    Nothing is written for a step with a non-finite loss or a later one.
-
-    ``epochs`` = (count, epoch -> batches) (default: the dataset's, ``default_epochs``); ``depth_type`` defaults to the
-    dataset's."""
-    import time
+def _train_setup(args, ablation, dev, depth_type):
+    """main.py:73-109: the model with the weights ``load_weights`` finds, Adam(1e-4) with Keras's epsilon, RMSE_log as the
+    tracked metric, and the optimizer state of the latest checkpoint when there is one.  Returns (model, optimizer, RMSE_log
+    metric, the step to resume from, whether the batches carry ground truth)."""
     from . import training as TR
     from .metrics import RootMeanSquaredLogError
-    torch.manual_seed(42)                                                       # tf.random.set_seed(42), main.py:76
     if depth_type is None:
         depth_type = {"kitti-raw": "velodyne"}.get(args.dataset, "map")          # the loader's depth_type (main.py:79)
-    n_epochs, epoch_batches = epochs if epochs is not None else default_epochs(args, rank, world, dev)
     model = M4Depth(depth_type=depth_type, nbre_levels=args.arch_depth, ablation_settings=ablation, is_training=True)
     model.load_numpy_weights(load_weights(args, ablation), dev)
     TR.set_trainable(model)
@@ -401,13 +404,12 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
                            capturable=args.graph)
     rmse_log = RootMeanSquaredLogError()
     model.compile(optimizer=opt, metrics=[rmse_log])
-    model.train_loss = getattr(args, "loss", "supervised")
-    model.photo_smooth = 1e-3 if getattr(args, "photo_smooth", None) is None else args.photo_smooth
-    model.photo_automask = not getattr(args, "no_photo_automask", False)
-    model.photo_scale = getattr(args, "photo_scale", None) or "level"
-    model.photo_sources = getattr(args, "photo_sources", None) or "prev"
-    # a batch without ground truth (a recording without depth.txt under --loss=photometric): RMSE_log is a 0/0 masked mean,
-    # so it is neither printed nor logged, and the loss alone decides whether a step was bad
+    model.train_loss = args.loss
+    model.photo_smooth = 1e-3 if args.photo_smooth is None else args.photo_smooth
+    model.photo_automask = not args.no_photo_automask
+    model.photo_scale = args.photo_scale or "level"
+    model.photo_sources = args.photo_sources or "prev"
+    # a recording without depth.txt under --loss=photometric has no ground truth
     has_gt = args.dataset == "synthetic" or args.records_path is None or records_have_depth(args)
     ck = latest_checkpoint(args)
     step0 = 0
@@ -417,111 +419,33 @@ def _train(args, ablation, rank, world, dev, epochs=None, depth_type=None, summa
         if os.path.isfile(opt_path):
             opt.load_state_dict(torch.load(opt_path, map_location=dev))
             _set_capturable(opt, args.graph, dev)
-    sync = D.all_reduce_gradients if world > 1 else None
-    saved, checked = set(), set()
+    return model, opt, rmse_log, step0, has_gt
 
-    def save(step):
-        # A step whose gradients are non-finite while its loss is finite (a stationary sample: DESIGN.md "Degenerate inputs",
-        # R6) leaves non-finite weights behind that TerminateOnNaN only sees one step later: look at the parameters where they
-        # are written -- once per save, reduced on the device, one host read, on every rank (the replicas hold the same
-        # weights, so all ranks stop together) -- never in the step itself.
-        if step not in checked:
-            checked.add(step)
-            if not bool(torch.stack([torch.isfinite(p.detach()).all() for p in model.parameters()]).all()):
-                raise _NonFiniteParameters(step)
-        if rank != 0 or step in saved:
-            return None
-        saved.add(step)
-        os.makedirs(_train_dir(args), exist_ok=True)
-        path = os.path.join(_train_dir(args), f"ckpt-{step}.npz")
-        np.savez(path, **model.numpy_weights())
-        torch.save(opt.state_dict(), path[:-4] + ".opt.pt")
-        print("saved", path)
-        CK.prune_checkpoints(_train_dir(args), args.max_keep)
-        return path
 
-    def report(step, loss, rmse):
-        if rank == 0:
-            print(format_step(step, loss, rmse if has_gt else None))
+def train(args, ablation, rank, world, dev, epochs=None, depth_type=None):
+    """``--mode=train|finetune``: ``train_loop`` over ``epochs`` = (count, epoch -> batches) (default: the dataset's,
+    ``default_epochs``; ``depth_type`` defaults to the dataset's) with the eager or the ``--graph`` stepper.  Several ranks =
+    data parallel: the global batch is sharded and the gradients are averaged with one RCCL all-reduce per step
+    (dist.all_reduce_gradients).  ``--log_dir``: rank 0 writes the summaries; the writer is closed on every way out."""
+    summary = None
+    if args.log_dir is not None and rank == 0:
+        from .summaries import TrainSummaryWriter
+        summary = TrainSummaryWriter(args.log_dir)
+    try:
+        torch.manual_seed(42)                                                   # tf.random.set_seed(42), main.py:76
+        if epochs is None:
+            epochs = default_epochs(args, rank, world, dev)
+        model, opt, rmse_log, step0, has_gt = _train_setup(args, ablation, dev, depth_type)
+        sync = D.all_reduce_gradients if world > 1 else None
+        if args.graph:
+            stepper = GraphStepper(model, rmse_log, step0, has_gt, sync, opt, args.summary_interval + 1, dev)
+        else:
+            stepper = EagerStepper(model, rmse_log, step0, has_gt, sync)
+        validate = (lambda path: validate_checkpoint(args, ablation, dev, path)) if args.enable_validation else None
+        return train_loop(args, stepper, CheckpointWriter(args, model, opt, rank), summary, epochs, step0, rank, validate)
+    finally:
         if summary is not None:
-            summary.scalars(step, loss, rmse if has_gt else None)
-
-    step_log = runner = geometry = None
-    logged = [step0]                                  # graph mode: the last step whose log row the host has read
-
-    def read_log():
-        """Graph mode: hands the unread log rows to the host (prints, the compiled RMSE_log Mean); returns the step of the first
-        non-finite loss or None."""
-        rows, first_bad = step_log.read()
-        for i, (loss, rmse) in enumerate(rows):
-            if first_bad >= 0 and i + logged[0] - step0 >= first_bad:
-                break                                 # the steps after the bad one are discarded
-            if has_gt:
-                rmse_log._update(torch.tensor(rmse))
-            report(logged[0] + i + 1, float(loss), float(rmse_log.result()))
-        logged[0] += len(rows)
-        return step0 + first_bad + 1 if first_bad >= 0 else None
-
-    def images_due(step):
-        return summary is not None and nan_step is None and (step - step0) % max(args.summary_interval, 1) == 0
-
-    step, t0, n_timed, nan_step = step0, None, 0, None
-    for epoch in range(n_epochs):
-        for data in epoch_batches(epoch):
-            if args.graph:
-                check_graph_batch(data, geometry)
-                if runner is None:
-                    geometry = _geometry(data)
-                    step_log = TR.TrainStepLog(max(args.summary_interval, 1) + 1, dev)
-                    runner = TR.GraphedTrainStep(model, data, opt, warmup=1, grad_sync=sync, step_log=step_log,
-                                                 loss=model.train_loss)
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                else:
-                    runner(data)
-                    n_timed += 1
-                step += 1
-                if (step - step0) % max(args.summary_interval, 1) == 0 or (args.save_every and step % args.save_every == 0):
-                    nan_step = read_log()
-                if images_due(step):
-                    summary.images(step, runner.static, runner.pyramid, runner.camera, has_gt=has_gt)
-            else:
-                out = model.train_step(data, grad_sync=sync)
-                step += 1
-                loss = float(out["loss"])
-                if t0 is None:
-                    t0 = time.perf_counter()
-                else:
-                    n_timed += 1
-                if not np.isfinite(loss):
-                    nan_step = step
-                else:
-                    report(step, loss, float(out["RMSE_log"]))
-                    if images_due(step):
-                        summary.images(step, data, model.last_pyramid, data["camera"], has_gt=has_gt)
-            if nan_step is not None:
-                break
-            if args.save_every and step % args.save_every == 0:
-                save(step)
-        if args.graph and nan_step is None and runner is not None:
-            nan_step = read_log()
-        if nan_step is not None:
-            print(f"step {nan_step}: non-finite loss, training stopped (TerminateOnNaN): nothing of epoch {epoch + 1} is saved")
-            return 1
-        if args.enable_validation:
-            path = save(step)
-            if path is None and rank == 0:
-                path = os.path.join(_train_dir(args), f"ckpt-{step}.npz")
-            if rank == 0:
-                validate_checkpoint(args, ablation, dev, path)
-    if n_timed and rank == 0:
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(f"train ({'graph' if args.graph else 'eager'}): {n_timed / dt:.2f} steps/s over {n_timed} steps "
-              "(the first step excluded)")
-    if not args.save_every or step % args.save_every != 0:
-        save(step)
-    return 0
+            summary.close()
 
 
 def validation_args(args):
@@ -549,12 +473,20 @@ def validate_checkpoint(args, ablation, dev, path):
         model = M4Depth(nbre_levels=vargs.arch_depth, ablation_settings=ablation)
         model.load_numpy_weights(read_weights(path), dev)
         model.compile(metrics=default_metrics())
-        metrics = evaluate(vargs, model, 0, 1, dev)
-        if metrics is not None:
-            write_perfs(vargs, model, metrics)
+        metrics = evaluate_and_write(vargs, model, 0, 1, dev)
         del model
         torch.cuda.synchronize()
-    write_validation(vargs, metrics, getattr(vargs, "consistency_means", None))
+    return metrics
+
+
+def evaluate_and_write(args, model, rank, world, dev):
+    """``evaluate``, then what rank 0 writes from it: the perfs file where there are metrics and, in ``--mode=validation``,
+    the best-N update with its lines.  Returns the metrics."""
+    metrics, consistency = evaluate(args, model, rank, world, dev)
+    if metrics is not None and rank == 0:
+        write_perfs(args, model, metrics)
+    if args.mode == "validation" and rank == 0:
+        write_validation(args, metrics, consistency)
     return metrics
 
 
@@ -591,72 +523,6 @@ def _stream_frame(frame, dev):
     return out
 
 
-def _check_eval_streams(parser, args):
-    if args.eval_streams < 0:
-        parser.error("--eval_streams must be >= 0")
-    if args.consistency and (not args.eval_streams or args.mode not in ("eval", "validation")):
-        parser.error("--consistency needs --eval_streams B (with or without --graph) in --mode=eval / --mode=validation: it scores "
-                     "whole trajectories, each frame against the one before it")
-    if not args.eval_streams:
-        return
-    if args.mode not in ("eval", "validation"):
-        parser.error("--eval_streams is a --mode=eval / --mode=validation option")
-    if args.dataset == "synthetic":
-        parser.error("--eval_streams runs the trajectories of a real dataset (--dataset midair | tartanair | kitti-raw | recording)")
-    if args.db_seq_len is not None:
-        parser.error("--eval_streams evaluates whole trajectories: it excludes --db_seq_len")
-
-
-def records_have_depth(args):
-    """Whether the trajectory files of ``--records_path`` name a ground-truth map (the loader's depth column): known on the
-    host before anything is loaded."""
-    import glob
-    from . import dataloaders as dl
-    if args.dataset == "recording":
-        return dl.get_loader("recording").has_depth(args.records_path)
-    col = dl.get_loader(args.dataset)._depth_column()
-    files = sorted(glob.glob(os.path.join(args.records_path, "**/*.csv"), recursive=True))
-    if not files:
-        return False
-    with open(files[0], newline="") as fh:
-        return col in fh.readline().rstrip("\r\n").split("\t")
-
-
-def check_save_args(parser, args):
-    """Refusals of the ``--save_*`` options; fills in their defaults and parses ``--save_panels`` into a tuple."""
-    from .export import PANELS
-    others = [f for f in ("save_format", "save_panels", "save_range", "save_err_max") if getattr(args, f) is not None]
-    others += [f for f in ("save_cloud",) if args.save_cloud]
-    cloud_others = [f for f in ("cloud_stride", "cloud_frame") if getattr(args, f) is not None]
-    if args.save_dir is not None and cloud_others and not args.save_cloud:
-        parser.error("--%s needs --save_cloud" % cloud_others[0])
-    others += cloud_others
-    if args.cloud_stride is not None and args.cloud_stride < 1:
-        parser.error("--cloud_stride must be >= 1")
-    args.cloud_stride = 2 if args.cloud_stride is None else args.cloud_stride
-    args.cloud_frame = args.cloud_frame or "world"
-    if args.save_dir is None:
-        if others:
-            parser.error("--%s needs --save_dir" % others[0])
-        return
-    if args.mode != "predict":
-        parser.error("--save_dir is a --mode=predict option")
-    args.save_format = args.save_format or "kitti16"
-    panels = tuple(p for p in (args.save_panels or "").split(",") if p)
-    if len(panels) > 4 or any(p not in PANELS for p in panels):
-        parser.error("--save_panels: a comma list of up to four of %s, got %r" % (",".join(PANELS), args.save_panels))
-    args.save_panels = panels
-    args.save_range = tuple(args.save_range) if args.save_range is not None else (1.0, 80.0)
-    args.save_err_max = 0.5 if args.save_err_max is None else args.save_err_max
-    if not (0 < args.save_range[0] < args.save_range[1]):
-        parser.error("--save_range NEAR FAR needs 0 < NEAR < FAR")
-    if not args.save_err_max > 0:
-        parser.error("--save_err_max must be > 0")
-    if any(p in ("gt", "err") for p in panels) and args.dataset != "synthetic" and args.records_path is not None \
-            and not records_have_depth(args):
-        parser.error("--save_panels %s: the records of --records_path name no ground-truth map" % ",".join(panels))
-
-
 def eval_streams(args, model, dev):
     """Streaming evaluation with ``--eval_streams`` B slots (m4depth_amd.stream_eval): per step one ``stream_step`` (or a
     ``GraphedStream`` replay) and one per-sample metric launch into a preallocated [n_steps,B,7] / [n_steps,B] device log; no
@@ -664,11 +530,10 @@ def eval_streams(args, model, dev):
     folded (total, count) loaded into the compiled metrics for the writer.
 
     ``--consistency`` adds one launch pair per step (``consistency.ConsistencyScorer``) into an [n_steps,B,6] / [n_steps,B] log
-    of its own and, after the last step, ``perfs-consistency-<dataset>.txt`` and ``consistency-frames-<dataset>.txt``; the means
-    are left in ``args.consistency_means``.  With ground truth the seven metrics are computed exactly as without the flag;
-    without it (a recording without depth.txt, csv files without a depth column) they are skipped.  Returns whether the seven
-    were computed."""
-    import time
+    of its own and, after the last step, ``perfs-consistency-<dataset>.txt`` and ``consistency-frames-<dataset>.txt``.  With
+    ground truth the seven metrics are computed exactly as without the flag; without it (a recording without depth.txt, csv
+    files without a depth column) they are skipped.  Returns (whether the seven were computed, the six consistency means or
+    None)."""
     from . import network_ops as nops
     from . import stream_eval as SE
     has_gt = records_have_depth(args) if args.consistency else True    # without --consistency the loader refuses or the step fails
@@ -694,7 +559,6 @@ def eval_streams(args, model, dev):
                  "camera": batch["camera"]}
         if args.graph:
             if runner is None:
-                from .network import GraphedStream
                 runner = GraphedStream(model, frame)
             est = runner(frame)["depth"]
         else:
@@ -718,78 +582,30 @@ def eval_streams(args, model, dev):
         total, count = SE.fold(rows_h, counted_h, sched.cells)
         for i, m in enumerate(model.compiled_metrics):
             m.load_state(torch.tensor(total[i], dtype=torch.float32, device=dev), count)
-    args.consistency_means = None
+    means = None
     if scorer is not None:
         c_total, c_count, frames = SE.fold_consistency(c_rows_h, c_counted_h, sched.cells)
-        args.consistency_means = SE.fold_result(c_total, c_count)
+        means = SE.fold_result(c_total, c_count)
         os.makedirs(args.ckpt_dir, exist_ok=True)
-        CS.write_perfs(CS.perfs_path(args.ckpt_dir, args.dataset), args.consistency_means)
+        CS.write_perfs(CS.perfs_path(args.ckpt_dir, args.dataset), means)
         CS.write_frames(CS.frames_path(args.ckpt_dir, args.dataset), frames)
-        for name, v in zip(CS.COLUMNS, args.consistency_means):
+        for name, v in zip(CS.COLUMNS, means):
             print(f"consistency {name}: {v:.6f}")
         print(f"wrote {CS.perfs_path(args.ckpt_dir, args.dataset)} and {CS.frames_path(args.ckpt_dir, args.dataset)} "
               f"({c_count} counted frames)")
-    return has_gt
+    return has_gt, means
 
 
-def evaluate(args, model, rank, world, dev):
-    """The eval / validation / predict loop of ``model`` (compiled with the 7 metrics): returns the metrics all-gathered over the
-    ranks (numpy [7]), or None for predict (rank 0 has then written predictions.npy)."""
-    runner = None
-    preds = []
-    writer = namer = None
-    if args.mode == "predict" and args.save_dir is not None:
-        from .export import PredictionWriter
-        writer = PredictionWriter(args.save_dir, args.save_format, args.save_panels, near=args.save_range[0],
-                                  far=args.save_range[1], err_max=args.save_err_max, cloud=args.save_cloud,
-                                  cloud_step=args.cloud_stride, cloud_frame=args.cloud_frame)
-    host_input = args.host_input and args.dataset == "synthetic" and args.mode != "predict"
-    if args.eval_streams:
-        if not eval_streams(args, model, dev):
-            return None                                # no ground truth (--consistency): there are no seven metrics
-        batches = ()
-    elif args.dataset == "synthetic":
-        batches = synthetic_batches(args, rank, world, dev, on_host=host_input)
-        if host_input:
-            batches = list(batches)                # generation is not part of the measured loop
-    else:
-        batches, _ = dataset_batches(args, "predict" if args.mode == "predict" else "eval", rank, world, dev)
-    stream_runner = []
-
-    def predict(frame):
-        if not args.stream:
-            return model.predict_step(frame)["depth"]
-        sf = _stream_frame(frame, dev)
-        if not args.graph:
-            return model.stream_step(sf)["depth"]
-        if not stream_runner:
-            from .network import GraphedStream
-            stream_runner.append(GraphedStream(model, sf))
-        return stream_runner[0](sf)["depth"]
-
-    import time
-    t_save = None
-
-    def emit(frame):
-        """One predicted frame batch: to the writer (its export launch follows the forward -- or the graph replay -- on the
-        same stream; nothing is kept), or to the list predictions.npy is made of."""
-        nonlocal namer, t_save
-        est = predict(frame)
-        if writer is None:
-            preds.append(est.cpu().numpy())
-            return
-        if namer is None:
-            from .export import FrameNamer
-            namer = FrameNamer(est.shape[0])
-            t_save = time.perf_counter()
-        want_gt = any(p in ("gt", "err") for p in writer.panels)
-        cloud = {}
-        if writer.cloud:                                       # the cloud launches follow the forward / the replay on its stream
-            cloud = dict(rot=frame["rot"], trans=frame["trans"], camera=frame["camera"], reset=frame["new_traj"])
-        writer.submit(est, namer(frame["new_traj"]), gt=frame.get("depth") if want_gt else None,
-                      rgb=frame["RGB_im"] if "rgb" in writer.panels or writer.cloud else None, **cloud)
-
-    n_frames, t_loop = 0, None
+def evaluate_sequences(args, model, rank, world, dev):
+    """The eval / validation loop over sequence batches (eager ``test_step``, or with ``--graph`` an eager warm-up, a metric
+    reset and a ``GraphedSequence`` replayed for every batch) or over the streaming frames of a real dataset (4-D, no
+    ``--db_seq_len``: always ``test_step``); the compiled metrics accumulate.  ``--host_input``: the synthetic batches are
+    generated before the loop, uploaded inside it, and the rate after the first batch is printed."""
+    host_input = args.host_input and args.dataset == "synthetic"
+    batches = input_batches(args, "eval", rank, world, dev, on_host=host_input)
+    if host_input:
+        batches = list(batches)                    # generation is not part of the measured loop
+    runner, n_frames, t_loop = None, 0, None
     for batch_idx, data in enumerate(batches):
         if host_input:
             if batch_idx == 1:                                 # the first batch is the warm-up (allocations, graph capture)
@@ -797,110 +613,96 @@ def evaluate(args, model, rank, world, dev):
                 t_loop, n_frames = time.perf_counter(), 0
             data = _upload(data, dev)
             n_frames += data["RGB_im"].shape[0] * data["RGB_im"].shape[1]
-        if data["RGB_im"].dim() == 4:            # streaming frame of a real dataset (db_seq_len None)
-            if args.mode == "predict":
-                emit(data)
-            else:
-                model.test_step(data)
-            continue
-        if args.mode == "predict":
-            for t in range(data["RGB_im"].shape[1]):
-                frame = {k: data[k][:, t] for k in ("depth", "RGB_im", "rot", "trans", "new_traj")}
-                frame["camera"] = data["camera"]
-                emit(frame)
-            continue
-        if args.graph:
-            if runner is None:
-                model.test_step(data)              # eager warm-up (state and scratch allocation, packed weights)
-                for m in model.compiled_metrics:
-                    m.reset_state()
-                runner = GraphedSequence(model, data)
-            model.graphed_test_step(data, runner)
-        else:
+        if not args.graph or data["RGB_im"].dim() == 4:
             model.test_step(data)
-    if writer is not None:
-        writer.close()
-        if namer is not None:
-            dt = time.perf_counter() - t_save
-            print(f"predict: wrote {writer.frames} frames ({args.save_format}"
-                  + (", panels " + ",".join(writer.panels) if writer.panels else "")
-                  + (f", clouds at stride {writer.cloud_step}" if writer.cloud else "")
-                  + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
-        return None
-    if args.mode == "predict":
-        if rank == 0:
-            os.makedirs(args.ckpt_dir, exist_ok=True)
-            np.save(os.path.join(args.ckpt_dir, "predictions.npy"), np.concatenate(preds, axis=0))
-        return None
-    if host_input and t_loop is not None:
+            continue
+        if runner is None:
+            model.test_step(data)              # eager warm-up (state and scratch allocation, packed weights)
+            for m in model.compiled_metrics:
+                m.reset_state()
+            runner = GraphedSequence(model, data)
+        model.graphed_test_step(data, runner)
+    if t_loop is not None:
         torch.cuda.synchronize()
         dt = time.perf_counter() - t_loop
         if rank == 0 and n_frames:
             print(f"host-resident input (pinned memory, PCIe copy inside the step): {n_frames / dt:.1f} frames/s per rank "
                   f"over {n_frames} frames")
+
+
+def evaluate(args, model, rank, world, dev):
+    """``--mode=eval|validation`` of ``model`` (compiled with the 7 metrics).  Returns (metrics, consistency): the metrics
+    all-gathered over the ranks (numpy [7]), or None where the set has no ground truth (``--consistency``), and the six
+    consistency means, or None without ``--consistency``."""
+    consistency = None
+    if args.eval_streams:
+        has_gt, consistency = eval_streams(args, model, dev)
+        if not has_gt:
+            return None, consistency
+    else:
+        evaluate_sequences(args, model, rank, world, dev)
     gathered = D.all_gather_metric_states(model.compiled_metrics, dev)
-    return D.reduce_metric_states(gathered).cpu().numpy()
+    return D.reduce_metric_states(gathered).cpu().numpy(), consistency
 
 
-def check_train_args(parser, args, world=None):
-    """Refusals of the training workflow's options.  ``world``: the number of ranks (default: WORLD_SIZE of the environment,
-    what dist.init_from_env will see)."""
-    if world is None:
-        world = int(os.environ.get("WORLD_SIZE", "1"))
-    if args.summary_interval < 1:
-        parser.error("--summary_interval must be >= 1")
-    if args.log_dir is not None and args.mode not in ("train", "finetune"):
-        parser.error("--log_dir is a --mode=train / --mode=finetune option")
-    if args.max_keep < 0:
-        parser.error("--max_keep must be >= 0")
-    if args.keep_top_n < 1:
-        parser.error("--keep_top_n must be >= 1")
-    if args.enable_validation:
-        if args.val_records_path is None:
-            parser.error("--enable_validation needs --val_records_path (the validation set's trajectory csv files)")
-        if args.db_path_config is None:
-            parser.error("--enable_validation needs --db_path_config (the validation set's dataset root)")
-        if world > 1:
-            parser.error("--enable_validation runs in-process on one GPU: it is refused with several ranks")
-    elif args.val_consistency:
-        parser.error("--val_consistency needs --enable_validation (it chooses how that validation scores)")
-    photo_opts = [f for f, on in (("photo_smooth", args.photo_smooth is not None), ("no_photo_automask", args.no_photo_automask),
-                                      ("photo_scale", args.photo_scale is not None), ("photo_sources", args.photo_sources is not None)) if on]
-    if args.loss != "supervised" and args.mode != "train":
-        parser.error("--loss=%s is a --mode=train option" % args.loss)
-    if photo_opts and args.loss != "photometric":
-        parser.error("--%s needs --loss=photometric" % photo_opts[0])
-    if args.photo_smooth is not None and not args.photo_smooth >= 0:
-        parser.error("--photo_smooth must be >= 0")
-    if args.mode == "train" and args.loss == "supervised" and args.dataset == "recording" and args.records_path is not None:
-        try:
-            if not records_have_depth(args):
-                parser.error("--mode=train on a recording without depth.txt needs --loss=photometric (the supervised loss reads "
-                             "ground-truth depth)")
-        except ValueError:
-            pass                                   # a malformed --records_path: check_recording_args reports it
-    if args.enable_validation and args.val_dataset == "recording" and args.val_records_path is not None:
-        from . import dataloaders as dl
-        try:
-            scored = dl.get_loader("recording").has_depth(args.val_records_path)
-        except ValueError as e:
-            parser.error("--val_records_path %s" % e)
-        if not scored and not args.val_consistency:
-            parser.error("--enable_validation: a recording of --val_records_path has no depth.txt -- validation scores against "
-                         "ground truth, which such a recording does not have")
-    if args.graph and args.mode in ("train", "finetune") and world > 1:
-        parser.error("--graph training is refused with several ranks (RCCL inside a captured training step is not supported)")
+def predict(args, model, batches, rank, dev):
+    """``--mode=predict``: every frame of ``batches`` through ``predict_step`` (``--stream``: ``stream_step``, with ``--graph``
+    replayed from a ``GraphedStream`` built on the first frame).  With ``--save_dir`` each estimate goes to the
+    ``PredictionWriter`` (its export launch follows the forward -- or the graph replay -- on the same stream; nothing is
+    kept); without it rank 0 writes them all to ``<ckpt_dir>/predictions.npy``."""
+    from .export import FrameNamer, PredictionWriter
+    writer = namer = runner = t_save = None
+    if args.save_dir is not None:
+        writer = PredictionWriter(args.save_dir, args.save_format, args.save_panels, near=args.save_range[0],
+                                  far=args.save_range[1], err_max=args.save_err_max, cloud=args.save_cloud,
+                                  cloud_step=args.cloud_stride, cloud_frame=args.cloud_frame)
+        want_gt = any(p in ("gt", "err") for p in writer.panels)
+    preds = []
+    for data in batches:
+        frames = [data]                            # one streaming frame of a real dataset (4-D), or a batch of sequences
+        if data["RGB_im"].dim() != 4:
+            frames = [dict({k: data[k][:, t] for k in ("depth", "RGB_im", "rot", "trans", "new_traj")}, camera=data["camera"])
+                      for t in range(data["RGB_im"].shape[1])]
+        for frame in frames:
+            if not args.stream:
+                est = model.predict_step(frame)["depth"]
+            else:
+                sf = _stream_frame(frame, dev)
+                if not args.graph:
+                    est = model.stream_step(sf)["depth"]
+                else:
+                    if runner is None:
+                        runner = GraphedStream(model, sf)
+                    est = runner(sf)["depth"]
+            if writer is None:
+                preds.append(est.cpu().numpy())
+                continue
+            if namer is None:
+                namer = FrameNamer(est.shape[0])
+                t_save = time.perf_counter()
+            cloud = {}
+            if writer.cloud:                                   # the cloud launches follow the forward / the replay on its stream
+                cloud = dict(rot=frame["rot"], trans=frame["trans"], camera=frame["camera"], reset=frame["new_traj"])
+            writer.submit(est, namer(frame["new_traj"]), gt=frame.get("depth") if want_gt else None,
+                          rgb=frame["RGB_im"] if "rgb" in writer.panels or writer.cloud else None, **cloud)
+    if writer is None:
+        if rank == 0:
+            os.makedirs(args.ckpt_dir, exist_ok=True)
+            np.save(os.path.join(args.ckpt_dir, "predictions.npy"), np.concatenate(preds, axis=0))
+        return
+    writer.close()
+    if namer is not None:
+        dt = time.perf_counter() - t_save
+        print(f"predict: wrote {writer.frames} frames ({args.save_format}"
+              + (", panels " + ",".join(writer.panels) if writer.panels else "")
+              + (f", clouds at stride {writer.cloud_step}" if writer.cloud else "")
+              + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
 
 
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.stream and args.mode != "predict":
-        parser.error("--stream is a --mode=predict option")
-    _check_eval_streams(parser, args)
-    check_train_args(parser, args)
-    check_recording_args(parser, args)
-    check_save_args(parser, args)
+    check_args(parser, args)
     rank, world, _, dev = D.init_from_env()
     if args.eval_streams and world > 1:
         raise SystemExit("streaming evaluation (--eval_streams) is sequential over the trajectories: run it on one rank")
@@ -914,12 +716,12 @@ def main(argv=None):
     model = M4Depth(nbre_levels=args.arch_depth, ablation_settings=ablation)
     model.load_numpy_weights(load_weights(args, ablation), dev)
     model.compile(metrics=default_metrics())
-    metrics = evaluate(args, model, rank, world, dev)
-    if metrics is not None and rank == 0:
-        write_perfs(args, model, metrics)
-    if args.mode == "validation" and rank == 0:
-        write_validation(args, metrics, getattr(args, "consistency_means", None))
+    if args.mode == "predict":
+        predict(args, model, input_batches(args, "predict", rank, world, dev), rank, dev)
+    else:
+        evaluate_and_write(args, model, rank, world, dev)
     return 0
+
 
 if __name__ == "__main__":
     sys.exit(main())
