@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 import torch
 
@@ -17,190 +18,89 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_FLAVOUR = os.environ.get("M4D_LIB_FLAVOUR", "product")
 LIB_PATH = os.path.join(_HERE, "libm4depth_hip_exp.so" if LIB_FLAVOUR == "experiments" else "libm4depth_hip.so")
 
-ABI_VERSION = 6               # M4D_ABI_VERSION of include/m4depth_hip.h this binding was written for
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
-_c_fp = ctypes.c_void_p       # device pointers travel as void*
-_c_int = ctypes.c_int
-_c_f = ctypes.c_float
-
-class NormLevel(ctypes.Structure):
-    """m4d_norm_level of include/m4depth_hip.h (one map of m4d_normalize_levels)."""
-    _fields_ = [("x", ctypes.c_void_p), ("out", ctypes.c_void_p), ("pixels", ctypes.c_longlong), ("C", ctypes.c_int),
-                ("nbre_cuts", ctypes.c_int)]
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong}
+_RESTYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "void": None, "const char*": ctypes.c_char_p}
+_TYPEDEF = re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_FUNCTION = re.compile(r"([\w\s*]+?)\b(m4d_\w+)\s*\(([^()]*)\)")
+_DECLARATOR = re.compile(r"([\w\s*]*?)(\w+)\s*(\[\d*\])?")
 
 
-class ResetLevel(ctypes.Structure):
-    """m4d_reset_level of include/m4depth_hip.h (one level of m4d_pyramid_reset)."""
-    _fields_ = [("features", ctypes.c_void_p), ("state_features", ctypes.c_void_p), ("depth_state", ctypes.c_void_p),
-                ("parallax", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("other", ctypes.c_void_p),
-                ("h", ctypes.c_int), ("w", ctypes.c_int), ("C", ctypes.c_int), ("nbre_cuts", ctypes.c_int),
-                ("parallax_value", ctypes.c_float)]
+def parse_header(text):
+    """The C ABI of a header as ctypes: ``(structs, functions, abi_version)``.
+
+    structs: typedef name -> ``ctypes.Structure`` class; functions: ``m4d_*`` name -> (restype, argtypes, argnames), in the
+    header's order; abi_version: the value of ``M4D_ABI_VERSION`` (None when the header defines none).  The rules, all of them:
+      - scalars: ``int`` -> c_int, ``float`` -> c_float, ``long long`` -> c_longlong; ``const`` is ignored;
+      - return types: ``int``, ``long long``, ``void`` (None) and ``const char*`` (c_char_p);
+      - a parameter that points to a struct typedef'd anywhere in the same header -> POINTER(that Structure); a struct field
+        sees only the structs typedef'd before its own;
+      - every other pointer or array parameter (``const float* x``, ``const int dims[6]``, ``const void* const* maps``,
+        ``void* stream``, ...) -> c_void_p: the header cannot tell a host array from a device pointer;
+      - struct fields follow the scalar and pointer rules; ``int a, b;`` declares several scalars; both ``typedef struct tag
+        {...} name;`` and ``typedef struct {...} name;`` are read;
+      - anything else (another scalar type, a struct by value, a function pointer, an array as a struct FIELD -- it is stored
+        inline, not as a pointer --, a preprocessor line continued with a backslash, text that is no declaration) raises
+        ValueError quoting the declaration.  Nothing defaults."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    continued = re.search(r"^[ \t]*#.*\\[ \t]*$", text, re.M)
+    if continued:
+        raise ValueError(f"m4depth_amd: no rule for a continued preprocessor line, `{continued.group(0).strip()}`")
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+M4D_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, re.M)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)                                  # guards, includes, the macro
+    text = re.sub(r'extern\s+"C"\s*\{|^[ \t]*\}[ \t]*$', "", text, flags=re.M)           # ... and what they wrap
+    structs = {}
+
+    def ctype(decl, where):
+        """(ctypes type, name) of one ``type name`` / ``type name[n]`` declarator."""
+        m = _DECLARATOR.fullmatch(decl.strip())
+        base = " ".join(w for w in (m.group(1).replace("*", " ") if m else "").split() if w != "const")
+        if m and base and (m.group(3) or "*" in m.group(1)):
+            struct = structs.get(base) if m.group(1).count("*") == 1 and not m.group(3) else None
+            return (ctypes.POINTER(struct) if struct else ctypes.c_void_p), m.group(2)
+        if base not in _SCALARS:
+            raise ValueError(f"m4depth_amd: no ctypes rule for `{decl.strip()}` in `{' '.join(where.split())}`")
+        return _SCALARS[base], m.group(2)
+
+    def typedef(m):
+        fields = []
+        for line in filter(None, (f.strip() for f in m.group(1).split(";"))):
+            first, *more = (d.strip() for d in line.split(","))
+            t, name = ctype(first, m.group(0))
+            if "[" in line or more and (t not in _SCALARS.values() or not all(re.fullmatch(r"\w+", d) for d in more)):
+                raise ValueError(f"m4depth_amd: no rule for an array field, and only plain scalars share a line: `{line}` of "
+                                 f"`{' '.join(m.group(0).split())}`")
+            fields += [(name, t)] + [(d, t) for d in more]
+        structs[m.group(2)] = type(m.group(2), (ctypes.Structure,), {"_fields_": fields})
+        return ""
+
+    functions = {}
+    for stmt in filter(None, (s.strip() for s in _TYPEDEF.sub(typedef, text).split(";"))):
+        m = _FUNCTION.fullmatch(stmt)
+        ret = re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())) if m else None
+        if ret not in _RESTYPES:
+            raise ValueError(f"m4depth_amd: no ctypes rule for the declaration `{' '.join(stmt.split())}`")
+        params = [] if m.group(3).strip() in ("", "void") else [ctype(p, stmt) for p in m.group(3).split(",")]
+        functions[m.group(2)] = (_RESTYPES[ret], tuple(t for t, _ in params), tuple(n for _, n in params))
+    return structs, functions, int(version.group(1)) if version else None
 
 
-# name -> argtypes; mirrors include/m4depth_hip.h one for one.
-_SIGNATURES = {
-    "m4d_backproject_fwd": [_c_fp, _c_fp, ctypes.POINTER(_c_int), _c_fp, _c_fp],
-    "m4d_backproject_bwd": [_c_fp, _c_fp, _c_fp, ctypes.POINTER(_c_int), _c_fp, _c_fp, _c_fp],
-    "m4d_dense_image_warp": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp],
-    "m4d_interpolate_bilinear": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp],
-    "m4d_parallax2depth": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_depth2parallax": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_prev_d2para": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_recompute_depth": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_reproject_flow": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_dscv_fwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp,
-                     _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                     _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_dscv_sncv_fwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp,
-                          _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                          _c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_f, _c_int, _c_fp, _c_int, _c_fp],
-    "m4d_sncv_fwd": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_fp],
-    "m4d_dscv_bwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp,
-                     _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                     _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_sncv_bwd": [_c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                     _c_int, _c_f, _c_fp, _c_fp, _c_fp],
-    "m4d_resize_bilinear_v1_bwd": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_level_post_bwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
-                           _c_fp, _c_fp],
-    "m4d_normalize_cuts_bwd": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_bias_act_bwd": [_c_fp, _c_fp, ctypes.c_longlong, _c_int, _c_f, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_pack_conv_weights": [_c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_pack_conv_weights_lat": [_c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_loss_level_fwd": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp],
-    "m4d_loss_level_bwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_decode_rgb8_resize": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_decode_depth_resize": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, ctypes.POINTER(_c_int),
-                                _c_fp, _c_fp],
-    "m4d_undistort_map": [_c_int, ctypes.POINTER(_c_f), ctypes.POINTER(_c_f), ctypes.POINTER(_c_f), _c_int, _c_int, _c_int, _c_int,
-                          _c_fp, _c_fp],
-    "m4d_decode_rgb8_remap": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_decode_depth16_remap": [_c_fp, _c_fp, _c_f, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_depth_export": [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, _c_int, _c_int,
-                         _c_int, _c_fp, _c_int, ctypes.POINTER(_c_int), _c_fp, _c_f, _c_f, _c_f, _c_fp, _c_fp],
-    "m4d_pose_accumulate": [_c_fp, _c_int, _c_fp, _c_fp, _c_int, _c_fp, _c_fp],
-    "m4d_depth_cloud": [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int,
-                        _c_f, _c_f, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_summary_images": [_c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(_c_int),
-                           ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
-                           ctypes.POINTER(ctypes.c_longlong), _c_int, _c_fp, _c_fp],
-    "m4d_normalize_cuts": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_resize_bilinear_v1": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_resize_nearest": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_bias_act": [_c_fp, _c_fp, ctypes.c_longlong, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_dinl_fwd": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp, _c_fp],
-    "m4d_dinl_fwd_padded": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp,
-                            _c_int, _c_int, _c_int, _c_int, _c_fp],
-    "m4d_bias_act_padded": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_fp],
-    "m4d_conv3x3_bias_act": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_conv3x3_bias_act_ws": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp,
-                                _c_fp, ctypes.c_longlong, _c_fp],
-    "m4d_conv3x3s_bias_act_ws": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f,
-                                 _c_fp, _c_fp, ctypes.c_longlong, _c_fp],
-    "m4d_conv3x3s_bias_act_wsb": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f,
-                                  _c_fp, _c_fp, ctypes.c_longlong, _c_fp],
-    "m4d_conv3x3_small_bias_act": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_conv3x3s_small_bias_act": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_conv3x3_small6_bias_act": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_conv3x3_lat": [_c_fp, _c_int, ctypes.c_longlong, _c_fp, _c_f, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f,
-                        _c_int, _c_int, _c_int, _c_fp, ctypes.c_longlong, _c_fp],
-    "m4d_conv3x3s_lat": [_c_fp, _c_int, ctypes.c_longlong, _c_fp, _c_f, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                         _c_f, _c_int, _c_int, _c_int, _c_fp, ctypes.c_longlong, _c_fp],
-    "m4d_conv3x3_lat_f16": [_c_fp, _c_int, ctypes.c_longlong, _c_fp, _c_f, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int,
-                            _c_f, _c_int, _c_int, _c_int, _c_fp, ctypes.c_longlong, _c_fp],
-    "m4d_partial_finish": [_c_fp, _c_int, ctypes.c_longlong, _c_fp, _c_f, ctypes.c_longlong, _c_int, _c_fp, _c_fp],
-    "m4d_conv3x3_wino_bias_act": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_conv3x3_wino2_bias_act": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_conv3x3_wino6_bias_act": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_conv3x3_wino6_bias_act_k": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_int, _c_fp],
-    "m4d_conv3x3_wino6_bias_act_ks": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_int,
-                                      _c_int, _c_int, _c_fp],
-    "m4d_conv3x3_winof16_bias_act_ks": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_fp,
-                                        _c_int, _c_int, _c_fp],
-    "m4d_enc_head_fwd": [_c_fp, _c_int, ctypes.c_longlong, ctypes.c_longlong, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int,
-                         _c_fp, _c_fp, _c_fp],
-    "m4d_enc_level0_stats": [_c_fp, _c_int, ctypes.c_longlong, ctypes.c_longlong, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp,
-                             _c_fp],
-    "m4d_enc_level0_apply": [_c_fp, _c_int, ctypes.c_longlong, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp,
-                             _c_fp, _c_f, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_enc_level0_fwd": [_c_fp, _c_int, ctypes.c_longlong, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp, _c_fp, _c_f,
-                           _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp],
-    "m4d_conv3x3s2_dinl_bias_act": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                    _c_f, _c_fp, _c_fp],
-    "m4d_refiner_tail": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
-                         _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_refiner_tail6": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
-                          _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_depth_metrics": [_c_fp, _c_fp, ctypes.c_longlong, _c_f, _c_fp, _c_fp, _c_fp, _c_f, _c_fp, _c_fp],
-    "m4d_depth_metrics_strided": [_c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_f, _c_fp, _c_fp, _c_fp,
-                                  _c_f, _c_fp, _c_fp],
-    "m4d_level_pre": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int,
-                      _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_level_pre_normalize": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int,
-                                _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_fp,
-                                _c_fp, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_level_front_supported": [_c_int, _c_int, _c_int, _c_int, _c_int],
-    "m4d_pyramid_reset_supported": [_c_int, _c_int],
-    "m4d_pyramid_reset": [ctypes.POINTER(ResetLevel), _c_int, _c_int, _c_fp],
-    "m4d_normalize_levels": [ctypes.POINTER(NormLevel), _c_int, _c_fp],
-    "m4d_level_front_small_supported": [_c_int, _c_int, _c_int, _c_int],
-    "m4d_level_front_small": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp,
-                              _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_f, _c_fp],
-    "m4d_level_front": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp,
-                        _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_f, _c_fp],
-    "m4d_level_front_r": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp,
-                          _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_f, _c_fp],
-    "m4d_conv3x3_wgrad": [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, ctypes.c_longlong, _c_fp, _c_fp],
-    "m4d_dilate2": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_camera_pyramid": [_c_fp, _c_fp, _c_int, _c_int, _c_fp, _c_fp, _c_fp],
-    "m4d_level_post": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
-                       _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_refiner_tail_m": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
-                           _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp],
-    "m4d_refiner_tail6_m": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
-                            _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp],
-    "m4d_level_post_m": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f,
-                         _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_f, _c_fp],
-    "m4d_stream_prepare": [_c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_depth_metrics_per_sample": [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_f, _c_fp,
-                                     _c_fp, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_train_log_step": [_c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_int, _c_fp,
-                           _c_fp, _c_fp, _c_fp],
-    "m4d_image_pyramid_box": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_photo_warp_fwd": [_c_fp, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_photo_loss_fwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_int, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_photo_loss_bwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_upsample_hp_fwd": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_upsample_hp_bwd": [_c_fp, _c_int, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_photo_identity_fwd": [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp],
-    "m4d_photo_min_fwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp, _c_fp, _c_fp],
-    "m4d_photo_min_bwd": [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_f, _c_fp, _c_fp],
-    "m4d_consistency_per_sample": [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp,
-                                   ctypes.c_longlong, _c_fp, _c_int, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int,
-                                   _c_fp, _c_fp, _c_fp, _c_fp],
-}
+def _parse(name):
+    with open(os.path.join(_INCLUDE, name)) as f:
+        return parse_header(f.read())
 
+
+# include/m4depth_hip.h is the only statement of the ABI: the signatures, both structs and the version are read from it
+_structs, SIGNATURES, ABI_VERSION = _parse("m4depth_hip.h")                     # ABI_VERSION = the header's M4D_ABI_VERSION
+NormLevel, ResetLevel = _structs["m4d_norm_level"], _structs["m4d_reset_level"]
 # include/m4depth_hip_experiments.h: present only in a `make EXPERIMENTS=1` build of the library (the launch tape and the
 # selectors of the not-dispatched Winograd kernels); bound when the library has them, ``has_experiments`` says whether
-_EXPERIMENT_SIGNATURES = {"m4d_tape_begin": [], "m4d_tape_end": [], "m4d_tape_length": [_c_int], "m4d_tape_replay": [_c_int, _c_fp],
-                          "m4d_tape_free": [_c_int]}
-_EXPERIMENT_VOID_SIGNATURES = {"m4d_wino6_set_variant": [_c_int], "m4d_wino6_set_half_tile_max_workgroups": [_c_int]}
-EXPERIMENT_SYMBOLS = list(_EXPERIMENT_SIGNATURES) + list(_EXPERIMENT_VOID_SIGNATURES)
-
-_LL_SIGNATURES = {"m4d_launch_count": [], "m4d_wino6_persistent_min_units": [], "m4d_conv3x3_workspace_floats": [_c_int, _c_int, _c_int, _c_int],
-                  "m4d_dinl_workspace_floats": [_c_int, _c_int], "m4d_metrics_workspace_bytes": [],
-                  "m4d_metrics_per_sample_workspace_bytes": [_c_int],
-                  "m4d_bias_act_bwd_workspace_floats": [ctypes.c_longlong, _c_int], "m4d_loss_workspace_floats": [],
-                  "m4d_train_log_workspace_bytes": [], "m4d_image_pyramid_floats": [_c_int, _c_int, _c_int, _c_int],
-                  "m4d_photo_workspace_bytes": [_c_int, _c_int, _c_int], "m4d_photo_min_workspace_bytes": [_c_int, _c_int, _c_int],
-                  "m4d_consistency_workspace_bytes": [_c_int, _c_int, _c_int],
-                  "m4d_depth_cloud_workspace_ints": [_c_int, _c_int, _c_int, _c_int],
-                  "m4d_conv3x3_wgrad_workspace_floats": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]}
-_VOID_SIGNATURES = {"m4d_dscv_set_variant": [_c_int], "m4d_dscv_set_fallback_counter": [_c_fp],
-                    "m4d_dscv_set_ablation": [_c_int], "m4d_dscv_set_stamps": [_c_fp], "m4d_wino_set_stamps": [_c_fp],
-                    "m4d_front_set_stamps": [_c_fp], "m4d_wino6_set_stamps": [_c_fp]}
-
-EXPORTED_SYMBOLS = ["m4d_abi_version", "m4d_build_info"] + list(_SIGNATURES) + list(_VOID_SIGNATURES) + list(_LL_SIGNATURES)
+EXPERIMENT_SIGNATURES = _parse("m4depth_hip_experiments.h")[1]
+EXPORTED_SYMBOLS, EXPERIMENT_SYMBOLS = list(SIGNATURES), list(EXPERIMENT_SIGNATURES)
+# the entry points that return a HIP status (launches and `_supported` queries) -> argtypes: what the launch recorder of
+# tests/test_level_dispatch.py wraps; a view of SIGNATURES, nothing is stated here
+_SIGNATURES = {n: a for n, (r, a, _) in SIGNATURES.items() if r is ctypes.c_int and n != "m4d_abi_version"}
 
 
 def _load():
@@ -210,32 +110,12 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C m4depth_amd/csrc`. "
             "There is no CPU / PyTorch fallback for the hot path.")
     lib = ctypes.CDLL(LIB_PATH)
-    lib.m4d_abi_version.restype = _c_int
-    lib.m4d_abi_version.argtypes = []
-    lib.m4d_build_info.restype = ctypes.c_char_p
-    lib.m4d_build_info.argtypes = []
-    for name, args in _SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the .so is stale: loud by design
-        fn.restype = _c_int
-        fn.argtypes = args
-    for name, args in _LL_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = ctypes.c_longlong
-        fn.argtypes = args
-    for name, args in _VOID_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = None
-        fn.argtypes = args
-    if hasattr(lib, "m4d_tape_begin"):
-        for name, args in _EXPERIMENT_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = _c_int
-            fn.argtypes = args
-        for name, args in _EXPERIMENT_VOID_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = None
-            fn.argtypes = args
-    if lib.m4d_abi_version() != ABI_VERSION:
+    for table in (SIGNATURES, EXPERIMENT_SIGNATURES if hasattr(lib, "m4d_tape_begin") else {}):
+        for name, (restype, argtypes, _) in table.items():
+            fn = getattr(lib, name)          # AttributeError if the .so is stale: loud by design
+            fn.restype = restype
+            fn.argtypes = argtypes
+    if lib.m4d_abi_version() != ABI_VERSION:     # the library was built from another header
         raise ImportError(f"m4depth_amd: ABI mismatch, library reports {lib.m4d_abi_version()}, binding expects {ABI_VERSION}")
     return lib
 

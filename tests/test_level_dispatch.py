@@ -105,12 +105,12 @@ def _recording(log):
         def rec(*args):
             row = []
             for a, t in zip(args, fn.argtypes):
-                if t is ctypes.c_void_p:
+                if t is ctypes.c_void_p and (a is None or isinstance(a, (int, ctypes.c_void_p))):
                     row.append(("ptr", (a.value if isinstance(a, ctypes.c_void_p) else a) or None))
                 elif isinstance(a, (int, float)):
                     row.append(("scalar", a))
-                else:
-                    row.append(("scalar", type(a).__name__))          # a struct array: m4d_pyramid_reset, m4d_normalize_levels
+                else:               # a host array: the structs of m4d_pyramid_reset / m4d_normalize_levels, a ``dims[6]``
+                    row.append(("scalar", type(a).__name__))
             log.append((name, row))
             return fn(*args)
         return rec

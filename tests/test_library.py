@@ -34,6 +34,162 @@ def test_header_symbols_exported():
         assert hasattr(raw, s) == _lib.has_experiments, f"{s}: experiments symbol {'missing from' if _lib.has_experiments else 'present in'} this build"
 
 
+MINI_HEADER = """\
+/* mini.h -- every form the binding's parser reads (and a trap: m4d_fake(int x); ) ( ( */
+#ifndef MINI_H_
+#define MINI_H_
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define M4D_ABI_VERSION 41   /* 41: + m4d_more(int y); 40: the rest */
+
+typedef struct m4d_tagged {
+  const float* src;   /* [n] input */
+  float* dst;         /* [n] output ) */
+  int a, b;
+  long long count;
+  float gain;
+} m4d_tagged;
+typedef struct { const void* p; int n; } m4d_anon;
+
+int m4d_version(void);
+long long m4d_count(void);
+const char* m4d_name(void);
+void m4d_set(int flag);
+/* spread over three lines */
+int m4d_spread(const float* x, const int d[6],
+               const void* const* p, unsigned char* m,
+               long long rows, float slope, void* stream);
+int m4d_structs(const m4d_tagged* levels, const m4d_anon* maps, int n, void* stream);
+long long m4d_sized(long long rows, int C);
+void m4d_stamps(unsigned long long* buf, const double* pose, int32_t* idx, const uint8_t* lut);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MINI_H_ */
+"""
+
+
+def test_parser_reads_every_declaration_form():
+    """parse_header on a literal header: multi-line declarations, comments holding declarations and stray parentheses, the
+    version macro with its trailing comment, the extern "C" guard, both typedef forms, the four return types, (void), and
+    every parameter rule -- exact restype, argtypes, argument names, struct fields and macro value."""
+    from m4depth_amd._lib import parse_header
+    i, f, ll, vp = ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_void_p
+    structs, functions, version = parse_header(MINI_HEADER)
+    assert version == 41
+    assert list(structs) == ["m4d_tagged", "m4d_anon"] and all(issubclass(s, ctypes.Structure) for s in structs.values())
+    assert structs["m4d_tagged"]._fields_ == [("src", vp), ("dst", vp), ("a", i), ("b", i), ("count", ll), ("gain", f)]
+    assert structs["m4d_anon"]._fields_ == [("p", vp), ("n", i)]
+    tagged, anon = ctypes.POINTER(structs["m4d_tagged"]), ctypes.POINTER(structs["m4d_anon"])
+    assert functions == {
+        "m4d_version": (i, (), ()),
+        "m4d_count": (ll, (), ()),
+        "m4d_name": (ctypes.c_char_p, (), ()),
+        "m4d_set": (None, (i,), ("flag",)),
+        "m4d_spread": (i, (vp, vp, vp, vp, ll, f, vp), ("x", "d", "p", "m", "rows", "slope", "stream")),
+        "m4d_structs": (i, (tagged, anon, i, vp), ("levels", "maps", "n", "stream")),
+        "m4d_sized": (ll, (ll, i), ("rows", "C")),
+        "m4d_stamps": (None, (vp, vp, vp, vp), ("buf", "pose", "idx", "lut")),
+    }
+    assert list(functions) == ["m4d_version", "m4d_count", "m4d_name", "m4d_set", "m4d_spread", "m4d_structs", "m4d_sized",
+                               "m4d_stamps"]
+    assert parse_header("int m4d_only(void);") == ({}, {"m4d_only": (i, (), ())}, None)
+
+
+@pytest.mark.parametrize("declaration", [
+    "int m4d_x(size_t n);",
+    "int m4d_x(double v);",
+    "int m4d_x(m4d_s level, void* stream);",                   # a struct by value
+    "int m4d_x(const float* x, widget w);",                     # no type the rules know
+    "int m4d_x(int);",                                          # no name: `int` is not read as one
+    "int m4d_x(int (*callback)(int), void* stream);",           # a function pointer
+    "double m4d_x(int n);",                                     # a return type outside the four
+    "int m4d_x(int n)",                                         # half a declaration: no terminator before the next one
+    "int other_prefix(int n);",
+    "typedef struct { double v; } m4d_t;",
+    "typedef struct { float *a, *b; } m4d_t;",
+    "typedef struct { int a, b[4]; } m4d_t;",
+    "typedef struct { int b[4]; } m4d_t;",                      # a field array is stored inline: not the parameter rule
+    "typedef struct { float m[9]; int n; } m4d_t;",
+    "#define M4D_DECLARE(a) \\",                                # the continuation line below would be read as a declaration
+])
+def test_parser_refuses_what_it_has_no_rule_for(declaration):
+    """Nothing defaults: a declaration outside the rules raises, and the message quotes it."""
+    from m4depth_amd._lib import parse_header
+    header = "typedef struct { int n; } m4d_s;\nint m4d_before(int a);\n" + declaration + "\nint m4d_after(void* stream);\n"
+    with pytest.raises(ValueError) as err:
+        parse_header(header)
+    assert declaration.rstrip(";") in str(err.value), str(err.value)
+
+
+def _declaration(txt, name):
+    """The comment-stripped text between the parentheses of ``name``'s declaration."""
+    (params,) = re.findall(r"\b%s\s*\(([^)]*)\)\s*;" % name, re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+    return params
+
+
+def test_binding_is_the_header():
+    """Every function bound on ``lib`` carries exactly the restype and argtypes derived from the headers; the derived
+    argument count equals an independent count of the declaration's comma-separated parameters; the parser's names are
+    header_symbols()'s."""
+    from m4depth_amd import _lib
+    for header, table, symbols in (("m4depth_hip.h", _lib.SIGNATURES, _lib.EXPORTED_SYMBOLS),
+                                   ("m4depth_hip_experiments.h", _lib.EXPERIMENT_SIGNATURES, _lib.EXPERIMENT_SYMBOLS)):
+        assert sorted(table) == sorted(symbols) == header_symbols(header)
+        txt = open(os.path.join(ROOT, "include", header)).read()
+        for name in symbols:
+            restype, argtypes, argnames = table[name]
+            params = _declaration(txt, name).strip()
+            count = 0 if params in ("", "void") else params.count(",") + 1
+            assert len(argtypes) == len(argnames) == count, name
+            assert all(re.fullmatch(r"[A-Za-z_]\w*", n) for n in argnames) and len(set(argnames)) == count, (name, argnames)
+            if table is _lib.SIGNATURES or _lib.has_experiments:
+                fn = getattr(_lib.lib, name)
+                assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
+    assert _lib.SIGNATURES["m4d_pyramid_reset"][1][0] is ctypes.POINTER(_lib.ResetLevel)
+    assert _lib.SIGNATURES["m4d_normalize_levels"][1][0] is ctypes.POINTER(_lib.NormLevel)
+    assert _lib.SIGNATURES["m4d_build_info"][0] is ctypes.c_char_p and _lib.SIGNATURES["m4d_dscv_set_variant"][0] is None
+    assert _lib.SIGNATURES["m4d_launch_count"][0] is ctypes.c_longlong
+    status = {n: a for n, (r, a, _) in _lib.SIGNATURES.items() if r is ctypes.c_int}
+    assert status.pop("m4d_abi_version") == () and _lib._SIGNATURES == status
+
+
+def test_struct_layout_matches_the_compiler(tmp_path):
+    """sizeof and every offsetof of EVERY struct the parser finds in the header, as the host C compiler lays them out, against
+    the derived ``ctypes.Structure`` classes."""
+    import shutil
+    import subprocess
+    from m4depth_amd import _lib
+    cc = next((p for p in (shutil.which("cc"), shutil.which("gcc"), shutil.which("clang", path="/opt/rocm/llvm/bin"),
+                           shutil.which("clang", path="/opt/rocm/lib/llvm/bin")) if p), None)
+    if cc is None:
+        pytest.skip("no host C compiler")
+    header = open(os.path.join(ROOT, "include", "m4depth_hip.h")).read()
+    classes = _lib.parse_header(header)[0]
+    assert sorted(classes) == sorted(re.findall(r"\}\s*(\w+)\s*;", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
+    assert classes["m4d_reset_level"]._fields_ == _lib.ResetLevel._fields_
+    assert classes["m4d_norm_level"]._fields_ == _lib.NormLevel._fields_
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "m4depth_hip.h"', 'int main(void) {']
+    for name, cls in classes.items():
+        lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'  printf("{name}.{field} %zu\\n", offsetof({name}, {field}));' for field, _ in cls._fields_]
+    (tmp_path / "layout.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")],
+                   check=True, capture_output=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    compiled = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    derived = {}
+    for name, cls in classes.items():
+        derived[name] = ctypes.sizeof(cls)
+        derived.update({f"{name}.{field}": getattr(cls, field).offset for field, _ in cls._fields_})
+    assert compiled == derived
+    assert derived["m4d_reset_level"] == ctypes.sizeof(_lib.ResetLevel) == 72
+    assert derived["m4d_norm_level"] == ctypes.sizeof(_lib.NormLevel) == 32
+
+
 def test_product_library_exports_only_the_header(tmp_path):
     """Every m4d_* symbol the shared library exports is declared in include/m4depth_hip.h (or, in an experiments build, in
     include/m4depth_hip_experiments.h): no undeclared entry points, no experiment kernels behind global setters in the

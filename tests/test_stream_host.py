@@ -28,8 +28,8 @@ def test_stream_symbols_declared_bound_exported():
     # one more argument each than the unmasked entry points: the mask and the reset parallax (the stream stays last)
     for masked, plain in (("m4d_refiner_tail6_m", "m4d_refiner_tail6"), ("m4d_refiner_tail_m", "m4d_refiner_tail"),
                           ("m4d_level_post_m", "m4d_level_post")):
-        a, p = _lib._SIGNATURES[masked], _lib._SIGNATURES[plain]
-        assert a[:-1] == p[:-1] + [_lib._c_fp, _lib._c_f] and a[-1] == p[-1]
+        a, p = _lib.SIGNATURES[masked][1], _lib.SIGNATURES[plain][1]
+        assert a[:-1] == p[:-1] + (ctypes.c_void_p, ctypes.c_float) and a[-1] == p[-1]
     assert _lib.lib.m4d_abi_version() == 6
 
 
