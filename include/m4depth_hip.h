@@ -453,6 +453,58 @@ int m4d_consistency_per_sample(const float* est, long long est_stride, const flo
                                const unsigned char* reset, const unsigned char* active, int b, int h, int w, void* workspace,
                                float* rows6, unsigned char* counted, void* stream);
 
+/* ---- Pose refinement: direct photometric alignment of the current frame against the previous one (csrc/m4d_align.hip) ----
+ * Gauss-Newton image alignment (Lucas-Kanade on SE(3), as in direct visual odometry: Kerl et al., ICRA 2013; Engel et al.,
+ * "Direct Sparse Odometry", 2018) started from the given motion (main.py --refine_pose).  Per sample: prev [H,W,3] and Dp
+ * [H,W,1], the previous frame's image and raw estimate; cur [H,W,3]; rot (a unit quaternion, rot_c = 4 only; normalised in
+ * double when it is read) and trans, the network's convention (a point X of the current camera is R X + t in the previous
+ * one); cam_f, cam_c the sample's own full-resolution camera.  The pose is held as (A, a) = (R^T, -R^T t), the motion from the
+ * previous camera (which has the depth) into the current one, in double on the device between iterations.
+ * One iteration at a level of stride s (a power of two), level map h = H/s, w = W/s:
+ *   images  grey = ((r + g) + b) / 3 of the box-pyramid level (m4d_image_pyramid_box; s = 1: the frames themselves);
+ *   camera  f/s, c/s;  depth of level pixel (i, j) = Dp at full-resolution pixel (i s + s/2, j s + s/2), one tap, clipped to
+ *           [0.01, 200]; a non-finite tap makes the pixel invalid;
+ *   query   m4d_photo_query (csrc/m4d_photo_common.h) on the float32 rounding of (A, a): X = depth (x_n, y_n, 1) with the
+ *           half-pixel centre, Y = A X + a, q = f Y.xy / Y.z + c - 0.5; valid = Y.z > 0, q inside [0,w-1] x [0,h-1], depth finite;
+ *   residual r = bilinear(cur_level, q) - prev_level(p); image gradient = the analytic derivative of that sample,
+ *           gx = (1-ay)(tr-tl) + ay(br-bl), gy = (1-ax)(bl-tl) + ax(br-tr);
+ *   Jacobian for the left perturbation Y <- exp(w^) Y + v: g = dr/dY = (gx fx / Z, gy fy / Z, -(gx fx Yx + gy fy Yy) / Z^2),
+ *           J = [g, Y x g] (translation first);  Huber weight wh = 1 if |r| <= huber else huber / |r|;
+ *   per-pixel terms in float32 (one rounding per operation), products and sums in double over the valid pixels:
+ *           H = sum wh J J^T (21 entries, upper triangle row-major), b = sum wh J r (6), cost = sum wh r^2, N;
+ *   step    (H/N + damping diag(H/N) + W) delta = -(b/N + W xi_acc), 6x6 Cholesky in double; W = diag(prior_t x3, prior_r x3)
+ *           a first-order prior towards the given pose, xi_acc the sum of the increments applied so far (0 = no prior);
+ *   update  A <- exp(w^) A, a <- exp(w^) a + v, xi_acc += delta.  A pivot <= 0, N = 0 or a non-finite value marks the sample
+ *           bad: its pose is left as it is and its later iterations do nothing.
+ * End: R' = A^T, t' = -A^T a, the quaternion of R' normalised with w >= 0, each rounded to float32 once.  The result is
+ *   rejected -- rot / trans written through bit for bit -- when reset[s] or !active[s] (none of the sample's images or maps is
+ *   read, as in m4d_consistency_per_sample), the sample is bad, no iteration ran, N / (h w) of the last iteration is below
+ *   min_cover, the cost/N of the last iteration is not below that of the first iteration at the same stride (both are taken
+ *   before that iteration's update: a level needs two iterations to be accepted), |t' - t| > cap_t (metres) or the angle
+ *   between R' and R > cap_r (radians).
+ * rows8 [b][8]: cost/N at the first and at the last iteration of the last stride, N / (h w) there, |t' - t|, the angle, the
+ *   iterations applied, the applied flag (1 / 0), 0; a masked-off sample's row is eight zeros.
+ * Workspace: m4d_pose_align_workspace_bytes(b, H, W) bytes (-1: a size the calls refuse), 8-byte aligned, private to the
+ *   frame between begin and end.  It opens with 64 doubles per sample that a caller may read: A (9, row-major), a (3),
+ *   xi_acc (6), the first and last cost/N, N / (h w), iterations, the bad flag, the stride of the last iteration, 8 unused, then
+ *   the folded sums of the last iteration (29: H, b, cost, N), 3 unused; the tile partials follow.
+ * Deterministic: no atomics, no zero-fill, block partials in double (wave64 shuffles, LDS across waves), folded in index
+ *   order by one wave per sample; sample s of a batch equals the launch on sample s alone bit for bit.  The decision is made
+ *   on the device; nothing synchronises; every call is plain launches (begin 1, iterate 2, end 1), capturable.
+ * Layout: batch strides in floats (>= the dense level image 3 h w, or H W for the estimate).  Invalid argument, no launch: a
+ *   NULL pointer, rot_c != 4, b outside [1, 65535], H or W < 3, H W > 2^24, s no power of two, H or W no multiple of s, level
+ *   h or w < 3, a stride below the dense image, huber <= 0, a negative damping / prior / min_cover / cap, a workspace off 8
+ *   bytes.  Additive entry points: ABI 6 unchanged. */
+long long m4d_pose_align_workspace_bytes(int b, int h, int w);
+int m4d_pose_align_begin(const float* rot, int rot_c, const float* trans, int b, int h, int w, void* workspace, void* stream);
+int m4d_pose_align_iterate(const float* cur, long long cur_stride, const float* prev, long long prev_stride,
+                           const float* est_prev, long long est_prev_stride, const float* cam_f, const float* cam_c,
+                           const unsigned char* reset, const unsigned char* active, int b, int h, int w, int s, float huber,
+                           float damping, float prior_t, float prior_r, void* workspace, void* stream);
+int m4d_pose_align_end(const float* rot, int rot_c, const float* trans, const unsigned char* reset, const unsigned char* active,
+                       int b, int h, int w, float min_cover, float cap_t, float cap_r, const void* workspace, float* rot_out,
+                       float* trans_out, float* rows8, void* stream);
+
 /* ---- m4depth_network.py: DepthEstimatorLevel glue -------------------------------- */
 
 /* Per-cut L2 normalisation (:179-189, tf.linalg.normalize, no epsilon). */

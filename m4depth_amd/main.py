@@ -532,8 +532,10 @@ def eval_streams(args, model, dev):
     ``--consistency`` adds one launch pair per step (``consistency.ConsistencyScorer``) into an [n_steps,B,6] / [n_steps,B] log
     of its own and, after the last step, ``perfs-consistency-<dataset>.txt`` and ``consistency-frames-<dataset>.txt``.  With
     ground truth the seven metrics are computed exactly as without the flag; without it (a recording without depth.txt, csv
-    files without a depth column) they are skipped.  Returns (whether the seven were computed, the six consistency means or
-    None)."""
+    files without a depth column) they are skipped.  ``--refine_pose`` puts ``pose_refine.PoseRefiner`` in front of every step
+    (eager launches, also before a graph replay, which copies the frame's motion into its static inputs): the network and the
+    scorer get the refined motion, its rows go to an [n_steps,B,8] log and, after the last step, to
+    ``pose-refine-frames-<dataset>.txt``.  Returns (whether the seven were computed, the six consistency means or None)."""
     from . import network_ops as nops
     from . import stream_eval as SE
     has_gt = records_have_depth(args) if args.consistency else True    # without --consistency the loader refuses or the step fails
@@ -549,6 +551,11 @@ def eval_streams(args, model, dev):
         scorer = CS.ConsistencyScorer(copy_estimate=args.graph)    # GraphedStream's output buffer is overwritten by the next replay
         c_rows = torch.empty((n_steps, B, len(CS.COLUMNS)), dtype=torch.float32, device=dev)
         c_counted = torch.empty((n_steps, B), dtype=torch.uint8, device=dev)
+    refiner = None
+    if args.refine_pose:                                           # a fixed schedule of launches in front of every step
+        from . import pose_refine as PR
+        refiner = PR.from_args(args, copy_estimate=args.graph)
+        p_rows = torch.empty((n_steps, B, len(PR.COLUMNS)), dtype=torch.float32, device=dev)
     active = (sched.cells[..., 0] >= 0).sum(axis=1)                # the schedule's, known on the host without a device read
     runner, t0 = None, None
     for step, batch in enumerate(ds):
@@ -557,12 +564,16 @@ def eval_streams(args, model, dev):
             t0 = time.perf_counter()
         frame = {"RGB_im": batch["RGB_im"], "rot": batch["rot"], "trans": batch["trans"], "new_traj": batch["reset"],
                  "camera": batch["camera"]}
+        if refiner is not None:                                    # the network and the scorer see the refined motion
+            frame = refiner.step(frame, batch["reset"], batch["active"], p_rows[step])
         if args.graph:
             if runner is None:
                 runner = GraphedStream(model, frame)
             est = runner(frame)["depth"]
         else:
             est = model.stream_step(frame)["depth"]
+        if refiner is not None:
+            refiner.keep(frame, est)
         if has_gt:
             nops.depth_metrics_per_sample(batch["depth"], est, batch["new_traj"], batch["active"], 80., rows=rows[step],
                                           counted=counted[step])
@@ -572,11 +583,13 @@ def eval_streams(args, model, dev):
         rows_h, counted_h = rows.cpu().numpy(), counted.cpu().numpy()
     if scorer is not None:
         c_rows_h, c_counted_h = c_rows.cpu().numpy(), c_counted.cpu().numpy()
+    if refiner is not None:
+        p_rows_h = p_rows.cpu().numpy()
     if t0 is not None:
         dt = time.perf_counter() - t0
         n = int(active[1:].sum())
         print(f"eval_streams {B} slots ({args.eval_streams_policy}, {'graph' if args.graph else 'eager'}"
-              f"{', consistency' if scorer is not None else ''}): {n / dt:.1f} "
+              f"{', consistency' if scorer is not None else ''}{', refine_pose' if refiner is not None else ''}): {n / dt:.1f} "
               f"sample-frames/s over {n} active sample-frames of {n_steps - 1} steps (the first step excluded)")
     if has_gt:
         total, count = SE.fold(rows_h, counted_h, sched.cells)
@@ -593,6 +606,12 @@ def eval_streams(args, model, dev):
             print(f"consistency {name}: {v:.6f}")
         print(f"wrote {CS.perfs_path(args.ckpt_dir, args.dataset)} and {CS.frames_path(args.ckpt_dir, args.dataset)} "
               f"({c_count} counted frames)")
+    if refiner is not None:
+        frames = SE.fold_pose_refine(p_rows_h, sched.cells)
+        os.makedirs(args.ckpt_dir, exist_ok=True)
+        PR.write_frames(PR.frames_path(args.ckpt_dir, args.dataset), frames)
+        applied = sum(1 for _, _, row in frames if row[6] != 0)
+        print(f"wrote {PR.frames_path(args.ckpt_dir, args.dataset)} ({applied} of {len(frames)} frames refined)")
     return has_gt, means
 
 
@@ -651,7 +670,10 @@ def predict(args, model, batches, rank, dev):
     ``PredictionWriter`` (its export launch follows the forward -- or the graph replay -- on the same stream; nothing is
     kept); without it rank 0 writes them all to ``<ckpt_dir>/predictions.npy``."""
     from .export import FrameNamer, PredictionWriter
-    writer = namer = runner = t_save = None
+    writer = namer = runner = t_save = refiner = None
+    if args.refine_pose:
+        from . import pose_refine as PR
+        refiner = PR.from_args(args, copy_estimate=args.graph)
     if args.save_dir is not None:
         writer = PredictionWriter(args.save_dir, args.save_format, args.save_panels, near=args.save_range[0],
                                   far=args.save_range[1], err_max=args.save_err_max, cloud=args.save_cloud,
@@ -668,12 +690,17 @@ def predict(args, model, batches, rank, dev):
                 est = model.predict_step(frame)["depth"]
             else:
                 sf = _stream_frame(frame, dev)
+                if refiner is not None:                        # the network and the clouds see the refined motion
+                    sf = refiner.step(sf, sf["new_traj"], torch.ones_like(sf["new_traj"], dtype=torch.uint8))
+                    frame = dict(frame, rot=sf["rot"], trans=sf["trans"])
                 if not args.graph:
                     est = model.stream_step(sf)["depth"]
                 else:
                     if runner is None:
                         runner = GraphedStream(model, sf)
                     est = runner(sf)["depth"]
+                if refiner is not None:
+                    refiner.keep(sf, est)
             if writer is None:
                 preds.append(est.cpu().numpy())
                 continue

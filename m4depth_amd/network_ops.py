@@ -448,6 +448,80 @@ def consistency_per_sample(est, est_prev, cur, prev, rot, trans, f, c, reset, ac
     return rows, counted
 
 
+POSE_ALIGN_STATE = 64        # doubles per sample at the head of the pose-alignment workspace (include/m4depth_hip.h)
+
+
+def _masks(reset, active, b):
+    for name, m in (("reset", reset), ("active", active)):
+        if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != (b,):
+            raise ValueError(f"{name}: expected a uint8 / bool [{b}] device tensor")
+    return (reset.view(torch.uint8) if reset.dtype == torch.bool else reset,
+            active.view(torch.uint8) if active.dtype == torch.bool else active)
+
+
+def _pose(rot, trans):
+    rot = as_f32(rot, "rot")
+    if rot.dim() != 2 or rot.shape[1] != 4:
+        raise ValueError(f"pose alignment needs quaternion rotations [b,4], got {tuple(rot.shape)}")
+    return rot, as_f32(trans, "trans").reshape(rot.shape[0], 3)
+
+
+def pose_align_begin(rot, trans, h, w):
+    """Opens the pose refinement of one frame (include/m4depth_hip.h, "Pose refinement"): the workspace of a [b,h,w] batch,
+    a float64 device tensor whose first ``b * POSE_ALIGN_STATE`` values are the per-sample state ((A, a) = (R^T, -R^T t) of
+    ``rot`` [b,4] / ``trans`` [b,3], xi_acc = 0).  One launch; the buffer is shared by the frames of a stream."""
+    rot, trans = _pose(rot, trans)
+    b = rot.shape[0]
+    nbytes = int(lib.m4d_pose_align_workspace_bytes(b, int(h), int(w)))
+    if nbytes < 0:
+        raise ValueError(f"pose alignment: a {b}x{h}x{w} batch is refused (h, w >= 3, h*w <= 2^24, b <= 65535)")
+    ws = _workspace("pose_align", nbytes, rot.device)[:nbytes // 4].view(torch.float64)
+    check(lib.m4d_pose_align_begin(dptr(rot, "rot"), 4, dptr(trans, "trans"), b, int(h), int(w), dptr(ws, "workspace", torch.float64),
+                                   stream_ptr()), "m4d_pose_align_begin")
+    return ws
+
+
+def pose_align_iterate(ws, cur, prev, est_prev, f, c, reset, active, stride, huber, damping=0.0, prior=(0.0, 0.0)):
+    """One Gauss-Newton iteration at ``stride``: ``cur`` / ``prev`` [b, H/stride, W/stride, 3] are the level images (the frames
+    themselves at stride 1, else the box-pyramid level), ``est_prev`` [b,H,W,1] the previous frame's full-resolution estimate
+    (all three dense images at a batch stride), ``f`` / ``c`` [b,2] the full-resolution cameras.  Two launches; updates ``ws``."""
+    if est_prev.dim() != 4 or est_prev.shape[3] != 1:
+        raise ValueError(f"est_prev: expected [b,H,W,1], got {tuple(est_prev.shape)}")
+    b, h, w, _ = est_prev.shape
+    stride = int(stride)
+    for name, t in (("cur", cur), ("prev", prev)):
+        if stride < 1 or tuple(t.shape) != (b, h // stride, w // stride, 3):
+            raise ValueError(f"{name}: expected {(b, h // max(stride, 1), w // max(stride, 1), 3)} at stride {stride}, got {tuple(t.shape)}")
+    reset, active = _masks(reset, active, b)
+    f, c = as_f32(f, "f").reshape(b, 2), as_f32(c, "c").reshape(b, 2)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(lib.m4d_pose_align_iterate(vp(cur), _batch_stride(cur, "cur"), vp(prev), _batch_stride(prev, "prev"), vp(est_prev),
+                                     _batch_stride(est_prev, "est_prev"), dptr(f, "f"), dptr(c, "c"),
+                                     dptr(reset, "reset", torch.uint8), dptr(active, "active", torch.uint8), b, h, w, stride,
+                                     float(huber), float(damping), float(prior[0]), float(prior[1]),
+                                     dptr(ws, "workspace", torch.float64), stream_ptr()), "m4d_pose_align_iterate")
+    return ws
+
+
+def pose_align_end(ws, rot, trans, reset, active, h, w, min_cover, caps, rot_out=None, trans_out=None, rows=None):
+    """Closes the refinement: the rejection rules decided on the device, then (rot_out [b,4], trans_out [b,3], rows [b,8]) --
+    the refined motion, or the given one bit for bit where the result is rejected; ``caps`` = (metres, radians).  ``rows`` may
+    be a view into a log.  One launch."""
+    rot, trans = _pose(rot, trans)
+    b = rot.shape[0]
+    reset, active = _masks(reset, active, b)
+    rot_out = torch.empty_like(rot) if rot_out is None else rot_out
+    trans_out = torch.empty_like(trans) if trans_out is None else trans_out
+    rows = torch.empty((b, 8), dtype=torch.float32, device=rot.device) if rows is None else rows
+    if tuple(rot_out.shape) != (b, 4) or tuple(trans_out.shape) != (b, 3) or tuple(rows.shape) != (b, 8):
+        raise ValueError(f"expected rot_out [{b},4], trans_out [{b},3] and rows [{b},8]")
+    check(lib.m4d_pose_align_end(dptr(rot, "rot"), 4, dptr(trans, "trans"), dptr(reset, "reset", torch.uint8),
+                                 dptr(active, "active", torch.uint8), b, int(h), int(w), float(min_cover), float(caps[0]),
+                                 float(caps[1]), dptr(ws, "workspace", torch.float64), dptr(rot_out, "rot_out"),
+                                 dptr(trans_out, "trans_out"), dptr(rows, "rows"), stream_ptr()), "m4d_pose_align_end")
+    return rot_out, trans_out, rows
+
+
 EXPORT_FORMATS = {None: 0, "kitti16": 1, "midair16": 2}          # the `format` argument of m4d_depth_export
 EXPORT_PANELS = {"rgb": 0, "est": 1, "gt": 2, "err": 3}          # its panel kinds
 

@@ -57,6 +57,20 @@ def build_parser():
                         "previous frame's (geo, a diagnostic); m4depth_amd.consistency.  Writes perfs-consistency-<dataset>.txt "
                         "and consistency-frames-<dataset>.txt; a set without ground truth (a recording without depth.txt) is then "
                         "accepted and the seven metrics are skipped")
+    p.add_argument("--refine_pose", action="store_true",
+                   help="--eval_streams / predict --stream: before every step, align the frame's motion to the images -- "
+                        "Gauss-Newton direct alignment of the current frame against the previous frame and its estimated depth, "
+                        "per sample on the GPU, started from the given motion (m4depth_amd.pose_refine; the defaults are "
+                        "untuned).  The network, --consistency and --save_cloud then see the refined motion; --eval_streams "
+                        "writes pose-refine-frames-<dataset>.txt")
+    p.add_argument("--refine_pose_strides", default=None, metavar="LIST",
+                   help="--refine_pose: comma list of pyramid strides, coarse to fine, powers of two (default 8,4,2)")
+    p.add_argument("--refine_pose_iters", type=int, default=None, metavar="N",
+                   help="--refine_pose: Gauss-Newton iterations per stride (default 4)")
+    p.add_argument("--refine_pose_prior", type=float, nargs=2, default=None, metavar=("LT", "LR"),
+                   help="--refine_pose: weights of the prior towards the given motion, per m^2 and per rad^2 (default 0 0: off)")
+    p.add_argument("--refine_pose_max", type=float, nargs=2, default=None, metavar=("METRES", "DEGREES"),
+                   help="--refine_pose: a correction larger than this is rejected and the given motion kept (default 0.05 0.5)")
     p.add_argument("--host_input", action="store_true",
                    help="synthetic eval: hand every batch over from pinned HOST memory (the PCIe copy is part of the step) and "
                         "print the frames/s of the loop -- the PCIe-inclusive rate, next to bench.py's HBM-resident one")
@@ -279,10 +293,53 @@ def check_save_args(parser, args):
         parser.error("--save_panels %s: the records of --records_path name no ground-truth map" % ",".join(panels))
 
 
+def check_refine_args(parser, args):
+    """Refusals of ``--refine_pose`` and its options; fills in their defaults (``pose_refine.DEFAULTS``) and parses
+    ``--refine_pose_strides`` into a tuple."""
+    import math
+    others = [f for f in ("refine_pose_strides", "refine_pose_iters", "refine_pose_prior", "refine_pose_max")
+              if getattr(args, f) is not None]
+    if not args.refine_pose:
+        if others:
+            parser.error("--%s needs --refine_pose" % others[0])
+        return
+    streams = args.mode in ("eval", "validation") and args.eval_streams > 0
+    if not streams and not (args.mode == "predict" and args.stream):
+        parser.error("--refine_pose needs --eval_streams B in --mode=eval / --mode=validation or --stream in --mode=predict (with "
+                     "or without --graph): it aligns each frame of a trajectory against the one before it")
+    from .pose_refine import DEFAULTS
+    if args.refine_pose_strides is None:
+        args.refine_pose_strides = DEFAULTS["strides"]
+    else:
+        try:
+            strides = tuple(int(v) for v in args.refine_pose_strides.split(","))
+        except ValueError:
+            strides = ()
+        if not strides or any(v < 1 or v & (v - 1) for v in strides):
+            parser.error("--refine_pose_strides: a comma list of powers of two, got %r" % args.refine_pose_strides)
+        args.refine_pose_strides = strides
+    if args.refine_pose_iters is None:
+        args.refine_pose_iters = DEFAULTS["iters"]
+    if args.refine_pose_iters < 1:
+        parser.error("--refine_pose_iters must be >= 1")
+    args.refine_pose_prior = tuple(args.refine_pose_prior) if args.refine_pose_prior is not None else DEFAULTS["prior"]
+    if not (args.refine_pose_prior[0] >= 0 and args.refine_pose_prior[1] >= 0):
+        parser.error("--refine_pose_prior LT LR must be >= 0")
+    args.refine_pose_max = tuple(args.refine_pose_max) if args.refine_pose_max is not None \
+        else (DEFAULTS["caps"][0], math.degrees(DEFAULTS["caps"][1]))
+    if not (args.refine_pose_max[0] >= 0 and args.refine_pose_max[1] >= 0):
+        parser.error("--refine_pose_max METRES DEGREES must be >= 0")
+    if args.height is not None and args.width is not None:
+        top = max(args.refine_pose_strides)
+        if args.height % top or args.width % top or args.height // top < 3 or args.width // top < 3:
+            parser.error("--refine_pose_strides: --height and --width must be multiples of the largest stride, at least 3 of them")
+
+
 def check_args(parser, args, world=None):
     """Every refusal of ``m4depth_amd.main``, in the order they win."""
     check_stream_args(parser, args)
     _check_eval_streams(parser, args)
+    check_refine_args(parser, args)
     check_train_args(parser, args, world)
     check_recording_args(parser, args)
     check_save_args(parser, args)

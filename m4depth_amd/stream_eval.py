@@ -138,6 +138,25 @@ def fold_consistency(rows, counted, cells, traj_order=None):
     return total, count, frames
 
 
+def fold_pose_refine(rows, cells, traj_order=None):
+    """The per-frame rows of ``pose_refine.PoseRefiner`` (``pose_refine.COLUMNS``) from its [n_steps,B,8] log, in the same
+    sequential walk (trajectory in ``traj_order``, default ascending = csv order; frame in order): the (trajectory, frame, row)
+    triples of every frame but a trajectory's first, which has no frame before it -- the frames ``--consistency`` scores."""
+    rows = np.asarray(rows, np.float32)
+    cells = np.asarray(cells)
+    if rows.shape[:2] != cells.shape[:2] or rows.shape[2:] != (8,):
+        raise ValueError(f"fold: rows {rows.shape} and cells {cells.shape} disagree")
+    st, sl = np.nonzero((cells[..., 0] >= 0) & (cells[..., 1] >= 1))
+    tr, fr = cells[st, sl, 0], cells[st, sl, 1]
+    if traj_order is None:
+        rank = tr
+    else:
+        pos = {int(t): i for i, t in enumerate(traj_order)}
+        rank = np.array([pos[int(t)] for t in tr], np.int64)
+    walk = np.lexsort((fr, rank))                    # trajectory, then frame
+    return [(int(tr[k]), int(fr[k]), rows[st[k], sl[k]].copy()) for k in walk]
+
+
 def fold_result(total, count):
     """``float32(total) / float32(count)`` (count 0 -> the totals themselves, as the writer's clamp to 1 gives)."""
     return (np.asarray(total, np.float32) / np.float32(max(int(count), 1))).astype(np.float32)
