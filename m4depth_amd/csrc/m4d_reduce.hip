@@ -8,6 +8,7 @@
 // Partial sums are combined in a fixed order (no atomics): results are run-to-run identical.  The DINL statistics are summed
 // in double from the first add on: a frame whose mean dwarfs its spread, or a flat frame (an all-zero one included), keeps
 // its digits, and the mean of a constant channel is exact, so its variance is exactly 0.
+#include <type_traits>
 #include <cstdlib>
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
@@ -374,6 +375,9 @@ __device__ __forceinline__ f32x4 enc0_conv1(const float* window_base, const int 
   return acc;
 }
 
+#ifndef M4D_E0S_ABL
+#define M4D_E0S_ABL 0   // timing ablations of enc0_stats_kernel (wrong results): 2 no MFMAs, 4 no double-precision sums
+#endif
 constexpr int kE0TW = 128, kE0TH = 8;              // statistics tile (pixels)
 constexpr int kE0RS = (kE0TW + 2) * 3;             // floats per staged RGB row (390)
 
@@ -383,23 +387,73 @@ constexpr int kE0RS = (kE0TW + 2) * 3;             // floats per staged RGB row 
 // variance by up to ~n: the sums are therefore taken in double from the first add on (y - K of two floats is exact in double),
 // and the cancellation costs ~n x 1e-16 instead of every digit.  Evaluated with the same expression by the statistics kernel
 // and by its finalisation.
-__device__ __forceinline__ float enc0_shift(const float* __restrict__ ib, const float* __restrict__ w27, const float* __restrict__ bias,
-                                            int h, int w, int j) {
+// In two halves, so that a caller can put the loads beside its other loads: enc0_shift_load requests the 27 weights of
+// channel j and the 27 RGB values of the centre window with independent loads (a tap outside the image reads pixel 0 instead
+// and is skipped below), enc0_shift_sum is the multiply-add chain in tap order -- one memory round trip, not one per tap.
+__device__ __forceinline__ void enc0_shift_load(const float* __restrict__ ib, const float* __restrict__ w27, int h, int w, int j,
+                                                float (&sw)[27], float (&sp)[27]) {
   const int cy = h / 2, cx = w / 2;
-  float y = bias[j];
+#pragma unroll
   for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
       const int gy = cy + ky - 1, gx = cx + kx - 1;
-      if (gy < 0 || gy >= h || gx < 0 || gx >= w) continue;
-      for (int ch = 0; ch < 3; ++ch) y = y + w27[((ky * 3 + kx) * 3 + ch) * 16 + j] * ib[((long long)gy * w + gx) * 3 + ch];
+      const bool ok = !(gy < 0 || gy >= h || gx < 0 || gx >= w);
+      const long long base = ok ? ((long long)gy * w + gx) * 3 : 0LL;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        sw[(ky * 3 + kx) * 3 + ch] = w27[((ky * 3 + kx) * 3 + ch) * 16 + j];
+        sp[(ky * 3 + kx) * 3 + ch] = ib[base + ch];
+      }
+    }
+}
+__device__ __forceinline__ float enc0_shift_sum(float bias_j, const float (&sw)[27], const float (&sp)[27], int h, int w) {
+  const int cy = h / 2, cx = w / 2;
+  float y = bias_j;
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int gy = cy + ky - 1, gx = cx + kx - 1;
+      const bool ok = !(gy < 0 || gy >= h || gx < 0 || gx >= w);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) y = ok ? y + sw[(ky * 3 + kx) * 3 + ch] * sp[(ky * 3 + kx) * 3 + ch] : y;
     }
   return y;
+}
+
+constexpr int kE0TE = (kE0TH + 2) * kE0RS;         // staged floats per statistics tile (3900)
+constexpr int kE0NL = (kE0TE + 255) / 256;         // ... per thread (16)
+static_assert(kE0RS > 256 && kE0RS < 512, "enc0_tile_load: thread t starts in row 0 and crosses at most one row end per step of 256");
+// Element idx = t + 256 i of the tile at (y0, x0) -> v[i], every load requested before the first is waited for: (row, column) of
+// idx advance by 256 without a division, and an element outside the image (or past the tile's end) reads the nearest pixel
+// inside -- no branch stands between two loads.  Returns the mask of the elements inside the image (bit i); enc0_tile_store applies it, so that
+// nothing touches v[] -- and waits for the loads -- between the two calls.
+__device__ __forceinline__ unsigned enc0_tile_load(const float* __restrict__ ib, int h, int w, int y0, int x0, int t, float (&v)[kE0NL]) {
+  const int row3 = w * 3, gy0 = y0 - 1, gc0 = (x0 - 1) * 3;
+  int r = 0, cc = t;
+  unsigned mask = 0u;
+#pragma unroll
+  for (int i = 0; i < kE0NL; ++i) {
+    const int gy = gy0 + r, gxc = gc0 + cc;
+    const bool in = r < kE0TH + 2 && gy >= 0 && gy < h && gxc >= 0 && gxc < row3;
+    v[i] = ib[(long long)min(max(gy, 0), h - 1) * row3 + min(max(gxc, 0), row3 - 1)];
+    mask |= in ? 1u << i : 0u;
+    cc += 256;
+    if (cc >= kE0RS) { cc -= kE0RS; ++r; }
+  }
+  return mask;
+}
+__device__ __forceinline__ void enc0_tile_store(float* __restrict__ tile, int t, const float (&v)[kE0NL], unsigned mask) {
+#pragma unroll
+  for (int i = 0; i < kE0NL; ++i)
+    if (t + 256 * i < kE0TE) tile[t + 256 * i] = (mask >> i & 1u) ? v[i] : 0.f;
 }
 
 // PASS 0: per-channel sums of conv1 + bias; PASS 1: sums of squared deviations from `mean` -- double partials in the layout of
 // dinl_partial_kernel ([image][block][16]), finished by dinl_finalize_kernel.  A workgroup walks tiles blockIdx.x, + gridDim.x, ...
 // PASS 2 (round 6): BOTH moments in one pass -- S1 = sum (y - K), S2 = sum (y - K)^2 with the per-image, per-channel shift K of
-// enc0_shift -- double partials [image][block][32] (16 x S1, 16 x S2), finished by enc0_moments_finalize_kernel: the level-0
+// enc0_shift_load / enc0_shift_sum -- double partials [image][block][32] (16 x S1, 16 x S2), finished by enc0_moments_finalize_kernel: the level-0
 // statistics are then TWO dependent launches instead of four (RGB totals, analytic mean, squared deviations, finalisation), 20 us
 // less at the head of a batch-1 step's critical path.  Every sum is a double, per lane, through the butterfly and the workgroup
 // combine, in a fixed order.
@@ -408,49 +462,70 @@ __global__ void __launch_bounds__(256)
 enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias,
                   const float* __restrict__ mean, int h, int w, int bsz, long long stride_b, long long stride_t,
                   int tiles_x, int n_tiles, double* __restrict__ partial) {
-  __shared__ float tile[(kE0TH + 2) * kE0RS];      // 15.6 KB
+  __shared__ float tile[2][kE0TE];                 // 2 x 15.6 KB: the next tile is staged while this one is consumed
   __shared__ double sh[2][4][16];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int j = lane & 15, g = lane >> 4;
   const int bi = blockIdx.y;
   const float* ib = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
+  // one round trip to memory for everything the first tile needs: its pixels, the lane's weights, and the shift's operands
+  float v[kE0NL];
+  int ti = blockIdx.x;
+  unsigned vmask = 0u;
+  if (ti < n_tiles) vmask = enc0_tile_load(ib, h, w, (ti / tiles_x) * kE0TH, (ti % tiles_x) * kE0TW, t, v);
+  float sw[27], sp[27];
+  if (PASS == 2) enc0_shift_load(ib, w27, h, w, j, sw, sp);
   int koff[7]; float wb[7];
   enc0_lane_setup(w27, lane, kE0RS, koff, wb);
   const float bias_j = bias[j];
-  const float mean_j = PASS == 1 ? mean[bi * 16 + j] : (PASS == 2 ? enc0_shift(ib, w27, bias, h, w, j) : 0.f);
+  const float mean_j = PASS == 1 ? mean[bi * 16 + j] : (PASS == 2 ? enc0_shift_sum(bias_j, sw, sp, h, w) : 0.f);
   const double shift_j = (double)mean_j;
   double csum = 0.0, csum2 = 0.0;
-  for (int ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
+  if (ti < n_tiles) enc0_tile_store(tile[0], t, v, vmask);
+  __syncthreads();
+  int cur = 0;
+  for (; ti < n_tiles; ti += gridDim.x) {
     const int y0 = (ti / tiles_x) * kE0TH, x0 = (ti % tiles_x) * kE0TW;
-    __syncthreads();                               // the previous tile has been consumed
-    for (int idx = t; idx < (kE0TH + 2) * kE0RS; idx += 256) {
-      const int r = idx / kE0RS, cc = idx - r * kE0RS;
-      const int gy = y0 - 1 + r, gxc = (x0 - 1) * 3 + cc;
-      const bool in = gy >= 0 && gy < h && gxc >= 0 && gxc < w * 3;
-      tile[idx] = in ? ib[(long long)gy * w * 3 + gxc] : 0.f;
-    }
-    __syncthreads();
+    const int tn = ti + gridDim.x;
+    const bool more = tn < n_tiles;                // (the same in every thread of the workgroup)
+    if (more) vmask = enc0_tile_load(ib, h, w, (tn / tiles_x) * kE0TH, (tn % tiles_x) * kE0TW, t, v);   // in flight during the MFMAs below
+    const float* tb = tile[cur];
+    // A tile that lies inside the image whole (every tile of a 384 x 1280 frame) takes the copy of this code whose per-pixel
+    // "inside the image" test is folded away: the kernel is bound by its VALU instructions, and that is a third of the sums'.
+    // (Rolled to four chains at a time: unrolled further, the scheduler keeps all sixteen results of a tile live beside the staged
+    //  registers, and the kernel no longer fits four workgroups per CU.)
+    auto tile_sums = [&](auto whole) {
+      constexpr bool kWhole = decltype(whole)::value;
+#pragma unroll 1
+      for (int rr = 0; rr < 2; ++rr) {
+        const int yl = 2 * wv + rr;
+#pragma unroll 4
+        for (int ct = 0; ct < kE0TW / 16; ++ct) {
+          const float* wnd = tb + yl * kE0RS + 3 * (16 * ct + j);
+          const f32x4 acc = (M4D_E0S_ABL & 2) ? f32x4{wnd[koff[0]], wnd[koff[1]], wnd[koff[2]], wnd[koff[3]]} : enc0_conv1(wnd, koff, wb);
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-      const int yl = 2 * wv + rr;
-#pragma unroll
-      for (int ct = 0; ct < kE0TW / 16; ++ct) {
-        const f32x4 acc = enc0_conv1(tile + yl * kE0RS + 3 * (16 * ct + j), koff, wb);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool valid = y0 + yl < h && x0 + 16 * ct + 4 * g + r < w;
-          float v = acc[r] + bias_j;
-          if (PASS == 1) { v = v - mean_j; v = v * v; }
-          if (PASS == 2) {
-            const double d = valid ? (double)v - shift_j : 0.0;
-            csum += d;
-            csum2 = fma(d, d, csum2);
-          } else {
-            csum += valid ? (double)v : 0.0;
+          for (int r = 0; r < 4; ++r) {
+            const bool valid = kWhole || (y0 + yl < h && x0 + 16 * ct + 4 * g + r < w);
+            float v1 = acc[r] + bias_j;
+            if (M4D_E0S_ABL & 4) { csum += r == 0 ? (double)v1 : 0.0; continue; }
+            if (PASS == 1) { v1 = v1 - mean_j; v1 = v1 * v1; }
+            if (PASS == 2) {
+              const double d = valid ? (double)v1 - shift_j : 0.0;
+              csum += d;
+              csum2 = fma(d, d, csum2);
+            } else {
+              csum += valid ? (double)v1 : 0.0;
+            }
           }
         }
       }
+    };
+    if (y0 + kE0TH <= h && x0 + kE0TW <= w) tile_sums(std::true_type{}); else tile_sums(std::false_type{});
+    if (more) {
+      enc0_tile_store(tile[cur ^ 1], t, v, vmask);
+      __syncthreads();                             // the other buffer is complete, and this one is consumed: the only barrier per tile
     }
+    cur ^= 1;
   }
   csum += __shfl_xor(csum, 16);                    // the four pixel groups of a channel: fixed butterfly
   csum += __shfl_xor(csum, 32);
@@ -477,17 +552,21 @@ enc0_moments_finalize_kernel(const float* __restrict__ img, const double* __rest
   __shared__ double sh[256];
   const int bi = blockIdx.x, t = threadIdx.x;
   const int c = t & 31, j = t >> 5;
-  // (the kernel is a latency chain on the head of the step: all of a thread's partials are requested before the first add, and
-  //  the shift -- 27 dependent scalar loads + multiply-adds -- is evaluated by 16 other threads meanwhile)
+  // (the kernel is a latency chain on the head of the step: the shift's operands -- every thread takes those of channel t & 15,
+  //  threads 0..15 use the result -- and all of a thread's partials are requested together, before the first add: one round trip;
+  //  a partial past the last block reads element 0 and becomes 0 by a select)
+  const float* ib0 = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
+  float sw[27], sp[27];
+  enc0_shift_load(ib0, w27, h, w, t & 15, sw, sp);
+  const float sbias = bias[t & 15];
   double pv[32];
   const int cnt = (nblk - j + 7) / 8;
 #pragma unroll
-  for (int i = 0; i < 32; ++i) pv[i] = i < cnt ? partial[((long long)bi * nblk + j + 8 * i) * 32 + c] : 0.0;
-  __shared__ float s_shift[16];
-  if (t >= 240) {
-    const float* ib0 = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
-    s_shift[t - 240] = enc0_shift(ib0, w27, bias, h, w, t - 240);
+  for (int i = 0; i < 32; ++i) {
+    const double x = partial[i < cnt ? ((long long)bi * nblk + j + 8 * i) * 32 + c : 0LL];
+    pv[i] = i < cnt ? x : 0.0;
   }
+  const float shift = enc0_shift_sum(sbias, sw, sp, h, w);
   double s = 0.0;
 #pragma unroll
   for (int i = 0; i < 32; ++i) s += pv[i];                         // block order j, j + 8, ...: fixed
@@ -501,7 +580,7 @@ enc0_moments_finalize_kernel(const float* __restrict__ img, const double* __rest
   if (t < 16) {
     const double n = (double)h * (double)w;
     const double m1 = sh[t] / n, m2 = sh[16 + t] / n;
-    mean[bi * 16 + t] = (float)((double)s_shift[t] + m1);
+    mean[bi * 16 + t] = (float)((double)shift + m1);
     const double v = m2 - m1 * m1;
     var[bi * 16 + t] = (float)(v > 0.0 ? v : 0.0);
   }
@@ -611,38 +690,80 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   const float* ib = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
   const int oy0 = (blockIdx.x / tiles_x) * kF0OH, ox0 = (blockIdx.x % tiles_x) * kF0OW;
   const int cy0 = 2 * oy0 - pad_y, cx0 = 2 * ox0 - pad_x;   // conv1 region origin (image coordinates; TF 'SAME': pad_before = 0 on even sizes, 1 on odd)
-  for (int idx = t; idx < kF0RH * kF0RS; idx += 256) {
-    const int r = idx / kF0RS, cc = idx - r * kF0RS;
-    const int gy = cy0 - 1 + r, gxc = (cx0 - 1) * 3 + cc;
-    const bool in = gy >= 0 && gy < h && gxc >= 0 && gxc < w * 3;
-    rgb[idx] = (in && !(M4D_E0_ABL & 1)) ? ib[(long long)gy * w * 3 + gxc] : 0.f;    // (gxc < 0 for cx0 - 1 < 0: C division, never indexed)
+  // staging: every load of the kernel -- the thread's 8 RGB elements idx = t + 256 i, the lane's weights of both convolutions,
+  // the statistics -- is requested before the first is waited for; (row, column) of idx advance without a division, and an
+  // element outside the image (or past the region's end) reads pixel 0 and becomes 0 by a select
+  constexpr int kNL = (kF0RH * kF0RS + 255) / 256, kStep = 256 - 2 * kF0RS;
+  static_assert(kStep >= 0 && kStep < kF0RS && 3 * kF0RS > 256, "the row / column walk below");
+  float sv[kNL];
+  {
+    const int row3 = w * 3, gy0 = cy0 - 1, gc0 = (cx0 - 1) * 3;
+    int r = (t >= kF0RS) + (t >= 2 * kF0RS), cc = t - r * kF0RS;
+#pragma unroll
+    for (int i = 0; i < kNL; ++i) {
+      const int gy = gy0 + r, gxc = gc0 + cc;
+      const bool in = r < kF0RH && gy >= 0 && gy < h && gxc >= 0 && gxc < row3 && !(M4D_E0_ABL & 1);
+      const float x = ib[in ? (long long)gy * row3 + gxc : 0LL];
+      sv[i] = in ? x : 0.f;
+      r += 2; cc += kStep;
+      if (cc >= kF0RS) { cc -= kF0RS; ++r; }
+    }
   }
   int koff[7]; float wb[7];
   enc0_lane_setup(w27, lane, kF0RS, koff, wb);
   const float bias_j = bias1[j];
   __shared__ float s_mu[16], s_dv[16], s_sc[16], s_bs[16];
-  if (t < 16) {
-    s_mu[t] = mean[bi * 16 + t];
-    s_dv[t] = 1.0f / (var[bi * 16 + t] + 1e-12f); // (x - mean) / (var + 1e-12): variance, not std (:47), as a multiply
-    s_sc[t] = dn_scale[t]; s_bs[t] = dn_bias[t];
-  }
+  const float st_mu = mean[bi * 16 + (t & 15)], st_var = var[bi * 16 + (t & 15)], st_sc = dn_scale[t & 15], st_bs = dn_bias[t & 15];
   float wb2[36];                                   // B operand of the second convolution: k = tap * 16 + channel = 4 s + g
 #pragma unroll
   for (int s = 0; s < 36; ++s) wb2[s] = w2[(4 * s + g) * 16 + j];
   const float bias2_j = bias2[j];
+#pragma unroll
+  for (int i = 0; i < kNL; ++i)
+    if (t + 256 * i < kF0RH * kF0RS) rgb[t + 256 * i] = sv[i];
+  if (t < 16) {
+    s_mu[t] = st_mu;
+    s_dv[t] = 1.0f / (st_var + 1e-12f);            // (x - mean) / (var + 1e-12): variance, not std (:47), as a multiply
+    s_sc[t] = st_sc; s_bs[t] = st_bs;
+  }
   __syncthreads();
-  // ---- phase 1a: conv1 + bias of the 561 region pixels as 36 tiles of 16 (pixel p = 16 tile + i, row-major), 9 per wave -> LDS
-  static_assert((kF0NP + 15) / 16 == 36, "nine 16-pixel tiles per wave");
-#pragma unroll 3                                   // three independent MFMA chains in flight (a chain is 7 dependent MFMAs)
-  for (int it = 0; it < 9; ++it) {
-    const int tl = wv + 4 * it;
-    const int pa = min(16 * tl + j, kF0NP - 1);    // this lane's A pixel
-    const int ay = pa / kF0CW, ax = pa - ay * kF0CW;
-    const f32x4 acc = (M4D_E0_ABL & 2) ? f32x4{wb[0], wb[1], wb[2], wb[3]} : enc0_conv1(rgb + ay * kF0RS + 3 * ax, koff, wb);
+  // ---- phase 1a: conv1 + bias of the 561 region pixels as 36 tiles of 16 (pixel p = 16 tile + i, row-major), 9 per wave -> LDS:
+  // three tiles at a time on three accumulators (a chain is 7 dependent MFMAs: three chains interleaved keep the pipe busy);
+  // only tile 35 is ragged (pixel 560 alone), the other 35 store unconditionally
+  static_assert((kF0NP + 15) / 16 == 36 && kF0NP > 16 * 35, "nine 16-pixel tiles per wave, the last one of wave 3 ragged");
+#pragma unroll 1                                   // (unrolled, the nine accumulators cost a workgroup per CU)
+  for (int it = 0; it < 9; it += 3) {
+    const float* wa[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int pa = min(16 * (wv + 4 * (it + u)) + j, kF0NP - 1);   // this lane's A pixel of tile u
+      const int ay = pa / kF0CW, ax = pa - ay * kF0CW;
+      wa[u] = rgb + ay * kF0RS + 3 * ax;
+    }
+    f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0, c2 = c0;
+    if (M4D_E0_ABL & 2) {
+      c0 = c1 = c2 = f32x4{wb[0], wb[1], wb[2], wb[3]};
+    } else {
+#pragma unroll
+      for (int s = 0; s < 7; ++s) {
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[0][koff[s]], wb[s], c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[1][koff[s]], wb[s], c1, 0, 0, 0);
+        c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[2][koff[s]], wb[s], c2, 0, 0, 0);
+      }
+    }
+    float* n0 = nrm + (16 * (wv + 4 * it) + 4 * g) * kF0NS + j;      // accumulator row r -> pixel 16 tile + 4 g + r
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int p = 16 * tl + 4 * g + r;           // the pixel of accumulator row r
-      if (p < kF0NP) nrm[p * kF0NS + j] = acc[r] + bias_j;
+      n0[r * kF0NS] = c0[r] + bias_j;
+      n0[(64 + r) * kF0NS] = c1[r] + bias_j;
+    }
+    if (it < 6 || wv < 3) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) n0[(128 + r) * kF0NS] = c2[r] + bias_j;
+    } else {                                       // tile 35
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (16 * 35 + 4 * g + r < kF0NP) n0[(128 + r) * kF0NS] = c2[r] + bias_j;
     }
   }
   __syncthreads();
@@ -665,16 +786,29 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   }
   __syncthreads();
   // ---- phase 2: 8 rows of 16 stride-2 outputs, 2 rows per wave; A[pixel i][k]: pixel (2 oy + ky, 2 i + kx), channel
+  // (the two rows' chains of 36 alternate on two accumulators, and the A operands of step s + 2 are read from LDS while step s
+  //  multiplies: one row after the other, every second MFMA waited for an LDS read issued just before it)
+  constexpr int kS2 = (M4D_E0_ABL & 8) ? 1 : 36;
+  const float* base2 = nrm + ((4 * wv) * kF0CW + 2 * j) * kF0NS + g;
+  auto a2 = [&](int rr, int s) {
+    const int tap = s >> 2, ky = tap / 3, kx = tap - 3 * ky;
+    return base2[((2 * rr + ky) * kF0CW + kx) * kF0NS + 4 * (s & 3)];
+  };
+  f32x4 acc2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  float xa[2][2] = {{a2(0, 0), a2(1, 0)}, {a2(0, kS2 > 1 ? 1 : 0), a2(1, kS2 > 1 ? 1 : 0)}};
+#pragma unroll
+  for (int s = 0; s < kS2; ++s) {
+    const float x0 = xa[s & 1][0], x1 = xa[s & 1][1];
+    if (s + 2 < kS2) { xa[s & 1][0] = a2(0, s + 2); xa[s & 1][1] = a2(1, s + 2); }
+    acc2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0, wb2[s], acc2[0], 0, 0, 0);
+    acc2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1, wb2[s], acc2[1], 0, 0, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);            // two LDS reads (step s + 2)
+    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);            // two MFMAs (step s)
+  }
 #pragma unroll
   for (int rr = 0; rr < 2; ++rr) {
     const int oyl = 2 * wv + rr;
-    const float* base = nrm + ((2 * oyl) * kF0CW + 2 * j) * kF0NS + g;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < ((M4D_E0_ABL & 8) ? 1 : 36); ++s) {
-      const int tap = s >> 2, ky = tap / 3, kx = tap - 3 * ky;
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(base[(ky * kF0CW + kx) * kF0NS + 4 * (s & 3)], wb2[s], acc, 0, 0, 0);
-    }
+    const f32x4 acc = acc2[rr];
     const int oy = oy0 + oyl;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
