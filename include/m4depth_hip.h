@@ -19,10 +19,11 @@
  *     enqueued asynchronously on `stream` (a hipStream_t passed as void*; NULL =
  *     the default stream).  No host synchronisation; the calls are re-entrant,
  *     safe from several host threads on different streams, and hipGraph-capturable.
- *     The ONLY process-wide state is the profiling / debugging hooks named
- *     m4d_*_set_* (cycle-stamp buffers, the DSCV kernel selector, ablation masks):
- *     all off by default, not meant to be flipped while another thread launches,
- *     and never touched by the product's dispatch (m4depth_amd/network.py) -- every
+ *     The ONLY process-wide state is the table of environment switches, read once
+ *     and never written again (m4d_switches_info), and the profiling / debugging
+ *     hooks named m4d_*_set_* (cycle-stamp buffers, the DSCV kernel selector,
+ *     ablation masks): all off by default, not meant to be flipped while another
+ *     thread launches, and never touched by the product's dispatch (m4depth_amd/network.py) -- every
  *     tuning choice of the dispatch (which Winograd kernel, its staggered first
  *     round) is an ARGUMENT of the call (ABI 6 removed round 5's
  *     m4d_wino6_set_stagger, the one setter the dispatch did touch).  The
@@ -48,7 +49,7 @@
 extern "C" {
 #endif
 
-#define M4D_ABI_VERSION 6   /* 6: + m4d_train_log_step, m4d_train_log_workspace_bytes (device-side step log of the replayed training step; additive within ABI 6); 6: + m4d_depth_metrics_per_sample, m4d_metrics_per_sample_workspace_bytes (per-sample metrics of batched streaming evaluation; additive within ABI 6); 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
+#define M4D_ABI_VERSION 6   /* 6: + m4d_switches_info (the environment switches the library runs with; additive within ABI 6); 6: + m4d_train_log_step, m4d_train_log_workspace_bytes (device-side step log of the replayed training step; additive within ABI 6); 6: + m4d_depth_metrics_per_sample, m4d_metrics_per_sample_workspace_bytes (per-sample metrics of batched streaming evaluation; additive within ABI 6); 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
 
 /* Library / device introspection (no GPU work). */
 int m4d_abi_version(void);
@@ -56,6 +57,11 @@ int m4d_abi_version(void);
  * the hipGraph capture of one -- is the number of launches the step is made of (bench.py: roofline.launches_per_step). */
 long long m4d_launch_count(void);
 const char* m4d_build_info(void);
+/* The environment switches of the library as this process read them (once, at the first call that needs one; never written
+ * again): a static string "name=value" per switch, space separated -- "sncv_variant=1 sncv_ys=0 sncv_small_px=6000
+ * wino_variant=4 wino4_min_wg=100 dscv_bwd_window_kb=48" with nothing set.  name = the variable without its M4D_ prefix, in
+ * lower case; INTEGRATION.md lists them.  Additive entry point: ABI 6 unchanged. */
+const char* m4d_switches_info(void);
 
 /* ---- the reference's native op ------------------------------------------------ */
 

@@ -135,6 +135,20 @@ def build_info() -> str:
     return lib.m4d_build_info().decode()
 
 
+def switches() -> dict:
+    """The environment switches of the library as this process read them (m4d_switches_info): {"sncv_variant": 1, ...}."""
+    return {k: int(v) for k, v in (item.split("=") for item in lib.m4d_switches_info().decode().split())}
+
+
+def assert_switches_follow_env(*variables):
+    """Every named variable that the environment sets is the value the library runs with: a comparison between processes that
+    differ only in a switch compares nothing if the library ignores it."""
+    got = switches()
+    for var in variables:
+        if var in os.environ:
+            assert got[var[4:].lower()] == int(os.environ[var]), f"{var}={os.environ[var]} but the library runs with {got}"
+
+
 def stream_ptr():
     """The current PyTorch HIP stream as a void* for the C ABI."""
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

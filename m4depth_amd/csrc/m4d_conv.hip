@@ -18,7 +18,6 @@
 //   ds_read_b128; rows are padded to 20 floats (conflict-free 16-byte reads).
 //   The global loads of the NEXT stage are issued into registers before the MFMAs of the
 //   current one (software pipeline), so one workgroup per SIMD already hides memory latency.
-#include <cstdlib>
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
 
@@ -36,7 +35,9 @@ struct ConvArgs {
   // DINL variant (encoder level 0): x is the RAW first convolution; DomainNormalization + leaky_relu(dn_slope) are applied
   // while the halo is committed to LDS (m4depth_network.py:44-48,82-84)
   const float* dn_mean; const float* dn_var; const float* dn_scale; const float* dn_bias; float dn_slope;
-  int ablate;                         // profiling only (M4D_CONV_ABLATE): 1 = no re-staging after the first stage, 2 = no MFMAs, 4 = no stores
+  int ablate;                         // profiling only: 1 = no re-staging after the first stage, 2 = no MFMAs, 4 = no stores.  Every host
+                                      // path passes 0 (the environment switch that set it is retired); the field and its branches stay
+                                      // until a measured change, because removing them changes the code of the hot kernels
 };
 
 constexpr int kTW = 16, kTH = 8;                    // output tile
@@ -677,8 +678,7 @@ void launch_conv(const ConvArgs& a, dim3 grid, hipStream_t s) {
 template <int STRIDE>
 void dispatch_conv(const ConvArgs& a, int nt, dim3 grid, hipStream_t s) {
   const long long blocks = (long long)grid.x * grid.y * grid.z;
-  static long long occ3_min_blocks = -1;       // M4D_CONV_OCC3_MIN_BLOCKS: A/B switch for the 3-workgroups-per-CU variant
-  if (occ3_min_blocks < 0) { const char* e = getenv("M4D_CONV_OCC3_MIN_BLOCKS"); occ3_min_blocks = e ? atoll(e) : 4 * 768; }
+  constexpr long long occ3_min_blocks = 4 * 768;   // grids from this size take the 3-workgroups-per-CU variant of the widest kernel
   // MINB pins each variant to the occupancy its natural register allocation had (2-3-3-4 workgroups per CU at
   // stride 1, 1-2-2-2 at stride 2) -- an explicit bound of 1 would let the scheduler hoist loads until only one fits.
   switch (nt) {
@@ -815,9 +815,7 @@ extern "C" int m4d_conv3x3s_bias_act_wsb(const float* x, const float* wp, const 
   a.x = x; a.wp = wp; a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout;
   a.CoutPad = CoutPad; a.n_chunks = (Cin + kKC - 1) / kKC;
   a.dn_mean = a.dn_var = a.dn_scale = a.dn_bias = nullptr; a.dn_slope = 1.0f;
-  static int ablate = -1;
-  if (ablate < 0) { const char* e = getenv("M4D_CONV_ABLATE"); ablate = e ? atoi(e) : 0; }
-  a.ablate = ablate;
+  a.ablate = 0;
   // TensorFlow 'SAME': out = ceil(in / stride), total pad = max((out-1)*stride + 3 - in, 0), before = total / 2
   a.oh = (h + stride - 1) / stride; a.ow = (w + stride - 1) / stride;
   const int tph = (a.oh - 1) * stride + 3 - h, tpw = (a.ow - 1) * stride + 3 - w;
@@ -838,10 +836,7 @@ extern "C" int m4d_conv3x3s_bias_act_wsb(const float* x, const float* wp, const 
   // (from the grid a launch on ``split_batch`` images would have: the same factor however many images this launch carries)
   const long long blocks = tiles * split_batch * (n32 / n_tiles_for(split_batch));
   int ksplit = 1;
-  static int sk_target = -1, sk_min_chunks = -1, sk_max = -1;     // tuning knobs (profiling): M4D_CONV_SPLITK_TARGET / _MIN_CHUNKS / _MAX
-  if (sk_target < 0) { const char* e = getenv("M4D_CONV_SPLITK_TARGET"); sk_target = e ? atoi(e) : 256; }
-  if (sk_min_chunks < 0) { const char* e = getenv("M4D_CONV_SPLITK_MIN_CHUNKS"); sk_min_chunks = e ? atoi(e) : 2; }
-  if (sk_max < 0) { const char* e = getenv("M4D_CONV_SPLITK_MAX"); sk_max = e ? atoi(e) : 16; }
+  constexpr int sk_target = 256, sk_min_chunks = 2, sk_max = 16;  // workgroups aimed at, chunks per split at least, splits at most
   if (workspace != nullptr && blocks < 128 && a.n_chunks >= 4) {
     ksplit = (int)((sk_target + blocks - 1) / blocks);
     if (ksplit > a.n_chunks / sk_min_chunks) ksplit = a.n_chunks / sk_min_chunks;

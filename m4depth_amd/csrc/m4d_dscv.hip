@@ -17,6 +17,7 @@
 // contiguous band of the image: the gathers of neighbouring pixels then hit the
 // XCD's own 4 MiB L2.
 #include "m4d_common.h"
+#include "m4d_switches.h"
 #include "m4d_sncv_small.h"
 #include "m4d_level_pre.h"
 #include "../../include/m4depth_hip.h"
@@ -727,6 +728,39 @@ extern "C" void m4d_dscv_set_ablation(int mask) { g_dscv_ablate = mask; }
 static int g_dscv_variant = 1;
 extern "C" void m4d_dscv_set_variant(int v) { g_dscv_variant = v; }
 
+// The channel / cut pairs of the 6-level pyramid (C = 16..192 in 1, 2, 2, 4, 4, 8 cuts) as (lanes per pixel, lanes per cut) =
+// (C / 4, C / cuts / 4): f(m4d_int<LP>{}, m4d_int<G>{}) for the pair that (lp, g) is, false for any other shape.
+template <class F>
+static bool dscv_pyramid_shape(int lp, int g, F&& f) {
+  if (lp == 4 && g == 4) return f(m4d_int<4>{}, m4d_int<4>{});        // C=16  k=1
+  if (lp == 8 && g == 4) return f(m4d_int<8>{}, m4d_int<4>{});        // C=32  k=2
+  if (lp == 16 && g == 8) return f(m4d_int<16>{}, m4d_int<8>{});      // C=64  k=2
+  if (lp == 24 && g == 6) return f(m4d_int<24>{}, m4d_int<6>{});      // C=96  k=4
+  if (lp == 32 && g == 8) return f(m4d_int<32>{}, m4d_int<8>{});      // C=128 k=4
+  if (lp == 48 && g == 6) return f(m4d_int<48>{}, m4d_int<6>{});      // C=192 k=8
+  return false;
+}
+// ... plus the two small shapes the unit tests use, which only the wave kernel is built for
+template <class F>
+static bool dscv_wave_shape(int lp, int g, F&& f) {
+  if (lp == 8 && g == 8) return f(m4d_int<8>{}, m4d_int<8>{});        // C=32  k=1
+  if (lp == 4 && g == 2) return f(m4d_int<4>{}, m4d_int<2>{});        // C=16  k=2
+  return dscv_pyramid_shape(lp, g, f);
+}
+
+// What every entry point fills the same way; the caller adds disp / disp_prev_t (or the maps they are evaluated from) and index_out.
+static DscvArgs dscv_args(const float* c1, const float* c2, const float* rot, int rot_c, const float* trans, const float* cam_f,
+                          const float* cam_c, int h, int w, int C, int r, int k, int cv_accum, float* cv, int cv_stride,
+                          float* prev_disp, float* log_center, int log_stride, float log_scale) {
+  DscvArgs a;
+  a.c1 = c1; a.c2 = c2; a.disp_prev_t = nullptr; a.disp = nullptr;
+  a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c;
+  a.h = h; a.w = w; a.C = C; a.r = r; a.k = k; a.nc = C / k; a.cv_accum = cv_accum;
+  a.cv = cv; a.cv_stride = cv_stride; a.prev_disp = prev_disp; a.log_center = log_center;
+  a.log_stride = log_stride; a.log_scale = log_scale; a.index_out = nullptr; a.ablate = g_dscv_ablate;
+  return a;
+}
+
 extern "C" int m4d_dscv_fwd(const float* c1, const float* c2, const float* disp_prev_t, const float* disp,
                             const float* rot, int rot_c, const float* trans, const float* cam_f,
                             const float* cam_c, int b, int h, int w, int C, int search_range, int nbre_cuts,
@@ -740,18 +774,14 @@ extern "C" int m4d_dscv_fwd(const float* c1, const float* c2, const float* disp_
   M4D_CHECK_ARG(cv_accum == 0 || cv_accum == 1);
   M4D_CHECK_ARG(cv_stride >= nbre_cuts * (2 * search_range + 1));
   M4D_CHECK_ARG(log_center == nullptr || log_stride >= 1);
-  DscvArgs a;
-  a.c1 = c1; a.c2 = c2; a.disp_prev_t = disp_prev_t; a.disp = disp;
-  a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c;
-  a.h = h; a.w = w; a.C = C; a.r = search_range; a.k = nbre_cuts; a.nc = C / nbre_cuts; a.cv_accum = cv_accum;
-  a.cv = cv; a.cv_stride = cv_stride; a.prev_disp = prev_disp; a.log_center = log_center;
-  a.log_stride = log_stride; a.log_scale = log_scale; a.index_out = index_out; a.ablate = g_dscv_ablate;
+  DscvArgs a = dscv_args(c1, c2, rot, rot_c, trans, cam_f, cam_c, h, w, C, search_range, nbre_cuts, cv_accum, cv, cv_stride,
+                         prev_disp, log_center, log_stride, log_scale);
+  a.disp_prev_t = disp_prev_t; a.disp = disp; a.index_out = index_out;
   hipStream_t s = (hipStream_t)stream;
   const bool aligned = (((uintptr_t)c1 | (uintptr_t)c2) & 15u) == 0 && (a.nc % 4 == 0);
   const int lp = C / 4, g = a.nc / 4;
   const bool fits = aligned && (2 * search_range + 1) <= 16;
-  // (LP, G) pairs of the 6-level pyramid (C = 16..192, cuts 1,2,2,4,4,8) plus the small
-  // shapes the unit tests use; everything else takes the generic kernel.
+  // The pyramid's shapes (the wave kernel: plus the small shapes the unit tests use); everything else takes the generic kernel.
   if (fits && (g_dscv_variant == 3 || g_dscv_variant == 4)) {     // hypotheses in-lane on the LDS window
     const bool ail = g_dscv_variant == 4;
     if (a.nc == 16 && nbre_cuts == 1 && launch_hyp<16, 1>(a, b, s, ail)) return M4D_LAUNCH_RESULT();
@@ -764,22 +794,10 @@ extern "C" int m4d_dscv_fwd(const float* c1, const float* c2, const float* disp_
     m4d_launch(dscv_generic_kernel, dim3(m4d_blocks(threads, 256), b), dim3(256), 0, s, a);
     return M4D_LAUNCH_RESULT();
   }
-  if (tile && lp == 4 && g == 4 && launch_tile<4, 4>(a, b, s)) return M4D_LAUNCH_RESULT();
-  if (tile && lp == 8 && g == 4 && launch_tile<8, 4>(a, b, s)) return M4D_LAUNCH_RESULT();
-  if (tile && lp == 16 && g == 8 && launch_tile<16, 8>(a, b, s)) return M4D_LAUNCH_RESULT();
-  if (tile && lp == 24 && g == 6 && launch_tile<24, 6>(a, b, s)) return M4D_LAUNCH_RESULT();
-  if (tile && lp == 32 && g == 8 && launch_tile<32, 8>(a, b, s)) return M4D_LAUNCH_RESULT();
-  if (tile && lp == 48 && g == 6 && launch_tile<48, 6>(a, b, s)) return M4D_LAUNCH_RESULT();
-  bool done = false;
-  if (fits && lp == 4 && g == 4) done = launch_wave<4, 4>(a, b, s);          // C=16  k=1
-  else if (fits && lp == 8 && g == 4) done = launch_wave<8, 4>(a, b, s);     // C=32  k=2
-  else if (fits && lp == 16 && g == 8) done = launch_wave<16, 8>(a, b, s);   // C=64  k=2
-  else if (fits && lp == 24 && g == 6) done = launch_wave<24, 6>(a, b, s);   // C=96  k=4
-  else if (fits && lp == 32 && g == 8) done = launch_wave<32, 8>(a, b, s);   // C=128 k=4
-  else if (fits && lp == 48 && g == 6) done = launch_wave<48, 6>(a, b, s);   // C=192 k=8
-  else if (fits && lp == 8 && g == 8) done = launch_wave<8, 8>(a, b, s);     // C=32  k=1
-  else if (fits && lp == 4 && g == 2) done = launch_wave<4, 2>(a, b, s);     // C=16  k=2
-  if (!done) {                                  // any other shape / search range
+  if (tile && dscv_pyramid_shape(lp, g, [&](auto LP, auto G) { return launch_tile<decltype(LP)::value, decltype(G)::value>(a, b, s); }))
+    return M4D_LAUNCH_RESULT();
+  const bool done = fits && dscv_wave_shape(lp, g, [&](auto LP, auto G) { return launch_wave<decltype(LP)::value, decltype(G)::value>(a, b, s); });
+  if (!done) {                                 // any other shape / search range
     const long long threads = (long long)h * w * nbre_cuts;
     m4d_launch(dscv_generic_kernel, dim3(m4d_blocks(threads, 256), b), dim3(256), 0, s, a);
   }
@@ -819,9 +837,7 @@ bool launch_front_small(const DscvArgs& a, int b, const m4d_sncv::SncvArgs& sa, 
 static bool front_small_shape(int C, int nbre_cuts, int dscv_range, int sncv_range) {
   if (C <= 0 || nbre_cuts <= 0 || C % nbre_cuts != 0 || (C / nbre_cuts) % 4 != 0) return false;
   if (!(dscv_range == 4 || dscv_range == 2) || sncv_range < 0) return false;
-  const int lp = C / 4, g = C / nbre_cuts / 4;
-  return (lp == 24 && g == 6) || (lp == 32 && g == 8) || (lp == 48 && g == 6) || (lp == 16 && g == 8) || (lp == 8 && g == 4) ||
-         (lp == 4 && g == 4);
+  return dscv_pyramid_shape(C / 4, C / nbre_cuts / 4, [](auto, auto) { return true; });
 }
 
 extern "C" int m4d_level_front_small_supported(int C, int nbre_cuts, int dscv_range, int sncv_range) {
@@ -843,12 +859,8 @@ extern "C" int m4d_level_front_small(const float* norm_f, const float* prev_f, c
   const int f_in = ncp * k + 1 + 4 + mo * mo * k + 1;            // cv | log para_l | other(4) | sncv | log para_t
   M4D_CHECK_ARG(f_stride >= f_in);
   const int log_off = ncp * k, other_off = log_off + 1, sncv_off = log_off + 5;
-  DscvArgs a;
-  a.c1 = norm_f; a.c2 = prev_f; a.disp_prev_t = nullptr; a.disp = nullptr;
-  a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c;
-  a.h = h; a.w = w; a.C = C; a.r = dscv_range; a.k = k; a.nc = C / k; a.cv_accum = cv_accum;
-  a.cv = f_input; a.cv_stride = f_stride; a.prev_disp = nullptr; a.log_center = f_input + (f_in - 1);
-  a.log_stride = f_stride; a.log_scale = log_scale; a.index_out = nullptr; a.ablate = g_dscv_ablate;
+  DscvArgs a = dscv_args(norm_f, prev_f, rot, rot_c, trans, cam_f, cam_c, h, w, C, dscv_range, k, cv_accum, f_input, f_stride,
+                         nullptr, f_input + (f_in - 1), f_stride, log_scale);
   a.pl_para = prev_l_parallax; a.ph = ph; a.pw = pw; a.depth_prev_t = depth_prev_t;
   m4d_sncv::SncvArgs sa;
   sa.c1 = norm_f; sa.c2 = norm_f; sa.h = h; sa.w = w; sa.C = C; sa.r = sncv_range; sa.d = 1; sa.k = k; sa.nc = C / k;
@@ -860,14 +872,9 @@ extern "C" int m4d_level_front_small(const float* norm_f, const float* prev_f, c
   pa.f_input = f_input; pa.f_stride = f_stride; pa.log_off = log_off; pa.other_off = other_off; pa.log_scale = log_scale;
   pa.depth_state_reset = nullptr;
   hipStream_t s = (hipStream_t)stream;
-  const int lp = C / 4, g = C / k / 4;
-  bool done = false;
-  if (lp == 24 && g == 6) done = launch_front_small<24, 6>(a, b, sa, pa, s);        // C=96  k=4
-  else if (lp == 32 && g == 8) done = launch_front_small<32, 8>(a, b, sa, pa, s);   // C=128 k=4
-  else if (lp == 48 && g == 6) done = launch_front_small<48, 6>(a, b, sa, pa, s);   // C=192 k=8
-  else if (lp == 16 && g == 8) done = launch_front_small<16, 8>(a, b, sa, pa, s);   // C=64  k=2
-  else if (lp == 8 && g == 4) done = launch_front_small<8, 4>(a, b, sa, pa, s);     // C=32  k=2
-  else if (lp == 4 && g == 4) done = launch_front_small<4, 4>(a, b, sa, pa, s);     // C=16  k=1
+  const bool done = dscv_pyramid_shape(C / 4, C / k / 4, [&](auto LP, auto G) {
+    return launch_front_small<decltype(LP)::value, decltype(G)::value>(a, b, sa, pa, s);
+  });
   if (!done) return (int)hipErrorInvalidValue;
   return M4D_LAUNCH_RESULT();
 }
@@ -885,30 +892,22 @@ extern "C" int m4d_dscv_sncv_fwd(const float* c1, const float* c2, const float* 
   const int nc = C / nbre_cuts, mo = 2 * sncv_search_range + 1;
   const bool aligned = (((uintptr_t)c1 | (uintptr_t)c2) & 15u) == 0 && (nc % 4 == 0);
   const int lp = C / 4, g = nc / 4;
-  static int small_px = -1;                            // the same threshold as m4d_sncv_fwd's small-map kernel
-  if (small_px < 0) { const char* e = getenv("M4D_SNCV_SMALL_PX"); small_px = e ? atoi(e) : 6000; }
+  const int small_px = m4d_switches().sncv_small_px;   // the threshold of m4d_sncv_fwd's small-map kernel
   const bool merged_ok = aligned && g_dscv_variant == 1 && (rot_c == 3 || rot_c == 4) && (cv_accum == 0 || cv_accum == 1) &&
                          cv_stride >= nbre_cuts * (2 * search_range + 1) && sncv_search_range >= 0 &&
                          sncv_out_stride >= mo * mo * nbre_cuts && (long long)b * h * w <= small_px &&
                          (log_center == nullptr || log_stride >= 1);
   if (merged_ok) {
-    DscvArgs a;
-    a.c1 = c1; a.c2 = c2; a.disp_prev_t = disp_prev_t; a.disp = disp;
-    a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c;
-    a.h = h; a.w = w; a.C = C; a.r = search_range; a.k = nbre_cuts; a.nc = nc; a.cv_accum = cv_accum;
-    a.cv = cv; a.cv_stride = cv_stride; a.prev_disp = prev_disp; a.log_center = log_center;
-    a.log_stride = log_stride; a.log_scale = log_scale; a.index_out = nullptr; a.ablate = g_dscv_ablate;
+    DscvArgs a = dscv_args(c1, c2, rot, rot_c, trans, cam_f, cam_c, h, w, C, search_range, nbre_cuts, cv_accum, cv, cv_stride,
+                           prev_disp, log_center, log_stride, log_scale);
+    a.disp_prev_t = disp_prev_t; a.disp = disp;
     m4d_sncv::SncvArgs sa;
     sa.c1 = c1; sa.c2 = c1; sa.h = h; sa.w = w; sa.C = C; sa.r = sncv_search_range; sa.d = 1; sa.k = nbre_cuts; sa.nc = nc;
     sa.out = sncv_out; sa.out_stride = sncv_out_stride; sa.th = sa.tw = sa.tiles_x = 0;
     hipStream_t s = (hipStream_t)stream;
-    bool done = false;
-    if (lp == 24 && g == 6) done = launch_wave_sncv<24, 6>(a, b, sa, s);        // C=96  k=4
-    else if (lp == 32 && g == 8) done = launch_wave_sncv<32, 8>(a, b, sa, s);   // C=128 k=4
-    else if (lp == 48 && g == 6) done = launch_wave_sncv<48, 6>(a, b, sa, s);   // C=192 k=8
-    else if (lp == 16 && g == 8) done = launch_wave_sncv<16, 8>(a, b, sa, s);   // C=64  k=2
-    else if (lp == 8 && g == 4) done = launch_wave_sncv<8, 4>(a, b, sa, s);     // C=32  k=2
-    else if (lp == 4 && g == 4) done = launch_wave_sncv<4, 4>(a, b, sa, s);     // C=16  k=1
+    const bool done = dscv_pyramid_shape(lp, g, [&](auto LP, auto G) {
+      return launch_wave_sncv<decltype(LP)::value, decltype(G)::value>(a, b, sa, s);
+    });
     if (done) return M4D_LAUNCH_RESULT();
   }
   const int rc = m4d_dscv_fwd(c1, c2, disp_prev_t, disp, rot, rot_c, trans, cam_f, cam_c, b, h, w, C, search_range, nbre_cuts,

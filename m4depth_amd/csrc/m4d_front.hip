@@ -21,7 +21,6 @@
 //      shuffle chain; the centre hypothesis also samples prev_d2para of the depth memory at its 4 corners;
 //   D  the stage goes out as whole rows.
 // Arithmetic, operand order and summation order are those of the separate kernels and of the oracle: bit-exact.
-#include <cstdlib>
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
 
@@ -469,45 +468,17 @@ extern "C" int m4d_level_front_r(const float* raw_f, float* norm_out, const floa
   // Tile / workgroup shape by geometry and size (profiles/r02_front_tile_sweep.txt): one workgroup's pipeline is a serial
   // chain (stage -> normalise -> SNCV -> DSCV -> store), so a launch needs several workgroups per CU in flight; small maps
   // (levels 2-3 at batch 1: 30720 / 7680 pixels) take half-height tiles with the SNCV window rows split four ways.
-  // M4D_FRONT_L1 / _L2 / _L3 force a shape (profiling).
-  static int v1 = -1, v2 = -1, v3 = -1;
-  if (v1 < 0) {
-    const char* e = getenv("M4D_FRONT_L1"); v1 = e ? atoi(e) : 0;
-    e = getenv("M4D_FRONT_L2"); v2 = e ? atoi(e) : 0;
-    e = getenv("M4D_FRONT_L3"); v3 = e ? atoi(e) : 0;
-  }
+  // Ten other tile shapes were measured within 0.6 % of these (profiles/r06_front_tile_ab.txt) and are no longer built.
   const bool small_map = (long long)b * h * w < 100000;
-  if (nc == 16 && nbre_cuts == 1) {
-    switch (v1) {
-      case 1: return launch_front<16, 1, 16, 8, 2>(a, s);
-      case 2: return launch_front<16, 1, 16, 8, 4>(a, s);
-      case 3: return launch_front<16, 1, 32, 8, 4>(a, s);
-      default: return launch_front<16, 1, 32, 8, 2>(a, s);
-    }
-  }
-  if (nc == 16 && nbre_cuts == 2) {
-    switch (v2 ? v2 : (small_map ? 4 : 5)) {
-      case 1: return launch_front<16, 2, 8, 8, 2>(a, s);
-      case 2: return launch_front<16, 2, 8, 8, 4>(a, s);
-      case 3: return launch_front<16, 2, 16, 4, 2>(a, s);
-      case 4: return launch_front<16, 2, 16, 4, 4>(a, s);
-      default: return launch_front<16, 2, 16, 8, 2>(a, s);
-    }
-  }
+  if (nc == 16 && nbre_cuts == 1) return launch_front<16, 1, 32, 8, 2>(a, s);
+  if (nc == 16 && nbre_cuts == 2) return small_map ? launch_front<16, 2, 16, 4, 4>(a, s) : launch_front<16, 2, 16, 8, 2>(a, s);
+  if (nc == 32 && nbre_cuts == 2) return small_map ? launch_front<32, 2, 16, 4, 4>(a, s) : launch_front<32, 2, 16, 8, 2>(a, s);
   // levels 4-6 of the 6-level pyramid (96 / 128 / 192 channels in 4 / 4 / 8 cuts: 24 / 32 / 48 lanes per pixel in the DSCV
   // phase, 6 or 8 lanes per cut): 8x8 tiles (8x4 for the 192-channel halo, 110 KB), half-size tiles with the window rows
   // split four ways on small maps
   if (nc == 24 && nbre_cuts == 4) return small_map ? launch_front<24, 4, 8, 4, 4>(a, s) : launch_front<24, 4, 8, 8, 2>(a, s);
   if (nc == 32 && nbre_cuts == 4) return small_map ? launch_front<32, 4, 8, 4, 4>(a, s) : launch_front<32, 4, 8, 8, 2>(a, s);
-  if (nc == 24 && nbre_cuts == 8) return small_map ? launch_front<24, 8, 4, 4, 4>(a, s) : launch_front<24, 8, 8, 4, 2>(a, s);
-  switch (v3 ? v3 : (small_map ? 5 : 6)) {
-    case 1: return launch_front<32, 2, 8, 8, 2>(a, s);
-    case 2: return launch_front<32, 2, 8, 4, 4>(a, s);
-    case 3: return launch_front<32, 2, 16, 4, 2>(a, s);
-    case 4: return launch_front<32, 2, 8, 8, 4>(a, s);
-    case 5: return launch_front<32, 2, 16, 4, 4>(a, s);
-    default: return launch_front<32, 2, 16, 8, 2>(a, s);
-  }
+  return small_map ? launch_front<24, 8, 4, 4, 4>(a, s) : launch_front<24, 8, 8, 4, 2>(a, s);
 }
 
 extern "C" int m4d_level_front(const float* raw_f, float* norm_out, const float* prev_f, const float* depth_prev_t,

@@ -20,8 +20,8 @@
 //
 // SNCV: out = leaky_relu(mean_c c1[p,c] * c2pad[p+d,c]); both gradients are gathers over
 // the (2r+1)^2 window, one lane per (pixel, 4 channels), deterministic.
-#include <cstdlib>
 #include "m4d_common.h"
+#include "m4d_switches.h"
 #include "../../include/m4depth_hip.h"
 
 namespace {
@@ -330,8 +330,7 @@ extern "C" int m4d_dscv_bwd(const float* c1, const float* c2, const float* disp_
   a.bh_log2 = ppb_log2 / 2; a.bw_log2 = ppb_log2 - a.bh_log2;
   // (4 * PPW not a power of two -- e.g. 12 lanes per pixel -- : the block holds the power of two below, the other slots idle)
   a.blocks_x = (w + (1 << a.bw_log2) - 1) >> a.bw_log2; a.blocks_y = (h + (1 << a.bh_log2) - 1) >> a.bh_log2;
-  static const int win_kb = [] { const char* e = getenv("M4D_DSCV_BWD_WINDOW_KB"); const int v = e ? atoi(e) : 48; return v < 0 ? 0 : (v > 64 ? 64 : v); }();
-  a.win_floats = win_kb * 256;                                     // 0 = the round-2 kernel's direct scatter (A/B)
+  a.win_floats = m4d_switches().dscv_bwd_window_kb * 256;          // M4D_DSCV_BWD_WINDOW_KB; 0 = the round-2 kernel's direct scatter (A/B)
   dim3 grid((unsigned)(a.blocks_x * a.blocks_y), b);
   m4d_launch(dscv_bwd_kernel, grid, dim3(256), (size_t)a.win_floats * sizeof(float), s, a);
   return M4D_LAUNCH_RESULT();

@@ -3,7 +3,6 @@
 // elementwise stages on either side of the refiner convolutions.  All of these are
 // one-pass, one-lane-per-pixel (or per element) streaming kernels: HBM-bound by
 // construction, no re-reads.
-#include <cstdlib>
 #include "m4d_common.h"
 #include "m4d_level_pre.h"
 #include "../../include/m4depth_hip.h"
@@ -359,9 +358,8 @@ extern "C" int m4d_normalize_cuts(const float* x, int b, int h, int w, int C, in
   const int nc = C / nbre_cuts;
   const long long items = (long long)b * h * w * nbre_cuts;
   const bool vec = (nc % 4 == 0) && ((((uintptr_t)x | (uintptr_t)out) & 15u) == 0);
-  static int grouped = -1;                     // M4D_NORMALIZE_GROUPED=0: the one-lane-per-run kernel (same bits)
-  if (grouped < 0) { const char* e = getenv("M4D_NORMALIZE_GROUPED"); grouped = e ? atoi(e) : 1; }
-  if (vec && grouped && items < (1LL << 40)) {
+  // the grouped kernel wherever it applies; every other width takes the one-lane-per-run kernel (same bits)
+  if (vec && items < (1LL << 40)) {
     hipStream_t s = (hipStream_t)stream;
     switch (nc) {
       case 8: launch_normalize_group<2>(x, items, out, s); return M4D_LAUNCH_RESULT();

@@ -9,7 +9,6 @@
 // in double from the first add on: a frame whose mean dwarfs its spread, or a flat frame (an all-zero one included), keeps
 // its digits, and the mean of a constant channel is exact, so its variance is exactly 0.
 #include <type_traits>
-#include <cstdlib>
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
 
@@ -381,7 +380,7 @@ __device__ __forceinline__ f32x4 enc0_conv1(const float* window_base, const int 
 constexpr int kE0TW = 128, kE0TH = 8;              // statistics tile (pixels)
 constexpr int kE0RS = (kE0TW + 2) * 3;             // floats per staged RGB row (390)
 
-// The shift of the single-pass statistics (PASS 2 below): conv1 + bias at the image's centre pixel.  On a typical frame it is one
+// The shift of the single-pass statistics (enc0_stats_kernel below): conv1 + bias at the image's centre pixel.  On a typical frame it is one
 // sample of the very distribution whose moments are taken, and var = S2 / n - (S1 / n)^2 cancels little.  On a frame whose
 // centre is unlike the rest (a flat or dark frame with a bright centre, a grey one with a black centre) (mean - K)^2 exceeds the
 // variance by up to ~n: the sums are therefore taken in double from the first add on (y - K of two floats is exact in double),
@@ -450,17 +449,16 @@ __device__ __forceinline__ void enc0_tile_store(float* __restrict__ tile, int t,
     if (t + 256 * i < kE0TE) tile[t + 256 * i] = (mask >> i & 1u) ? v[i] : 0.f;
 }
 
-// PASS 0: per-channel sums of conv1 + bias; PASS 1: sums of squared deviations from `mean` -- double partials in the layout of
-// dinl_partial_kernel ([image][block][16]), finished by dinl_finalize_kernel.  A workgroup walks tiles blockIdx.x, + gridDim.x, ...
-// PASS 2 (round 6): BOTH moments in one pass -- S1 = sum (y - K), S2 = sum (y - K)^2 with the per-image, per-channel shift K of
+// BOTH moments of conv1 + bias in one pass -- S1 = sum (y - K), S2 = sum (y - K)^2 with the per-image, per-channel shift K of
 // enc0_shift_load / enc0_shift_sum -- double partials [image][block][32] (16 x S1, 16 x S2), finished by enc0_moments_finalize_kernel: the level-0
-// statistics are then TWO dependent launches instead of four (RGB totals, analytic mean, squared deviations, finalisation), 20 us
-// less at the head of a batch-1 step's critical path.  Every sum is a double, per lane, through the butterfly and the workgroup
-// combine, in a fixed order.
-template <int PASS>
+// statistics are TWO dependent launches (round 5 took four: RGB totals, analytic mean, squared deviations, finalisation; slower,
+// profiles/r06_enc0_single_pass_ab.txt, and retired).  A workgroup walks tiles blockIdx.x, + gridDim.x, ...  Every sum is a double,
+// per lane, through the butterfly and the workgroup combine, in a fixed order.
+// (`unused` was the mean of the retired two-pass variance; it stays in the signature because dropping it moves the kernel's other
+//  arguments, which changes the kernel's code and belongs in a measured change.)
 __global__ void __launch_bounds__(256)
 enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias,
-                  const float* __restrict__ mean, int h, int w, int bsz, long long stride_b, long long stride_t,
+                  const float* __restrict__ unused, int h, int w, int bsz, long long stride_b, long long stride_t,
                   int tiles_x, int n_tiles, double* __restrict__ partial) {
   __shared__ float tile[2][kE0TE];                 // 2 x 15.6 KB: the next tile is staged while this one is consumed
   __shared__ double sh[2][4][16];
@@ -474,12 +472,11 @@ enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   unsigned vmask = 0u;
   if (ti < n_tiles) vmask = enc0_tile_load(ib, h, w, (ti / tiles_x) * kE0TH, (ti % tiles_x) * kE0TW, t, v);
   float sw[27], sp[27];
-  if (PASS == 2) enc0_shift_load(ib, w27, h, w, j, sw, sp);
+  enc0_shift_load(ib, w27, h, w, j, sw, sp);
   int koff[7]; float wb[7];
   enc0_lane_setup(w27, lane, kE0RS, koff, wb);
   const float bias_j = bias[j];
-  const float mean_j = PASS == 1 ? mean[bi * 16 + j] : (PASS == 2 ? enc0_shift_sum(bias_j, sw, sp, h, w) : 0.f);
-  const double shift_j = (double)mean_j;
+  const double shift_j = (double)enc0_shift_sum(bias_j, sw, sp, h, w);
   double csum = 0.0, csum2 = 0.0;
   if (ti < n_tiles) enc0_tile_store(tile[0], t, v, vmask);
   __syncthreads();
@@ -506,16 +503,11 @@ enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const bool valid = kWhole || (y0 + yl < h && x0 + 16 * ct + 4 * g + r < w);
-            float v1 = acc[r] + bias_j;
+            const float v1 = acc[r] + bias_j;
             if (M4D_E0S_ABL & 4) { csum += r == 0 ? (double)v1 : 0.0; continue; }
-            if (PASS == 1) { v1 = v1 - mean_j; v1 = v1 * v1; }
-            if (PASS == 2) {
-              const double d = valid ? (double)v1 - shift_j : 0.0;
-              csum += d;
-              csum2 = fma(d, d, csum2);
-            } else {
-              csum += valid ? (double)v1 : 0.0;
-            }
+            const double d = valid ? (double)v1 - shift_j : 0.0;
+            csum += d;
+            csum2 = fma(d, d, csum2);
           }
         }
       }
@@ -529,20 +521,18 @@ enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   }
   csum += __shfl_xor(csum, 16);                    // the four pixel groups of a channel: fixed butterfly
   csum += __shfl_xor(csum, 32);
-  if (PASS == 2) {
-    csum2 += __shfl_xor(csum2, 16);
-    csum2 += __shfl_xor(csum2, 32);
-  }
+  csum2 += __shfl_xor(csum2, 16);
+  csum2 += __shfl_xor(csum2, 32);
   if (lane < 16) { sh[0][wv][lane] = csum; sh[1][wv][lane] = csum2; }
   __syncthreads();
-  constexpr int NQ = PASS == 2 ? 32 : 16;          // 16 x S1 (+ 16 x S2)
+  constexpr int NQ = 32;                           // 16 x S1, 16 x S2
   if (t < NQ) {
     const int q = t >> 4, c = t & 15;
     partial[((long long)bi * gridDim.x + blockIdx.x) * NQ + t] = ((sh[q][0][c] + sh[q][1][c]) + sh[q][2][c]) + sh[q][3][c];
   }
 }
 
-// mean = K + S1 / n, var = S2 / n - (S1 / n)^2 (the biased variance of tf.math.reduce_variance) from the PASS-2 double partials,
+// mean = K + S1 / n, var = S2 / n - (S1 / n)^2 (the biased variance of tf.math.reduce_variance) from the double partials above,
 // added in block order by a fixed tree: run-to-run identical.  One workgroup per image; thread (c, j): channel c
 // (32 columns: 16 x S1, 16 x S2), every 8th block from j.
 __global__ void __launch_bounds__(256)
@@ -583,83 +573,6 @@ enc0_moments_finalize_kernel(const float* __restrict__ img, const double* __rest
     mean[bi * 16 + t] = (float)((double)shift + m1);
     const double v = m2 - m1 * m1;
     var[bi * 16 + t] = (float)(v > 0.0 ? v : 0.0);
-  }
-}
-
-// The MEAN of the first convolution's output needs no convolution: the layer is linear, so
-//   mean_c = bias_c + (1 / hw) sum_{ky,kx,ch} w[ky][kx][ch][c] * S(ky - 1, kx - 1, ch),
-// S(dy, dx, ch) = the sum of channel ch over the pixels a tap (dy, dx) sees = the whole image minus one border row / column
-// (plus the corner both exclude): per image and channel the total, the first / last row and column sums and the corners.
-// enc0_rgb_total_kernel: per-workgroup partial totals; enc0_mean_kernel (one workgroup per image): totals + borders in
-// double, then the 27 x 16 combination.
-__global__ void __launch_bounds__(256)
-enc0_rgb_total_kernel(const float* __restrict__ img, int hw, int bsz, long long stride_b, long long stride_t, float* __restrict__ partial) {
-  __shared__ float sh[4][3];
-  const int t = threadIdx.x, bi = blockIdx.y;
-  const float* ib = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  for (int p = blockIdx.x * 256 + t; p < hw; p += gridDim.x * 256) {
-    s0 += ib[(long long)p * 3]; s1 += ib[(long long)p * 3 + 1]; s2 += ib[(long long)p * 3 + 2];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-  if ((t & 63) == 0) { sh[t >> 6][0] = s0; sh[t >> 6][1] = s1; sh[t >> 6][2] = s2; }
-  __syncthreads();
-  if (t < 3) partial[((long long)bi * gridDim.x + blockIdx.x) * 3 + t] = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
-}
-
-__global__ void __launch_bounds__(256)
-enc0_mean_kernel(const float* __restrict__ img, const float* __restrict__ partial, int nblk, const float* __restrict__ w27,
-                 const float* __restrict__ bias, int h, int w, int bsz, long long stride_b, long long stride_t, float* __restrict__ mean) {
-  // sums[ch][0] total, [1] row 0, [2] row h-1, [3] column 0, [4] column w-1: every thread gathers its share of all 15, then
-  // one fixed tree over the 256 threads for all of them at once
-  __shared__ double red[15][256];
-  __shared__ double sums[3][5];
-  const int t = threadIdx.x, bi = blockIdx.x;
-  const float* ib = img + (long long)(bi % bsz) * stride_b + (long long)(bi / bsz) * stride_t;
-  double acc[15];
-#pragma unroll
-  for (int q = 0; q < 15; ++q) acc[q] = 0.0;
-  for (int k = t; k < nblk; k += 256)
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) acc[ch * 5] += (double)partial[((long long)bi * nblk + k) * 3 + ch];
-  for (int x = t; x < w; x += 256)
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      acc[ch * 5 + 1] += (double)ib[(long long)x * 3 + ch];
-      acc[ch * 5 + 2] += (double)ib[((long long)(h - 1) * w + x) * 3 + ch];
-    }
-  for (int y = t; y < h; y += 256)
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      acc[ch * 5 + 3] += (double)ib[((long long)y * w) * 3 + ch];
-      acc[ch * 5 + 4] += (double)ib[((long long)y * w + (w - 1)) * 3 + ch];
-    }
-#pragma unroll
-  for (int q = 0; q < 15; ++q) red[q][t] = acc[q];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o)
-#pragma unroll
-      for (int q = 0; q < 15; ++q) red[q][t] += red[q][t + o];
-    __syncthreads();
-  }
-  if (t < 15) sums[t / 5][t % 5] = red[t][0];
-  __syncthreads();
-  if (t < 16) {
-    double m = 0.0;
-    for (int ky = 0; ky < 3; ++ky)
-      for (int kx = 0; kx < 3; ++kx)
-        for (int ch = 0; ch < 3; ++ch) {
-          // tap (dy, dx) = (ky - 1, kx - 1): dy = -1 never reaches the last row, dy = +1 never the first (same for columns)
-          const int ry = ky == 0 ? h - 1 : (ky == 2 ? 0 : -1), cx = kx == 0 ? w - 1 : (kx == 2 ? 0 : -1);
-          double sv = sums[ch][0];
-          if (ry >= 0) sv -= sums[ch][ry == 0 ? 1 : 2];
-          if (cx >= 0) sv -= sums[ch][cx == 0 ? 3 : 4];
-          if (ry >= 0 && cx >= 0) sv += (double)ib[((long long)ry * w + cx) * 3 + ch];
-          m += (double)w27[((ky * 3 + kx) * 3 + ch) * 16 + t] * sv;
-        }
-    mean[bi * 16 + t] = (float)((double)bias[t] + m / ((double)h * (double)w));
   }
 }
 
@@ -895,40 +808,16 @@ extern "C" int m4d_enc_level0_stats(const float* images, int bsz, long long stri
   M4D_CHECK_ARG(b > 0 && h > 0 && w > 0 && bsz > 0 && b % bsz == 0 && stride_b >= 0 && stride_t >= 0);
   M4D_CHECK_ARG((((uintptr_t)workspace) & 7u) == 0);
   hipStream_t s = (hipStream_t)stream;
-  const int C = 16, hw = h * w;
   const int tiles_x = (w + kE0TW - 1) / kE0TW, n_tiles = tiles_x * ((h + kE0TH - 1) / kE0TH);
-  const int nblk = n_tiles < kDinlMaxBlocks ? n_tiles : kDinlMaxBlocks;
   double* partial = reinterpret_cast<double*>(workspace);
-  // process-wide settings, read once (thread-safe initialisation of a function-local static) and never written again
-  static const int single_pass = [] { const char* e = getenv("M4D_ENC0_SINGLE_PASS"); return e ? atoi(e) : 1; }();
-  static const int analytic_mean_env = [] { const char* e = getenv("M4D_ENC0_ANALYTIC_MEAN"); return e ? atoi(e) : 1; }();
-  if (single_pass) {   // M4D_ENC0_SINGLE_PASS=0: round 5's four launches (A/B timing)
-    // 32 doubles per block in the same workspace -> at most 256 blocks per image; BALANCED: every workgroup the same number of tiles
-    // (384x1280: 480 tiles -> 240 workgroups of exactly two, not 224 of two + 32 of one)
-    const int cap = kDinlMaxBlocks / 2, per = (n_tiles + cap - 1) / cap;
-    const int nb2 = (n_tiles + per - 1) / per;
-    m4d_launch(enc0_stats_kernel<2>, dim3(nb2, b), dim3(256), 0, s, images, w1_hwio, bias1, (const float*)nullptr, h, w, bsz,
-               stride_b, stride_t, tiles_x, n_tiles, partial);
-    m4d_launch(enc0_moments_finalize_kernel, dim3(b), dim3(256), 0, s, images, (const double*)partial, nb2, w1_hwio, bias1, h, w, bsz,
-               stride_b, stride_t, mean, var);
-    return M4D_LAUNCH_RESULT();
-  }
-  // M4D_ENC0_ANALYTIC_MEAN=0: the mean from a convolution pass instead; on one row / column a border would be excluded twice
-  const bool analytic_mean = analytic_mean_env && h > 1 && w > 1;
-  if (analytic_mean) {
-    int nb3 = (hw + 256 * 16 - 1) / (256 * 16);
-    if (nb3 > kDinlMaxBlocks) nb3 = kDinlMaxBlocks;
-    m4d_launch(enc0_rgb_total_kernel, dim3(nb3, b), dim3(256), 0, s, images, hw, bsz, stride_b, stride_t, workspace);
-    m4d_launch(enc0_mean_kernel, dim3(b), dim3(256), 0, s, images, (const float*)workspace, nb3, w1_hwio, bias1, h, w, bsz,
-                       stride_b, stride_t, mean);
-  } else {
-    m4d_launch(enc0_stats_kernel<0>, dim3(nblk, b), dim3(256), 0, s, images, w1_hwio, bias1, (const float*)nullptr, h, w, bsz,
-                       stride_b, stride_t, tiles_x, n_tiles, partial);
-    m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk, C, hw, mean);
-  }
-  m4d_launch(enc0_stats_kernel<1>, dim3(nblk, b), dim3(256), 0, s, images, w1_hwio, bias1, (const float*)mean, h, w, bsz,
-                     stride_b, stride_t, tiles_x, n_tiles, partial);
-  m4d_launch(dinl_finalize_kernel, dim3(b), dim3(256), 0, s, (const double*)partial, nblk, C, hw, var);
+  // 32 doubles per block in the workspace of m4d_dinl_workspace_floats -> at most 256 blocks per image; BALANCED: every workgroup
+  // the same number of tiles (384x1280: 480 tiles -> 240 workgroups of exactly two, not 224 of two + 32 of one)
+  const int cap = kDinlMaxBlocks / 2, per = (n_tiles + cap - 1) / cap;
+  const int nb2 = (n_tiles + per - 1) / per;
+  m4d_launch(enc0_stats_kernel, dim3(nb2, b), dim3(256), 0, s, images, w1_hwio, bias1, (const float*)nullptr, h, w, bsz,
+             stride_b, stride_t, tiles_x, n_tiles, partial);
+  m4d_launch(enc0_moments_finalize_kernel, dim3(b), dim3(256), 0, s, images, (const double*)partial, nb2, w1_hwio, bias1, h, w, bsz,
+             stride_b, stride_t, mean, var);
   return M4D_LAUNCH_RESULT();
 }
 

@@ -10,8 +10,8 @@
 // window out of LDS with ds_read_b128.  HBM traffic is the algorithmic minimum
 // plus the halo: read C floats (x halo factor) and write (2r+1)^2 * k floats per
 // pixel.
-#include <cstdlib>
 #include "m4d_common.h"
+#include "m4d_switches.h"
 #include "m4d_sncv_small.h"
 #include "../../include/m4depth_hip.h"
 
@@ -303,8 +303,7 @@ bool launch_sncv7_ys(const float* c, int b, int h, int w, float* out, int out_st
 // Row split by how many (pixel, cut) items the launch has: enough lanes for ~8 waves per SIMD without a split -> YS = 1.
 template <int NC, int K, int TW, int TH>
 bool launch_sncv7(const float* c, int b, int h, int w, float* out, int out_stride, hipStream_t s) {
-  static int ys_env = -1;                             // M4D_SNCV_YS = 1 | 2 | 4 forces the split (profiling)
-  if (ys_env < 0) { const char* e = getenv("M4D_SNCV_YS"); ys_env = e ? atoi(e) : 0; }
+  const int ys_env = m4d_switches().sncv_ys;           // M4D_SNCV_YS = 1 | 2 | 4 forces the split (profiling)
   const long long items = (long long)b * h * w * K;
   int ys = ys_env ? ys_env : (items >= 1000000 ? 1 : (items >= 400000 ? 2 : 4));
   if (NC > 16 && ys > 2) ys = 2;                       // 32 channels per cut do not fit the 128 VGPRs of a 1024-thread workgroup
@@ -384,10 +383,8 @@ extern "C" int m4d_sncv_fwd(const float* c1, const float* c2, int b, int h, int 
   const int R = search_range * dilation_rate;
   const bool aligned = (((uintptr_t)c1 | (uintptr_t)c2) & 15u) == 0;
   const bool nc_ok = a.nc == 4 || a.nc == 8 || a.nc == 16 || a.nc == 24 || a.nc == 32;
-  static int variant = -1;                  // M4D_SNCV_VARIANT=0 disables the specialised kernels (debugging)
-  if (variant < 0) { const char* e = getenv("M4D_SNCV_VARIANT"); variant = e ? atoi(e) : 1; }
-  static int small_px = -1;                 // M4D_SNCV_SMALL_PX: maps up to this many pixels (batch included) take the small-map kernel
-  if (small_px < 0) { const char* e = getenv("M4D_SNCV_SMALL_PX"); small_px = e ? atoi(e) : 6000; }
+  const int variant = m4d_switches().sncv_variant;     // M4D_SNCV_VARIANT=0 disables the specialised kernels (debugging)
+  const int small_px = m4d_switches().sncv_small_px;   // M4D_SNCV_SMALL_PX: maps up to this many pixels (batch included) take the small-map kernel
   if (variant == 1 && aligned && nc_ok && (long long)b * h * w <= small_px) {
     a.th = a.tw = a.tiles_x = 0;
     switch (a.nc) {

@@ -19,8 +19,8 @@
 // x NT MFMAs per wave.  After the K loop the 16 positions of a (tile, cout) live in four waves; they meet in
 // LDS (two passes of 16 tiles per N-tile) for the output transform.
 // Deterministic: fixed summation order, no atomics.
-#include <cstdlib>
 #include "m4d_common.h"
+#include "m4d_switches.h"
 #include "../../include/m4depth_hip.h"
 
 namespace {
@@ -32,7 +32,9 @@ struct WinoArgs {
   int b, h, w, Cin, Cout, CoutPad, n_chunks, tiles_x, tiles_y;
   float slope;
   unsigned long long* stamps;   // profiling only (m4d_wino_set_stamps): per workgroup, per chunk, 5 cycle counters of wave 0
-  int ablate;      // profiling only (M4D_WINO_ABLATE): 1 = weights loaded once, 2 = no MFMAs, 4 = no input transform, 8 = no epilogue
+  int ablate;      // profiling only: 1 = weights loaded once, 2 = no MFMAs, 4 = no input transform, 8 = no epilogue.  Every host path
+                   // passes 0 (the environment switch that set it is retired); the field and its branches stay until a measured
+                   // change, because removing them changes the code of the hot kernels
 };
 
 constexpr int kTW = 16, kTH = 8;                 // output tile (pixels)
@@ -816,10 +818,7 @@ extern "C" int m4d_conv3x3_wino_bias_act(const float* x, const float* wu, const 
   a.x = x; a.wu = wu; a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout;
   a.CoutPad = CoutPad; a.n_chunks = (Cin + kKC - 1) / kKC; a.slope = slope;
   a.tiles_x = (w + kTW - 1) / kTW; a.tiles_y = (h + kTH - 1) / kTH;
-  static int ablate = -1;
-  if (ablate < 0) { const char* e = getenv("M4D_WINO_ABLATE"); ablate = e ? atoi(e) : 0; }
-  a.ablate = ablate;
-  a.stamps = g_wino_stamps;
+  a.ablate = 0; a.stamps = g_wino_stamps;
 
   hipStream_t s = (hipStream_t)stream;
   if ((CoutPad / 32) % 2 == 0) launch_wino<2>(a, s);
@@ -845,9 +844,7 @@ extern "C" int m4d_conv3x3_wino2_bias_act(const float* x, const float* wu8, cons
   // for 2-chunk layers; inside the pipelined step, where other frames' kernels share the chip, it pays from ~100 workgroups:
   // +0.5 % frames/s at batch 1, round 2); otherwise kernel 2 (twice as many, smaller workgroups).  Same results bit for bit.
   // M4D_WINO_VARIANT=2 forces kernel 2, M4D_WINO4_MIN_WG moves the threshold.
-  static int variant = -1, min_wg4 = -1;
-  if (variant < 0) { const char* e = getenv("M4D_WINO_VARIANT"); variant = e ? atoi(e) : 4; }
-  if (min_wg4 < 0) { const char* e = getenv("M4D_WINO4_MIN_WG"); min_wg4 = e ? atoi(e) : 100; }
+  const int variant = m4d_switches().wino_variant, min_wg4 = m4d_switches().wino4_min_wg;
   if (variant == 4 && CoutPad % 64 == 0 && Cin >= 32 && Cin % 8 == 0 && (long long)a.tiles_x * a.tiles_y * (CoutPad / 64) * b >= min_wg4) {
     constexpr size_t lds4 = (size_t)(4 * 4 * 2 * 32 * 36) * sizeof(float);              // epilogue staging 147 KB (K loop: 126 KB)
     static_assert(lds4 >= (size_t)(2 * kRawF + 2 * kVF) * sizeof(float), "epilogue staging must cover the K-loop buffers");

@@ -33,7 +33,6 @@
 // accumulator zeroing), the last chunk is peeled and issues no DMA (nothing for the epilogue to drain).  HALF units: a cout group
 // of <= 32 channels (Cout = 96's second group, Cout = 32) runs N-tile 0 only, a second instantiation of the K loop.
 // Deterministic: fixed summation order, no atomics.
-#include <cstdlib>
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
 
@@ -562,11 +561,7 @@ extern "C" void m4d_wino6_set_half_tile_max_workgroups(int max_wg) { g_wino6_hal
 int m4d_wino6p_launch(const float* x, const void* wu6, const float* bias, int b, int h, int w, int Cin, int Cout, int CoutPad,
                       float slope, float* out, int units_per_wg, int stagger_us, int stagger_phases, void* stream);
 
-extern "C" long long m4d_wino6_persistent_min_units(void) {
-  static const long long v = [] { const char* e = getenv("M4D_WINO6P_MIN_UNITS"); const long long u = e ? atoll(e) : 0;
-                                  return u > 0 ? u : kPersistentMinUnits; }();             // (env: measurement knob)
-  return v;
-}
+extern "C" long long m4d_wino6_persistent_min_units(void) { return kPersistentMinUnits; }
 
 extern "C" int m4d_conv3x3_wino6_bias_act(const float* x, const void* wu6, const float* bias, int b, int h, int w,
                                           int Cin, int Cout, int CoutPad, float slope, float* out, void* stream) {

@@ -30,7 +30,6 @@
 //   vmcnt(2) close them (slot 0 / slot 1 of the next unit landed), then the epilogue's barriers publish them.
 // Deterministic: a unit's arithmetic does not depend on which workgroup runs it; bit-identical to conv3x3_wino6_kernel
 // (tests/test_gpu_ops.py::test_persistent_winograd_is_bitwise_the_one_tile_kernel).
-#include <cstdlib>
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
 
@@ -548,11 +547,7 @@ int m4d_wino6p_launch(const float* x, const void* wu6, const float* bias, int b,
   const int n_groups = CoutPad / 64;
   a.team = (units_per_wg <= 0 && n_cu % 8 == 0 && n_cu / 8 >= n_groups && units >= 4ll * n_cu) ? 1 : 0;
   a.stagger = stagger_us * 100; a.phases = stagger_us > 0 ? stagger_phases : 1;
-  // M4D_WINO6P_MAX_WG (measurement knob): at most this many persistent workgroups -- the other CUs stay free for the kernels of
-  // the other frames' coarse levels, whose workgroups otherwise each wait for one of this kernel's ~27-us units to end
-  static const int max_wg = [] { const char* e = getenv("M4D_WINO6P_MAX_WG"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1 << 30; }();
-  const int cu_used = n_cu < max_wg ? n_cu : max_wg;
-  const long long per_wg = (units + cu_used - 1) / cu_used;
+  const long long per_wg = (units + n_cu - 1) / n_cu;
   const unsigned grid = units_per_wg > 0 ? (unsigned)((units + units_per_wg - 1) / units_per_wg)
                                          : a.team ? (unsigned)n_cu : (unsigned)((units + per_wg - 1) / per_wg);
   m4d_launch(conv3x3_wino6p_kernel, dim3(grid), dim3(512), (size_t)pLds, (hipStream_t)stream, a);

@@ -277,12 +277,73 @@ def test_integration_doc_lists_exactly_the_switches_the_package_reads():
         in_code |= set(re.findall(r"\bM4D_[A-Z0-9_]+", open(path).read()))
     in_code.discard("M4D_ABI_VERSION")                   # the header's version macro (named in a comment of _lib.py), no switch
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    section = doc[doc.index("## 4. Kernel-selection switches"):]
-    in_table = set()
+    in_table = _doc_table_switches("## 4. Kernel-selection switches")
+    assert in_table == in_code, (sorted(in_code - in_table), sorted(in_table - in_code))
+
+
+def _doc_table_switches(heading):
+    """The ``M4D_*`` names in the first column of the table under INTEGRATION.md's section ``heading`` (up to the next ``## ``)."""
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index(heading) + len(heading):]
+    section = section[:section.index("\n## ")] if "\n## " in section else section
+    names = set()
     for line in section.splitlines():
         if line.startswith("| `M4D_"):
-            in_table |= set(re.findall(r"\bM4D_[A-Z0-9_]+", line.split("|")[1]))
-    assert in_table == in_code, (sorted(in_code - in_table), sorted(in_table - in_code))
+            names |= set(re.findall(r"\bM4D_[A-Z0-9_]+", line.split("|")[1]))
+    return names
+
+
+LIBRARY_SWITCH_DEFAULTS = {"sncv_variant": 1, "sncv_ys": 0, "sncv_small_px": 6000, "wino_variant": 4, "wino4_min_wg": 100,
+                           "dscv_bwd_window_kb": 48}
+
+
+def test_library_reads_the_environment_only_in_its_switch_table():
+    """Comments stripped, ``getenv`` occurs under m4depth_amd/csrc and tools/experiments/csrc only in the translation unit that
+    defines m4d_switches(), and the ``M4D_*`` names read there are the rows of INTEGRATION.md section 5, no more and no fewer."""
+    readers, names = [], set()
+    for d in (os.path.join(ROOT, "m4depth_amd", "csrc"), os.path.join(ROOT, "tools", "experiments", "csrc")):
+        for n in sorted(os.listdir(d)):
+            if not n.endswith((".hip", ".h", ".hpp", ".cpp")):
+                continue
+            code = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(d, n)).read(), flags=re.S)
+            if re.search(r"\bgetenv\b", code):
+                readers.append(n)
+                assert re.search(r"\bm4d_switches\s*\(\s*\)\s*\{", code), f"{n} reads the environment but does not define m4d_switches()"
+                names |= set(re.findall(r'"(M4D_[A-Z0-9_]+)"', code))
+    assert readers == ["m4d_api.hip"], readers
+    assert names == _doc_table_switches("## 5. Switches of the library itself")
+    assert {n[4:].lower() for n in names} == set(LIBRARY_SWITCH_DEFAULTS)
+
+
+def _child(call, restype, **env):
+    """``call`` on the library in a fresh process (plain ctypes: no package import, a fraction of a second) with the M4D_*
+    variables of ``env`` and no others."""
+    import subprocess, sys
+    from m4depth_amd import _lib
+    full = {k: v for k, v in os.environ.items() if not k.startswith("M4D_")}
+    full.update(env)
+    code = (f"import ctypes; f = ctypes.CDLL({_lib.LIB_PATH!r}).{call}; f.restype = ctypes.{restype}; r = f(); "
+            "print(r.decode() if isinstance(r, bytes) else r)")
+    r = subprocess.run([sys.executable, "-c", code], env=full, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stdout.strip()
+
+
+def test_switches_info_reflects_the_environment():
+    """m4d_switches_info() in a child process: the defaults of INTEGRATION.md section 5 with nothing set, the environment's values
+    with every kept variable set to something else (M4D_DSCV_BWD_WINDOW_KB clamped to 0..64)."""
+    show = ("m4d_switches_info", "c_char_p")
+    parse = lambda text: {k: int(v) for k, v in (item.split("=") for item in text.split())}
+    assert parse(_child(*show)) == LIBRARY_SWITCH_DEFAULTS
+    other = {"sncv_variant": 0, "sncv_ys": 2, "sncv_small_px": 100000, "wino_variant": 2, "wino4_min_wg": 7, "dscv_bwd_window_kb": 16}
+    assert parse(_child(*show, **{"M4D_" + k.upper(): str(v) for k, v in other.items()})) == other
+    assert parse(_child(*show, M4D_DSCV_BWD_WINDOW_KB="200"))["dscv_bwd_window_kb"] == 64
+    assert parse(_child(*show, M4D_DSCV_BWD_WINDOW_KB="-3"))["dscv_bwd_window_kb"] == 0
+
+
+def test_a_retired_switch_is_not_read():
+    """M4D_WINO6P_MIN_UNITS moved the persistent-kernel threshold until it was retired: the library answers 2048 whatever it says."""
+    assert _child("m4d_wino6_persistent_min_units", "c_longlong", M4D_WINO6P_MIN_UNITS="900") == "2048"
 
 
 def test_library_sources_enqueue_no_memset():

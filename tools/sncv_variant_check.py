@@ -17,7 +17,8 @@ if a.compare:
             print(os.path.basename(other), k, "bit-identical" if same else f"DIFFERENT max {(ref[k] - y[k]).abs().max().item():.3e}")
     sys.exit(0)
 import m4depth_amd as M
-from m4depth_amd import network_ops as nops
+from m4depth_amd import _lib, network_ops as nops
+_lib.assert_switches_follow_env("M4D_SNCV_VARIANT", "M4D_SNCV_YS", "M4D_SNCV_SMALL_PX")   # or every run takes the same kernel
 dev = torch.device("cuda:0")
 out = {"in": {}, "out": {}}
 g = torch.Generator().manual_seed(5)

@@ -15,6 +15,8 @@ if a.compare:
         same = torch.equal(x[k].view(torch.int32), y[k].view(torch.int32))
         print(k, "bit-identical" if same else f"DIFFERENT max {(x[k] - y[k]).abs().max().item():.3e}")
     sys.exit(0)
+from m4depth_amd import _lib
+_lib.assert_switches_follow_env("M4D_WINO_VARIANT", "M4D_WINO4_MIN_WG")   # or both runs take the same kernel and agree vacuously
 dev = torch.device("cuda:0")
 out = {"in": {}, "out": {}}
 g = torch.Generator().manual_seed(3)
