@@ -221,6 +221,18 @@ int m4d_conv3x3_wino6_bias_act_ks(const float* x, const void* wu6, const float* 
 int m4d_conv3x3_winof16_bias_act_ks(const float* x, const void* wuh, const float* bias, int b, int h, int w,
                                     int Cin, int Cout, int CoutPad, float slope, float* out,
                                     int stagger_us, int stagger_phases, void* stream);
+/* The same call in a CHAIN of such layers: the kernel derives its input scales from the largest finite |x| of every input pixel,
+ * which m4d_conv3x3_winof16_bias_act_ks finds by reading the halo of every unit once more, and which the layer that wrote x had
+ * in registers.  pm_out (or NULL): uint32 [b][h][w][CoutPad/64], written by this call -- per pixel and group of 64 output
+ * channels the largest min(bits(|y|), 0x7f7fffff) over the group's real channels of the values as stored (NaN counts as 0);
+ * needs CoutPad - Cout < 64; every element is written, by plain stores.  pm_in (or NULL): uint32 [b][h][w][ceil(Cin/64)], the
+ * pm_out of the call that wrote exactly this x (same b, h, w, Cout = this Cin) -- read instead of the scan.  Only the exponent
+ * field of a maximum enters a scale, so outputs are the bits of the _ks call whenever pm_in holds the maxima of x (to the
+ * exponent); with both NULL this IS the _ks call.  Both 4-byte aligned, distinct.  Additive entry point: ABI 6 unchanged. */
+int m4d_conv3x3_winof16_bias_act_pm(const float* x, const void* wuh, const float* bias, int b, int h, int w,
+                                    int Cin, int Cout, int CoutPad, float slope, float* out,
+                                    const unsigned* pm_in, unsigned* pm_out,
+                                    int stagger_us, int stagger_phases, void* stream);
 
 /* The tail of a level in one kernel: the last two DispRefiner convolutions (32 -> 16 + leaky_relu(0.1), 16 -> 5;
  * m4depth_network.py:109-135) and m4d_level_post (:247-260).  x32 [b,h,w,32]; w6p [9][16][32] = kernel[ky][kx][k][n] as

@@ -16,7 +16,10 @@
 //   from a scan of the tile's whole halo at the start of the unit, issued behind the prologue's DMAs (raw halo of chunk 0 and
 //   the first B fragments do not depend on it).  An Inf / NaN among a position's inputs makes that position non-finite
 //   whatever the scale (hi = Inf, lo = Inf - Inf), as in the bf16 split: the scan clamps to the largest finite value so that
-//   the scale itself stays finite.
+//   the scale itself stays finite.  In a chain of these layers the scan is a second pass over 18 x 18 x Cin floats per unit for
+//   values the producing layer held in registers: with pm_out its epilogue leaves one word per pixel and 64-channel group, and
+//   with pm_in the next layer reads those 324 x ceil(Cin/64) words instead (m4d_conv3x3_winof16_bias_act_pm; same scales, same
+//   bits).
 // Everything else as m4d_wino6.hip: 8 waves, two per SIMD, a 16x16-pixel x 64-cout unit per workgroup, raw halo and B
 // fragments by LDS-DMA with hand-counted vmcnt waits (now 1 raw + 2 fragment pieces per wave and position), the first and the
 // last chunk peeled, HALF units for a last cout group of <= 32 channels, XCD tile mapping, the staggered first round.
@@ -34,6 +37,8 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct WinoF16Args {
   const float* x; const unsigned char* wu; const short* wexp; const float* bias; float* out;
+  const unsigned* pm_in;        // [b][h][w][ceil(Cin/64)] pixel maxima of x as its producer wrote them, or null: scan the halo
+  unsigned* pm_out;             // [b][h][w][CoutPad/64] pixel maxima of out for the next layer, or null
   int b, h, w, Cin, Cout, CoutPad, n_chunks, tiles_x, tiles_y;
   float slope;
   int phases;                   // power of two <= 32
@@ -208,7 +213,22 @@ conv3x3_winof16_kernel(const WinoF16Args a) {
 
   // ---- row scales.  Per halo pixel the largest |x| over all Cin: 8 lanes per pixel (128 contiguous bytes per pixel and load),
   // pixels t / 8 + 64 r; pixels outside the image (and past the halo) count as 0.  Then per tile the maximum over its 4x4 patch.
-  {
+  //   pm_in: the layer that wrote x left these maxima beside it (its epilogue, below), one word per pixel and group of 64
+  // channels -- thread p takes halo pixel p's, and x itself is read by the DMAs only.  The scales use the exponent field of a
+  // maximum alone, so the two sources need not agree on a denormal maximum (a scan may flush it to 0; exponent 0 either way).
+  if (a.pm_in) {
+    if (t < kH * kH) {
+      const int hy = t / kH, hx = t - hy * kH;
+      const int gy = tile_y - 1 + hy, gx = tile_x - 1 + hx;
+      const int G = (a.Cin + 63) >> 6;
+      unsigned u = 0u;
+      if (gy >= 0 && gy < a.h && gx >= 0 && gx < a.w) {
+        const unsigned* q = a.pm_in + (((long long)bi * a.h + gy) * a.w + gx) * G;
+        for (int g = 0; g < G; ++g) u = max(u, q[g]);
+      }
+      pm[t] = min(u, 0x7f7fffffu);                 // (as written; the bound keeps a scale finite whatever the caller hands in)
+    }
+  } else {
     const int g = t & 7, p0 = t >> 3, nq = a.Cin >> 2;
     constexpr int kR = (kH * kH + 63) / 64;        // 6
     int poff[kR];
@@ -454,6 +474,41 @@ conv3x3_winof16_kernel(const WinoF16Args a) {
       }
     }
     const int ox = tile_x + 2 * tx2, oy = tile_y + 2 * ty2;
+    if (a.pm_out) {
+      // The maxima the next layer's scan would find, from the values as stored: per pixel the largest finite |y| over this
+      // group's real channels (NaN counts as 0, Inf as the largest finite float; a padded channel carries a clamped bias and
+      // does not count).  The 16 lanes (8 in a half unit) that hold a tile's channels are neighbours: reduced by DPP as in the
+      // scan.  One plain store per pixel and group; every pixel of the image belongs to exactly one unit per group.
+      // v_max3 drops NaN operands (the stored values are results of arithmetic: quiet), as in the scan; the four pixels' DPP
+      // chains are issued side by side.
+      const bool allv = ng * 64 + (half ? 32 : 64) <= a.Cout;        // (workgroup-uniform) no padded channel in this unit
+      unsigned pu[2][2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int l = 0; l < 2; ++l) {
+          float v[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = (allv || co + e < a.Cout) ? y[k][l][e] : 0.f;
+          pu[k][l] = min(__float_as_uint(max3_abs(max3_abs(0.f, v[0], v[1]), v[2], v[3])), 0x7f7fffffu);
+        }
+#define M4D_WF_PMAX(ctrl)                                                                                              \
+  _Pragma("unroll") for (int k = 0; k < 2; ++k) _Pragma("unroll") for (int l = 0; l < 2; ++l)                            \
+    pu[k][l] = max(pu[k][l], (unsigned)__builtin_amdgcn_update_dpp(0, (int)pu[k][l], ctrl, 0xf, 0xf, false));
+      M4D_WF_PMAX(0x141)                           // row_half_mirror
+      M4D_WF_PMAX(0xb1)                            // quad_perm [1,0,3,2]
+      M4D_WF_PMAX(0x4e)                            // quad_perm [2,3,0,1]
+      if (!half) { M4D_WF_PMAX(0x140) }            // row_mirror
+#undef M4D_WF_PMAX
+      if (cq16 == 0) {
+        unsigned* pp = a.pm_out + (((long long)bi * a.h + oy) * a.w + ox) * n_groups + ng;
+#pragma unroll
+        for (int l = 0; l < 2; ++l)
+#pragma unroll
+          for (int k = 0; k < 2; ++k)
+            if (ox + k < a.w && oy + l < a.h) pp[((long long)l * a.w + k) * n_groups] = pu[k][l];
+      }
+    }
     float* op = oimg + ((long long)oy * a.w + ox) * a.Cout + co;
     if (fast) {
 #pragma unroll
@@ -476,8 +531,9 @@ conv3x3_winof16_kernel(const WinoF16Args a) {
 
 }  // namespace
 
-extern "C" int m4d_conv3x3_winof16_bias_act_ks(const float* x, const void* wuh, const float* bias, int b, int h, int w,
+extern "C" int m4d_conv3x3_winof16_bias_act_pm(const float* x, const void* wuh, const float* bias, int b, int h, int w,
                                                int Cin, int Cout, int CoutPad, float slope, float* out,
+                                               const unsigned* pm_in, unsigned* pm_out,
                                                int stagger_us, int stagger_phases, void* stream) {
   M4D_CHECK_ARG(x && wuh && bias && out && b > 0 && h > 0 && w > 0 && Cin >= 16 && Cout > 0);
   M4D_CHECK_ARG(CoutPad % 64 == 0 && CoutPad >= Cout && Cin % 16 == 0);
@@ -485,7 +541,10 @@ extern "C" int m4d_conv3x3_winof16_bias_act_ks(const float* x, const void* wuh, 
   M4D_CHECK_ARG((long long)h * w * Cin * 4 < (1ll << 31));                              // one image = one buffer descriptor
   M4D_CHECK_ARG(stagger_us >= 0 && stagger_us <= 1000);
   M4D_CHECK_ARG(stagger_us == 0 || (stagger_phases >= 1 && stagger_phases <= 32 && !(stagger_phases & (stagger_phases - 1))));
+  M4D_CHECK_ARG(((((uintptr_t)pm_in) & 3u) == 0) && ((((uintptr_t)pm_out) & 3u) == 0));
+  M4D_CHECK_ARG(!pm_out || (CoutPad - Cout < 64 && (const void*)pm_out != (const void*)pm_in));   // one word per real cout group
   WinoF16Args a;
+  a.pm_in = pm_in; a.pm_out = pm_out;
   a.x = x; a.wu = reinterpret_cast<const unsigned char*>(wuh); a.bias = bias; a.out = out;
   a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout; a.CoutPad = CoutPad; a.n_chunks = Cin / 16; a.slope = slope;
   // the per-cout exponents t_n follow the fragments: [CoutPad] int16
@@ -497,4 +556,11 @@ extern "C" int m4d_conv3x3_winof16_bias_act_ks(const float* x, const void* wuh, 
   M4D_LDS_OPT_IN(&conv3x3_winof16_kernel);
   m4d_launch(conv3x3_winof16_kernel, grid, dim3(512), (size_t)kLdsBytes, (hipStream_t)stream, a);
   return M4D_LAUNCH_RESULT();
+}
+
+extern "C" int m4d_conv3x3_winof16_bias_act_ks(const float* x, const void* wuh, const float* bias, int b, int h, int w,
+                                               int Cin, int Cout, int CoutPad, float slope, float* out,
+                                               int stagger_us, int stagger_phases, void* stream) {
+  return m4d_conv3x3_winof16_bias_act_pm(x, wuh, bias, b, h, w, Cin, Cout, CoutPad, slope, out, nullptr, nullptr, stagger_us,
+                                         stagger_phases, stream);
 }

@@ -147,6 +147,17 @@ small_map_conv_pixels = int(_os.environ.get("M4D_CONV_SMALL_PX", "2048"))
 # small-map kernels.  (The kernel's stride-2 and M-over-waves forms stay in the library, measured and not dispatched: DESIGN.md.)
 lat_conv_max_pixels = int(_os.environ.get("M4D_LAT_CONV_PX", "2048"))
 
+# A chain of layers on the fp16 two-term Winograd kernel (csrc/m4d_wino_f16.hip: levels 1-3's conv1 .. conv5): a layer called with
+# ``final=False`` leaves the per-pixel maxima of its output beside it (network_ops.ActMaxima), and the next layer, if it runs on
+# that kernel and reads exactly that tensor, takes its input scales from them instead of scanning every unit's halo once more
+# (18 x 18 x Cin floats per unit, about 2.5 reads of the whole input per layer).  Same bits.  M4D_WINO_HANDOVER=0 = every layer
+# scans: for interleaved A/B runs and the tests.  On maps of at least _WINO_HANDOVER_MIN_TILES 16x16 tiles (batch included: levels
+# 1-2 of the 384x1280 pyramid at batch 1) -- a property of the map, so the layer that writes and the layer that reads decide alike;
+# below it (level 3: 30 tiles) a layer is one partial round of units and the saving is 0.6 us a layer (profiles/wino_f16_handover.txt),
+# and tests/test_level_dispatch.py holds ``forward`` on maps of up to 30 tiles to launch rows recorded before the hand-over existed.
+wino_handover = _os.environ.get("M4D_WINO_HANDOVER", "1") == "1"
+_WINO_HANDOVER_MIN_TILES = 100
+
 # The whole level front (normalise + level_pre + DSCV + SNCV -> complete refiner-input rows) as ONE kernel
 # (csrc/m4d_front.hip) wherever it has an instantiation: the default settings and 16 channels x 1-2 cuts or 32 x 2 (levels 1-3
 # of the 6-level pyramid); maps of at most fused_front_min_pixels pixels (batch included) and every other configuration keep
@@ -426,9 +437,10 @@ class _Conv3x3SameTF(torch.nn.Module):
         units = b * (-(-h // 16)) * (-(-w // 16)) * (-(-self.out_channels // 64))
         return int(us) if units >= _WINO6_STAGGER_MIN_WG else 0
 
-    def plan(self, b, h, w, cin, final=True):
+    def plan(self, b, h, w, cin, final=True, maxima=False):
         """What ``forward`` does with a [b,h,w,cin] input: the kernel (a key of ``_CONV_LAUNCH``), the packed layout it reads and
-        the launch extras.  Pure: launches nothing, touches no tensor.
+        the launch extras.  Pure: launches nothing, touches no tensor.  ``maxima``: the input comes with its producer's pixel
+        maxima (``network_ops.ActMaxima``); the plan says whether this layer reads them and whether it writes its own.
         The encoder is run on frames stacked along the batch axis, and how many are stacked depends on the launch mode
         (all T frames, two batches in the pipelined forward, one frame when streaming): its kernel choice must not
         depend on that, or the modes stop being bit-identical -- it is decided from the per-image grid x the SEQUENCE batch
@@ -447,8 +459,14 @@ class _Conv3x3SameTF(torch.nn.Module):
         if wino == 6:
             # "f16x2": one workgroup per (tile, 64 couts) at every batch -- ahead of the bf16x3 persistent kernel at batch 32 too
             # (DESIGN.md section 6), so the kernel choice does not depend on the batch at all
-            p = ConvPlan("wino6", "winof16" if conv_arith == "f16x2" else "wino6", None, wino6_kernel,
-                         self.launch_stagger_us(b, h, w))
+            # the fp16 kernel hands pixel maxima on: written for a consumer that is another layer (``final`` = False), read where
+            # the input is the producer's tensor itself -- this layer's own Cin, no channel padding (``wino_handover``, on maps
+            # that are large enough)
+            hand = (conv_arith == "f16x2" and wino_handover
+                    and b * (-(-h // 16)) * (-(-w // 16)) >= _WINO_HANDOVER_MIN_TILES)
+            p = ConvPlan("wino6", "winof16" if conv_arith == "f16x2" else "wino6", None, wino6_kernel, self.launch_stagger_us(b, h, w),
+                         bool(hand and maxima and self.weight is not None and cin == self.weight.shape[1]),
+                         bool(hand and not final))
         elif wino:
             p = ConvPlan("wino", "wino16", None, None, None) if wino == 1 else ConvPlan("wino2", "wino8", None, None, None)
         elif one_launch and s == 1 and small_conv_split:
@@ -468,6 +486,7 @@ class _Conv3x3SameTF(torch.nn.Module):
         ``PartialAct`` input is finished here first (one launch) if this layer runs on any other kernel."""
         if isinstance(x_nhwc, nops.PartialAct) and not self.lat_eligible(*x_nhwc.shape):
             x_nhwc = x_nhwc.dense()
+        maxima = isinstance(x_nhwc, nops.ActMaxima)
         if not x_nhwc.is_cuda:
             raise RuntimeError("m4depth_amd convolutions run on the GPU only (libm4depth_hip.so): got a CPU tensor; "
                                "there is no CPU fallback")
@@ -475,14 +494,17 @@ class _Conv3x3SameTF(torch.nn.Module):
             self._build(x_nhwc.shape[-1], x_nhwc.device)
         if self.stride not in (1, 2):
             raise ValueError(f"stride {self.stride} is not supported by the HIP convolution")
-        p = self.plan(*x_nhwc.shape, final)
+        p = self.plan(*x_nhwc.shape, final, maxima)
+        if maxima and not p.reads_maxima:                  # every other kernel reads the finished tensor
+            x_nhwc = x_nhwc.dense()
         wts = self.packed(p.layout, x_nhwc.shape[-1])      # (more channels than the layer's Cin: a zero-padded input)
         launch = _CONV_LAUNCH[p.kernel][1]
         act = 1.0 if slope is None else slope
         return _timed("conv", self.tag, lambda: launch(self, x_nhwc, wts, act, p))
 
 
-ConvPlan = namedtuple("ConvPlan", ("kernel", "layout", "lat_config", "wino6_kernel", "stagger_us"))
+ConvPlan = namedtuple("ConvPlan", ("kernel", "layout", "lat_config", "wino6_kernel", "stagger_us", "reads_maxima", "writes_maxima"),
+                      defaults=(False, False))
 LevelPlan = namedtuple("LevelPlan", ("route", "normalize", "f_stride", "tail"))       # ``DepthEstimatorLevel.plan``
 
 # Packed weight layouts: pack function over the host HWIO kernel, whether the device copy is viewed as int16 (bf16 / fp16 bit
@@ -507,7 +529,7 @@ _CONV_LAUNCH = {
         x, w, c.bias, c.out_channels, act, config=p.lat_config)),
     "wino6": ("conv3x3_wino6_bias_act", lambda c, x, w, act, p: nops.conv3x3_wino6_bias_act(
         x, w[0], c.bias, c.out_channels, w[1], act, kernel=p.wino6_kernel, stagger_us=p.stagger_us,
-        stagger_phases=_WINO6_STAGGER_PHASES, arith=conv_arith)),
+        stagger_phases=_WINO6_STAGGER_PHASES, arith=conv_arith, want_maxima=p.writes_maxima)),
     "wino": ("conv3x3_wino_bias_act", lambda c, x, w, act, p: nops.conv3x3_wino_bias_act(
         x, w[0], c.bias, c.out_channels, w[1], act)),
     "wino2": ("conv3x3_wino2_bias_act", lambda c, x, w, act, p: nops.conv3x3_wino2_bias_act(
@@ -896,7 +918,7 @@ class DepthEstimatorLevel(torch.nn.Module):
             for ci, conv in enumerate(convs[:5]):
                 x = conv(x, slope=0.1, final=(ci == 4))                   # the fused tail reads a finished tensor
                 if debug_tap is not None:
-                    debug_tap(f"refiner_conv{ci + 1}", lvl, x.dense() if isinstance(x, nops.PartialAct) else x)
+                    debug_tap(f"refiner_conv{ci + 1}", lvl, x.dense() if isinstance(x, (nops.PartialAct, nops.ActMaxima)) else x)
             w6p, w7p = self._tail_weights(convs, p.tail == "tail6")
             tail_fn = {"tail6": nops.refiner_tail6, "tail": nops.refiner_tail}[p.tail]
             para_curr_l, depth, other = _timed("tail", lvl, lambda: tail_fn(

@@ -1088,29 +1088,73 @@ def conv3x3_small6_bias_act(x, wp6, bias, cout, cout_pad, slope=0.1):
     return out
 
 
-def conv3x3_winof16_bias_act(x, wuh, bias, cout, cout_pad, slope=0.1, stagger_us=0, stagger_phases=16):
+class ActMaxima:
+    """A finished activation ``tensor`` [b,h,w,C] together with ``maxima`` [b,h,w,ceil(C/64)] (int32 bits), per pixel and
+    group of 64 channels the largest finite |value| as the fp16 Winograd kernel that wrote the tensor saw it
+    (m4d_conv3x3_winof16_bias_act_pm, ``pm_out``).  The next such layer derives its input scales from them instead of scanning
+    its halo; every other consumer takes ``dense()``, the tensor itself (no launch)."""
+
+    def __init__(self, tensor, maxima):
+        self.tensor, self.maxima = tensor, maxima
+
+    @property
+    def shape(self):
+        return self.tensor.shape
+
+    @property
+    def is_cuda(self):
+        return self.tensor.is_cuda
+
+    @property
+    def device(self):
+        return self.tensor.device
+
+    def dense(self):
+        return self.tensor
+
+
+def conv3x3_winof16_bias_act(x, wuh, bias, cout, cout_pad, slope=0.1, stagger_us=0, stagger_phases=16, want_maxima=False):
     """The convolution of conv3x3_wino6_bias_act with float32 operands split into two fp16 terms after a power-of-two scale
     (per Winograd tile / per output channel), three fp16 MFMA products per term pair, float32 accumulation
-    (csrc/m4d_wino_f16.hip).  ``wuh`` = pack_conv_weights_winof16 on the device (int16)."""
+    (csrc/m4d_wino_f16.hip).  ``wuh`` = pack_conv_weights_winof16 on the device (int16).  ``x`` an ``ActMaxima``: the input
+    scales come from its maxima, not from a scan of the halo; ``want_maxima``: returns an ``ActMaxima`` for the next layer
+    (allocated like the output).  The same bits either way."""
+    pm_in = None
+    if isinstance(x, ActMaxima):
+        x, pm_in = x.tensor, x.maxima
     x = as_f32(x, "x")
     b, h, w, cin = x.shape
     out = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)
-    check(lib.m4d_conv3x3_winof16_bias_act_ks(dptr(x, "x"), dptr(wuh, "wuh", torch.int16), dptr(bias, "bias"), b, h, w, cin,
-                                              int(cout), int(cout_pad), float(slope), dptr(out), int(stagger_us),
-                                              int(stagger_phases), stream_ptr()),
-          "m4d_conv3x3_winof16_bias_act_ks")
-    return out
+    if pm_in is None and not want_maxima:
+        check(lib.m4d_conv3x3_winof16_bias_act_ks(dptr(x, "x"), dptr(wuh, "wuh", torch.int16), dptr(bias, "bias"), b, h, w, cin,
+                                                  int(cout), int(cout_pad), float(slope), dptr(out), int(stagger_us),
+                                                  int(stagger_phases), stream_ptr()),
+              "m4d_conv3x3_winof16_bias_act_ks")
+        return out
+    if pm_in is not None and tuple(pm_in.shape) != (b, h, w, -(-cin // 64)):
+        raise ValueError(f"conv3x3_winof16_bias_act: maxima {tuple(pm_in.shape)} do not belong to an input {tuple(x.shape)}")
+    pm_out = torch.empty((b, h, w, int(cout_pad) // 64), dtype=torch.int32, device=x.device) if want_maxima else None
+    check(lib.m4d_conv3x3_winof16_bias_act_pm(dptr(x, "x"), dptr(wuh, "wuh", torch.int16), dptr(bias, "bias"), b, h, w, cin,
+                                              int(cout), int(cout_pad), float(slope), dptr(out), dptr(pm_in, "maxima", torch.int32),
+                                              dptr(pm_out, "maxima", torch.int32), int(stagger_us), int(stagger_phases), stream_ptr()),
+          "m4d_conv3x3_winof16_bias_act_pm")
+    return ActMaxima(out, pm_out) if want_maxima else out
 
 
-def conv3x3_wino6_bias_act(x, wu6, bias, cout, cout_pad, slope=0.1, kernel=0, stagger_us=0, stagger_phases=16, arith="bf16x3"):
+def conv3x3_wino6_bias_act(x, wu6, bias, cout, cout_pad, slope=0.1, kernel=0, stagger_us=0, stagger_phases=16, arith="bf16x3",
+                           want_maxima=False):
     """3x3 stride-1 TF-'SAME' convolution + bias + leaky_relu(slope): Winograd F(2x2,3x3), float32 operands split into
     three bf16 terms, six bf16 MFMA products per term pair, float32 accumulation.  ``kernel``: 0 = chosen from the grid,
     1 = one workgroup per (tile, 64 couts) (csrc/m4d_wino6.hip), 2 = persistent workgroups (csrc/m4d_wino6p.hip); same bits.
     ``stagger_us`` > 0: the one-workgroup-per-unit kernel starts its first round of workgroups in ``stagger_phases`` groups spread
     over that many microseconds (a per-launch ARGUMENT, m4d_conv3x3_wino6_bias_act_ks; same bits).  ``arith`` = "f16x2": the
-    same layer on the fp16 two-term kernel (conv3x3_winof16_bias_act; ``wu6`` = pack_conv_weights_winof16, ``kernel`` ignored)."""
+    same layer on the fp16 two-term kernel (conv3x3_winof16_bias_act; ``wu6`` = pack_conv_weights_winof16, ``kernel`` ignored;
+    an ``ActMaxima`` input and ``want_maxima`` are that kernel's alone)."""
     if arith == "f16x2":
-        return conv3x3_winof16_bias_act(x, wu6, bias, cout, cout_pad, slope, stagger_us=stagger_us, stagger_phases=stagger_phases)
+        return conv3x3_winof16_bias_act(x, wu6, bias, cout, cout_pad, slope, stagger_us=stagger_us, stagger_phases=stagger_phases,
+                                        want_maxima=want_maxima)
+    if want_maxima or isinstance(x, ActMaxima):
+        raise ValueError("conv3x3_wino6_bias_act: pixel maxima are handed on by the f16x2 kernel only")
     x = as_f32(x, "x")
     b, h, w, cin = x.shape
     out = torch.empty((b, h, w, cout), dtype=torch.float32, device=x.device)

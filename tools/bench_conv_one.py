@@ -11,6 +11,8 @@ ap.add_argument("--w", type=int, default=640); ap.add_argument("--iters", type=i
 ap.add_argument("--winograd", type=int, default=0, help="0 = direct MFMA kernel, 1 / 2 = fp32-MFMA Winograd kernel 1 / 2(4), 6 = the bf16-split Winograd kernel, 7 = the fp16-split Winograd kernel")
 ap.add_argument("--variant", type=int, default=0, help="(experiments build) m4d_wino6_set_variant: 2 = the wide kernel, 3 = the half-tile kernel")
 ap.add_argument("--kernel", type=int, default=0, help="m4d_conv3x3_wino6_bias_act_k: 0 = the library's choice, 1 = one workgroup per unit, 2 = persistent")
+ap.add_argument("--handover", default="", choices=["", "read", "write", "both"],
+                help="--winograd 7 in a chain: the layer reads its input's pixel maxima instead of scanning its halo / writes its output's / both")
 a = ap.parse_args()
 if a.variant:
     from m4depth_amd._lib import lib
@@ -25,6 +27,12 @@ if a.winograd == 6:
 elif a.winograd == 7:
     wp, cpad = nops.pack_conv_weights_winof16(k.numpy()); wp = wp.view("int16")
     fn = nops.conv3x3_winof16_bias_act
+    if a.handover:
+        if a.handover in ("read", "both"):   # what the producing layer would have written: bits of the largest |x| per 64 channels
+            g = -(-a.cin // 64)
+            xa = torch.nn.functional.pad(x.abs(), (0, g * 64 - a.cin)).view(torch.int32)
+            x = nops.ActMaxima(x, xa.reshape(a.batch, a.h, a.w, g, 64).amax(dim=-1).contiguous())
+        fn = lambda *args_: nops.conv3x3_winof16_bias_act(*args_, want_maxima=a.handover in ("write", "both"))
 elif a.winograd:
     wp, cpad = nops.pack_conv_weights_winograd(k.numpy(), chunk=8 if a.winograd == 2 else 16)
     fn = nops.conv3x3_wino2_bias_act if a.winograd == 2 else nops.conv3x3_wino_bias_act
@@ -40,4 +48,4 @@ for _ in range(a.iters): fn(x, wpd, bias, a.cout, cpad, 0.1)
 e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) * 1e3 / a.iters
 fl = 2 * 9 * a.cin * a.cout * a.h * a.w * a.batch
-print(f"conv {a.cin}->{a.cout} {a.h}x{a.w} b={a.batch}: {us:.1f} us/launch, {fl / us / 1e6:.1f} TFLOP/s")
+print(f"conv {a.cin}->{a.cout}{' handover ' + a.handover if a.handover else ''} {a.h}x{a.w} b={a.batch}: {us:.1f} us/launch, {fl / us / 1e6:.1f} TFLOP/s")
