@@ -20,15 +20,16 @@
  *     the default stream).  No host synchronisation; the calls are re-entrant,
  *     safe from several host threads on different streams, and hipGraph-capturable.
  *     The ONLY process-wide state is the table of environment switches, read once
- *     and never written again (m4d_switches_info), and the profiling / debugging
- *     hooks named m4d_*_set_* (cycle-stamp buffers, the DSCV kernel selector,
- *     ablation masks): all off by default, not meant to be flipped while another
- *     thread launches, and never touched by the product's dispatch (m4depth_amd/network.py) -- every
- *     tuning choice of the dispatch (which Winograd kernel, its staggered first
- *     round) is an ARGUMENT of the call (ABI 6 removed round 5's
- *     m4d_wino6_set_stagger, the one setter the dispatch did touch).  The
- *     measured-and-not-dispatched alternative kernels and the launch tape are not
- *     in this library: `make EXPERIMENTS=1`, include/m4depth_hip_experiments.h;
+ *     and never written again (m4d_switches_info), the launch counter
+ *     (m4d_launch_count) and the DSCV kernel selector m4d_dscv_set_variant, the one
+ *     setter of this library: the tests use it to run every DSCV kernel, the
+ *     product's dispatch (m4depth_amd/network.py) never touches it, and it is not
+ *     meant to be flipped while another thread launches.  Every tuning choice of the
+ *     dispatch (which Winograd kernel, its staggered first round) is an ARGUMENT of
+ *     the call.  No kernel of this library carries a profiling hook: the cycle-stamp
+ *     buffers, the DSCV fallback counter, the measured-and-not-dispatched alternative
+ *     kernels and the launch tape exist only in `make EXPERIMENTS=1`
+ *     (include/m4depth_hip_experiments.h); the timing ablations are gone;
  *   - return value: 0 on success, otherwise a hipError_t code (1 =
  *     hipErrorInvalidValue for bad arguments).  Never exits the process (the
  *     reference launcher does `exit(-1)`, backproject_op_gpu.cu.cc:95-100);
@@ -49,7 +50,7 @@
 extern "C" {
 #endif
 
-#define M4D_ABI_VERSION 6   /* 6: + m4d_switches_info (the environment switches the library runs with; additive within ABI 6); 6: + m4d_train_log_step, m4d_train_log_workspace_bytes (device-side step log of the replayed training step; additive within ABI 6); 6: + m4d_depth_metrics_per_sample, m4d_metrics_per_sample_workspace_bytes (per-sample metrics of batched streaming evaluation; additive within ABI 6); 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
+#define M4D_ABI_VERSION 6   /* 6: m4d_wino_set_stamps, m4d_wino6_set_stamps, m4d_front_set_stamps, m4d_dscv_set_stamps, m4d_dscv_set_fallback_counter (profiling hooks, never part of the reference surface) moved to m4depth_hip_experiments.h, - m4d_dscv_set_ablation (deleted with every other timing ablation); 6: + m4d_switches_info (the environment switches the library runs with; additive within ABI 6); 6: + m4d_train_log_step, m4d_train_log_workspace_bytes (device-side step log of the replayed training step; additive within ABI 6); 6: + m4d_depth_metrics_per_sample, m4d_metrics_per_sample_workspace_bytes (per-sample metrics of batched streaming evaluation; additive within ABI 6); 6 (round 6): + m4d_refiner_tail6_m, m4d_refiner_tail_m, m4d_level_post_m, m4d_stream_prepare (batched streaming inference with per-sample resets; additive, no existing entry point changed), m4d_normalize_levels, m4d_level_front_small(_supported) (a coarse level opens with ONE launch), m4d_conv3x3_wino6_bias_act_ks (the staggered first round as a per-launch argument), - m4d_wino6_set_stagger (process-wide state on the launch path), - m4d_conv3x3_lat_chain (measured 12.5 us per hand-over, never dispatched: deleted); 5 (round 5): + m4d_depth_metrics_strided, m4d_launch_count, m4d_conv3x3_lat, m4d_conv3x3s_lat, m4d_partial_finish, m4d_level_front_r, m4d_wino6_persistent_min_units, m4d_pack_conv_weights_lat, m4d_conv3x3_lat_chain, m4d_pyramid_reset(_supported), m4d_enc_level0_stats / _apply, m4d_wino6_set_stagger; 4 (round 4): + m4d_conv3x3_wino6_bias_act_k; the wino6 kernel selectors and the launch tape moved to m4depth_hip_experiments.h */
 
 /* Library / device introspection (no GPU work). */
 int m4d_abi_version(void);
@@ -137,18 +138,10 @@ int m4d_dscv_fwd(const float* c1, const float* c2, const float* disp_prev_t, con
                  float* log_center, int log_stride, float log_scale,
                  int32_t* index_out, void* stream);
 
-/* Tuning / debugging hooks of the DSCV (process-wide, not part of the reference surface):
+/* The kernel selector of the DSCV (process-wide, not part of the reference surface; bit-identical results):
  * variant 0 = generic kernel, 1 = wave kernel with global gathers (default: fastest measured),
- * 2 = LDS search-window kernel, 3 / 4 = LDS window with 3 / all hypotheses per lane.  The fallback counter (device uint32, may be NULL) is incremented by
- * every workgroup of the window kernel whose footprint box did not fit the LDS window. */
+ * 2 = LDS search-window kernel, 3 / 4 = LDS window with 3 / all hypotheses per lane. */
 void m4d_dscv_set_variant(int variant);
-void m4d_dscv_set_fallback_counter(unsigned int* device_counter);
-/* Profiling only: ablation mask for the hypothesis-per-lane kernel (1 = skip cv stores, 2 = skip
- * corner loads, 4 = skip the centre / warped-parallax outputs).  Results are then meaningless. */
-void m4d_dscv_set_ablation(int mask);
-/* Profiling only: 6 uint64 per workgroup of the hypothesis-per-lane kernel = cycle counter at
- * entry / after the box reduction / after window staging / at exit, window pixels, window width. */
-void m4d_dscv_set_stamps(unsigned long long* device_buffer);
 
 /* cost_volume, the SNCV (:284-313): out channel ((y*(2r+1)+x)*k + kk) =
  * leaky_relu(mean_c c1[j,i,c] * c2pad[j+y*d, i+x*d, c], 0.1), written at
@@ -176,10 +169,6 @@ int m4d_conv3x3_wino_bias_act(const float* x, const float* wu, const float* bias
  * [ceil(Cin/8)][16 positions][CoutPad][8 channels]; Cin % 4 == 0, x 16-byte aligned. */
 int m4d_conv3x3_wino2_bias_act(const float* x, const float* wu8, const float* bias, int b, int h, int w,
                                int Cin, int Cout, int CoutPad, float slope, float* out, void* stream);
-/* Profiling only: 202 uint64 per workgroup (first 512 of batch item 0) = cycle counter of wave 0 at kernel entry / exit and,
- * per K chunk (first 40), at chunk start / after the first barrier / after the input transform / after the second barrier /
- * after the MFMA loop.  NULL switches it off. */
-void m4d_wino_set_stamps(unsigned long long* device_buffer);
 /* The same convolution with float32 operands on the BF16 matrix cores: every float32 operand is the exact sum of three
  * bf16 terms, six of the nine term products are accumulated in float32 (the dropped ones are below float32's product
  * rounding): float32 accuracy at 2.67x less matrix-core time.  wu6 = the transformed filter split and packed on the host
@@ -199,8 +188,6 @@ int m4d_conv3x3_wino6_bias_act_k(const float* x, const void* wu6, const float* b
 /* Grids of at least this many (16x16-pixel tile, 64-cout) units run on the persistent-workgroup form of the kernel above when
  * `kernel` is 0 (what bench.py needs to name the kernel its roofline layer ran on). */
 long long m4d_wino6_persistent_min_units(void);
-/* Profiling only (tools/wino6_phases.py): per-position cycle stamps of the first 64 workgroups; NULL switches it off. */
-void m4d_wino6_set_stamps(unsigned long long* device_buffer);
 /* The same call with a STAGGERED FIRST ROUND as well (ABI 6; replaces round 5's process-wide m4d_wino6_set_stagger): with
  * stagger_us > 0 the one-workgroup-per-unit kernel starts its first 256 workgroups (one per CU) in stagger_phases groups (a
  * power of two <= 32) spread over stagger_us microseconds (<= 1000): identical workgroups would otherwise free every CU at the
@@ -612,7 +599,6 @@ int m4d_level_front_small(const float* norm_f, const float* prev_f, const float*
  * m4d_level_front_supported: 1 if the (C, cuts, ranges, row stride) combination has a kernel (f_stride must be 58*cuts+6
  * rounded up to a multiple of 8), else 0 -- the caller then uses the three separate entry points. */
 int m4d_level_front_supported(int C, int nbre_cuts, int dscv_range, int sncv_range, int f_stride);
-void m4d_front_set_stamps(unsigned long long* device_buffer);   /* profiling: 8 x u64 per workgroup, phase cycle stamps */
 int m4d_level_front(const float* raw_f, float* norm_out, const float* prev_f, const float* depth_prev_t,
                     const float* prev_l_parallax, const float* prev_l_other, int ph, int pw,
                     const float* rot, int rot_c, const float* trans, const float* cam_f, const float* cam_c,

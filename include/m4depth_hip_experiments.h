@@ -1,9 +1,10 @@
 /*
  * m4depth_hip_experiments.h -- entry points that exist ONLY in a `make -C m4depth_amd/csrc EXPERIMENTS=1` build of
- * libm4depth_hip.so (m4d_build_info() then says "+experiments").  Everything here was measured, found not to be faster
- * end to end, and is NOT dispatched by the product (DESIGN_HISTORY.md); it stays buildable for the bit-identity tests and
- * the profiling tools that compare against it.  The selectors are PROCESS-WIDE state: set them from one thread, while
- * nothing is launching.
+ * libm4depth_hip.so (m4d_build_info() then says "+experiments").  The alternative kernels here were measured, found not to
+ * be faster end to end, and are NOT dispatched by the product (DESIGN_HISTORY.md); they stay buildable for the bit-identity
+ * tests and the profiling tools that compare against them.  The profiling hooks at the end make kernels write cycle stamps or
+ * counters into a buffer the CALLER sizes; the product's kernels do not contain them.  Selectors and hooks are PROCESS-WIDE
+ * state: set them from one thread, while nothing is launching.
  */
 #ifndef M4DEPTH_HIP_EXPERIMENTS_H_
 #define M4DEPTH_HIP_EXPERIMENTS_H_
@@ -35,6 +36,24 @@ int m4d_tape_replay(int tape, void* stream);
 int m4d_tape_free(int tape);
 /* The scatter backwards (m4d_backproject_bwd, m4d_dscv_bwd) zero their outputs with a kernel launch (m4d_zero_f32), which
  * is recorded like any other launch. */
+
+/* ---- profiling hooks: NULL (the default) switches a hook off; results are unchanged while one is on.  The buffer must hold
+ * what the hook's description says for the launch that follows -- the kernels do not know its size. */
+/* Winograd kernel 4 of m4d_conv3x3_wino2_bias_act (tools/wino4_phases.py): 202 uint64 per workgroup (first 512 of batch item
+ * 0) = cycle counter of wave 0 at kernel entry / end of the K loop, per K chunk (first 40) at five phase boundaries, and (last
+ * word) at the end of the epilogue. */
+void m4d_wino_set_stamps(unsigned long long* device_buffer);
+/* m4d_conv3x3_wino6_bias_act on the one-workgroup-per-unit kernel (tools/wino6_phases.py): 1280 uint64 for each of the first
+ * 64 workgroups, per-position cycle stamps of every wave.  While set, every launch takes that kernel. */
+void m4d_wino6_set_stamps(unsigned long long* device_buffer);
+/* The fused level front (tools/bench_kernels.py): 8 uint64 per workgroup, 7 phase cycle stamps. */
+void m4d_front_set_stamps(unsigned long long* device_buffer);
+/* The hypothesis-per-lane DSCV kernels (m4d_dscv_set_variant 3 / 4): 6 uint64 per workgroup = cycle counter at entry / after
+ * the box reduction / after window staging / at exit, window pixels, window width. */
+void m4d_dscv_set_stamps(unsigned long long* device_buffer);
+/* The DSCV window kernels (variants 2-4): a device uint32 incremented by every workgroup whose footprint box did not fit the
+ * LDS window. */
+void m4d_dscv_set_fallback_counter(unsigned int* device_counter);
 
 #ifdef __cplusplus
 }

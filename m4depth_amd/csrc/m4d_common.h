@@ -54,6 +54,15 @@ inline void m4d_launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t l
   hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<KArgs>(args)...);
 }
 
+// ---- M4D_STAMP(...): the code of the cycle-stamp and counter hooks (include/m4depth_hip_experiments.h) ---------------------
+// `make EXPERIMENTS=1` compiles what it encloses -- the `stamps` field of an args struct, the stamp stores of a kernel, the
+// setter's global on the host side; in the product library it expands to nothing, so no product kernel carries a hook.
+#if M4D_EXPERIMENTS
+#define M4D_STAMP(...) __VA_ARGS__
+#else
+#define M4D_STAMP(...)
+#endif
+
 // ---- zero-fill of a buffer that atomic adds then scatter into: a KERNEL, not hipMemsetAsync ---------------------------------
 // Inside a captured training step (training.GraphedTrainStep) a memset node was not reliably ordered against the kernel nodes
 // around it on replay: the scatter's sums came out with stale or missing terms in some replays.

@@ -35,9 +35,6 @@ struct ConvArgs {
   // DINL variant (encoder level 0): x is the RAW first convolution; DomainNormalization + leaky_relu(dn_slope) are applied
   // while the halo is committed to LDS (m4depth_network.py:44-48,82-84)
   const float* dn_mean; const float* dn_var; const float* dn_scale; const float* dn_bias; float dn_slope;
-  int ablate;                         // profiling only: 1 = no re-staging after the first stage, 2 = no MFMAs, 4 = no stores.  Every host
-                                      // path passes 0 (the environment switch that set it is retired); the field and its branches stay
-                                      // until a measured change, because removing them changes the code of the hot kernels
 };
 
 constexpr int kTW = 16, kTH = 8;                    // output tile
@@ -256,14 +253,13 @@ conv3x3_mfma_kernel(const ConvArgs a) {
       const int s = st % SPC;
       const bool has_next = st + 1 < n_stages;
       const int nchunk = chunk_lo + (st + 1) / SPC, ns = (st + 1) % SPC;
-      const bool restage = has_next && !(a.ablate & 1);
-      if (restage) {
+      if (has_next) {
         load_b(nchunk, ns);
         if (ns == 0) load_a(nchunk);
       }
-      if (!(a.ablate & 2)) mfma_stage(s, 0);
+      mfma_stage(s, 0);
       __syncthreads();                               // all waves done with lds_b (and lds_a when ns == 0)
-      if (restage) {
+      if (has_next) {
         commit_b(0);
         if (ns == 0) commit_a();
       }
@@ -287,7 +283,6 @@ conv3x3_mfma_kernel(const ConvArgs a) {
     }
     return;
   }
-  if (a.ablate & 4) { if (acc[0][0] != 1.2345e-30f) return; }   // profiling only: no output stores (the compare keeps the MFMAs alive)
   float* oimg = a.out + (long long)bi * a.oh * a.ow * a.Cout;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
@@ -710,7 +705,7 @@ static int launch_conv3x3_small(const float* x, const float* wp, const float* bi
   a.x = x; a.wp = wp; a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout;
   a.CoutPad = CoutPad; a.n_chunks = (Cin + kKC - 1) / kKC;
   a.dn_mean = a.dn_var = a.dn_scale = a.dn_bias = nullptr; a.dn_slope = 1.0f;
-  a.ablate = 0; a.slope = slope;
+  a.slope = slope;
   a.oh = (h + stride - 1) / stride; a.ow = (w + stride - 1) / stride;
   const int tot_y = (a.oh - 1) * stride + 3 - h, tot_x = (a.ow - 1) * stride + 3 - w;   // TF 'SAME'
   a.pad_y = (tot_y > 0 ? tot_y : 0) / 2; a.pad_x = (tot_x > 0 ? tot_x : 0) / 2;
@@ -745,7 +740,7 @@ extern "C" int m4d_conv3x3_small6_bias_act(const float* x, const void* wp6, cons
   a.x = x; a.wp = reinterpret_cast<const float*>(wp6); a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout;
   a.CoutPad = CoutPad; a.n_chunks = (Cin + kKC - 1) / kKC;
   a.dn_mean = a.dn_var = a.dn_scale = a.dn_bias = nullptr; a.dn_slope = 1.0f;
-  a.ablate = 0; a.oh = h; a.ow = w; a.pad_y = a.pad_x = 1; a.slope = slope;
+  a.oh = h; a.ow = w; a.pad_y = a.pad_x = 1; a.slope = slope;
   a.tiles_x = (w + kSW - 1) / kSW; a.tiles_y = (h + kSH - 1) / kSH;
   a.ksplit = 1; a.chunks_per_split = a.n_chunks; a.ws = nullptr;
   constexpr size_t lds = (size_t)4 * (kS6A + kS6B) * sizeof(float);                     // 134 KB
@@ -776,7 +771,7 @@ extern "C" int m4d_conv3x3s2_dinl_bias_act(const float* x_raw, const float* mean
   M4D_CHECK_ARG(((((uintptr_t)x_raw) & 7u) == 0) && ((((uintptr_t)wp) & 15u) == 0));
   ConvArgs a;
   a.x = x_raw; a.wp = wp; a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = 16; a.Cout = Cout;
-  a.CoutPad = CoutPad; a.n_chunks = 1; a.ablate = 0;
+  a.CoutPad = CoutPad; a.n_chunks = 1;
   a.oh = (h + 1) / 2; a.ow = (w + 1) / 2;
   const int tph = (a.oh - 1) * 2 + 3 - h, tpw = (a.ow - 1) * 2 + 3 - w;
   a.pad_y = (tph > 0 ? tph : 0) / 2; a.pad_x = (tpw > 0 ? tpw : 0) / 2;
@@ -815,7 +810,6 @@ extern "C" int m4d_conv3x3s_bias_act_wsb(const float* x, const float* wp, const 
   a.x = x; a.wp = wp; a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout;
   a.CoutPad = CoutPad; a.n_chunks = (Cin + kKC - 1) / kKC;
   a.dn_mean = a.dn_var = a.dn_scale = a.dn_bias = nullptr; a.dn_slope = 1.0f;
-  a.ablate = 0;
   // TensorFlow 'SAME': out = ceil(in / stride), total pad = max((out-1)*stride + 3 - in, 0), before = total / 2
   a.oh = (h + stride - 1) / stride; a.ow = (w + stride - 1) / stride;
   const int tph = (a.oh - 1) * stride + 3 - h, tpw = (a.ow - 1) * stride + 3 - w;

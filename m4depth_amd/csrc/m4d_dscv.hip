@@ -33,7 +33,6 @@ struct DscvArgs {
   int h, w, C, r, k, nc, cv_accum;
   float* cv; int cv_stride; float* prev_disp; float* log_center; int log_stride; float log_scale;
   int32_t* index_out;
-  int ablate;            // profiling only (m4d_dscv_set_ablation): 1 = no cv stores, 2 = no corner loads, 4 = no centre feature
   // ONFLY instantiations only (m4d_level_front_small: the level's opening glue is not a launch of its own, so its two maps do
   // not exist): disp = 2 x the x2 upsampling of the coarser level's parallax (pl_para [b,ph,pw], NULL at the coarsest level: 1),
   // disp_prev_t at a corner = prev_d2para of the depth memory there -- the expressions of level_pre_body, evaluated in place
@@ -291,8 +290,8 @@ __device__ __forceinline__ void dscv_stage_window(const float* __restrict__ img,
 struct DscvTileArgs {
   DscvArgs d;
   int tw, th, tiles_x, tiles, win_cap_px;
-  unsigned int* fallback_counter;               // optional: counts workgroups that took the global path
-  unsigned long long* stamps;                   // optional (profiling): 4 s_memtime stamps + window size per workgroup
+  M4D_STAMP(unsigned int* fallback_counter;)    // m4d_dscv_set_fallback_counter: counts workgroups that took the global path
+  M4D_STAMP(unsigned long long* stamps;)        // m4d_dscv_set_stamps: 4 cycle-counter stamps + window size per workgroup
 };
 
 template <int LP, int G, int NCP>
@@ -355,11 +354,8 @@ dscv_tile_kernel(const DscvTileArgs ta) {
 
   // ---- phase 2: stage the window (each byte once, coalesced rows)
   const float* c2img = a.c2 + (long long)bi * hw * C;
-  if (use_lds) {
-    dscv_stage_window<C>(c2img, win, a.w, ymin, xmin, WH, WW, t);
-  } else if (t == 0 && ta.fallback_counter) {
-    atomicAdd(ta.fallback_counter, 1u);
-  }
+  if (use_lds) dscv_stage_window<C>(c2img, win, a.w, ymin, xmin, WH, WW, t);
+  M4D_STAMP(else if (t == 0 && ta.fallback_counter) atomicAdd(ta.fallback_counter, 1u);)
   __syncthreads();
 
   // ---- phase 3: wave layout of dscv_wave_kernel, corners from LDS
@@ -414,8 +410,8 @@ dscv_hyp_kernel(const DscvTileArgs ta) {
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
   const M4dMotion m = m4d_load_motion(a.rot, a.rot_c, a.trans, a.cam_f, a.cam_c, bi);
-  unsigned long long* st = ta.stamps ? ta.stamps + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 6 : nullptr;
-  if (st && t == 0) st[0] = __builtin_readcyclecounter();
+  M4D_STAMP(unsigned long long* st = ta.stamps ? ta.stamps + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 6 : nullptr;)
+  M4D_STAMP(if (st && t == 0) st[0] = __builtin_readcyclecounter();)
 
   // ---- phase 1: footprint bounding box from the two end hypotheses of pixel t
   int ymin = 0x7fffffff, ymax = -1, xmin = 0x7fffffff, xmax = -1;
@@ -451,18 +447,14 @@ dscv_hyp_kernel(const DscvTileArgs ta) {
   xmax = max(max(red[3], red[7]), max(red[11], red[15]));
   const int WH = ymax - ymin + 2, WW = xmax - xmin + 2;
   const bool use_lds = ymax >= 0 && WH * WW <= ta.win_cap_px;      // block-uniform
-  if (st && t == 0) { st[1] = __builtin_readcyclecounter(); st[4] = (unsigned long long)(WH * WW); st[5] = (unsigned long long)WW; }
+  M4D_STAMP(if (st && t == 0) { st[1] = __builtin_readcyclecounter(); st[4] = (unsigned long long)(WH * WW); st[5] = (unsigned long long)WW; })
 
   // ---- phase 2: stage the window
   const float* c2img = a.c2 + (long long)bi * hw * C;
-  if (use_lds) {
-    if (!(a.ablate & 16)) dscv_stage_window<C>(c2img, win, a.w, ymin, xmin, WH, WW, t);
-  } else if (t == 0 && ta.fallback_counter) {
-    atomicAdd(ta.fallback_counter, 1u);
-  }
+  if (use_lds) dscv_stage_window<C>(c2img, win, a.w, ymin, xmin, WH, WW, t);
+  M4D_STAMP(else if (t == 0 && ta.fallback_counter) atomicAdd(ta.fallback_counter, 1u);)
   __syncthreads();
-  if (st && t == 0) st[2] = __builtin_readcyclecounter();
-  if (a.ablate & 8) { if (st && t == 0) st[3] = st[2]; return; }
+  M4D_STAMP(if (st && t == 0) st[2] = __builtin_readcyclecounter();)
 
   // ---- phase 3: lane = (pixel slot, cut, hypothesis group)
   const int slot = lane / LPP;
@@ -503,10 +495,7 @@ dscv_hyp_kernel(const DscvTileArgs ta) {
       m4d_bilinear_axis(qy, a.h, y0, ay);
       m4d_bilinear_axis(qx, a.w, x0, ax);
       float4 vtl[CH], vtr[CH], vbl[CH], vbr[CH];
-      if (a.ablate & 2) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) { vtl[c] = vtr[c] = vbl[c] = vbr[c] = make_float4(ax, ay, ax, ay); }
-      } else if (use_lds) {
+      if (use_lds) {
         const float* p = win + ((y0 - ymin) * WW + (x0 - xmin)) * CP + kk * NC;
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -547,9 +536,8 @@ dscv_hyp_kernel(const DscvTileArgs ta) {
         }
       }
       if (active && hyp_on) {
-        if (!(a.ablate & 1) || acc == 12345.f)
-          a.cv[gp * a.cv_stride + kk * NCP + hyp] = m4d_round_half(acc / (float)NC);     // :277-278
-        if (kk == 0 && !(a.ablate & 4)) {
+        a.cv[gp * a.cv_stride + kk * NCP + hyp] = m4d_round_half(acc / (float)NC);       // :277-278
+        if (kk == 0) {
           if (a.index_out) {
             a.index_out[(gp * NCP + hyp) * 2] = y0;
             a.index_out[(gp * NCP + hyp) * 2 + 1] = x0;
@@ -566,7 +554,7 @@ dscv_hyp_kernel(const DscvTileArgs ta) {
       asm volatile("" ::: "memory");
     }
   }
-  if (st && t == 0) st[3] = __builtin_readcyclecounter();
+  M4D_STAMP(if (st && t == 0) st[3] = __builtin_readcyclecounter();)
 }
 
 // Any C / cuts / alignment / search range: one lane per (pixel, cut), scalar loads.
@@ -640,8 +628,8 @@ bool launch_wave(const DscvArgs& a, int b, hipStream_t s) {
 // Tile geometry / LDS budget of the window variant.  52 KiB per workgroup = three
 // workgroups per CU (160 KiB): one stages while the others gather.
 constexpr size_t kDscvLdsBudget = 52 * 1024;
-unsigned int* g_dscv_fallback_counter = nullptr;     // debug hook (m4d_dscv_set_fallback_counter)
-unsigned long long* g_dscv_stamps = nullptr;         // debug hook (m4d_dscv_set_stamps)
+M4D_STAMP(unsigned int* g_dscv_fallback_counter = nullptr;)     // m4d_dscv_set_fallback_counter
+M4D_STAMP(unsigned long long* g_dscv_stamps = nullptr;)         // m4d_dscv_set_stamps
 
 template <int LP, int G, int NCP>
 void launch_tile_ncp(const DscvTileArgs& ta, int b, hipStream_t s) {
@@ -677,8 +665,7 @@ bool launch_hyp(const DscvArgs& a, int b, hipStream_t s, bool all_in_lane) {
       ta.tiles_x = (a.w + tw - 1) / tw;
       ta.tiles = ta.tiles_x * ((a.h + th - 1) / th);
       ta.win_cap_px = (int)((budget - fixed) / (CP * sizeof(float)));
-      ta.fallback_counter = g_dscv_fallback_counter;
-      ta.stamps = g_dscv_stamps;
+      M4D_STAMP(ta.fallback_counter = g_dscv_fallback_counter; ta.stamps = g_dscv_stamps;)
       if (all_in_lane) launch_hyp_ncp<NC, K, 9, 9>(ta, b, budget, s);
       else launch_hyp_ncp<NC, K, 9, 3>(ta, b, budget, s);
       return true;
@@ -707,8 +694,7 @@ bool launch_tile(const DscvArgs& a, int b, hipStream_t s) {
   ta.tiles_x = (a.w + tw - 1) / tw;
   ta.tiles = ta.tiles_x * ((a.h + th - 1) / th);
   ta.win_cap_px = (int)((kDscvLdsBudget - fixed) / (CP * sizeof(float)));
-  ta.fallback_counter = g_dscv_fallback_counter;
-  ta.stamps = nullptr;
+  M4D_STAMP(ta.fallback_counter = g_dscv_fallback_counter; ta.stamps = nullptr;)
   if (ncp == 9) launch_tile_ncp<LP, G, 9>(ta, b, s);
   else launch_tile_ncp<LP, G, 5>(ta, b, s);
   return true;
@@ -716,13 +702,10 @@ bool launch_tile(const DscvArgs& a, int b, hipStream_t s) {
 
 }  // namespace
 
-extern "C" void m4d_dscv_set_fallback_counter(unsigned int* device_counter) {
-  g_dscv_fallback_counter = device_counter;
-}
-
+#if M4D_EXPERIMENTS
+extern "C" void m4d_dscv_set_fallback_counter(unsigned int* device_counter) { g_dscv_fallback_counter = device_counter; }
 extern "C" void m4d_dscv_set_stamps(unsigned long long* device_buffer) { g_dscv_stamps = device_buffer; }
-static int g_dscv_ablate = 0;
-extern "C" void m4d_dscv_set_ablation(int mask) { g_dscv_ablate = mask; }
+#endif
 // 0: generic, 1: wave kernel (global gathers; DEFAULT -- fastest measured, profiles/),
 // 2: LDS window + channels-across-lanes, 3 / 4: LDS window + 3 / all hypotheses per lane.
 static int g_dscv_variant = 1;
@@ -757,7 +740,7 @@ static DscvArgs dscv_args(const float* c1, const float* c2, const float* rot, in
   a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c;
   a.h = h; a.w = w; a.C = C; a.r = r; a.k = k; a.nc = C / k; a.cv_accum = cv_accum;
   a.cv = cv; a.cv_stride = cv_stride; a.prev_disp = prev_disp; a.log_center = log_center;
-  a.log_stride = log_stride; a.log_scale = log_scale; a.index_out = nullptr; a.ablate = g_dscv_ablate;
+  a.log_stride = log_stride; a.log_scale = log_scale; a.index_out = nullptr;
   return a;
 }
 

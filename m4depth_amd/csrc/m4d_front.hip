@@ -49,7 +49,7 @@ struct FrontArgs {
   int b, h, w;
   float* f_input; float log_scale; int cv_accum;
   int tiles_x, tiles_y;
-  unsigned long long* stamps;  // profiling only (m4d_front_set_stamps): 7 cycle-counter stamps per workgroup
+  M4D_STAMP(unsigned long long* stamps;)  // m4d_front_set_stamps: 7 cycle-counter stamps per workgroup
 };
 
 // RD / RS = the DSCV / SNCV search ranges: 4 / 3 are the reference's (m4depth_network.py:221,232); 6 / 6 is BASELINE configs[4]
@@ -76,11 +76,15 @@ struct FrontGeom {
   static constexpr int RPL = (MO + YS - 1) / YS;
   static constexpr int NPASS = (P + NW * PPW - 1) / (NW * PPW);
   static_assert(IT % 64 == 0 && NT <= 1024 && P <= NT, "whole waves per row group; one lane per pixel in the upsampling step");
+  // waves per SIMD the register allocation must leave room for.  The level-5 shape on large maps (32 channels x 4 cuts, 8x8
+  // tile, 512 threads) sits at the 128-register edge of 4 waves: without the bound hipcc settles on 130 registers and 3 waves
+  // (profiles/profiling_hooks_removed.txt)
+  static constexpr int MIN_WAVES = (NC == 32 && K == 4 && TW == 8 && TH == 8 && YS == 2 && RD == 4) ? 4 : 1;
   static_assert(LP >= 4 && LP <= 64, "the centre hypothesis spreads its 4 corners over 4 lanes of the pixel");
 };
 
 template <int NC, int K, int TW, int TH, int YS, bool SEQ16, int RD = 4, int RS = 3>
-__global__ void __launch_bounds__(TW * TH * K * YS)
+__global__ void __launch_bounds__(TW * TH * K * YS, (FrontGeom<NC, K, TW, TH, YS, RD, RS>::MIN_WAVES))
 level_front_kernel(const FrontArgs a) {
   using Gm = FrontGeom<NC, K, TW, TH, YS, RD, RS>;
   constexpr int R = Gm::R, MO = Gm::MO, NCP = Gm::NCP, C = Gm::C, CP = Gm::CP, C4 = Gm::C4, HWT = Gm::HWT, HHT = Gm::HHT;
@@ -99,8 +103,8 @@ level_front_kernel(const FrontArgs a) {
   const int tile_y = (tl / a.tiles_x) * TH, tile_x = (tl % a.tiles_x) * TW;
   const int h = a.h, w = a.w, hw = h * w;
   const M4dMotion m = m4d_load_motion(a.rot, a.rot_c, a.trans, a.cam_f, a.cam_c, bi);
-  unsigned long long* st = a.stamps ? a.stamps + (long long)blockIdx.x * 8 : nullptr;
-  if (st && t == 0) st[0] = __builtin_readcyclecounter();
+  M4D_STAMP(unsigned long long* st = a.stamps ? a.stamps + (long long)blockIdx.x * 8 : nullptr;)
+  M4D_STAMP(if (st && t == 0) st[0] = __builtin_readcyclecounter();)
 
   // ---- A1: raw halo -> registers (unconditional clamped loads: a load under a branch is waited for at the merge)
   {
@@ -147,7 +151,7 @@ level_front_kernel(const FrontArgs a) {
     }
   }
   __syncthreads();
-  if (st && t == 0) st[1] = __builtin_readcyclecounter();
+  M4D_STAMP(if (st && t == 0) st[1] = __builtin_readcyclecounter();)
   // ---- A2: normalise every (pixel, cut) run of the halo in place (tf.linalg.normalize: x / sqrt(sum x^2), sequential sum)
   for (int it = t; it < HHT * HWT * K; it += NT) {
     const int hp = it / K, kk = it % K;
@@ -169,7 +173,7 @@ level_front_kernel(const FrontArgs a) {
       *reinterpret_cast<float4*>(p + 4 * c) = make_float4(v[c].x / nrm, v[c].y / nrm, v[c].z / nrm, v[c].w / nrm);
   }
   __syncthreads();
-  if (st && t == 0) st[2] = __builtin_readcyclecounter();
+  M4D_STAMP(if (st && t == 0) st[2] = __builtin_readcyclecounter();)
   // ---- B1: the tile's normalised features -> temporal memory (coalesced 16-byte stores)
   {
     float* nout = a.norm_out + (long long)bi * hw * C;
@@ -218,7 +222,7 @@ level_front_kernel(const FrontArgs a) {
       }
     }
   }
-  if (st && t == 0) st[3] = __builtin_readcyclecounter();
+  M4D_STAMP(if (st && t == 0) st[3] = __builtin_readcyclecounter();)
   // ---- C0: the DSCV lanes take their 4 channels of c1 (pre-rounded to half, :276) out of the halo before it dies
   const int lane = t & 63, wave = t >> 6;
   const int slot = lane / LP;                                  // pixel slot in the wave
@@ -255,7 +259,7 @@ level_front_kernel(const FrontArgs a) {
       for (int c = F_IN; c < F_ST; ++c) row[c] = 0.f;                        // channel padding of the refiner input stays zero
     }
   }
-  if (st && t == 0) st[4] = __builtin_readcyclecounter();
+  M4D_STAMP(if (st && t == 0) st[4] = __builtin_readcyclecounter();)
   // ---- C2: DSCV (get_parallax_sweeping_cv), wave layout: LP lanes per pixel, PPW pixels per wave
   {
     const float* c2img = a.c2 + (long long)bi * hw * C + 4 * q;
@@ -374,7 +378,7 @@ level_front_kernel(const FrontArgs a) {
     }
   }
   __syncthreads();
-  if (st && t == 0) st[5] = __builtin_readcyclecounter();
+  M4D_STAMP(if (st && t == 0) st[5] = __builtin_readcyclecounter();)
   // ---- D: the tile's refiner-input rows, contiguous in HBM per tile row
   // 16 bytes per lane (round 4): the stage's rows have an odd stride (conflict-free column writes above), so a lane gathers its
   // four floats with four ds_read_b32 -- 64 lanes of one read still hit 64 distinct banks (bank = 4 quad + pixel + i) -- and
@@ -391,7 +395,7 @@ level_front_kernel(const FrontArgs a) {
       if (oy < h && ox < w) m4d_store16(fin + ((long long)oy * w + ox) * F_ST + 4 * q4, v0, v1, v2, v3);
     }
   }
-  if (st && t == 0) st[6] = __builtin_readcyclecounter();
+  M4D_STAMP(if (st && t == 0) st[6] = __builtin_readcyclecounter();)
 }
 
 template <int NC, int K, int TW, int TH, int YS, bool SEQ16, int RD = 4, int RS = 3>
@@ -414,11 +418,13 @@ int launch_front(const FrontArgs& a, hipStream_t s) {
   return a.cv_accum ? launch_front_acc<NC, K, TW, TH, YS, true, RD, RS>(a, s) : launch_front_acc<NC, K, TW, TH, YS, false, RD, RS>(a, s);
 }
 
-unsigned long long* g_front_stamps = nullptr;        // debug hook (m4d_front_set_stamps)
+M4D_STAMP(unsigned long long* g_front_stamps = nullptr;)
 
 }  // namespace
 
+#if M4D_EXPERIMENTS
 extern "C" void m4d_front_set_stamps(unsigned long long* device_buffer) { g_front_stamps = device_buffer; }
+#endif
 
 extern "C" int m4d_level_front_supported(int C, int nbre_cuts, int dscv_range, int sncv_range, int f_stride) {
   if (nbre_cuts <= 0 || C % nbre_cuts != 0) return 0;
@@ -453,7 +459,7 @@ extern "C" int m4d_level_front_r(const float* raw_f, float* norm_out, const floa
   a.rot = rot; a.rot_c = rot_c; a.trans = trans; a.cam_f = cam_f; a.cam_c = cam_c;
   a.b = b; a.h = h; a.w = w; a.f_input = f_input; a.log_scale = log_scale; a.cv_accum = cv_accum;
   a.tiles_x = a.tiles_y = 0;
-  a.stamps = g_front_stamps;
+  M4D_STAMP(a.stamps = g_front_stamps;)
   hipStream_t s = (hipStream_t)stream;
   const int nc = C / nbre_cuts;
   if (dscv_range == 6) {

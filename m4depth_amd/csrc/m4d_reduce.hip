@@ -374,9 +374,6 @@ __device__ __forceinline__ f32x4 enc0_conv1(const float* window_base, const int 
   return acc;
 }
 
-#ifndef M4D_E0S_ABL
-#define M4D_E0S_ABL 0   // timing ablations of enc0_stats_kernel (wrong results): 2 no MFMAs, 4 no double-precision sums
-#endif
 constexpr int kE0TW = 128, kE0TH = 8;              // statistics tile (pixels)
 constexpr int kE0RS = (kE0TW + 2) * 3;             // floats per staged RGB row (390)
 
@@ -499,12 +496,11 @@ enc0_stats_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
 #pragma unroll 4
         for (int ct = 0; ct < kE0TW / 16; ++ct) {
           const float* wnd = tb + yl * kE0RS + 3 * (16 * ct + j);
-          const f32x4 acc = (M4D_E0S_ABL & 2) ? f32x4{wnd[koff[0]], wnd[koff[1]], wnd[koff[2]], wnd[koff[3]]} : enc0_conv1(wnd, koff, wb);
+          const f32x4 acc = enc0_conv1(wnd, koff, wb);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const bool valid = kWhole || (y0 + yl < h && x0 + 16 * ct + 4 * g + r < w);
             const float v1 = acc[r] + bias_j;
-            if (M4D_E0S_ABL & 4) { csum += r == 0 ? (double)v1 : 0.0; continue; }
             const double d = valid ? (double)v1 - shift_j : 0.0;
             csum += d;
             csum2 = fma(d, d, csum2);
@@ -576,9 +572,6 @@ enc0_moments_finalize_kernel(const float* __restrict__ img, const double* __rest
   }
 }
 
-#ifndef M4D_E0_ABL
-#define M4D_E0_ABL 0    // timing ablations of enc0_fused_kernel (wrong results): 1 no staging loads, 2 no conv1 MFMAs, 4 no normalisation pass, 8 no conv2 MFMAs, 16 no stores
-#endif
 constexpr int kF0OW = 16, kF0OH = 8;               // stride-2 output tile
 constexpr int kF0CW = 2 * kF0OW + 1, kF0CH = 2 * kF0OH + 1;   // conv1 region it needs: 33 x 17 (TF 'SAME' on an even size pads bottom / right)
 constexpr int kF0RW = kF0CW + 2, kF0RH = kF0CH + 2;            // RGB region 35 x 19
@@ -588,7 +581,6 @@ constexpr int kF0NP = kF0CW * kF0CH;               // 561 conv1 pixels
 
 // conv1 recomputed on the 33x17 region, + bias, DomainNormalization, leaky_relu(dn_slope) -> LDS (zero outside the
 // image: the stride-2 convolution's padding), then conv3x3 stride 2 (16 -> 16) + bias + leaky_relu(slope) -> out.
-__device__ __forceinline__ bool v_dummy(float x) { return x != 1.2345e-30f; }
 __global__ void __launch_bounds__(256)
 enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, const float* __restrict__ bias1,
                   const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ dn_scale,
@@ -615,7 +607,7 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
 #pragma unroll
     for (int i = 0; i < kNL; ++i) {
       const int gy = gy0 + r, gxc = gc0 + cc;
-      const bool in = r < kF0RH && gy >= 0 && gy < h && gxc >= 0 && gxc < row3 && !(M4D_E0_ABL & 1);
+      const bool in = r < kF0RH && gy >= 0 && gy < h && gxc >= 0 && gxc < row3;
       const float x = ib[in ? (long long)gy * row3 + gxc : 0LL];
       sv[i] = in ? x : 0.f;
       r += 2; cc += kStep;
@@ -654,15 +646,11 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
       wa[u] = rgb + ay * kF0RS + 3 * ax;
     }
     f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0, c2 = c0;
-    if (M4D_E0_ABL & 2) {
-      c0 = c1 = c2 = f32x4{wb[0], wb[1], wb[2], wb[3]};
-    } else {
 #pragma unroll
-      for (int s = 0; s < 7; ++s) {
-        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[0][koff[s]], wb[s], c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[1][koff[s]], wb[s], c1, 0, 0, 0);
-        c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[2][koff[s]], wb[s], c2, 0, 0, 0);
-      }
+    for (int s = 0; s < 7; ++s) {
+      c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[0][koff[s]], wb[s], c0, 0, 0, 0);
+      c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[1][koff[s]], wb[s], c1, 0, 0, 0);
+      c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[2][koff[s]], wb[s], c2, 0, 0, 0);
     }
     float* n0 = nrm + (16 * (wv + 4 * it) + 4 * g) * kF0NS + j;      // accumulator row r -> pixel 16 tile + 4 g + r
 #pragma unroll
@@ -681,7 +669,7 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   }
   __syncthreads();
   // ---- phase 1b: DomainNormalization + leaky_relu per pixel, in place (one thread per pixel: the 1/sqrt once, not per channel)
-  for (int p = t; p < ((M4D_E0_ABL & 4) ? 0 : kF0NP); p += 256) {
+  for (int p = t; p < kF0NP; p += 256) {
     const int py = p / kF0CW, px = p - py * kF0CW;
     const bool inside = cy0 + py >= 0 && cy0 + py < h && cx0 + px >= 0 && cx0 + px < w;
     float* q = nrm + p * kF0NS;
@@ -701,14 +689,14 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
   // ---- phase 2: 8 rows of 16 stride-2 outputs, 2 rows per wave; A[pixel i][k]: pixel (2 oy + ky, 2 i + kx), channel
   // (the two rows' chains of 36 alternate on two accumulators, and the A operands of step s + 2 are read from LDS while step s
   //  multiplies: one row after the other, every second MFMA waited for an LDS read issued just before it)
-  constexpr int kS2 = (M4D_E0_ABL & 8) ? 1 : 36;
+  constexpr int kS2 = 36;
   const float* base2 = nrm + ((4 * wv) * kF0CW + 2 * j) * kF0NS + g;
   auto a2 = [&](int rr, int s) {
     const int tap = s >> 2, ky = tap / 3, kx = tap - 3 * ky;
     return base2[((2 * rr + ky) * kF0CW + kx) * kF0NS + 4 * (s & 3)];
   };
   f32x4 acc2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  float xa[2][2] = {{a2(0, 0), a2(1, 0)}, {a2(0, kS2 > 1 ? 1 : 0), a2(1, kS2 > 1 ? 1 : 0)}};
+  float xa[2][2] = {{a2(0, 0), a2(1, 0)}, {a2(0, 1), a2(1, 1)}};
 #pragma unroll
   for (int s = 0; s < kS2; ++s) {
     const float x0 = xa[s & 1][0], x1 = xa[s & 1][1];
@@ -726,7 +714,7 @@ enc0_fused_kernel(const float* __restrict__ img, const float* __restrict__ w27, 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int ox = ox0 + 4 * g + r;
-      if (oy < oh && ox < ow && !((M4D_E0_ABL & 16) && v_dummy(acc[r]))) {
+      if (oy < oh && ox < ow) {
         float v = acc[r] + bias2_j;
         v = v > 0.f ? v : v * slope;
         out[(((long long)bi * oh + oy) * ow + ox) * 16 + j] = v;

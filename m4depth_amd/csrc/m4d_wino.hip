@@ -31,10 +31,7 @@ struct WinoArgs {
   const float* x; const float* wu; const float* bias; float* out;
   int b, h, w, Cin, Cout, CoutPad, n_chunks, tiles_x, tiles_y;
   float slope;
-  unsigned long long* stamps;   // profiling only (m4d_wino_set_stamps): per workgroup, per chunk, 5 cycle counters of wave 0
-  int ablate;      // profiling only: 1 = weights loaded once, 2 = no MFMAs, 4 = no input transform, 8 = no epilogue.  Every host path
-                   // passes 0 (the environment switch that set it is retired); the field and its branches stay until a measured
-                   // change, because removing them changes the code of the hot kernels
+  M4D_STAMP(unsigned long long* stamps;)   // m4d_wino_set_stamps (kernel 4): per workgroup, per chunk, 5 cycle counters of wave 0
 };
 
 constexpr int kTW = 16, kTH = 8;                 // output tile (pixels)
@@ -64,8 +61,7 @@ conv3x3_wino_kernel(const WinoArgs a) {
     if ((n_tiles & 7) == 0) {
       const int xcd = L & 7, idx = L >> 3;
       const int tpx = n_tiles >> 3;
-      if (a.ablate & 64) { tile = xcd * tpx + idx / n_groups; ng = idx % n_groups; }
-      else { ng = idx / tpx; tile = xcd * tpx + idx % tpx; }          // an XCD walks its band once per N-group
+      ng = idx / tpx; tile = xcd * tpx + idx % tpx;                   // an XCD walks its band once per N-group
     } else {
       tile = L / n_groups;
       ng = L % n_groups;
@@ -167,21 +163,12 @@ conv3x3_wino_kernel(const WinoArgs a) {
   load_b(0, 0);
   if (n_frag > 1) load_b(1, 1);
   if (n_frag > 2) load_b(2, 2);
-  unsigned long long* st = (a.stamps != nullptr && t == 0 && blockIdx.y == 0 && blockIdx.x < 512)
-                               ? a.stamps + (long long)blockIdx.x * (5 * 40 + 2) : nullptr;
-  if (st) st[0] = __builtin_readcyclecounter();
   for (int chunk = 0; chunk < a.n_chunks; ++chunk) {
-    if (st && chunk < 40) st[2 + chunk * 5 + 0] = __builtin_readcyclecounter();
-    if (!(a.ablate & 32) || chunk == 0) commit_raw();
-    if (st && chunk < 40 && (a.ablate & 128)) st[2 + chunk * 5 + 1] = __builtin_readcyclecounter();     // variant: stamp 1 = after the commit
-    if (chunk + 1 < a.n_chunks && !(a.ablate & 16)) load_raw(chunk + 1);
-    if (st && chunk < 40 && (a.ablate & 256)) st[2 + chunk * 5 + 1] = __builtin_readcyclecounter();     // variant: stamp 1 = after the load issue
+    commit_raw();
+    if (chunk + 1 < a.n_chunks) load_raw(chunk + 1);
     __syncthreads();                               // raw visible; every wave is done with V
-    if (st && chunk < 40 && !(a.ablate & 384)) st[2 + chunk * 5 + 1] = __builtin_readcyclecounter();
-    if (!(a.ablate & 4)) transform();
-    if (st && chunk < 40) st[2 + chunk * 5 + 2] = __builtin_readcyclecounter();
+    transform();
     __syncthreads();
-    if (st && chunk < 40) st[2 + chunk * 5 + 3] = __builtin_readcyclecounter();
 #pragma unroll
     for (int pi = 0; pi < 4; ++pi) {
       const float* ap = vlane + pi * kNT32 * kRS;
@@ -192,23 +179,16 @@ conv3x3_wino_kernel(const WinoArgs a) {
       for (int nt = 0; nt < NT; ++nt) {
         const int ring = (NT * pi + nt) % 4;
         const int q = NT * (4 * chunk + pi) + nt;
-        if (q + 3 < n_frag && !(a.ablate & 1)) load_b(q + 3, (ring + 3) % 4);
+        if (q + 3 < n_frag) load_b(q + 3, (ring + 3) % 4);
         const float4 b0 = bq[ring][0], b1 = bq[ring][1];
         const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-        if (!(a.ablate & 2)) {
 #pragma unroll
-          for (int ks = 0; ks < 8; ++ks)
-            acc[pi][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks], bv[ks], acc[pi][nt], 0, 0, 0);
-        } else {
-          acc[pi][nt][0] += av[0] * bv[0];
-        }
+        for (int ks = 0; ks < 8; ++ks)
+          acc[pi][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks], bv[ks], acc[pi][nt], 0, 0, 0);
       }
     }
-    if (st && chunk < 40) st[2 + chunk * 5 + 4] = __builtin_readcyclecounter();
   }
-  if (st) st[2 + (a.n_chunks < 40 ? a.n_chunks : 40) * 5 - 1] = __builtin_readcyclecounter();
   __syncthreads();                                 // the epilogue's M buffer aliases raw / V
-  if ((a.ablate & 8) && acc[0][0][0] != 1.2345e-30f) return;
 
   // ---- output transform Y = A^T M A.  Wave w holds row i = w of the 4x4 position grid (positions 4w..4w+3 = columns
   // j = 0..3), so the column half, R[i][k] = (M A)[i][k], is done in registers; only the two R values per (tile, cout)
@@ -270,7 +250,6 @@ conv3x3_wino_kernel(const WinoArgs a) {
     }
     if (nt + 1 < NT) __syncthreads();
   }
-  if (st) st[1] = __builtin_readcyclecounter();
 }
 
 template <int NT>
@@ -393,9 +372,6 @@ conv3x3_wino2_kernel(const WinoArgs a) {
   const int n_frag = a.n_chunks * 4;
   auto load_b = [&](int q, int buf) { bq[buf] = *reinterpret_cast<const float4*>(wlane + (q >> 2) * w_chunk + (q & 3) * w_pos); };
 
-  unsigned long long* st = (a.stamps != nullptr && t == 0 && blockIdx.y == 0 && blockIdx.x < 512)
-                               ? a.stamps + (long long)blockIdx.x * (5 * 40 + 2) : nullptr;
-  if (st) st[0] = __builtin_readcyclecounter();
   // (Tried: raw halo double buffered in LDS with the commit of chunk c+1 and the loads of chunk c+2 issued inside the
   // MFMA phase of chunk c -- one phase less per chunk on paper, 5 % slower measured: hipcc places the commit's wait and
   // the address arithmetic in front of the MFMAs instead of between them.)
@@ -408,15 +384,11 @@ conv3x3_wino2_kernel(const WinoArgs a) {
     for (int cc = 0; cc < 2; ++cc) {               // two chunks per iteration: the ring index (4 * chunk + pi) % 8 is static
       const int chunk = chunk0 + cc;
       if (chunk < a.n_chunks) {
-        if (st && chunk < 40) st[2 + chunk * 5 + 0] = __builtin_readcyclecounter();
         commit_raw();
         if (chunk + 1 < a.n_chunks) load_raw(chunk + 1);
         __syncthreads();                           // raw visible; every wave is done with V
-        if (st && chunk < 40) st[2 + chunk * 5 + 1] = __builtin_readcyclecounter();
         transform();
-        if (st && chunk < 40) st[2 + chunk * 5 + 2] = __builtin_readcyclecounter();
         __syncthreads();
-        if (st && chunk < 40) st[2 + chunk * 5 + 3] = __builtin_readcyclecounter();
         // A fragments are read one position ahead of the MFMAs that use them (the LDS round trip otherwise sits in front
         // of every 8-MFMA group), and the weight prefetch is unconditional (index clamped): no branch inside the loop.
         float4 af[2][2];
@@ -442,7 +414,6 @@ conv3x3_wino2_kernel(const WinoArgs a) {
               acc[pi][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ks], bv[ks], acc[pi][mt], 0, 0, 0);
           }
         }
-        if (st && chunk < 40) st[2 + chunk * 5 + 4] = __builtin_readcyclecounter();
       }
     }
   }
@@ -506,7 +477,6 @@ conv3x3_wino2_kernel(const WinoArgs a) {
     }
     if (mt == 0) __syncthreads();
   }
-  if (st) st[1] = __builtin_readcyclecounter();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -668,9 +638,9 @@ conv3x3_wino4_kernel(const WinoArgs a) {
   };
 
   // phase stamps (m4d_wino_set_stamps): thread 0 of the first 512 workgroups
-  unsigned long long* st = (STAMPS && a.stamps != nullptr && t == 0 && blockIdx.y == 0 && blockIdx.x < 512)
-                               ? a.stamps + (long long)blockIdx.x * (5 * 40 + 2) : nullptr;
-  if (STAMPS && st) st[0] = __builtin_readcyclecounter();
+  M4D_STAMP(unsigned long long* st = (STAMPS && a.stamps != nullptr && t == 0 && blockIdx.y == 0 && blockIdx.x < 512)
+                                         ? a.stamps + (long long)blockIdx.x * (5 * 40 + 2) : nullptr;)
+  M4D_STAMP(if (STAMPS && st) st[0] = __builtin_readcyclecounter();)
   // ---- prologue: raw(0) -> V(0), raw(1) committed, raw(2) in registers
   load_raw(0);
 #pragma unroll
@@ -693,7 +663,7 @@ conv3x3_wino4_kernel(const WinoArgs a) {
         const float* raw_next = raw + (cc ^ 1) * kRawF;    // raw(chunk + 1), committed during the previous phase
         float* raw_free = raw + cc * kRawF;                // raw(chunk) was transformed during the previous phase
         float* v_next = V + (cc ^ 1) * kVF;
-        if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 0] = __builtin_readcyclecounter();
+        M4D_STAMP(if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 0] = __builtin_readcyclecounter();)
         float4 af[2][2];
         af[0][0] = *reinterpret_cast<const float4*>(vlane);
         af[0][1] = *reinterpret_cast<const float4*>(vlane + 32 * kRS2);
@@ -711,12 +681,12 @@ conv3x3_wino4_kernel(const WinoArgs a) {
           // which otherwise run this stream in lockstep -- slower.)
           if (pi == 0) read_raw(raw_next);
           if (pi == 2) {
-            if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 1] = __builtin_readcyclecounter();
+            M4D_STAMP(if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 1] = __builtin_readcyclecounter();)
             transform_write(v_next);
-            if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 2] = __builtin_readcyclecounter();
+            M4D_STAMP(if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 2] = __builtin_readcyclecounter();)
           }
           if (pi == 3) {
-            if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 3] = __builtin_readcyclecounter();
+            M4D_STAMP(if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 3] = __builtin_readcyclecounter();)
             commit_raw(raw_free);
             load_raw(min(chunk + 3, last));
           }
@@ -733,12 +703,12 @@ conv3x3_wino4_kernel(const WinoArgs a) {
             }
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 4] = __builtin_readcyclecounter();
+        M4D_STAMP(if (STAMPS && st && chunk < 40) st[2 + chunk * 5 + 4] = __builtin_readcyclecounter();)
         __syncthreads();
       }
     }
   }
-  if (STAMPS && st) st[1] = __builtin_readcyclecounter();
+  M4D_STAMP(if (STAMPS && st) st[1] = __builtin_readcyclecounter();)
   // every wave is past the barrier that ends the last phase: raw / V are free, the epilogue buffer aliases them
 
   // ---- output transform: rows of A^T (M A) through LDS per (N-tile, M-tile), then one 2x2-output item x 4 couts per thread
@@ -803,11 +773,13 @@ conv3x3_wino4_kernel(const WinoArgs a) {
       }
     }
   }
-  if (STAMPS && st) st[2 + 5 * 40 - 1] = __builtin_readcyclecounter();      // end of the epilogue (slot of chunk 39, never a real chunk here)
+  M4D_STAMP(if (STAMPS && st) st[2 + 5 * 40 - 1] = __builtin_readcyclecounter();)      // end of the epilogue (slot of chunk 39, never a real chunk here)
 }
 
+#if M4D_EXPERIMENTS
 static unsigned long long* g_wino_stamps = nullptr;
 extern "C" void m4d_wino_set_stamps(unsigned long long* device_buffer) { g_wino_stamps = device_buffer; }
+#endif
 
 extern "C" int m4d_conv3x3_wino_bias_act(const float* x, const float* wu, const float* bias, int b, int h, int w,
                                          int Cin, int Cout, int CoutPad, float slope, float* out, void* stream) {
@@ -818,7 +790,6 @@ extern "C" int m4d_conv3x3_wino_bias_act(const float* x, const float* wu, const 
   a.x = x; a.wu = wu; a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout;
   a.CoutPad = CoutPad; a.n_chunks = (Cin + kKC - 1) / kKC; a.slope = slope;
   a.tiles_x = (w + kTW - 1) / kTW; a.tiles_y = (h + kTH - 1) / kTH;
-  a.ablate = 0; a.stamps = g_wino_stamps;
 
   hipStream_t s = (hipStream_t)stream;
   if ((CoutPad / 32) % 2 == 0) launch_wino<2>(a, s);
@@ -835,7 +806,7 @@ extern "C" int m4d_conv3x3_wino2_bias_act(const float* x, const float* wu8, cons
   a.x = x; a.wu = wu8; a.bias = bias; a.out = out; a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout;
   a.CoutPad = CoutPad; a.n_chunks = (Cin + kC2 - 1) / kC2; a.slope = slope;
   a.tiles_x = (w + kT2 - 1) / kT2; a.tiles_y = (h + kT2 - 1) / kT2;
-  a.ablate = 0; a.stamps = g_wino_stamps;
+  M4D_STAMP(a.stamps = g_wino_stamps;)
   constexpr size_t lds = (size_t)(kHP2 * kRS2 + 16 * kNT64 * kRS2) * sizeof(float);     // 15.2 + 48 KB
   M4D_LDS_OPT_IN(&conv3x3_wino2_kernel);           // more than 64 KB of dynamic LDS needs the opt-in
   const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * (CoutPad / 32)), (unsigned)b);
@@ -848,11 +819,14 @@ extern "C" int m4d_conv3x3_wino2_bias_act(const float* x, const float* wu8, cons
   if (variant == 4 && CoutPad % 64 == 0 && Cin >= 32 && Cin % 8 == 0 && (long long)a.tiles_x * a.tiles_y * (CoutPad / 64) * b >= min_wg4) {
     constexpr size_t lds4 = (size_t)(4 * 4 * 2 * 32 * 36) * sizeof(float);              // epilogue staging 147 KB (K loop: 126 KB)
     static_assert(lds4 >= (size_t)(2 * kRawF + 2 * kVF) * sizeof(float), "epilogue staging must cover the K-loop buffers");
-    if (a.stamps) M4D_LDS_OPT_IN(&conv3x3_wino4_kernel<true>);
-    else M4D_LDS_OPT_IN(&conv3x3_wino4_kernel<false>);
     const dim3 grid4((unsigned)(a.tiles_x * a.tiles_y * (CoutPad / 64)), (unsigned)b);
-    if (a.stamps) m4d_launch(conv3x3_wino4_kernel<true>, grid4, dim3(512), lds4, (hipStream_t)stream, a);
-    else m4d_launch(conv3x3_wino4_kernel<false>, grid4, dim3(512), lds4, (hipStream_t)stream, a);
+    M4D_STAMP(if (a.stamps) {
+      M4D_LDS_OPT_IN(&conv3x3_wino4_kernel<true>);
+      m4d_launch(conv3x3_wino4_kernel<true>, grid4, dim3(512), lds4, (hipStream_t)stream, a);
+      return M4D_LAUNCH_RESULT();
+    })
+    M4D_LDS_OPT_IN(&conv3x3_wino4_kernel<false>);
+    m4d_launch(conv3x3_wino4_kernel<false>, grid4, dim3(512), lds4, (hipStream_t)stream, a);
     return M4D_LAUNCH_RESULT();
   }
   m4d_launch(conv3x3_wino2_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);

@@ -36,10 +36,6 @@
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
 
-#ifndef M4D_W6_ABL
-#define M4D_W6_ABL 0       // timing ablations of the K loop (wrong results; tools/w6_ablate.sh): 1 no barrier, 2 no fragment DMA,
-#endif                     // 4 no raw-halo DMA, 8 no fragment LDS reads, 16 no A-operand generation, 32 no DMA waits
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -51,8 +47,8 @@ struct Wino6Args {
   const float* x; const unsigned char* wu; const float* bias; float* out;
   int b, h, w, Cin, Cout, CoutPad, n_chunks, tiles_x, tiles_y;
   float slope;
-  unsigned long long* stamps;   // profiling only (m4d_wino6_set_stamps, tools/wino6_phases.py): 64 workgroups x 1280 words
-  int phases;                   // power of two <= 32
+  M4D_STAMP(unsigned long long* stamps;)   // m4d_wino6_set_stamps, tools/wino6_phases.py: 64 workgroups x 1280 words
+  alignas(16) int phases;       // power of two <= 32.  (alignas: one layout with and without `stamps`, so the kernel's code is the same in both flavours)
   int stagger;                  // > 0: the first-round workgroups start up to this many 100-MHz ticks apart (see the launcher)
 };
 
@@ -235,17 +231,19 @@ conv3x3_wino6_kernel(const Wino6Args a) {
   auto frag = [&](int slot, int nt, int part) {
     return *reinterpret_cast<const bf16x8*>(bring_p + slot * 6144 + (nt * 3 + part) * 1024 + bl);
   };
-  auto frag_l = [&](bf16x8& dst, int slot, int nt, int part) { if (!(M4D_W6_ABL & 8)) dst = frag(slot, nt, part); };
-  auto gen_l = [&](int c, int e, u32x4 (&A)[3]) { if (!(M4D_W6_ABL & 16)) gen_pair(c, e, A); };
 #define M4D_W6_WAIT(nn) asm volatile("s_waitcnt vmcnt(" #nn ") lgkmcnt(0)" ::: "memory")
 
+  // the K loop generates its operands through this one call site of gen_pair: with gen_pair named at each of its 14 places hipcc
+  // allocates the kernel's registers differently (same instructions, ~270 of them on other registers); every measurement of
+  // this kernel was made with the allocation below
+  auto gen_next = [&](int c, int e, u32x4 (&A)[3]) { gen_pair(c, e, A); };
   f32x16 acc[4][2];                                // (never zeroed: the first chunk multiplies onto the constant 0)
 
-  // stamps (profiling build only): lane 0 of every wave of the first 64 workgroups; per workgroup 1280 words: per wave 32
+  // stamps (experiments build only): lane 0 of every wave of the first 64 workgroups; per workgroup 1280 words: per wave 32
   // positions x (after barrier, -, before wait, after wait), then at 1024 the header of wave 0 (start, end of K loop, end)
-  unsigned long long* st = (STAMPS && a.stamps != nullptr && lane == 0 && blockIdx.y == 0 && blockIdx.x < 64)
-                               ? a.stamps + (long long)blockIdx.x * 1280 + wv * 128 : nullptr;
-  if (STAMPS && st && wv == 0) st[1024 + 0] = __builtin_readcyclecounter();
+  M4D_STAMP(unsigned long long* st = (STAMPS && a.stamps != nullptr && lane == 0 && blockIdx.y == 0 && blockIdx.x < 64)
+                                         ? a.stamps + (long long)blockIdx.x * 1280 + wv * 128 : nullptr;)
+  M4D_STAMP(if (STAMPS && st && wv == 0) st[1024 + 0] = __builtin_readcyclecounter();)
 
   // ---- prologue: raw(0), B(0), B(1) | B(2), raw(1), B(3) by DMA in the order the K loop's vmcnt counts
   // assume: every end-of-position wait of the K loop is vmcnt(4 + 4) = "this position's and the previous position's DMAs may
@@ -309,20 +307,20 @@ conv3x3_wino6_kernel(const Wino6Args a) {
   // soon as the part's last MFMA is issued (lo after block 0, mid after block 1); the hi part, needed until the end, is
   // double buffered.
 #define M4D_W6_BLOCK0(c, cn, next_slot, valu, NEXT)                                                                    \
-  if (NEXT) { frag_l(B0[((c) & 1) ^ 1][0], next_slot, 0, 0); if (NTL == 2) frag_l(B0[((c) & 1) ^ 1][1], next_slot, 1, 0); \
-              gen_l(cn, 0, A[((c) & 1) ^ 1]); gen_l(cn, 1, A[((c) & 1) ^ 1]); }                                          \
+  if (NEXT) { B0[((c) & 1) ^ 1][0] = frag(next_slot, 0, 0); if (NTL == 2) B0[((c) & 1) ^ 1][1] = frag(next_slot, 1, 0); \
+              gen_next(cn, 0, A[((c) & 1) ^ 1]); gen_next(cn, 1, A[((c) & 1) ^ 1]); }                                  \
   M4D_W6_MFMA0(c, 0, B2) M4D_W6_MFMA(c, 2, B0[(c) & 1])                                                                \
-  if (NEXT) { asm volatile("" : "+v"(A[((c) & 1) ^ 1][0][0]), "+v"(A[((c) & 1) ^ 1][0][1])); M4D_W6_PIPE(valu) }         \
+  if (NEXT) { asm volatile("" : "+v"(A[((c) & 1) ^ 1][0][0]), "+v"(A[((c) & 1) ^ 1][0][1])); M4D_W6_PIPE(valu) }       \
   __builtin_amdgcn_sched_barrier(0);
 #define M4D_W6_BLOCK1(c, cn, next_slot, valu, NEXT)                                                                    \
-  if (NEXT) { frag_l(B2[0], next_slot, 0, 2); if (NTL == 2) frag_l(B2[1], next_slot, 1, 2);                              \
-              gen_l(cn, 2, A[((c) & 1) ^ 1]); }                                                                          \
+  if (NEXT) { B2[0] = frag(next_slot, 0, 2); if (NTL == 2) B2[1] = frag(next_slot, 1, 2);                              \
+              gen_next(cn, 2, A[((c) & 1) ^ 1]); }                                                                     \
   M4D_W6_MFMA(c, 1, B1) M4D_W6_MFMA(c, 0, B1)                                                                          \
   if (NEXT) { asm volatile("" : "+v"(A[((c) & 1) ^ 1][0][2])); M4D_W6_PIPE(valu) }                                     \
   __builtin_amdgcn_sched_barrier(0);
 #define M4D_W6_BLOCK2(c, cn, next_slot, valu, NEXT)                                                                    \
-  if (NEXT) { frag_l(B1[0], next_slot, 0, 1); if (NTL == 2) frag_l(B1[1], next_slot, 1, 1);                              \
-              gen_l(cn, 3, A[((c) & 1) ^ 1]); }                                                                          \
+  if (NEXT) { B1[0] = frag(next_slot, 0, 1); if (NTL == 2) B1[1] = frag(next_slot, 1, 1);                              \
+              gen_next(cn, 3, A[((c) & 1) ^ 1]); }                                                                     \
   M4D_W6_MFMA(c, 1, B0[(c) & 1]) M4D_W6_MFMA(c, 0, B0[(c) & 1])                                                        \
   if (NEXT) { pin_a(A[((c) & 1) ^ 1]); M4D_W6_PIPE(valu) }                                                             \
   __builtin_amdgcn_sched_barrier(0);
@@ -332,12 +330,9 @@ conv3x3_wino6_kernel(const Wino6Args a) {
   // DMAs (one raw piece at columns 0-2, this wave's half of B four positions ahead); the MFMAs of this position interleaved
   // with the A operands of the next; then vmcnt(N) leaves exactly the DMAs of this and the previous position in flight
   // (N = 6 + their raw pieces), i.e. everything the barrier of the next position publishes has landed.
-  int stq = 0;
-#define M4D_W6_STAMP(k) if (STAMPS && st && stq < 32) st[stq * 4 + (k)] = __builtin_readcyclecounter();
-#define W6L_BARRIER() do { if (!(M4D_W6_ABL & 1)) __builtin_amdgcn_s_barrier(); } while (0)
-#define W6L_RAW(...) do { if (!(M4D_W6_ABL & 4)) raw_dma(__VA_ARGS__); } while (0)
-#define W6L_BDMA(...) do { if (!(M4D_W6_ABL & 2)) b_dma(__VA_ARGS__); } while (0)
-#define W6L_WAIT(nn) do { if (!(M4D_W6_ABL & 32)) { M4D_W6_WAIT(nn); } } while (0)
+  M4D_STAMP(int stq = 0;)
+#define M4D_W6_STAMP(k) M4D_STAMP(if (STAMPS && st && stq < 32) st[stq * 4 + (k)] = __builtin_readcyclecounter();)
+#define M4D_W6_STAMP_NEXT() M4D_STAMP(if (STAMPS) ++stq;)
   auto k_loop = [&](auto ntl_tag) __attribute__((always_inline)) {
   constexpr int NTL = decltype(ntl_tag)::value;
   asm volatile("" ::: "memory");                   // (nothing below is hoisted above the branch that picks the instantiation)
@@ -363,56 +358,56 @@ conv3x3_wino6_kernel(const Wino6Args a) {
     const int rnext_c = min(chunk + 2, last);
     const float4* rnext = raw + ((chunk + 1) & 1) * kRawSlots;
     // position 0: A(1) from t1, t2
-    W6L_BARRIER();
+    __builtin_amdgcn_s_barrier();
     M4D_W6_STAMP(0)
     M4D_W6_BLOCK0(0, 1, 1, 7, true)
-    if (!LAST) W6L_RAW(rnext_c, chunk & 1, 0);
+    if (!LAST) raw_dma(rnext_c, chunk & 1, 0);
     M4D_W6_BLOCK1(0, 1, 1, 4, true)
-    if (!LAST) W6L_BDMA(wn, 0);
+    if (!LAST) b_dma(wn, 0);
     M4D_W6_BLOCK2(0, 1, 1, 4, true)
     M4D_W6_STAMP(2)
-    if (!LAST) W6L_WAIT(8);                                                       // this position's DMAs + the previous position's
-    else W6L_WAIT(4);
+    if (!LAST) M4D_W6_WAIT(8);                                                       // this position's DMAs + the previous position's
+    else M4D_W6_WAIT(4);
     M4D_W6_STAMP(3)
-    if (STAMPS) ++stq;
+    M4D_W6_STAMP_NEXT()
     // position 1: A(2) from t2, t1
-    W6L_BARRIER();
+    __builtin_amdgcn_s_barrier();
     M4D_W6_STAMP(0)
     M4D_W6_BLOCK0(1, 2, 2, 7, true)
-    if (!LAST) W6L_RAW(rnext_c, chunk & 1, 1);
+    if (!LAST) raw_dma(rnext_c, chunk & 1, 1);
     M4D_W6_BLOCK1(1, 2, 2, 4, true)
-    if (!LAST) W6L_BDMA(wn + w_pos, 1);
+    if (!LAST) b_dma(wn + w_pos, 1);
     M4D_W6_BLOCK2(1, 2, 2, 4, true)
     M4D_W6_STAMP(2)
-    if (!LAST) W6L_WAIT(8);
-    else W6L_WAIT(0);
+    if (!LAST) M4D_W6_WAIT(8);
+    else M4D_W6_WAIT(0);
     M4D_W6_STAMP(3)
-    if (STAMPS) ++stq;
+    M4D_W6_STAMP_NEXT()
     // position 2: A(3) from t1, t3; columns 0, 2 of t(chunk + 1)
-    W6L_BARRIER();
+    __builtin_amdgcn_s_barrier();
     M4D_W6_STAMP(0)
     M4D_W6_BLOCK0(2, 3, 3, 7, true)
-    if (!LAST) { W6L_RAW(rnext_c, chunk & 1, 2); read_t(rnext, 0); }
+    if (!LAST) { raw_dma(rnext_c, chunk & 1, 2); read_t(rnext, 0); }
     M4D_W6_BLOCK1(2, 3, 3, 6, true)
-    if (!LAST) { W6L_BDMA(wn + 2 * w_pos, 2); pin_t(0); }
+    if (!LAST) { b_dma(wn + 2 * w_pos, 2); pin_t(0); }
     M4D_W6_BLOCK2(2, 3, 3, 6, true)
     M4D_W6_STAMP(2)
-    if (!LAST) W6L_WAIT(8);
+    if (!LAST) M4D_W6_WAIT(8);
     else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       // (the fragment reads for position 3)
     M4D_W6_STAMP(3)
-    if (STAMPS) ++stq;
+    M4D_W6_STAMP_NEXT()
     // position 3: columns 1, 3 of t(chunk + 1) first (A(chunk + 1, 0) = t0 - t2 needs column ... 0 and 2 only)
-    W6L_BARRIER();
+    __builtin_amdgcn_s_barrier();
     M4D_W6_STAMP(0)
     M4D_W6_BLOCK0(3, 0, 0, 7, !LAST)
-    if (!LAST) { W6L_RAW(rnext_c, chunk & 1, 3); read_t(rnext, 1); }
+    if (!LAST) { raw_dma(rnext_c, chunk & 1, 3); read_t(rnext, 1); }
     M4D_W6_BLOCK1(3, 0, 0, 6, !LAST)
-    if (!LAST) { W6L_BDMA(wn + 3 * w_pos, 3); pin_t(1); }
+    if (!LAST) { b_dma(wn + 3 * w_pos, 3); pin_t(1); }
     M4D_W6_BLOCK2(3, 0, 0, 6, !LAST)
     M4D_W6_STAMP(2)
-    if (!LAST) W6L_WAIT(8);
+    if (!LAST) M4D_W6_WAIT(8);
     M4D_W6_STAMP(3)
-    if (STAMPS) ++stq;
+    M4D_W6_STAMP_NEXT()
     if (!LAST) wc = wn;
   };
   chunk_body(0, m4d_int<1>{}, m4d_int<0>{});     // (a single-chunk layer, Cin = 16, ends here: with its surplus fetches, as before)
@@ -429,9 +424,10 @@ conv3x3_wino6_kernel(const Wino6Args a) {
 #undef M4D_W6_BLOCK2
 #undef M4D_W6_PIPE
 #undef M4D_W6_STAMP
+#undef M4D_W6_STAMP_NEXT
   M4D_W6_WAIT(0);                                  // no DMA may land in LDS once the epilogue reuses it
 #undef M4D_W6_WAIT
-  if (STAMPS && st && wv == 0) st[1024 + 1] = __builtin_readcyclecounter();
+  M4D_STAMP(if (STAMPS && st && wv == 0) st[1024 + 1] = __builtin_readcyclecounter();)
   __syncthreads();                                 // every wave is done with raw / the rings: the epilogue buffer aliases them
 
   // ---- output transform: rows of A^T (M A) through LDS per (N-tile, M-tile), then one 2x2-output item x 4 couts per thread.
@@ -515,7 +511,7 @@ conv3x3_wino6_kernel(const Wino6Args a) {
           }
     }
   }
-  if (STAMPS && st && wv == 0) st[1024 + 2] = __builtin_readcyclecounter();
+  M4D_STAMP(if (STAMPS && st && wv == 0) st[1024 + 2] = __builtin_readcyclecounter();)
 }
 
 // Grids of at least this many (tile, 64-cout) units run on the persistent kernel (m4d_wino6p.hip): 8 per CU of the 256.  Measured
@@ -525,15 +521,13 @@ conv3x3_wino6_kernel(const Wino6Args a) {
 // interleaved runs: static unit ranges against the dispatcher's dynamic placement beside other frames' kernels), the batch-32
 // step does (+3.6 %, 1988 -> 2060 frames/s).
 constexpr long long kPersistentMinUnits = 2048;
-unsigned long long* g_wino6_stamps = nullptr;       // profiling hook (m4d_wino6_set_stamps): process-wide, NULL = off
 #if M4D_EXPERIMENTS
+unsigned long long* g_wino6_stamps = nullptr;       // m4d_wino6_set_stamps: process-wide, NULL = off
 int g_wino6_half_max_wg = 0;                       // grids of at most this many workgroups take the half-tile kernel under variant 0 (default: none)
 int g_wino6_variant = 0;                           // 0 / 1 = this file's kernel, 2 = the wide kernel (m4d_wino6w.hip), 3 = the half-tile kernel
 #endif
 
 }  // namespace
-
-extern "C" void m4d_wino6_set_stamps(unsigned long long* device_buffer) { g_wino6_stamps = device_buffer; }
 
 // ---- staggered first round ---------------------------------------------------------------------------------------------------
 // A launch of this kernel puts ONE workgroup on every CU (154 KB of LDS) and all of them take the same time: the CUs free in
@@ -553,6 +547,7 @@ int m4d_wino6w_launch(const float* x, const void* wu6, const float* bias, int b,
 // m4d_wino6h.hip: 16x8 pixels x 64 couts per workgroup (half the tile: twice the workgroups) for small grids
 int m4d_wino6h_launch(const float* x, const void* wu6, const float* bias, int b, int h, int w, int Cin, int Cout, int CoutPad,
                       float slope, float* out, void* stream);
+extern "C" void m4d_wino6_set_stamps(unsigned long long* device_buffer) { g_wino6_stamps = device_buffer; }
 extern "C" void m4d_wino6_set_variant(int variant) { g_wino6_variant = variant; }
 extern "C" void m4d_wino6_set_half_tile_max_workgroups(int max_wg) { g_wino6_half_max_wg = max_wg; }
 #endif
@@ -591,7 +586,7 @@ extern "C" int m4d_conv3x3_wino6_bias_act_ks(const float* x, const void* wu6, co
     // file's kernel (a cheaper epilogue, and the dispatcher places its workgroups dynamically beside other frames' kernels)
     const long long units = (long long)b * ((w + kT - 1) / kT) * ((h + kT - 1) / kT) * (CoutPad / 64);
     const bool persistent = kernel == 2 || units_per_wg > 0 || (kernel == 0 && Cin >= 32 && units >= m4d_wino6_persistent_min_units());
-    if (persistent && g_wino6_stamps == nullptr)
+    if (persistent M4D_STAMP(&& g_wino6_stamps == nullptr))
       return m4d_wino6p_launch(x, wu6, bias, b, h, w, Cin, Cout, CoutPad, slope, out, units_per_wg,
                                units_per_wg > 0 ? stagger_us : 0, stagger_phases, stream);
   }
@@ -610,7 +605,7 @@ extern "C" int m4d_conv3x3_wino6_bias_act_ks(const float* x, const void* wu6, co
   a.x = x; a.wu = reinterpret_cast<const unsigned char*>(wu6); a.bias = bias; a.out = out;
   a.b = b; a.h = h; a.w = w; a.Cin = Cin; a.Cout = Cout; a.CoutPad = CoutPad; a.n_chunks = Cin / 16; a.slope = slope;
   a.tiles_x = (w + kT - 1) / kT; a.tiles_y = (h + kT - 1) / kT;
-  a.stamps = g_wino6_stamps;
+  M4D_STAMP(a.stamps = g_wino6_stamps;)
   a.stagger = stagger_us * 100;                    // 100-MHz ticks (wall_clock64); the one-workgroup-per-unit kernel only
   a.phases = stagger_us > 0 ? stagger_phases : 1;
   constexpr size_t lds_epi = (size_t)(4 * 4 * 2 * 32 * 36 + 32) * sizeof(float);        // epilogue staging 147 KB (+ N-tile 1's skew)
@@ -619,9 +614,12 @@ extern "C" int m4d_conv3x3_wino6_bias_act_ks(const float* x, const void* wu6, co
   static_assert(lds <= 160 * 1024, "LDS budget of one CU");
   const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * (CoutPad / 64)), (unsigned)b);
   // more than 64 KB of dynamic LDS needs the opt-in, per kernel
-  if (a.stamps) M4D_LDS_OPT_IN(&conv3x3_wino6_kernel<true>);
-  else M4D_LDS_OPT_IN(&conv3x3_wino6_kernel<false>);
-  if (a.stamps) m4d_launch(conv3x3_wino6_kernel<true>, grid, dim3(512), lds, (hipStream_t)stream, a);
-  else m4d_launch(conv3x3_wino6_kernel<false>, grid, dim3(512), lds, (hipStream_t)stream, a);
+  M4D_STAMP(if (a.stamps) {
+    M4D_LDS_OPT_IN(&conv3x3_wino6_kernel<true>);
+    m4d_launch(conv3x3_wino6_kernel<true>, grid, dim3(512), lds, (hipStream_t)stream, a);
+    return M4D_LAUNCH_RESULT();
+  })
+  M4D_LDS_OPT_IN(&conv3x3_wino6_kernel<false>);
+  m4d_launch(conv3x3_wino6_kernel<false>, grid, dim3(512), lds, (hipStream_t)stream, a);
   return M4D_LAUNCH_RESULT();
 }

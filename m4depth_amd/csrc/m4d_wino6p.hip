@@ -33,10 +33,6 @@
 #include "m4d_common.h"
 #include "../../include/m4depth_hip.h"
 
-#ifndef M4D_W6P_ABL
-#define M4D_W6P_ABL 0      // timing ablations (wrong results; tools/w6p_ablate.sh): 1 no epilogue passes at all, 2 no global stores,
-#endif                     // 8 no DMA waits in the first two positions of a unit (what the epilogue's stores cost through vmcnt)
-
 namespace {
 
 typedef float p6_f32x16 __attribute__((ext_vector_type(16)));
@@ -286,9 +282,6 @@ conv3x3_wino6p_kernel(const Wino6PArgs a) {
   if (NEXT) { pin_a(A[((c) & 1) ^ 1]); P6_PIPE(valu) }                                                                 \
   __builtin_amdgcn_sched_barrier(0);
 
-  if (M4D_W6P_ABL & 16) {                           // experiment: de-phase the CUs (their epilogue store bursts coincide otherwise)
-    for (int i = 0; i < (int)(blockIdx.x & 7); ++i) __builtin_amdgcn_s_sleep(127);
-  }
   // ---- true prologue (once per workgroup): raw(0), B(0), B(1), raw(1) | B(2), B(3) -- the state every later unit starts from
   Unit cur = decode(u0);
   set_raw_source(cur);
@@ -352,7 +345,7 @@ conv3x3_wino6p_kernel(const Wino6PArgs a) {
       P6_BLOCK1(0, 1, 1, 4, true)
       b_dma(wn, 0, voff_cur);
       P6_BLOCK2(0, 1, 1, 4, true)
-      if (!(M4D_W6P_ABL & 8) || chunk > 0) { P6_WAIT(7); }
+      P6_WAIT(7);
       // position 1: A(2) from t2, t1
       __builtin_amdgcn_s_barrier();
       P6_BLOCK0(1, 2, 2, 7, true)
@@ -360,7 +353,7 @@ conv3x3_wino6p_kernel(const Wino6PArgs a) {
       P6_BLOCK1(1, 2, 2, 4, true)
       b_dma(wn + w_pos, 1, voff_cur);
       P6_BLOCK2(1, 2, 2, 4, true)
-      if (!(M4D_W6P_ABL & 8) || chunk > 0) { P6_WAIT(8); }
+      P6_WAIT(8);
       // position 2: A(3) from t1, t3; columns 0, 2 of t(chunk + 1)
       __builtin_amdgcn_s_barrier();
       P6_BLOCK0(2, 3, 3, 7, true)
@@ -454,9 +447,7 @@ conv3x3_wino6p_kernel(const Wino6PArgs a) {
         const int tile = omt * 32 + tl;            // Winograd tile 0..63 of the workgroup (8 x 8)
         const int ox = cur.tile_x + 2 * (tile & 7) + kcol, oy = cur.tile_y + 2 * (tile >> 3);
         float* op = oimg + ((long long)oy * a.w + ox) * a.Cout + co;
-        if (M4D_W6P_ABL & 2) {
-          if (y[0][0] + y[1][1] + y[0][2] + y[1][3] == 123.456f) op[0] = 1.f;      // keeps the arithmetic alive
-        } else if (fast) {
+        if (fast) {
           // UNIFORM condition (whole tile, every cout quad of the group real, 16-byte rows) and nothing but the two 16-byte
           // stores in this arm: under a per-lane condition hipcc merged this arm with the guarded one below and stored the
           // second row as four separate dwords (the 12.8-B/clk pattern of tools/micro/store_issue_probe.hip, 4x slower)
@@ -472,14 +463,8 @@ conv3x3_wino6p_kernel(const Wino6PArgs a) {
             }
         }
       };
-      if (M4D_W6P_ABL & 1) {                                                    // keep the K loop's products alive
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt) asm volatile("" : : "v"(acc[c][nt]));
-      }
-#pragma unroll
-      for (int pass = 0; pass < ((M4D_W6P_ABL & 1) ? 0 : 4); ++pass) {
+      for (int pass = 0; pass < 4; ++pass) {
         const int kcol = pass >> 1, omt = pass & 1;
         if (mt == omt) {
 #pragma unroll
@@ -504,7 +489,7 @@ conv3x3_wino6p_kernel(const Wino6PArgs a) {
         b_dma(wnext + 2 * w_pos, 2, voff_nxt);
         b_dma(wnext + 3 * w_pos, 3, voff_nxt);
       }
-      if (!(M4D_W6P_ABL & 1)) finish(3);
+      finish(3);
     }
     };
     if (half) unit_body(m4d_int<1>{}); else unit_body(m4d_int<2>{});

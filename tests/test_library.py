@@ -32,6 +32,12 @@ def test_header_symbols_exported():
     assert _lib.has_experiments == ("+experiments" in _lib.build_info())
     for s in exp:
         assert hasattr(raw, s) == _lib.has_experiments, f"{s}: experiments symbol {'missing from' if _lib.has_experiments else 'present in'} this build"
+    # process-wide setters: the product header has ONE, the DSCV kernel selector; the profiling hooks (stamp buffers, the DSCV
+    # fallback counter) are declared by the experiments header only, and the ablation mask is gone from both
+    assert [s for s in syms if "_set_" in s] == ["m4d_dscv_set_variant"]
+    assert {"m4d_wino_set_stamps", "m4d_wino6_set_stamps", "m4d_front_set_stamps", "m4d_dscv_set_stamps",
+            "m4d_dscv_set_fallback_counter"} <= set(exp)
+    assert "m4d_dscv_set_ablation" not in syms + exp
 
 
 MINI_HEADER = """\

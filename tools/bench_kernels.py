@@ -1,6 +1,8 @@
 """Stand-alone timing of the hand-written cost-volume kernels on the tensors of a real
 model step (level ``--level`` of the 384x1280 pyramid, batch ``--batch``), for quick
-iteration and for rocprofv3 --pmc passes (many identical launches, nothing else)."""
+iteration and for rocprofv3 --pmc passes (many identical launches, nothing else).  ``--hooks`` adds
+the phase cycle stamps and the DSCV fallback counter, which only the experiments build of the
+library has (include/m4depth_hip_experiments.h)."""
 import argparse
 import ctypes
 import os
@@ -14,7 +16,7 @@ sys.path.insert(0, ROOT)
 os.environ["M4D_FUSED_FRONT"] = "0"                          # the model step below must leave the separate kernels' inputs behind
 import m4depth_amd as M                                     # noqa: E402
 from m4depth_amd import synthetic as S                      # noqa: E402
-from m4depth_amd._lib import lib, dptr, stream_ptr          # noqa: E402
+from m4depth_amd._lib import lib, dptr, stream_ptr, require_experiments   # noqa: E402
 
 
 def main():
@@ -23,13 +25,15 @@ def main():
     ap.add_argument("--level", type=int, default=1)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--which", default="dscv,sncv")
-    ap.add_argument("--ablate", type=int, default=0)
+    ap.add_argument("--hooks", action="store_true", help="phase stamps of the front and of dscv[lds-hyp*], fallback counter of the DSCV window kernels")
     ap.add_argument("--smooth", action="store_true", help="replace the parallax maps by smooth fields (coherent gathers)")
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--dscv-range", type=int, default=4)
     ap.add_argument("--sncv-range", type=int, default=3, help="with --height 768 --width 2560 --dscv-range 6 --sncv-range 6: BASELINE configs[4]")
     args = ap.parse_args()
+    if args.hooks:
+        require_experiments("tools/bench_kernels.py --hooks (m4d_front_set_stamps, m4d_dscv_set_stamps, m4d_dscv_set_fallback_counter)")
     dev = torch.device("cuda:0")
     H, Wd, L = args.height, args.width, 6
     RD, RS = args.dscv_range, args.sncv_range
@@ -86,7 +90,6 @@ def main():
                                      dptr(rot), rot.shape[1], dptr(tr), dptr(cf), dptr(cc), b, h, w, C, k, RD, RS, 0,
                                      dptr(f_front), F_st, 0.25, stream_ptr())
 
-    lib.m4d_dscv_set_ablation(args.ablate)
     counter = torch.zeros(1, dtype=torch.int32, device=dev)
     variants = [("dscv[wave]", run_dscv, 1), ("dscv[lds-window]", run_dscv, 2), ("dscv[lds-hyp]", run_dscv, 3), ("dscv[lds-hyp9]", run_dscv, 4),
                 ("sncv", run_sncv, None), ("front", run_front, None)]
@@ -96,6 +99,7 @@ def main():
             continue
         if variant is not None:
             lib.m4d_dscv_set_variant(variant)
+        if variant is not None and args.hooks:
             lib.m4d_dscv_set_fallback_counter(ctypes.c_void_p(counter.data_ptr()))
             counter.zero_()
             fn()
@@ -115,7 +119,7 @@ def main():
                     print(f"  {name}: cycles/workgroup box {d[0]:.0f}  stage {d[1]:.0f}  gather+compute {d[2]:.0f}  | window px mean "
                           f"{float(st[:, 4].mean()):.0f} max {float(st[:, 4].max()):.0f}, width mean {float(st[:, 5].mean()):.1f}; "
                           f"kernel span {(float(st[:, 3].max()) - float(st[:, 0].min())) / 1e3:.0f} kcycles over {len(st)} workgroups", flush=True)
-        if name == "front":
+        if name == "front" and args.hooks:
             tiles = max(4096, b * h * w // 32 + 64)       # 8 stamps per WORKGROUP: the smallest front tile is 8x4 pixels (a fixed 4096 rows
                                                           # let batch-32 runs write past the buffer: a GPU memory fault under rocprofv3)
             stamps = torch.zeros((tiles, 8), dtype=torch.int64, device=dev)

@@ -3,7 +3,8 @@ import os, sys, ctypes, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from m4depth_amd import network_ops as nops
-from m4depth_amd._lib import lib
+from m4depth_amd._lib import lib, require_experiments
+require_experiments("tools/wino4_phases.py (m4d_wino_set_stamps)")
 dev = torch.device("cuda:0")
 h, w, cin, cout = 192, 640, 128, 128
 x = torch.randn(1, h, w, cin, device=dev)

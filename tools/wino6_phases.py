@@ -4,7 +4,8 @@ import os, sys, ctypes, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from m4depth_amd import network_ops as nops
-from m4depth_amd._lib import lib
+from m4depth_amd._lib import lib, require_experiments
+require_experiments("tools/wino6_phases.py (m4d_wino6_set_stamps)")
 dev = torch.device("cuda:0")
 for (h, w, cin, cout) in [(192, 640, 128, 128), (96, 320, 128, 128), (192, 640, 64, 128)]:
     x = torch.randn(1, h, w, cin, device=dev)
