@@ -937,6 +937,59 @@ int m4d_depth_cloud(const float* depth, long long depth_stride, const float* rgb
 /* int32 elements of m4d_depth_cloud's workspace (0 for a geometry it refuses). */
 long long m4d_depth_cloud_workspace_ints(int b, int h, int w, int step);
 
+/* ---- Multi-view depth check (main.py --save_cloud --cloud_views K): keep a pixel only if earlier frames confirm it (csrc/m4d_confidence.hip) ---- */
+
+/* The forward-backward reprojection check of multi-view stereo fusion (MVSNet, Yao et al. ECCV 2018; COLMAP's fusion), against
+ * up to K = views earlier frames of the sample's own trajectory, kept in a ring on the device.
+ * depth [b,h,w,1] float32, image s at depth + s * depth_stride ELEMENTS (>= h*w: read in place); cam_f, cam_c [b,2]: the
+ * sample's full-resolution camera, assumed the same for every frame since the sample's last reset; pose [b,7] float64 camera-to-
+ * world as m4d_pose_accumulate leaves it (qw qx qy qz tx ty tz), used as stored (not renormalised); reset [b] uint8 device mask
+ * (may be NULL = nobody).
+ * State: ring_depth [(K+1),b,h,w] float32 and ring_pose [(K+1),b,7] float64.  Slot `head` (0..K) is WRITTEN by this call; the
+ * slots (head - j) mod (K+1), j = 1..K, hold the frames j steps back and are only read, so the slot written is never one that
+ * is read and the launch needs no ordering between workgroups.  The host advances head by one mod K+1 after every call.
+ * age_in / age_out [b] int32, distinct buffers the host swaps after every call: the earlier frames of the sample's trajectory
+ * the ring holds.
+ *   a = (force_all || reset[s]) ? 0 : min(age_in[s], K)      (a negative age_in counts as 0)
+ *   age_out[s] = min(a + 1, K)
+ * Only the views j = 1..a are looked at: after a reset the other slots may hold another trajectory, or nothing.
+ * Per pixel (row, col) of sample s, d = depth as it comes:
+ *   d not finite or d <= 0 : n_views = 0.  Otherwise, float32 with m4d_depth_cloud's operand order:
+ *   Xc = ((((col + 0.5f) - cx) / fx) * d, (((row + 0.5f) - cy) / fy) * d, d)
+ *   and from here float64, one rounding per operation; f and c are the float32 values widened.  R(q) as get_rot_mat writes it.
+ *   View j, (qk, tk) = ring_pose of its slot, (qc, tc) = pose[s]:
+ *     Rr = R(qk)^T R(qc):  Rr[i][j] = (Rk[0][i] Rc[0][j] + Rk[1][i] Rc[1][j]) + Rk[2][i] Rc[2][j]
+ *     tr = R(qk)^T (tc - tk): D = tc - tk;  tr[i] = (Rk[0][i] D[0] + Rk[1][i] D[1]) + Rk[2][i] D[2]
+ *     X  = Rr Xc + tr:      X[i] = ((Rr[i][0] Xc.x + Rr[i][1] Xc.y) + Rr[i][2] Xc.z) + tr[i];   z = X[2]
+ *     u  = ((fx X[0]) / z + cx) - 0.5,  v = ((fy X[1]) / z + cy) - 0.5        (integer values are pixel centres)
+ *     the view TESTS the pixel when z > 0, 0 <= u <= w-1, 0 <= v <= h-1 and the four taps below are finite and > 0:
+ *       u32 = (float) u, x0 = min((int) floorf(u32), w-2), ax = u32 - (float) x0;  v32, y0, ay likewise (indices are clamped to
+ *       the map before any load);  d00, d01, d10, d11 = ring_depth[slot][s] at (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1);
+ *       float32: top = d00 + ax * (d01 - d00), bot = d10 + ax * (d11 - d10), dk = top + ay * (bot - top)
+ *     back:  Yk = ((((u + 0.5) - cx) / fx) * dk, (((v + 0.5) - cy) / fy) * dk, dk);  E = Yk - tr;
+ *            Yc = Rr^T E:   Yc[i] = (Rr[0][i] E[0] + Rr[1][i] E[1]) + Rr[2][i] E[2];  Yc[2] > 0 is required
+ *            pu = ((fx Yc[0]) / Yc[2] + cx) - 0.5,  pv = ((fy Yc[1]) / Yc[2] + cy) - 0.5
+ *     the view CONFIRMS the pixel when  (pu - col)^2 + (pv - row)^2 < (double) tol_px * (double) tol_px  and
+ *            fabs(Yc[2] - d) < (double) tol_rel * d          (no square root, no division)
+ *   n_views [b,h,w] uint8 = the number of confirming views, 0..a;
+ *   depth_f [b,h,w] float32 (may be NULL) = the bits of d where n_views >= min_views, else the quiet NaN 0x7FC00000;
+ *   ring_depth[head][s] = the bits of d, unfiltered; ring_pose[head][s] = pose[s].
+ * A NaN pose (a zero quaternion upstream) makes every comparison false: n_views = 0.  Every element of n_views, depth_f, the ring
+ * slot `head` and age_out is written and nothing else; no atomics, no zero-fill; sample s of a batch launch equals a launch on
+ * sample s alone bit for bit.  One plain launch: capturable for fixed arguments, but head and the age buffers change per frame,
+ * so export.PredictionWriter calls it eagerly.  Four pixels per thread; when h*w and depth_stride are multiples of 4, depth,
+ * ring_depth and depth_f 16-byte and n_views 4-byte aligned, they leave as one dword and 16-byte stores, else element by element
+ * with the same bits.
+ * Returns 1 without a launch for: a NULL pointer other than reset or depth_f, b outside 1..65535, h or w < 2, h*w > 2^24, views
+ * outside 1..8, head outside 0..views, min_views outside 1..views, tol_px or tol_rel not > 0 (NaN included), age_in == age_out,
+ * depth_stride < h*w, a float / int pointer off 4 bytes, pose or ring_pose off 8.  Additive entry points: ABI 6 unchanged. */
+int m4d_depth_views(const float* depth, long long depth_stride, const float* cam_f, const float* cam_c, const double* pose,
+                    const unsigned char* reset, int force_all, int b, int h, int w, int views, int head, float* ring_depth,
+                    double* ring_pose, const int* age_in, int* age_out, float tol_px, float tol_rel, int min_views,
+                    unsigned char* n_views, float* depth_f, void* stream);
+/* float32 elements of m4d_depth_views' ring_depth, (views+1) b h w; -1 for a geometry it refuses. */
+long long m4d_depth_views_ring_floats(int b, int h, int w, int views);
+
 /* ---- training summaries (main.py --mode=train --log_dir): float32 maps -> the uint8 images of a TensorBoard event -------- */
 
 /* Up to 16 float32 maps of different sizes -> uint8 images, in one launch.  src, stride, h, w, c, kind and out_offset are

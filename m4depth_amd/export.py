@@ -10,6 +10,10 @@ With ``cloud=True`` the writer also keeps one camera-to-world pose per sample on
 turns every estimate into a dense list of coloured vertices (``network_ops.depth_cloud``) and writes it as a binary PLY file
 beside the PNGs; the host never redoes the camera model or the pose chain, and never reads a vertex count before the slot's
 event has passed.
+
+With ``cloud_views=K`` a cloud keeps only the pixels that up to K earlier frames of the sample's trajectory confirm
+(``network_ops.depth_views``: a forward-backward reprojection check against a ring of the last K estimates and poses on the
+device); the depth PNG and the panels keep showing the raw estimate.
 """
 from __future__ import annotations
 
@@ -126,8 +130,25 @@ def read_cloud_ply(path):
     return raw[:, :12].copy().view(np.float32), raw[:, 12:].copy(), pose
 
 
+def read_conf_png(path, views):
+    """A ``<name>_conf.png`` of ``PredictionWriter(save_conf=True)`` as the counts it was made of: uint8 [h,w], the number of
+    earlier frames (0..``views``) that confirmed the pixel; the file holds ``count * 255 // views``."""
+    from PIL import Image
+    views = int(views)
+    if not 1 <= views <= nops.VIEWS_MAX:
+        raise ValueError(f"views: expected 1..{nops.VIEWS_MAX}, got {views}")
+    with Image.open(path) as im:
+        if im.mode != "L":
+            raise ValueError(f"{path}: not an 8-bit grey image")
+        grey = np.asarray(im, dtype=np.uint8).astype(np.int64)
+    counts = (grey * views + 254) // 255
+    if not np.array_equal(counts * 255 // views, grey):
+        raise ValueError(f"{path}: not the confirmation counts of {views} views")
+    return counts.astype(np.uint8)
+
+
 class _Slot:
-    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0):
+    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False):
         self.depth_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
         self.depth_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
         self.panels_d = self.panels_h = None
@@ -143,6 +164,10 @@ class _Slot:
             self.pose_h = torch.empty((b, 7), dtype=torch.float64).pin_memory()
             self.reset_d = torch.empty(b, dtype=torch.uint8, device=dev)
             self.reset_h = torch.empty(b, dtype=torch.uint8).pin_memory()
+        self.conf_d = self.conf_h = None
+        if conf:
+            self.conf_d = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+            self.conf_h = torch.empty((b, h, w), dtype=torch.uint8).pin_memory()
         self.event = torch.cuda.Event()
         self.pending = 0
 
@@ -161,10 +186,19 @@ class PredictionWriter:
     trajectory's first camera (``cloud_frame="world"``) or of the frame's own camera (``"camera"``); the frame's
     camera-to-world pose is in the header either way (``read_cloud_ply``).  Each slot then also owns a [b,cap,16] byte vertex
     buffer with its pinned twin, the counts and a pinned copy of the poses; the whole ``cap`` region crosses PCIe every step
-    (the count is only known on the device), the worker writes the first ``counts[s]`` vertices."""
+    (the count is only known on the device), the worker writes the first ``counts[s]`` vertices.
+
+    ``cloud_views=K`` (1..8; needs ``cloud``) filters the clouds: a pixel gives a vertex only if at least ``cloud_min_views``
+    (default min(2, K)) of the up to K earlier frames of its trajectory confirm it within ``cloud_tol`` = (pixels, relative
+    depth) -- ``network_ops.depth_views``, one more launch per submit, at full resolution whatever ``cloud_step`` is.  The
+    writer then owns the ring of the last K + 1 estimates and poses, (K+1) b h w floats.  The rule is strict: the first
+    ``cloud_min_views`` frames of every trajectory give clouds without vertices.  ``save_conf=True`` also writes
+    ``<name>_conf.png``: 8-bit grey, ``confirming views * 255 // K`` (``read_conf_png``).  ``cloud_kept`` / ``cloud_cap`` sum the
+    vertices written and the vertices a cloud could hold at most, over the frames the workers have finished."""
 
     def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
-                 encode=True, cloud=False, cloud_step=2, cloud_frame="world"):
+                 encode=True, cloud=False, cloud_step=2, cloud_frame="world", cloud_views=0, cloud_min_views=None,
+                 cloud_tol=(1.0, 0.01), save_conf=False):
         if fmt not in FORMATS:
             raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
         panels = tuple(panels)
@@ -176,7 +210,26 @@ class PredictionWriter:
             raise ValueError("slots and threads must be >= 1")
         if int(cloud_step) < 1 or cloud_frame not in CLOUD_FRAMES:
             raise ValueError(f"cloud_step must be >= 1 and cloud_frame one of {CLOUD_FRAMES}, got {cloud_step}, {cloud_frame!r}")
+        cloud_views = int(cloud_views)
+        if not 0 <= cloud_views <= nops.VIEWS_MAX:
+            raise ValueError(f"cloud_views must be 0 (off) or 1..{nops.VIEWS_MAX}, got {cloud_views}")
+        if cloud_views and not cloud:
+            raise ValueError("cloud_views needs cloud=True: the check runs on the clouds' pose chain")
+        if save_conf and not cloud_views:
+            raise ValueError("save_conf needs cloud_views >= 1")
+        if cloud_min_views is not None and not cloud_views:
+            raise ValueError("cloud_min_views needs cloud_views >= 1")
+        cloud_min_views = min(2, cloud_views) if cloud_min_views is None else int(cloud_min_views)
+        if cloud_views and not 1 <= cloud_min_views <= cloud_views:
+            raise ValueError(f"cloud_min_views must be in 1..{cloud_views}, got {cloud_min_views}")
+        cloud_tol = tuple(float(v) for v in cloud_tol)
+        if len(cloud_tol) != 2 or not (cloud_tol[0] > 0 and cloud_tol[1] > 0):
+            raise ValueError(f"cloud_tol: expected (pixels > 0, relative depth > 0), got {cloud_tol}")
         self.cloud, self.cloud_step, self.cloud_frame = bool(cloud), int(cloud_step), cloud_frame
+        self.cloud_views, self.cloud_min_views, self.cloud_tol, self.save_conf = cloud_views, cloud_min_views, cloud_tol, bool(save_conf)
+        self._views = None                                 # depth_views' ring and ages, next to the pose chain
+        self._views_n = self._views_depth = None           # [b,h,w] counts (without save_conf) and the filtered copy
+        self.cloud_kept = self.cloud_cap = 0               # vertices written / vertices the clouds could hold, finished frames
         self._pose = None                                  # [b,7] float64 device state of the cloud: camera-to-world poses
         self.out_dir, self.fmt, self.panels = str(out_dir), fmt, panels
         self.near, self.far, self.err_max = float(near), float(far), float(err_max)
@@ -208,7 +261,7 @@ class PredictionWriter:
         b, h, w = est.shape[:3]
         self._geometry = (b, h, w)
         cap = nops.cloud_capacity(h, w, self.cloud_step) if self.cloud else 0
-        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap) for _ in range(self.n_slots)]
+        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf) for _ in range(self.n_slots)]
         if any(p != "rgb" for p in self.panels):
             self._lut = torch.from_numpy(default_lut()).to(est.device)
         for i in range(self.n_slots):
@@ -238,6 +291,19 @@ class PredictionWriter:
                 slot.reset_d.copy_(slot.reset_h, non_blocking=True)
                 mask = slot.reset_d
         nops.pose_accumulate(rot, trans, self._pose, reset=mask, force_all=first)
+        if self.cloud_views:                               # the clouds see the filtered copy; PNG and panels the estimate
+            b, h, w = est.shape[:3]
+            if self._views is None:
+                self._views = nops.depth_views_state(b, h, w, self.cloud_views, est.device)
+                self._views_depth = torch.empty((b, h, w, 1), dtype=torch.float32, device=est.device)
+                if not self.save_conf:
+                    self._views_n = torch.empty((b, h, w), dtype=torch.uint8, device=est.device)
+            # est may be a buffer the next graph replay overwrites: the ring copy happens in this launch, on this stream
+            _, est = nops.depth_views(est, camera["f"], camera["c"], self._pose, self._views, reset=mask, force_all=first,
+                                      tol_px=self.cloud_tol[0], tol_rel=self.cloud_tol[1], min_views=self.cloud_min_views,
+                                      n_views=slot.conf_d if self.save_conf else self._views_n, depth_f=self._views_depth)
+            if self.save_conf:
+                slot.conf_h.copy_(slot.conf_d, non_blocking=True)
         nops.depth_cloud(est, rgb, camera["f"], camera["c"], step=self.cloud_step, near=self.near, far=self.far,
                          pose=self._pose if self.cloud_frame == "world" else None, vertices=slot.cloud_d, counts=slot.counts_d)
         slot.cloud_h.copy_(slot.cloud_d, non_blocking=True)
@@ -276,6 +342,8 @@ class PredictionWriter:
                 jobs.append((name + "_panels.png", slot.panels_h, s))
             if self.cloud:
                 jobs.append((name + "_cloud.ply", None, s))
+            if self.save_conf:
+                jobs.append((name + "_conf.png", slot.conf_h, s))
         slot.pending = len(jobs)
         self.frames += len(names)
         for job in jobs:
@@ -285,6 +353,10 @@ class PredictionWriter:
         slot = self._slots[index]
         try:
             slot.event.synchronize()
+            if host is None and self.cloud_views:          # counts the host already has: the share the filter kept
+                with self._lock:
+                    self.cloud_kept += int(slot.counts_h[s])
+                    self.cloud_cap += slot.cloud_h.shape[1]
             if self.encode:
                 path = os.path.join(self.out_dir, rel_path)
                 os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -295,6 +367,8 @@ class PredictionWriter:
                     arr = host[s].numpy()
                     if arr.dtype == np.int16:
                         arr = arr.view(np.uint16)          # PIL mode I;16
+                    elif host is slot.conf_h:              # counts -> grey
+                        arr = (arr.astype(np.uint16) * 255 // self.cloud_views).astype(np.uint8)
                     Image.fromarray(arr).save(path, format="PNG", compress_level=self.compress_level)
         except BaseException as e:                         # kept for close(); the slot is freed all the same
             with self._lock:

@@ -677,7 +677,8 @@ def predict(args, model, batches, rank, dev):
     if args.save_dir is not None:
         writer = PredictionWriter(args.save_dir, args.save_format, args.save_panels, near=args.save_range[0],
                                   far=args.save_range[1], err_max=args.save_err_max, cloud=args.save_cloud,
-                                  cloud_step=args.cloud_stride, cloud_frame=args.cloud_frame)
+                                  cloud_step=args.cloud_stride, cloud_frame=args.cloud_frame, cloud_views=args.cloud_views,
+                                  cloud_min_views=args.cloud_min_views, cloud_tol=args.cloud_tol, save_conf=args.save_conf)
         want_gt = any(p in ("gt", "err") for p in writer.panels)
     preds = []
     for data in batches:
@@ -723,6 +724,8 @@ def predict(args, model, batches, rank, dev):
         print(f"predict: wrote {writer.frames} frames ({args.save_format}"
               + (", panels " + ",".join(writer.panels) if writer.panels else "")
               + (f", clouds at stride {writer.cloud_step}" if writer.cloud else "")
+              + (f", {writer.cloud_views}-view check kept {writer.cloud_kept} of {writer.cloud_cap} cloud pixels "
+                 f"({100.0 * writer.cloud_kept / max(writer.cloud_cap, 1):.1f} %)" if writer.cloud_views else "")
               + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
 
 

@@ -651,6 +651,76 @@ def depth_cloud(depth, rgb, cam_f, cam_c, step=2, near=1.0, far=80.0, pose=None,
     return vertices, counts
 
 
+VIEWS_MAX = 8                                                   # m4d_depth_views: at most this many earlier frames
+
+
+def depth_views_state(b, h, w, views, device):
+    """The state ``depth_views`` keeps between frames: {"ring_depth" [(views+1),b,h,w] float32, "ring_pose" [(views+1),b,7]
+    float64, "age" [two [b] int32 buffers, zeroed: in, out], "head": 0, "views": views}.  The ring tensors start uninitialised:
+    a slot is read only after it was written (age counts the written ones)."""
+    b, h, w, views = int(b), int(h), int(w), int(views)
+    if lib.m4d_depth_views_ring_floats(b, h, w, views) < 0:
+        raise ValueError(f"depth_views_state: need b in 1..65535, h, w >= 2, h*w <= 2^24 and views in 1..{VIEWS_MAX}, got "
+                         f"b {b}, h {h}, w {w}, views {views}")
+    return {"ring_depth": torch.empty((views + 1, b, h, w), dtype=torch.float32, device=device),
+            "ring_pose": torch.empty((views + 1, b, 7), dtype=torch.float64, device=device),
+            "age": [torch.zeros(b, dtype=torch.int32, device=device), torch.zeros(b, dtype=torch.int32, device=device)],
+            "head": 0, "views": views}
+
+
+def depth_views(depth, cam_f, cam_c, pose, state, reset=None, force_all=False, tol_px=1.0, tol_rel=0.01, min_views=None,
+                n_views=None, depth_f=None):
+    """The multi-view depth check of one frame batch (m4d_depth_views): returns (n_views [b,h,w] uint8, depth_f [b,h,w,1]
+    float32).  ``depth`` [b,h,w,1] float32 device tensor with dense images at a batch stride; ``cam_f`` / ``cam_c`` [b,2];
+    ``pose`` [b,7] float64 as ``pose_accumulate`` keeps it; ``state`` from ``depth_views_state`` -- this call writes the frame
+    into ring slot ``state["head"]``, then advances the head and swaps the age buffers on the host.  ``reset``: uint8 / bool [b]
+    device mask of the samples that start a trajectory, ``force_all``: all of them.  ``n_views`` counts the earlier frames (up
+    to ``state["views"]``) that confirm a pixel within ``tol_px`` pixels and ``tol_rel`` relative depth; ``depth_f`` is
+    ``depth`` with NaN where fewer than ``min_views`` (default min(2, views)) do; both may be given as destinations (the
+    buffers of export.PredictionWriter).  Nothing synchronises."""
+    if depth.dim() != 4 or depth.shape[3] != 1:
+        raise ValueError(f"depth: expected [b,h,w,1], got {tuple(depth.shape)}")
+    b, h, w = depth.shape[:3]
+    views = int(state["views"])
+    min_views = min(2, views) if min_views is None else int(min_views)
+    if not 1 <= min_views <= views:
+        raise ValueError(f"min_views must be in 1..{views}, got {min_views}")
+    if not (float(tol_px) > 0 and float(tol_rel) > 0):
+        raise ValueError(f"need tol_px > 0 and tol_rel > 0, got {tol_px}, {tol_rel}")
+    if tuple(cam_f.shape) != (b, 2) or tuple(cam_c.shape) != (b, 2):
+        raise ValueError(f"cam_f / cam_c: expected [{b},2], got {tuple(cam_f.shape)} and {tuple(cam_c.shape)}")
+    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (b, 7):
+        raise ValueError(f"pose: expected a [{b},7] float64 device tensor")
+    ring_depth, ring_pose, (age_in, age_out) = state["ring_depth"], state["ring_pose"], state["age"]
+    if tuple(ring_depth.shape) != (views + 1, b, h, w) or tuple(ring_pose.shape) != (views + 1, b, 7) \
+            or tuple(age_in.shape) != (b,) or tuple(age_out.shape) != (b,) or not 0 <= int(state["head"]) <= views:
+        raise ValueError(f"state: not a depth_views_state of {(b, h, w)} with {views} views")
+    if reset is not None:
+        if not isinstance(reset, torch.Tensor) or reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (b,):
+            raise ValueError(f"reset: expected a uint8 / bool [{b}] device tensor")
+        reset = reset.view(torch.uint8) if reset.dtype == torch.bool else reset
+    ds = _batch_stride(depth, "depth")
+    dev = depth.device
+    if n_views is None:
+        n_views = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+    elif tuple(n_views.shape) != (b, h, w):
+        raise ValueError(f"n_views: expected {(b, h, w)}, got {tuple(n_views.shape)}")
+    if depth_f is None:
+        depth_f = torch.empty((b, h, w, 1), dtype=torch.float32, device=dev)
+    elif tuple(depth_f.shape) != (b, h, w, 1):
+        raise ValueError(f"depth_f: expected {(b, h, w, 1)}, got {tuple(depth_f.shape)}")
+    check(lib.m4d_depth_views(ctypes.c_void_p(depth.data_ptr()), ds, dptr(as_f32(cam_f, "cam_f"), "cam_f"),
+                              dptr(as_f32(cam_c, "cam_c"), "cam_c"), dptr(pose, "pose", torch.float64),
+                              dptr(reset, "reset", torch.uint8), int(bool(force_all)), b, h, w, views, int(state["head"]),
+                              dptr(ring_depth, "ring_depth"), dptr(ring_pose, "ring_pose", torch.float64),
+                              dptr(age_in, "age_in", torch.int32), dptr(age_out, "age_out", torch.int32), float(tol_px),
+                              float(tol_rel), min_views, dptr(n_views, "n_views", torch.uint8), dptr(depth_f, "depth_f"),
+                              stream_ptr()), "m4d_depth_views")
+    state["head"] = (int(state["head"]) + 1) % (views + 1)
+    state["age"] = [age_out, age_in]
+    return n_views, depth_f
+
+
 SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                     # the `kind` argument of m4d_summary_images
 SUMMARY_MAX_MAPS = 16
 

@@ -94,6 +94,19 @@ def build_parser():
     p.add_argument("--cloud_frame", default=None, choices=["world", "camera"],
                    help="--save_cloud: coordinates in the frame of the trajectory's first camera (world, the default; the "
                         "frame-to-frame motions are chained on the GPU) or of each frame's own camera")
+    # the four options of the multi-view check are absent from the namespace until given (SUPPRESS): check_save_args fills in
+    # their defaults, and a parse without them yields exactly the destinations it yielded before they existed
+    p.add_argument("--cloud_views", type=int, default=argparse.SUPPRESS, metavar="K",
+                   help="--save_cloud: keep a pixel only if earlier frames of its trajectory confirm it -- its 3-D point, seen "
+                        "from up to K (1..8) earlier frames, lands on a surface they estimated too and projects back onto the "
+                        "pixel (default 0 = off).  Strict: the first --cloud_min_views frames of a trajectory give empty clouds")
+    p.add_argument("--cloud_min_views", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="--cloud_views: confirming frames a pixel needs, 1..K (default min(2, K))")
+    p.add_argument("--cloud_tol", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("PX", "REL"),
+                   help="--cloud_views: a frame confirms within PX pixels of reprojection error and REL relative depth "
+                        "difference (default 1.0 0.01: MVSNet's fusion thresholds, untuned for this network)")
+    p.add_argument("--save_conf", action="store_true", default=argparse.SUPPRESS,
+                   help="--cloud_views: also write <frame>_conf.png, 8-bit grey = confirming frames * 255 // K")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--loss", default="supervised", choices=["supervised", "photometric"],
                    help="train: supervised = the reference's log-depth L1 against ground truth; photometric = the reprojection "
@@ -271,6 +284,27 @@ def check_save_args(parser, args):
         parser.error("--cloud_stride must be >= 1")
     args.cloud_stride = 2 if args.cloud_stride is None else args.cloud_stride
     args.cloud_frame = args.cloud_frame or "world"
+    # the multi-view check runs on the clouds' pose chain: every option of it needs --save_cloud (and so --save_dir)
+    for f in ("cloud_views", "cloud_min_views", "cloud_tol"):
+        setattr(args, f, getattr(args, f, None))
+    args.save_conf = bool(getattr(args, "save_conf", False))
+    view_others = [f for f in ("cloud_views", "cloud_min_views", "cloud_tol") if getattr(args, f) is not None]
+    view_others += [f for f in ("save_conf",) if args.save_conf]
+    if view_others and not args.save_cloud:
+        parser.error("--%s needs --save_cloud" % view_others[0])
+    if args.cloud_views is not None and not 0 <= args.cloud_views <= 8:
+        parser.error("--cloud_views must be 0 (off) or 1..8")
+    args.cloud_views = args.cloud_views or 0
+    dependents = [f for f in view_others if f != "cloud_views"]
+    if dependents and not args.cloud_views:
+        parser.error("--%s needs --cloud_views" % dependents[0])
+    if args.cloud_min_views is not None and not 1 <= args.cloud_min_views <= args.cloud_views:
+        parser.error("--cloud_min_views must be in 1..%d (--cloud_views)" % args.cloud_views)
+    if args.cloud_views and args.cloud_min_views is None:
+        args.cloud_min_views = min(2, args.cloud_views)
+    args.cloud_tol = tuple(args.cloud_tol) if args.cloud_tol is not None else (1.0, 0.01)
+    if not (args.cloud_tol[0] > 0 and args.cloud_tol[1] > 0):
+        parser.error("--cloud_tol PX REL needs PX > 0 and REL > 0")
     if args.save_dir is None:
         if others:
             parser.error("--%s needs --save_dir" % others[0])

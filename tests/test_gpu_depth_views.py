@@ -1,0 +1,666 @@
+"""Multi-view depth check (m4d_depth_views, network_ops.depth_views, export.PredictionWriter(cloud_views=K), main.py
+--cloud_views) against the numpy restatement of include/m4depth_hip.h in tests/depth_views_ref.py.
+
+The kernel's arithmetic is + - * / on float32 and float64, one rounding per operation in a stated order, and its outputs are
+counts and copied bits: everything is compared exactly.  The only freedom is the last bit of nothing -- there is no sqrt, exp or
+fused operation in the path -- so a (pixel, view) pair can differ from numpy only if a compiler reassociates; the band rule of
+test 4 (a pair whose residual lies within a relative 1e-9 of its threshold may go either way) is kept for the driver test, where
+the poses come through ``%.17g`` text."""
+import csv
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import depth_views_ref as R
+from helpers import F, npy, cameras_np, make_fake_dataset
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 0xA5
+GUARD = 64                                                                      # bytes; keeps 16-byte alignment of what follows
+QNAN = 0x7FC00000
+SHAPES = [(37, 53), (64, 64)]                                                   # odd (element path) / multiple of 4 (vector path)
+B = 3
+
+
+def scene(h, w, n=R.N_POSES, noise=None, scale=1.0):
+    cam = cameras_np(B, h, w)
+    maps, poses = R.scene(cam, n=n, noise=noise, h=h, w=w, scale=scale)
+    return cam, maps, poses
+
+
+_cache = {}
+
+
+def clean(h, w):
+    if (h, w) not in _cache:
+        cam, maps, poses = scene(h, w)
+        for a in (maps, poses):
+            a.setflags(write=False)
+        _cache[(h, w)] = (cam, maps, poses)
+    return _cache[(h, w)]
+
+
+def filled_state(cam, maps, poses, K, frames=5):
+    """The restatement's state after ``frames`` frames of the scene."""
+    st = R.State(B, maps.shape[2], maps.shape[3], K)
+    for k in range(frames):
+        st.step(maps[k], cam["f"], cam["c"], poses[k], force_all=(k == 0))
+    return st
+
+
+def guarded(dev, array):
+    """(flat uint8 device buffer with GUARD sentinel bytes on both sides, the view of ``array``'s shape and dtype in it)."""
+    array = np.ascontiguousarray(array)
+    raw = torch.from_numpy(array.view(np.uint8).reshape(-1).copy())
+    flat = torch.full((GUARD + raw.numel() + GUARD,), SENTINEL, dtype=torch.uint8, device=dev)
+    flat[GUARD:GUARD + raw.numel()] = raw.to(dev)
+    tdtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
+              np.dtype(np.uint8): torch.uint8}[array.dtype]
+    return flat, flat[GUARD:GUARD + raw.numel()].view(tdtype).view(*array.shape)
+
+
+def guards_intact(flat):
+    flat = npy(flat)
+    return (flat[:GUARD] == SENTINEL).all() and (flat[-GUARD:] == SENTINEL).all()
+
+
+def launch(dev, depth, cam, pose, st, age_in, reset=None, force_all=False, strided=False, misalign=False, **kw):
+    """One m4d_depth_views launch on copies of the restatement's state ``st`` (not advanced), every output inside guards.
+    Returns a dict of numpy results after checking the guards, the read slots and the written slot."""
+    from m4depth_amd import network_ops as nops
+    b, h, w = depth.shape
+    K = st.views
+    sent_f = np.frombuffer(bytes([SENTINEL] * 4), F)[0]
+    ring_d0 = st.ring_depth.copy()
+    ring_d0[st.head] = sent_f                                                   # the slot to be written: sentinel bits
+    ring_p0 = st.ring_pose.copy()
+    ring_p0[st.head] = np.frombuffer(bytes([SENTINEL] * 8), np.float64)[0]
+    ring_flat, ring_d = guarded(dev, ring_d0)
+    pose_flat, ring_p = guarded(dev, ring_p0)
+    age_flat, age_out = guarded(dev, np.full(b, -7, np.int32))
+    pad = 4 if misalign else 0                                                  # 4 bytes off: 16-byte stores are not possible
+    n_flat, n_views = guarded(dev, np.full(b * h * w + pad, SENTINEL, np.uint8))
+    f_flat, depth_f = guarded(dev, np.full(b * h * w + pad // 4, sent_f, F))
+    n_views = n_views[pad:].view(b, h, w)
+    depth_f = depth_f[pad // 4:].view(b, h, w, 1)
+    if strided:                                                                 # a frame slice of a [B,T,H,W,1] batch, read in place
+        full = torch.full((b, 2, h, w, 1), float("nan"), device=dev)
+        full[:, 1] = torch.from_numpy(depth.reshape(b, h, w, 1).copy()).to(dev)
+        d = full[:, 1]
+        assert d.stride(0) == 2 * h * w
+    else:
+        d = torch.from_numpy(depth.reshape(b, h, w, 1).copy()).to(dev)
+    state = {"ring_depth": ring_d, "ring_pose": ring_p, "views": K, "head": st.head,
+             "age": [torch.from_numpy(np.asarray(age_in, np.int32).copy()).to(dev), age_out]}
+    mask = None if reset is None else torch.from_numpy(np.asarray(reset, bool)).to(dev)
+    got_n, got_f = nops.depth_views(d, torch.from_numpy(cam["f"].copy()).to(dev), torch.from_numpy(cam["c"].copy()).to(dev),
+                                    torch.from_numpy(pose.copy()).to(dev), state, reset=mask, force_all=force_all,
+                                    n_views=n_views, depth_f=depth_f, **kw)
+    torch.cuda.synchronize()
+    assert got_n is n_views and got_f is depth_f
+    assert state["head"] == (st.head + 1) % (K + 1) and state["age"][0] is age_out
+    for name, flat in (("ring_depth", ring_flat), ("ring_pose", pose_flat), ("age_out", age_flat), ("n_views", n_flat),
+                       ("depth_f", f_flat)):
+        assert guards_intact(flat), f"bytes outside {name} overwritten"
+    if pad:
+        assert (npy(n_flat)[GUARD:GUARD + pad] == SENTINEL).all() and (npy(f_flat)[GUARD:GUARD + pad] == SENTINEL).all()
+    ring_d, ring_p = npy(ring_d), npy(ring_p)
+    for slot in range(K + 1):
+        if slot != st.head:                                                     # the K read slots: unchanged (NaN patterns included)
+            assert np.array_equal(ring_d[slot].view(np.uint32), ring_d0[slot].view(np.uint32)), f"ring slot {slot} changed"
+            assert np.array_equal(ring_p[slot].view(np.uint64), ring_p0[slot].view(np.uint64)), f"ring pose {slot} changed"
+    assert np.array_equal(ring_d[st.head].view(np.uint32), depth.view(np.uint32)), "ring slot head is not the input's bits"
+    assert np.array_equal(ring_p[st.head].view(np.uint64), pose.view(np.uint64)), "ring pose head is not the input pose"
+    return {"n_views": npy(n_views), "depth_f": npy(depth_f)[..., 0], "age_out": npy(age_out)}
+
+
+def want_of(depth, cam, pose, st, age_in, **kw):
+    return R.depth_views(depth, cam["f"], cam["c"], pose, st.ring_depth.copy(), st.ring_pose.copy(), np.asarray(age_in, np.int32),
+                         st.head, st.views, **kw)
+
+
+def assert_same(got, want, what=""):
+    bad = np.argwhere(got["n_views"] != want["n_views"])
+    assert len(bad) == 0, f"{what}: n_views differs on {len(bad)} pixels; first at {bad[0]}: {got['n_views'][tuple(bad[0])]} " \
+                          f"vs {want['n_views'][tuple(bad[0])]}"
+    assert np.array_equal(got["depth_f"].view(np.uint32), want["depth_f"].view(np.uint32)), f"{what}: depth_f bits differ"
+    assert np.array_equal(got["age_out"], want["age_out"]), (what, got["age_out"], want["age_out"])
+
+
+# ---- 1: the kernel against the restatement ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", [1, 4])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_kernel_matches_the_restatement(dev, shape, K):
+    cam, maps, poses = clean(*shape)
+    st = filled_state(cam, maps, poses, K)
+    ages = [0, 2, K]                                                            # 2 is capped at K = 1
+    for reset in (None, [False, False, True], [True, True, True]):
+        want = want_of(maps[5], cam, poses[5], st, ages, reset=reset)
+        got = launch(dev, maps[5], cam, poses[5], st, ages, reset=reset, strided=True)
+        assert_same(got, want, f"reset {reset}")
+        expect_age = [1, min(min(2, K) + 1, K), K]
+        if reset is not None:
+            expect_age = [1 if r else a for r, a in zip(reset, expect_age)]
+        assert list(got["age_out"]) == expect_age
+        assert (got["n_views"][0] == 0).all()
+        if reset is None:
+            assert (got["n_views"][1] > 0).any() and (got["n_views"][2] == K).any() and got["n_views"][1].max() == min(2, K)
+            keep = got["n_views"] >= min(2, K)
+            assert keep.any() and (~keep).any()
+            assert (got["depth_f"].view(np.uint32)[~keep] == QNAN).all()
+    want = want_of(maps[5], cam, poses[5], st, [K, K, K], force_all=True)
+    got = launch(dev, maps[5], cam, poses[5], st, [K, K, K], force_all=True)
+    assert_same(got, want, "force_all")
+    assert (got["n_views"] == 0).all() and list(got["age_out"]) == [1, 1, 1]
+    for mv in range(1, K + 1):                                                  # every min_views; tolerances that reject some
+        kw = dict(min_views=mv, tol_px=2e-5, tol_rel=4e-6)
+        want = want_of(maps[5], cam, poses[5], st, [K, K, K], **kw)
+        assert 0.05 < want["confirmed"].sum() / want["tested"].sum() < 0.95
+        assert_same(launch(dev, maps[5], cam, poses[5], st, [K, K, K], **kw), want, f"min_views {mv}")
+
+
+def test_unaligned_outputs_take_the_element_path(dev):
+    """64 x 64 with n_views and depth_f four bytes off a 16-byte boundary: the same bits, nothing outside written."""
+    cam, maps, poses = clean(64, 64)
+    st = filled_state(cam, maps, poses, 4)
+    want = want_of(maps[5], cam, poses[5], st, [4, 4, 4])
+    assert_same(launch(dev, maps[5], cam, poses[5], st, [4, 4, 4], misalign=True), want)
+    assert_same(launch(dev, maps[5], cam, poses[5], st, [4, 4, 4]), want)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_without_a_filtered_copy(dev, shape):
+    """depth_f = NULL through the C ABI: the counts, the ring slot and the ages as with it, nothing else written."""
+    import ctypes
+    from m4depth_amd._lib import lib, check, stream_ptr
+    h, w = shape
+    K = 4
+    cam, maps, poses = clean(h, w)
+    st = filled_state(cam, maps, poses, K)
+    want = want_of(maps[5], cam, poses[5], st, [K, 2, K])
+    ring_flat, ring_d = guarded(dev, st.ring_depth)
+    pose_flat, ring_p = guarded(dev, st.ring_pose)
+    n_flat, n_views = guarded(dev, np.full((B, h, w), SENTINEL, np.uint8))
+    age_flat, age_out = guarded(dev, np.full(B, -7, np.int32))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)             # noqa: E731
+    depth, f_d, c_d, pose, age_in = t(maps[5]), t(cam["f"]), t(cam["c"]), t(poses[5]), t(np.array([K, 2, K], np.int32))
+    p = lambda x: ctypes.c_void_p(x.data_ptr())                                 # noqa: E731
+    check(lib.m4d_depth_views(p(depth), h * w, p(f_d), p(c_d), p(pose), None, 0, B, h, w, K, st.head, p(ring_d), p(ring_p),
+                              p(age_in), p(age_out), 1.0, 0.01, 2, p(n_views), None, stream_ptr()), "m4d_depth_views")
+    torch.cuda.synchronize()
+    for flat in (ring_flat, pose_flat, n_flat, age_flat):
+        assert guards_intact(flat)
+    assert np.array_equal(npy(n_views), want["n_views"]) and np.array_equal(npy(age_out), want["age_out"])
+    assert np.array_equal(npy(ring_d)[st.head].view(np.uint32), maps[5].view(np.uint32))
+    assert np.array_equal(npy(ring_p)[st.head], poses[5])
+
+
+# ---- 2: a sequence through depth_views_state: wrap-around, a reset in mid-sequence ----------------------------------------------
+@pytest.mark.parametrize("shape,K", [((37, 53), 1), ((37, 53), 4), ((64, 64), 4)], ids=["37x53-K1", "37x53-K4", "64x64-K4"])
+def test_sequence_matches_frame_by_frame(dev, shape, K):
+    from m4depth_amd import network_ops as nops
+    h, w = shape
+    n = K + 3
+    cam, maps, poses = scene(h, w, n=n, scale=0.6)
+    resets = {min(3, n - 2): np.array([False, True, False])}
+    ref = R.State(B, h, w, K)
+    state = nops.depth_views_state(B, h, w, K, dev)
+    f_d, c_d = torch.from_numpy(cam["f"].copy()).to(dev), torch.from_numpy(cam["c"].copy()).to(dev)
+    heads = []
+    for k in range(n):
+        reset = resets.get(k)
+        want = ref.step(maps[k], cam["f"], cam["c"], poses[k], force_all=(k == 0), reset=reset)
+        heads.append(state["head"])
+        ages = state["age"]
+        got_n, got_f = nops.depth_views(torch.from_numpy(maps[k].reshape(B, h, w, 1).copy()).to(dev), f_d, c_d,
+                                        torch.from_numpy(poses[k].copy()).to(dev), state,
+                                        reset=None if reset is None else torch.from_numpy(reset).to(dev).view(torch.uint8),
+                                        force_all=(k == 0))
+        assert state["age"][0] is ages[1] and state["age"][1] is ages[0]        # swapped
+        got = {"n_views": npy(got_n), "depth_f": npy(got_f)[..., 0], "age_out": npy(state["age"][0])}
+        assert_same(got, want, f"frame {k}")
+        assert want["tested"].sum(0)[0].max() == min(k, K)
+    assert heads == [k % (K + 1) for k in range(n)] and state["head"] == n % (K + 1)
+    assert np.array_equal(npy(state["ring_depth"]).view(np.uint32), ref.ring_depth.view(np.uint32))
+    assert np.array_equal(npy(state["ring_pose"]), ref.ring_pose)
+
+
+# ---- 3: a sample of a batch = the sample alone ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_batch_sample_equals_the_sample_alone(dev, shape):
+    from m4depth_amd import network_ops as nops
+    h, w = shape
+    K = 4
+    cam, maps, poses = clean(h, w)
+    st = filled_state(cam, maps, poses, K)
+    ages, reset = [K, 2, K], np.array([False, False, True])
+
+    def run(rows):
+        n = len(rows)
+        state = {"ring_depth": torch.from_numpy(st.ring_depth[:, rows].copy()).to(dev),
+                 "ring_pose": torch.from_numpy(st.ring_pose[:, rows].copy()).to(dev), "views": K, "head": st.head,
+                 "age": [torch.tensor([ages[r] for r in rows], dtype=torch.int32, device=dev),
+                         torch.zeros(n, dtype=torch.int32, device=dev)]}
+        got_n, got_f = nops.depth_views(torch.from_numpy(maps[5][rows].reshape(n, h, w, 1).copy()).to(dev),
+                                        torch.from_numpy(cam["f"][rows].copy()).to(dev), torch.from_numpy(cam["c"][rows].copy()).to(dev),
+                                        torch.from_numpy(poses[5][rows].copy()).to(dev), state,
+                                        reset=torch.from_numpy(reset[rows]).to(dev))
+        return npy(got_n), npy(got_f).view(np.uint32), npy(state["age"][0]), npy(state["ring_depth"]).view(np.uint32)
+
+    batch = run([0, 1, 2])
+    assert batch[0][0].max() == K and (batch[0][2] == 0).all()
+    for s in range(B):
+        alone = run([s])
+        for what in range(3):                                                   # n_views, depth_f, age_out: [b, ...]
+            assert np.array_equal(batch[what][s], alone[what][0]), (s, what)
+        assert np.array_equal(batch[3][:, s], alone[3][:, 0]), s                # the ring: [(K+1), b, h, w]
+
+
+# ---- 4: residuals on both sides of the thresholds ----------------------------------------------------------------------------------
+NOISE = (7, 0.015)              # seed, peak amplitude: smooth multiplicative noise of about 1 % on every map
+BAND = 1e-9
+
+
+def near_threshold(want, tol_px, tol_rel):
+    """(pixel, view) pairs whose restated residual lies within a relative BAND of its threshold."""
+    tol2, rel = np.float64(F(tol_px)) * np.float64(F(tol_px)), np.float64(F(tol_rel))
+    lim = rel * want["zc"][None]
+    with np.errstate(invalid="ignore"):
+        return want["tested"] & ((np.abs(want["r_px2"] - tol2) <= BAND * tol2) | (np.abs(want["r_z"] - lim) <= BAND * lim))
+
+
+def assert_same_outside_band(got_n, want, tol_px, tol_rel, what=""):
+    near = near_threshold(want, tol_px, tol_rel)
+    tested = int(want["tested"].sum())
+    assert near.sum() * 10 ** 4 <= tested, f"{what}: {near.sum()} of {tested} tested pairs sit on a threshold"
+    per_pixel = near.sum(0)
+    diff = np.abs(got_n.astype(int) - want["n_views"].astype(int))
+    assert (diff[per_pixel == 0] == 0).all(), f"{what}: {(diff[per_pixel == 0] != 0).sum()} pixels away from any threshold differ"
+    assert (diff <= per_pixel).all(), what
+    return int(near.sum())
+
+
+@pytest.mark.parametrize("tol", [(1.0, 0.01), (0.02, 0.5)], ids=["rel", "px"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_decisions_on_both_sides_of_the_thresholds(dev, shape, tol):
+    K = 4
+    cam, maps, poses = scene(*shape, noise=NOISE)
+    st = filled_state(cam, maps, poses, K)
+    want = want_of(maps[5], cam, poses[5], st, [K, K, K], tol_px=tol[0], tol_rel=tol[1])
+    tested, confirmed = want["tested"].sum(), want["confirmed"].sum()
+    print(f"{shape} tol {tol}: {tested} tested pairs, {confirmed} confirmed, {tested - confirmed} rejected")
+    assert confirmed >= 0.1 * tested and tested - confirmed >= 0.1 * tested     # a condition on the case, checked on the CPU too
+    got = launch(dev, maps[5], cam, poses[5], st, [K, K, K], tol_px=tol[0], tol_rel=tol[1])
+    assert_same_outside_band(got["n_views"], want, tol[0], tol[1])
+    undecided = near_threshold(want, *tol).any(0)
+    keep = want["n_views"] >= 2
+    assert np.array_equal(got["depth_f"].view(np.uint32)[~undecided], want["depth_f"].view(np.uint32)[~undecided])
+    assert keep.any() and (~keep).any()
+
+
+# ---- 5: degenerate inputs ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["nan-current", "zero-earlier", "nan-pose", "nan-ring-pose", "stationary", "mixed-invalid"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_degenerate_inputs(dev, shape, case):
+    K = 4
+    cam, maps, poses = clean(*shape)
+    maps, poses = maps.copy(), poses.copy()
+    if case == "nan-current":
+        maps[5] = np.nan
+    elif case == "zero-earlier":
+        maps[4] = 0.0
+    elif case == "nan-pose":
+        poses[5, 1] = np.nan
+    elif case == "nan-ring-pose":
+        poses[3, 2] = np.nan
+    elif case == "stationary":
+        poses[:] = poses[2:3]
+        maps[:] = maps[2:3]
+    else:
+        rng = np.random.default_rng(5)
+        bad = np.array([np.nan, np.inf, -np.inf, 0.0, -2.0, 1e-30, 3e38], F)
+        for k in (3, 5):
+            spots = rng.permutation(maps[k].size)[:300]
+            maps[k].reshape(-1)[spots] = rng.choice(bad, 300)
+    st = filled_state(cam, maps, poses, K)
+    want = want_of(maps[5], cam, poses[5], st, [K, K, K])
+    got = launch(dev, maps[5], cam, poses[5], st, [K, K, K])
+    assert_same(got, want, case)
+    n = got["n_views"]
+    if case == "nan-current":
+        assert (n == 0).all() and (got["depth_f"].view(np.uint32) == QNAN).all()
+    elif case == "zero-earlier":
+        assert not want["tested"][0].any() and n.max() == K - 1
+    elif case == "nan-pose":
+        assert (n[1] == 0).all() and n[0].max() == K and n[2].max() == K
+    elif case == "nan-ring-pose":
+        assert not want["tested"][1, 2].any() and n[2].max() == K - 1 and n[0].max() == K
+    elif case == "stationary":
+        assert (n[:, 1:-1, 1:-1] == K).all()
+    else:
+        assert (n == 0).any() and (n == K).any()
+
+
+# ---- 6: the writer -------------------------------------------------------------------------------------------------------------------
+def rgb_bytes(v):
+    v = np.asarray(v, F)
+    v = np.where(np.isnan(v), F(0.0), v)
+    return np.rint(np.minimum(np.maximum(v, F(0.0)), F(1.0)) * F(255.0)).astype(np.uint8)
+
+
+def apply_pose(pose, x, y, z):
+    r = R.rot(pose[:4])
+    X, Y, Z = (np.asarray(v, np.float64) for v in (x, y, z))
+    return [((r[i][0] * X + r[i][1] * Y) + r[i][2] * Z) + np.float64(pose[4 + i]) for i in range(3)]
+
+
+def cloud_of(depth, colours, f, c, step, near, far, pose=None):
+    """m4d_depth_cloud restated for one sample (the rule tests/test_gpu_cloud.py holds the kernel to): depth [h,w] float32,
+    colours [h,w,3] uint8 -> (xyz float32 [n,3], rgba uint8 [n,4]) in raster order; a non-finite depth gives no vertex."""
+    depth = np.asarray(depth, F)
+    keep = np.zeros(depth.shape, bool)
+    with np.errstate(invalid="ignore"):
+        keep[::step, ::step] = (np.isfinite(depth) & (depth >= F(near)) & (depth <= F(far)))[::step, ::step]
+    rows, cols = np.nonzero(keep)
+    d = depth[rows, cols]
+    x = (((cols.astype(F) + F(0.5)) - F(c[0])) / F(f[0])) * d
+    y = (((rows.astype(F) + F(0.5)) - F(c[1])) / F(f[1])) * d
+    xyz = np.stack([x, y, d], axis=1).astype(F).reshape(-1, 3)
+    if pose is not None:
+        xyz = np.stack([v.astype(F) for v in apply_pose(pose, x, y, d)], axis=1).reshape(-1, 3)
+    rgba = np.concatenate([colours[rows, cols], np.full((len(rows), 1), 255, np.uint8)], axis=1)
+    return xyz, rgba
+
+
+def as_bytes(xyz, rgba):
+    return np.concatenate([np.ascontiguousarray(xyz, F).view(np.uint8).reshape(-1, 12), rgba], axis=1)
+
+
+def within_one_ulp(got, want):
+    got, want = np.asarray(got, F), np.asarray(want, F)
+    return (got == want) | (got == np.nextafter(want, F(np.inf))) | (got == np.nextafter(want, F(-np.inf)))
+
+
+def relative_motion(prev, cur):
+    """(rot [4], trans [3]) float32 with X_prev = R(rot) X_cur + trans, from two camera-to-world poses."""
+    pw, px, py, pz = prev[:4] * np.array([1, -1, -1, -1])                       # conj(q_prev) q_cur
+    w, x, y, z = cur[:4]
+    q = np.array([pw * w - px * x - py * y - pz * z, pw * x + px * w + py * z - pz * y, pw * y - px * z + py * w + pz * x,
+                  pw * z + px * y - py * x + pz * w])
+    rp = np.array(R.rot(prev[:4]), np.float64)
+    return q.astype(F), (rp.T @ (cur[4:] - prev[4:])).astype(F)
+
+
+def test_prediction_writer_filters_the_clouds(dev, tmp_path):
+    """Three samples over seven frames of the scene, K = 2, sample 1 restarting at frame 4, ring of two slots: every PLY is the
+    cloud of the restated filter's depth under the pose its own header carries, every _conf.png the restated counts; a writer
+    without the option writes the unfiltered clouds with one launch fewer per submit."""
+    from PIL import Image
+    from m4depth_amd._lib import lib
+    from m4depth_amd.export import PredictionWriter, FrameNamer, read_cloud_ply, read_conf_png
+    h, w, K, steps, step = 37, 53, 2, 7, 1
+    cam, maps, poses = scene(h, w, n=steps, scale=0.6)
+    rng = np.random.default_rng(3)
+    rgb = rng.random((steps, B, h, w, 3)).astype(F)
+    flags = [[k == 0, k in (0, 4), k == 0] for k in range(steps)]
+    camera = {k: torch.from_numpy(v.copy()).to(dev) for k, v in cam.items()}
+    near, far = 1.0, 80.0
+    outs, launches = {}, {}
+    for key, kw in (("views", dict(cloud_views=K, save_conf=True)), ("plain", {})):
+        outs[key] = str(tmp_path / key)
+        namer = FrameNamer(B)
+        n0 = lib.m4d_launch_count()
+        with PredictionWriter(outs[key], "kitti16", near=near, far=far, slots=2, cloud=True, cloud_step=step, cloud_frame="camera",
+                              **kw) as writer:
+            names = []
+            for k in range(steps):
+                motion = [relative_motion(poses[k - 1, s], poses[k, s]) if k else (np.array([1, 0, 0, 0], F), np.zeros(3, F))
+                          for s in range(B)]
+                rot = torch.from_numpy(np.stack([m[0] for m in motion])).to(dev)
+                trans = torch.from_numpy(np.stack([m[1] for m in motion])).to(dev)
+                names.append(namer(flags[k]))
+                writer.submit(torch.from_numpy(maps[k].reshape(B, h, w, 1).copy()).to(dev), names[-1],
+                              rgb=torch.from_numpy(rgb[k]).to(dev), rot=rot, trans=trans, camera=camera,
+                              reset=np.array(flags[k]) if k % 2 else torch.tensor(flags[k], device=dev))
+        launches[key] = lib.m4d_launch_count() - n0
+        if key == "views":
+            kept, cap = writer.cloud_kept, writer.cloud_cap
+    assert launches["plain"] == 4 * steps and launches["views"] == 5 * steps    # export, pose, two cloud passes (+ the check)
+    ref = R.State(B, h, w, K)
+    total = 0
+    for k in range(steps):
+        got_pose = np.stack([read_cloud_ply(os.path.join(outs["views"], names[k][s] + "_cloud.ply"))[2] for s in range(B)])
+        assert np.abs(got_pose[0] - (poses[k, 0] if k else [1, 0, 0, 0, 0, 0, 0])).max() < 1e-6       # the chain follows the scene
+        want = ref.step(maps[k], cam["f"], cam["c"], got_pose, force_all=(k == 0), reset=np.array(flags[k]))
+        colours = rgb_bytes(rgb[k])
+        for s in range(B):
+            stem = os.path.join(outs["views"], names[k][s])
+            assert np.array_equal(read_conf_png(stem + "_conf.png", K), want["n_views"][s]), (k, s)
+            with Image.open(stem + "_conf.png") as im:
+                assert im.mode == "L" and np.array_equal(np.asarray(im), want["n_views"][s].astype(int) * 255 // K)
+            xyz, rgba, _ = read_cloud_ply(stem + "_cloud.ply")
+            assert np.array_equal(as_bytes(xyz, rgba), as_bytes(*cloud_of(want["depth_f"][s], colours[s], cam["f"][s], cam["c"][s],
+                                                                         step, near, far))), (k, s)
+            total += len(xyz)
+            first_frames = k < 2 or (s == 1 and 4 <= k < 6)                      # min_views = 2 frames of every trajectory
+            assert (len(xyz) == 0) == first_frames, (k, s, len(xyz))
+            raw_xyz, raw_rgba, raw_pose = read_cloud_ply(os.path.join(outs["plain"], names[k][s] + "_cloud.ply"))
+            assert np.array_equal(as_bytes(raw_xyz, raw_rgba), as_bytes(*cloud_of(maps[k, s], colours[s], cam["f"][s], cam["c"][s],
+                                                                                 step, near, far))), (k, s)
+            assert np.array_equal(raw_pose, got_pose[s]) and len(raw_xyz) == h * w
+            for suffix in ("_depth.png",):                                      # the PNG keeps showing the raw estimate
+                with open(stem + suffix, "rb") as a, open(os.path.join(outs["plain"], names[k][s] + suffix), "rb") as b_:
+                    assert a.read() == b_.read()
+    assert (kept, cap) == (total, steps * B * h * w) and 0 < kept < cap
+    assert not [f for _, _, fs in os.walk(outs["plain"]) for f in fs if f.endswith("_conf.png")]
+
+
+# ---- 7: the driver -------------------------------------------------------------------------------------------------------------------
+PATHS = {"frames": [], "stream": ["--stream"], "stream-graph": ["--stream", "--graph"]}
+N_TRAJ, N_FRAMES, SIZE, K_DRV, MIN_DRV, STRIDE = 2, 8, 64, 4, 2, 2
+# --cloud_tol = this percentile of the restated residuals over the tested pairs.  The network is He-initialised and its estimates
+# of consecutive frames have little to do with each other (depths from -0.3 to the 1000 m clip, median 0.6): at the median the
+# restated filter kept 0.1 % of the candidates of the frames past min_views, at the 80th percentile 15 %, at the 90th 24 %
+PERCENTILE = 90
+_runs = {}
+
+
+@pytest.fixture(scope="module")
+def dataset(tmp_path_factory):
+    root = str(tmp_path_factory.mktemp("views"))
+    db, rec = make_fake_dataset(root, "midair", n_traj=N_TRAJ, n_frames=N_FRAMES, size=(SIZE, SIZE))
+    cfg = os.path.join(root, "datasets_location.json")
+    with open(cfg, "w") as fh:
+        json.dump({"midair": "./db"}, fh)
+    return {"root": root, "rec": rec, "cfg": cfg}
+
+
+def run_driver(dataset, key, extra):
+    if key not in _runs:
+        from m4depth_amd import main as MAIN
+        from m4depth_amd._lib import lib
+        out = os.path.join(dataset["root"], key)
+        n0 = lib.m4d_launch_count()
+        assert MAIN.main(["--mode", "predict", "--dataset", "midair", "--db_path_config", dataset["cfg"], "--records_path",
+                          dataset["rec"], "--arch_depth", "2", "--height", str(SIZE), "--width", str(SIZE), "--ckpt_dir",
+                          out + "_ckpt"] + [a.replace("OUT", out) for a in extra]) == 0
+        _runs[key] = (out, lib.m4d_launch_count() - n0)
+    return _runs[key]
+
+
+def pose_step(pose, rot, trans, reset):
+    """m4d_pose_accumulate of one sample in numpy float64."""
+    if reset:
+        return np.array([1, 0, 0, 0, 0, 0, 0], np.float64)
+    w, x, y, z = (np.float64(v) for v in rot)
+    n = np.sqrt(((w * w + x * x) + y * y) + z * z)
+    w, x, y, z = w / n, x / n, y / n, z / n
+    pw, px, py, pz = pose[:4]
+    t = apply_pose(pose, *(np.float64(v) for v in trans))
+    rw = ((pw * w - px * x) - py * y) - pz * z
+    rx = ((pw * x + px * w) + py * z) - pz * y
+    ry = ((pw * y - px * z) + py * w) + pz * x
+    rz = ((pw * z + px * y) - py * x) + pz * w
+    m = np.sqrt(((rw * rw + rx * rx) + ry * ry) + rz * rz)
+    return np.array([rw / m, rx / m, ry / m, rz / m, t[0], t[1], t[2]], np.float64)
+
+
+def csv_pose_chain(dataset, traj):
+    with open(os.path.join(dataset["rec"], f"set_{traj}", f"traj_{traj:04d}.csv"), newline="") as fh:
+        rows = list(csv.DictReader(fh, delimiter="\t"))
+    poses, pose = [], None
+    for k, row in enumerate(rows):
+        rot = np.array([row[c] for c in ("qw", "qx", "qy", "qz")], np.float64).astype(F)
+        trans = np.array([row[c] for c in ("tx", "ty", "tz")], np.float64).astype(F)
+        pose = pose_step(pose, rot, trans, k == 0)
+        poses.append(pose)
+    return np.stack(poses)
+
+
+CAM_DRV = {"f": np.array([[0.5 * SIZE, 0.5 * SIZE]], F), "c": np.array([[0.5 * SIZE, 0.5 * SIZE]], F)}
+
+
+def restate(preds, poses, tol):
+    """The filter over the run's frames [N_TRAJ * N_FRAMES, h, w] with ``poses`` [same, 7]: a list of restatement results."""
+    ref, outs = R.State(1, SIZE, SIZE, K_DRV), []
+    for i in range(len(preds)):
+        outs.append(ref.step(preds[i][None], CAM_DRV["f"], CAM_DRV["c"], poses[i][None], reset=np.array([i % N_FRAMES == 0]),
+                             force_all=(i == 0), tol_px=tol[0], tol_rel=tol[1], min_views=MIN_DRV))
+    return outs
+
+
+def plan(dataset):
+    """The plain run's depths, the kept depth range (as the cloud tests take it) and --cloud_tol: the PERCENTILE-th percentile of
+    the restated residuals over the tested pairs under the csv's pose chain.  Every run writes the same predictions.npy, so the
+    thresholds are fixed numbers that fall in the middle of what this network does."""
+    if "plan" not in _runs:
+        out, _ = run_driver(dataset, "plain", [])
+        preds = np.load(out + "_ckpt/predictions.npy")[..., 0]
+        assert preds.shape == (N_TRAJ * N_FRAMES, SIZE, SIZE) and np.isfinite(preds).all()
+        near, far = (float(F(v)) for v in np.percentile(preds, [20, 80]))
+        assert 0 < near < far
+        poses = np.concatenate([csv_pose_chain(dataset, t) for t in range(N_TRAJ)])
+        outs = restate(preds, poses, (1.0, 0.01))
+        r_px = np.concatenate([np.sqrt(o["r_px2"][o["tested"] & np.isfinite(o["r_px2"])]) for o in outs])
+        r_rel = np.concatenate([(o["r_z"] / o["zc"][None])[o["tested"] & np.isfinite(o["r_z"])] for o in outs])
+        assert len(r_px) > 1000
+        tol = (float(F(np.percentile(r_px, PERCENTILE))), float(F(np.percentile(r_rel, PERCENTILE))))
+        print(f"driver: {len(r_px)} tested pairs, --cloud_tol {tol}, depth range {near} .. {far}")
+        assert tol[0] > 0 and tol[1] > 0
+        _runs["plan"] = (preds, near, far, tol)
+    return _runs["plan"]
+
+
+def views_run(dataset, path, views=True):
+    _, near, far, tol = plan(dataset)
+    extra = ["--cloud_views", str(K_DRV), "--cloud_tol", repr(tol[0]), repr(tol[1]), "--save_conf"] if views else []
+    return run_driver(dataset, f"{path}_{'views' if views else 'cloud'}",
+                      PATHS[path] + ["--save_dir", "OUT", "--save_cloud", "--cloud_stride", str(STRIDE), "--save_range", repr(near),
+                                     repr(far)] + extra)
+
+
+def frame_files(out):
+    files = sorted(os.path.join(d, f) for d in sorted(os.listdir(out)) for f in os.listdir(os.path.join(out, d)))
+    return files, [f for f in files if f.endswith("_depth.png")]
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+def test_driver_filters_the_clouds(dev, dataset, path):
+    from PIL import Image
+    from m4depth_amd.export import read_cloud_ply, read_conf_png
+    preds, near, far, tol = plan(dataset)
+    out, _ = views_run(dataset, path)
+    files, depth_files = frame_files(out)
+    assert len(depth_files) == N_TRAJ * N_FRAMES and len(files) == 3 * len(depth_files)
+    stems = [os.path.join(out, name[:-len("_depth.png")]) for name in depth_files]
+    clouds = [read_cloud_ply(stem + "_cloud.ply") for stem in stems]
+    poses = np.stack([c[2] for c in clouds])                                    # the device's poses, as the headers carry them
+    chain = np.concatenate([csv_pose_chain(dataset, t) for t in range(N_TRAJ)])
+    assert np.abs(poses - chain).max() <= 1e-12
+    outs = restate(preds, poses, tol)
+    kept = candidates = 0
+    for i, (stem, (xyz, rgba, pose), want) in enumerate(zip(stems, clouds, outs)):
+        traj, k = divmod(i, N_FRAMES)
+        got_n = read_conf_png(stem + "_conf.png", K_DRV)
+        near_pairs = assert_same_outside_band(got_n[None], want, tol[0], tol[1], stem) if want["tested"].any() else 0
+        if k < MIN_DRV:                                                         # both trajectories: the second is not confirmed by the first
+            assert len(xyz) == 0 and got_n.max() <= k, (stem, len(xyz))
+        if k == 0:
+            assert (got_n == 0).all()
+        if near_pairs:
+            continue                                                            # (never seen; the counts above were held to the band)
+        with Image.open(os.path.join(dataset["root"], "db", f"traj_{traj}", "color", f"{k:06d}.JPEG")) as im:
+            colours = rgb_bytes(np.asarray(im.convert("RGB"), F) / F(255.0))
+        want_xyz, want_rgba = cloud_of(want["depth_f"][0], colours, CAM_DRV["f"][0], CAM_DRV["c"][0], STRIDE, near, far, pose=pose)
+        cam_xyz, _ = cloud_of(want["depth_f"][0], colours, CAM_DRV["f"][0], CAM_DRV["c"][0], STRIDE, near, far)
+        assert len(xyz) == len(want_xyz) and np.array_equal(rgba, want_rgba), stem
+        assert within_one_ulp(xyz, want_xyz).all(), stem
+        if k == 0 or np.array_equal(pose, [1, 0, 0, 0, 0, 0, 0]):
+            assert np.array_equal(as_bytes(xyz, rgba), as_bytes(cam_xyz, want_rgba))
+        if k >= MIN_DRV:
+            kept += len(xyz)
+            candidates += len(cloud_of(preds[i], colours, CAM_DRV["f"][0], CAM_DRV["c"][0], STRIDE, near, far)[0])
+    print(f"{path}: the filter kept {kept} of {candidates} candidates of the frames past min_views ({100.0 * kept / candidates:.1f} %)")
+    assert 0.1 * candidates <= kept <= 0.9 * candidates
+
+
+def test_driver_camera_frame_is_exact(dev, dataset):
+    """Camera-frame coordinates are float32 arithmetic: byte for byte."""
+    from PIL import Image
+    from m4depth_amd.export import read_cloud_ply
+    preds, near, far, tol = plan(dataset)
+    out, _ = run_driver(dataset, "frames_views_camera",
+                        ["--save_dir", "OUT", "--save_cloud", "--cloud_frame", "camera", "--cloud_stride", "3", "--save_range", repr(near),
+                         repr(far), "--cloud_views", str(K_DRV), "--cloud_tol", repr(tol[0]), repr(tol[1])])
+    files, depth_files = frame_files(out)
+    assert len(files) == 2 * len(depth_files) == 2 * N_TRAJ * N_FRAMES           # no _conf.png without --save_conf
+    stems = [os.path.join(out, name[:-len("_depth.png")]) for name in depth_files]
+    clouds = [read_cloud_ply(stem + "_cloud.ply") for stem in stems]
+    outs = restate(preds, np.stack([c[2] for c in clouds]), tol)
+    total = 0
+    for i, (stem, (xyz, rgba, _), want) in enumerate(zip(stems, clouds, outs)):
+        if near_threshold(want, *tol).any():
+            continue
+        traj, k = divmod(i, N_FRAMES)
+        with Image.open(os.path.join(dataset["root"], "db", f"traj_{traj}", "color", f"{k:06d}.JPEG")) as im:
+            colours = rgb_bytes(np.asarray(im.convert("RGB"), F) / F(255.0))
+        want_b = as_bytes(*cloud_of(want["depth_f"][0], colours, CAM_DRV["f"][0], CAM_DRV["c"][0], 3, near, far))
+        assert np.array_equal(as_bytes(xyz, rgba), want_b), stem
+        total += len(xyz)
+    assert total > 0
+
+
+def test_driver_paths_write_identical_files(dev, dataset):
+    outs = [views_run(dataset, path)[0] for path in PATHS]
+    names, _ = frame_files(outs[0])
+    assert len(names) == 3 * N_TRAJ * N_FRAMES
+    for other in outs[1:]:
+        for name in names:
+            with open(os.path.join(outs[0], name), "rb") as a, open(os.path.join(other, name), "rb") as b_:
+                assert a.read() == b_.read(), (other, name)
+
+
+def test_driver_adds_one_launch_per_frame(dev, dataset, capsys):
+    cloud_out, with_cloud = views_run(dataset, "frames", views=False)
+    _, with_views = views_run(dataset, "frames")
+    assert with_views - with_cloud == N_TRAJ * N_FRAMES
+    files, depth_files = frame_files(cloud_out)
+    assert len(files) == 2 * len(depth_files) and not [f for f in files if f.endswith("_conf.png")]
+
+
+def test_driver_reports_the_kept_share(dev, dataset, capsys):
+    from m4depth_amd import main as MAIN
+    _, near, far, tol = plan(dataset)
+    out = os.path.join(dataset["root"], "report")
+    assert MAIN.main(["--mode", "predict", "--dataset", "midair", "--db_path_config", dataset["cfg"], "--records_path", dataset["rec"],
+                      "--arch_depth", "2", "--height", str(SIZE), "--width", str(SIZE), "--ckpt_dir", out + "_ckpt", "--save_dir", out,
+                      "--save_cloud", "--save_range", repr(near), repr(far), "--cloud_views", "2", "--cloud_min_views", "1",
+                      "--cloud_tol", repr(tol[0]), repr(tol[1])]) == 0
+    line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("predict: wrote")]
+    assert len(line) == 1 and "2-view check kept " in line[0] and " cloud pixels (" in line[0], line
+    kept, cap = (int(v) for v in line[0].split("check kept ")[1].split(" cloud pixels")[0].split(" of "))
+    assert cap == N_TRAJ * N_FRAMES * (SIZE // 2) ** 2 and 0 < kept < cap
