@@ -990,6 +990,64 @@ int m4d_depth_views(const float* depth, long long depth_stride, const float* cam
 /* float32 elements of m4d_depth_views' ring_depth, (views+1) b h w; -1 for a geometry it refuses. */
 long long m4d_depth_views_ring_floats(int b, int h, int w, int views);
 
+/* ---- Voxel maps (main.py --save_dir --save_map VOXEL): the clouds of a trajectory merged into one map (csrc/m4d_voxelmap.hip) ---- */
+
+/* The map of a trajectory is the voxel-grid reduction of the vertices of that trajectory's per-frame clouds: its input is exactly
+ * the 16-byte vertices m4d_depth_cloud wrote for those frames (float32 x, y, z in the world frame, uint8 r, g, b, a; whatever
+ * stride, depth range and multi-view filter made them) and nothing is recomputed from depth.  Every accumulator is an unsigned
+ * 64-bit integer, so the map does not depend on the order in which threads arrive and can be compared bit for bit.
+ *
+ * Per vertex, voxel = the float32 edge length widened to double:
+ *   a non-finite x, y or z                                            : dropped_range += 1
+ *   gx = (double) x / voxel,  ix = floor(gx);  ix < -2^20 or >= 2^20  : dropped_range += 1        (likewise y, z)
+ *   ox = min((int) floor((gx - ix) * 256.0), 255)      in 0..255 (the minimum only acts where gx - ix rounds to 1.0: a negative
+ *                                                      gx closer to zero than 2^-54)
+ *   key = ((ix + 2^20) << 42) | ((iy + 2^20) << 21) | (iz + 2^20);   the empty slot is all ones, which no key is
+ *   the voxel's record: n += 1, sx += ox, sy += oy, sz += oz, sr += r, sg += g, sb += b;
+ *   old = atomic max(last_stamp, stamp);  old < stamp : frames += 1     -- exactly one arrival per voxel and call sees that, so
+ *   frames is the number of distinct stamps (frames) that observed the voxel, whatever the order.
+ *
+ * State: one buffer of m4d_voxel_map_state_words(b, L) unsigned 64-bit words, 8-byte aligned:
+ *   words [4 s, 4 s + 4)                     : the statistics of sample s -- observations (vertices read), dropped_range,
+ *                                              dropped_full, occupied (slots claimed);
+ *   words 4 b + (s 2^L + slot) 10 + 0 .. 9   : the record of `slot` of sample s -- key, n, sx, sy, sz, sr, sg, sb, last_stamp,
+ *                                              frames.  An empty record is key = all ones and nine zeros.
+ * The table of a sample is an open-addressing table of 2^L slots, L in 6..26, with linear probing from the top L bits of
+ * key * 0x9E3779B97F4A7C15 (mod 2^64); 80 bytes per slot: 168 MB per sample at L = 21.  A key lives in one slot only; which one
+ * depends on the arrival order, the record's content does not.
+ *
+ * m4d_voxel_map_integrate: vertices [b, cap, 16 bytes] and counts [b] int32 as m4d_depth_cloud left them on the device (a count
+ * is clamped to 0..cap); stamp >= 1, the same for the whole call.  One launch, one thread per vertex.  Keys are read and claimed
+ * with agent-scope atomics only (a load, a compare-and-swap), the sums are agent-scope atomic adds.  The probe of a vertex takes
+ * at most 128 trips; a vertex whose probe runs out, or that meets an empty slot while `occupied` has reached 3/4 of the slots, is
+ * counted in dropped_full and stored nowhere (claims already on their way when the mark is reached still land: occupied may pass
+ * the mark by the number of those).  Nothing waits for another thread and no loop depends on what the table holds.  Lanes of a
+ * wave that follow each other with one key are summed in registers first and their first lane issues the atomics: integer sums,
+ * the same bits.  observations = n summed over the table + dropped_range + dropped_full, always.
+ * A batch launch leaves in the table of sample s what a launch on sample s alone leaves; a sample with counts[s] = 0 is not
+ * touched.
+ *
+ * m4d_voxel_map_extract: the records of sample s with frames >= min_frames, compacted in no particular order:
+ *   keys_out[i] = key (unsigned 64-bit),  vertices_out[i] = 16 bytes like a cloud vertex:
+ *   px = (float) (((double) ix + ((double) sx / (double) n + 0.5) / 256.0) * voxel)        (likewise y, z)
+ *   r = (2 sr + n) / (2 n) in integer arithmetic (the mean rounded half up; likewise g, b),  a = min(frames, 255).
+ *   count: one unsigned 64-bit device word the caller zeroes; the launch adds the number of qualifying records to it.  Records
+ *   beyond out_cap are counted and not written.  One launch; the state is only read.
+ *
+ * m4d_voxel_map_clear: one launch that makes every record of the samples with mask[s] != 0 (mask NULL: of all samples) empty and
+ * their statistics zero.  A fresh state is a cleared one.
+ *
+ * Each returns 1 without a launch for: a NULL pointer (other than mask), b outside 1..65535, L outside 6..26, cap outside
+ * 1..2^24, voxel not > 0 or not finite, stamp < 1, s outside 0..b-1, min_frames < 1, out_cap < 1, state / keys_out / count off 8
+ * bytes, vertices / vertices_out off 16, counts off 4.  Plain launches (capturable).  Additive entry points: ABI 6 unchanged. */
+int m4d_voxel_map_integrate(const void* vertices, const int* counts, int b, int cap, float voxel, long long stamp, void* state,
+                            int log2_slots, void* stream);
+int m4d_voxel_map_extract(const void* state, int b, int log2_slots, int s, int min_frames, float voxel, void* keys_out,
+                          void* vertices_out, long long out_cap, void* count, void* stream);
+int m4d_voxel_map_clear(void* state, const unsigned char* mask, int b, int log2_slots, void* stream);
+/* unsigned 64-bit words of the state, b (4 + 10 * 2^L); -1 for a geometry the entries refuse. */
+long long m4d_voxel_map_state_words(int b, int log2_slots);
+
 /* ---- training summaries (main.py --mode=train --log_dir): float32 maps -> the uint8 images of a TensorBoard event -------- */
 
 /* Up to 16 float32 maps of different sizes -> uint8 images, in one launch.  src, stride, h, w, c, kind and out_offset are

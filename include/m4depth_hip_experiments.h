@@ -22,6 +22,11 @@ void m4d_wino6_set_variant(int variant);
  * (default 0 = none: faster alone on small grids, no gain inside the frame pipeline). */
 void m4d_wino6_set_half_tile_max_workgroups(int max_wg);
 
+/* m4d_voxel_map_integrate (include/m4depth_hip.h) without the in-wave combining of equal keys: every vertex probes the table and
+ * issues its own atomics.  Same arguments, same bits; what tools/bench_voxel_map.py measures the product kernel against. */
+int m4d_voxel_map_integrate_uncombined(const void* vertices, const int* counts, int b, int cap, float voxel, long long stamp,
+                                       void* state, int log2_slots, void* stream);
+
 /* ---- launch tape (csrc/m4d_tape.hip): a recorded sequence of this library's kernel launches, replayed as PLAIN STREAM
  * LAUNCHES from one host loop -- the host-side cost of a hipGraph replay without its effect on concurrent small kernels
  * (DESIGN_HISTORY.md).  Between m4d_tape_begin()

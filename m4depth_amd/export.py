@@ -14,6 +14,10 @@ event has passed.
 With ``cloud_views=K`` a cloud keeps only the pixels that up to K earlier frames of the sample's trajectory confirm
 (``network_ops.depth_views``: a forward-backward reprojection check against a ring of the last K estimates and poses on the
 device); the depth PNG and the panels keep showing the raw estimate.
+
+With ``save_map=VOXEL`` the vertices of every step are also merged, on the device, into one voxel map per sample
+(``network_ops.voxel_map_integrate``: a hash table of integer sums); when a sample's trajectory ends the map is extracted,
+written as ``map.ply`` into the trajectory's directory by a worker thread (``write_map_ply``) and the table cleared.
 """
 from __future__ import annotations
 
@@ -130,6 +134,40 @@ def read_cloud_ply(path):
     return raw[:, :12].copy().view(np.float32), raw[:, 12:].copy(), pose
 
 
+_MAP_FIELDS = ("voxel", "min_frames", "observations", "dropped_range", "dropped_full", "occupied")
+
+
+def write_map_ply(path, vertices, voxel, min_frames, stats):
+    """The voxel map of a trajectory as a binary PLY file with the per-frame clouds' property list (``read_cloud_ply`` reads
+    it): ``vertices`` [n,16] uint8 as ``network_ops.voxel_map_extract`` returns them, one per voxel in ascending key order --
+    float x, y, z (the mean position of the voxel's points), uchar red, green, blue (their mean colour) and alpha = the number
+    of frames that saw the voxel, capped at 255.  The map lives in the world frame: the pose comment is the identity.
+    ``comment voxel_map`` holds the edge length, ``min_frames`` and the map's statistics ``stats`` (observations,
+    dropped_range, dropped_full, occupied), as name value pairs."""
+    body = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1, 16)
+    info = dict(stats, voxel="%.9g" % np.float32(voxel), min_frames=int(min_frames))
+    header = ["ply", "format binary_little_endian 1.0", "comment pose 1 0 0 0 0 0 0",
+              "comment voxel_map " + " ".join("%s %s" % (k, info[k]) for k in _MAP_FIELDS),
+              "element vertex %d" % len(body)] + _PLY_PROPERTIES + ["end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(body.data)
+
+
+def read_map_ply(path):
+    """A ``map.ply`` of ``PredictionWriter(save_map=...)``: (xyz float32 [n,3], rgba uint8 [n,4], info) with ``info`` the
+    ``comment voxel_map`` line as a dict -- voxel (float) and min_frames, observations, dropped_range, dropped_full, occupied
+    (int)."""
+    xyz, rgba, pose = read_cloud_ply(path)
+    with open(path, "rb") as fh:
+        head = fh.read(4096).split(b"end_header")[0].decode("ascii").splitlines()
+    lines = [l.split()[2:] for l in head if l.startswith("comment voxel_map ")]
+    if len(lines) != 1 or tuple(lines[0][0::2]) != _MAP_FIELDS or not np.array_equal(pose, [1, 0, 0, 0, 0, 0, 0]):
+        raise ValueError(f"{path}: not a voxel map of PredictionWriter")
+    info = {k: (float(v) if k == "voxel" else int(v)) for k, v in zip(lines[0][0::2], lines[0][1::2])}
+    return xyz, rgba, info
+
+
 def read_conf_png(path, views):
     """A ``<name>_conf.png`` of ``PredictionWriter(save_conf=True)`` as the counts it was made of: uint8 [h,w], the number of
     earlier frames (0..``views``) that confirmed the pixel; the file holds ``count * 255 // views``."""
@@ -148,7 +186,7 @@ def read_conf_png(path, views):
 
 
 class _Slot:
-    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False):
+    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False, cloud_host=True):
         self.depth_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
         self.depth_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
         self.panels_d = self.panels_h = None
@@ -158,10 +196,11 @@ class _Slot:
         self.cloud_d = None
         if cloud_cap:
             self.cloud_d = torch.empty((b, cloud_cap, 16), dtype=torch.uint8, device=dev)
-            self.cloud_h = torch.empty((b, cloud_cap, 16), dtype=torch.uint8).pin_memory()
             self.counts_d = torch.empty(b, dtype=torch.int32, device=dev)
-            self.counts_h = torch.empty(b, dtype=torch.int32).pin_memory()
-            self.pose_h = torch.empty((b, 7), dtype=torch.float64).pin_memory()
+            if cloud_host:                                 # a writer of maps alone keeps the vertices on the device
+                self.cloud_h = torch.empty((b, cloud_cap, 16), dtype=torch.uint8).pin_memory()
+                self.counts_h = torch.empty(b, dtype=torch.int32).pin_memory()
+                self.pose_h = torch.empty((b, 7), dtype=torch.float64).pin_memory()
             self.reset_d = torch.empty(b, dtype=torch.uint8, device=dev)
             self.reset_h = torch.empty(b, dtype=torch.uint8).pin_memory()
         self.conf_d = self.conf_h = None
@@ -194,11 +233,24 @@ class PredictionWriter:
     writer then owns the ring of the last K + 1 estimates and poses, (K+1) b h w floats.  The rule is strict: the first
     ``cloud_min_views`` frames of every trajectory give clouds without vertices.  ``save_conf=True`` also writes
     ``<name>_conf.png``: 8-bit grey, ``confirming views * 255 // K`` (``read_conf_png``).  ``cloud_kept`` / ``cloud_cap`` sum the
-    vertices written and the vertices a cloud could hold at most, over the frames the workers have finished."""
+    vertices written and the vertices a cloud could hold at most, over the frames the workers have finished.
+
+    ``save_map=VOXEL`` (metres; with or without ``cloud``) also writes ``<directory of the trajectory's frames>/map.ply``: the
+    vertices of the trajectory's clouds merged into one vertex per occupied voxel (include/m4depth_hip.h, ``write_map_ply``).
+    After ``depth_cloud`` of every submit ``network_ops.voxel_map_integrate`` adds the step's compacted vertices -- made with
+    ``cloud_step``, [near, far] and the ``cloud_views`` filter, as they lie in the slot's device buffer -- to the sample's hash
+    table of 2^``map_slots_log2`` slots (168 MB per sample at the default 21), stamped with the writer's step counter.  A
+    sample whose host-side ``reset`` flag is set has its map extracted (voxels at least ``map_min_frames`` frames saw), handed
+    to a worker thread and cleared before the new frame goes in, and ``close()`` does that for every open trajectory: the loop
+    waits for the device once per finished trajectory, never per frame.  The map needs the world frame, host-side reset flags
+    (a device mask raises ValueError) and names with one directory per trajectory (``FrameNamer``'s).  Without ``cloud`` the
+    cloud launches still run, their buffers stay on the device and no ``_cloud.ply`` is written.  ``maps``, ``map_voxels``,
+    ``map_dropped_range`` and ``map_dropped_full`` sum over the maps handed to the workers: a ``map_dropped_full`` > 0 says
+    that ``map_slots_log2`` is too small for the scene."""
 
     def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
                  encode=True, cloud=False, cloud_step=2, cloud_frame="world", cloud_views=0, cloud_min_views=None,
-                 cloud_tol=(1.0, 0.01), save_conf=False):
+                 cloud_tol=(1.0, 0.01), save_conf=False, save_map=None, map_min_frames=2, map_slots_log2=21):
         if fmt not in FORMATS:
             raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
         panels = tuple(panels)
@@ -213,7 +265,16 @@ class PredictionWriter:
         cloud_views = int(cloud_views)
         if not 0 <= cloud_views <= nops.VIEWS_MAX:
             raise ValueError(f"cloud_views must be 0 (off) or 1..{nops.VIEWS_MAX}, got {cloud_views}")
-        if cloud_views and not cloud:
+        save_map = None if save_map is None else float(np.float32(save_map))
+        map_min_frames = 2 if map_min_frames is None else map_min_frames           # None: the default, as for cloud_min_views
+        map_slots_log2 = 21 if map_slots_log2 is None else map_slots_log2
+        if save_map is not None and not (0 < save_map < float("inf")):
+            raise ValueError(f"save_map: the voxel edge must be a finite length > 0, got {save_map}")
+        if save_map is not None and cloud_frame != "world":
+            raise ValueError("save_map needs cloud_frame='world': a map merges the frames of a trajectory in one frame")
+        if save_map is not None and (int(map_min_frames) < 1 or not 6 <= int(map_slots_log2) <= 26):
+            raise ValueError(f"need map_min_frames >= 1 and map_slots_log2 in 6..26, got {map_min_frames}, {map_slots_log2}")
+        if cloud_views and not (cloud or save_map is not None):
             raise ValueError("cloud_views needs cloud=True: the check runs on the clouds' pose chain")
         if save_conf and not cloud_views:
             raise ValueError("save_conf needs cloud_views >= 1")
@@ -231,6 +292,12 @@ class PredictionWriter:
         self._views_n = self._views_depth = None           # [b,h,w] counts (without save_conf) and the filtered copy
         self.cloud_kept = self.cloud_cap = 0               # vertices written / vertices the clouds could hold, finished frames
         self._pose = None                                  # [b,7] float64 device state of the cloud: camera-to-world poses
+        self.save_map, self.map_min_frames, self.map_slots_log2 = save_map, int(map_min_frames), int(map_slots_log2)
+        self._geometry3d = self.cloud or save_map is not None      # the pose chain and the cloud launches run
+        self._map = None                                   # network_ops.voxel_map_state, allocated with the slots
+        self._map_dirs = None                              # per sample: the directory of its open trajectory
+        self._step = 0                                     # submits so far: the stamp of a step's vertices
+        self.maps = self.map_voxels = self.map_dropped_range = self.map_dropped_full = 0
         self.out_dir, self.fmt, self.panels = str(out_dir), fmt, panels
         self.near, self.far, self.err_max = float(near), float(far), float(err_max)
         self.n_slots, self.compress_level, self.encode = int(slots), int(compress_level), bool(encode)
@@ -260,17 +327,54 @@ class PredictionWriter:
     def _allocate(self, est):
         b, h, w = est.shape[:3]
         self._geometry = (b, h, w)
-        cap = nops.cloud_capacity(h, w, self.cloud_step) if self.cloud else 0
-        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf) for _ in range(self.n_slots)]
+        cap = nops.cloud_capacity(h, w, self.cloud_step) if self._geometry3d else 0
+        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf, self.cloud)
+                       for _ in range(self.n_slots)]
+        if self.save_map is not None:
+            self._map = nops.voxel_map_state(b, self.map_slots_log2, est.device)
         if any(p != "rgb" for p in self.panels):
             self._lut = torch.from_numpy(default_lut()).to(est.device)
         for i in range(self.n_slots):
             self._free.put(i)
 
-    def _submit_cloud(self, slot, est, rgb, rot, trans, camera, reset):
-        """The cloud of one step into ``slot``, on the current stream: pose update, compaction, copies."""
+    def _finish_map(self, s):
+        """The map of sample ``s``'s open trajectory to a worker thread; the caller clears the table on the same stream."""
+        keys, vertices, stats = nops.voxel_map_extract(self._map, s, self.map_min_frames, self.save_map)   # the one wait
+        host = torch.empty(vertices.shape, dtype=torch.uint8)
+        if len(keys):                                      # (an empty map is written too: a trajectory nothing survived of)
+            host = host.pin_memory()
+            host.copy_(vertices, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        self.maps += 1
+        self.map_voxels += len(keys)
+        self.map_dropped_range += stats["dropped_range"]
+        self.map_dropped_full += stats["dropped_full"]
+        self._pool.submit(self._work_map, os.path.join(self._map_dirs[s], "map.ply"), host, event, stats)
+
+    def _work_map(self, rel_path, host, event, stats):
+        try:
+            event.synchronize()
+            if self.encode:
+                path = os.path.join(self.out_dir, rel_path)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                write_map_ply(path, host.numpy(), self.save_map, self.map_min_frames, stats)
+        except BaseException as e:
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+
+    def _submit_cloud(self, slot, est, rgb, rot, trans, camera, reset, names):
+        """The cloud of one step into ``slot``, on the current stream: pose update, compaction, copies; with ``save_map`` the
+        maps of the trajectories that ended, then the step's vertices into the maps."""
         if rgb is None or rot is None or trans is None or camera is None:
-            raise ValueError("a writer with cloud=True needs rgb, rot, trans and camera at every submit")
+            raise ValueError("a writer with cloud=True or save_map needs rgb, rot, trans and camera at every submit")
+        if self.save_map is not None:
+            if torch.is_tensor(reset) and reset.is_cuda:
+                raise ValueError("save_map needs host-side reset flags: which trajectory ended is decided on the host")
+            dirs = [os.path.dirname(n) for n in names]
+            if len(set(dirs)) != len(dirs):
+                raise ValueError(f"save_map needs names with one directory per sample and trajectory, got {list(names)}")
         first = self._pose is None
         if first:
             self._pose = torch.empty((est.shape[0], 7), dtype=torch.float64, device=est.device)
@@ -290,6 +394,10 @@ class PredictionWriter:
                 slot.reset_h.numpy()[:] = reset
                 slot.reset_d.copy_(slot.reset_h, non_blocking=True)
                 mask = slot.reset_d
+                if self.save_map is not None and reset.any():
+                    for s in np.nonzero(reset)[0]:         # the trajectories that ended with the previous frame
+                        self._finish_map(int(s))
+                    nops.voxel_map_clear(self._map, mask)
         nops.pose_accumulate(rot, trans, self._pose, reset=mask, force_all=first)
         if self.cloud_views:                               # the clouds see the filtered copy; PNG and panels the estimate
             b, h, w = est.shape[:3]
@@ -306,9 +414,13 @@ class PredictionWriter:
                 slot.conf_h.copy_(slot.conf_d, non_blocking=True)
         nops.depth_cloud(est, rgb, camera["f"], camera["c"], step=self.cloud_step, near=self.near, far=self.far,
                          pose=self._pose if self.cloud_frame == "world" else None, vertices=slot.cloud_d, counts=slot.counts_d)
-        slot.cloud_h.copy_(slot.cloud_d, non_blocking=True)
-        slot.counts_h.copy_(slot.counts_d, non_blocking=True)
-        slot.pose_h.copy_(self._pose, non_blocking=True)
+        if self.save_map is not None:
+            nops.voxel_map_integrate(slot.cloud_d, slot.counts_d, self.save_map, self._step, self._map)
+            self._map_dirs = dirs
+        if self.cloud:
+            slot.cloud_h.copy_(slot.cloud_d, non_blocking=True)
+            slot.counts_h.copy_(slot.counts_d, non_blocking=True)
+            slot.pose_h.copy_(self._pose, non_blocking=True)
 
     def submit(self, est, names, gt=None, rgb=None, rot=None, trans=None, camera=None, reset=None):
         """``est`` [b,h,w,1] (+ ``gt`` / ``rgb`` as the panels need) of one step; ``names``: b relative paths without suffix.
@@ -329,8 +441,9 @@ class PredictionWriter:
             slot.depth_h.copy_(slot.depth_d, non_blocking=True)
             if slot.panels_d is not None:
                 slot.panels_h.copy_(slot.panels_d, non_blocking=True)
-            if self.cloud:
-                self._submit_cloud(slot, est, rgb, rot, trans, camera, reset)
+            self._step += 1
+            if self._geometry3d:
+                self._submit_cloud(slot, est, rgb, rot, trans, camera, reset, names)
             slot.event.record()
         except BaseException:
             self._free.put(index)
@@ -386,6 +499,15 @@ class PredictionWriter:
         if self._closed:
             return
         self._closed = True
+        try:
+            if self._map_dirs is not None:                 # the open trajectories end here
+                for s in range(len(self._map_dirs)):
+                    self._finish_map(s)
+                self._map_dirs = None
+        except BaseException as e:
+            with self._lock:
+                if self._error is None:
+                    self._error = e
         if self._slots is not None:
             for _ in range(self.n_slots):
                 self._free.get()

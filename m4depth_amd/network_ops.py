@@ -721,7 +721,87 @@ def depth_views(depth, cam_f, cam_c, pose, state, reset=None, force_all=False, t
     return n_views, depth_f
 
 
-SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                     # the `kind` argument of m4d_summary_images
+VOXEL_MAP_STATS = ("observations", "dropped_range", "dropped_full", "occupied")   # the statistics words of m4d_voxel_map_*
+VOXEL_MAP_RECORD = 10                                           # words of a table record: key, n, sx sy sz, sr sg sb, last_stamp, frames
+
+
+def voxel_map_state(b, slots_log2, device):
+    """The state of ``b`` voxel maps with 2^``slots_log2`` slots each (include/m4depth_hip.h), cleared: {"words": the int64
+    buffer the library works on, "stats": its [b,4] head, "table": its [b, 2^L, 10] records, "b", "slots_log2", and the scratch
+    of ``voxel_map_extract`` once it has run}.  The words are unsigned on the device; torch shows them as int64."""
+    b, slots_log2 = int(b), int(slots_log2)
+    words = int(lib.m4d_voxel_map_state_words(b, slots_log2))
+    if words < 0:
+        raise ValueError(f"voxel_map_state: need b in 1..65535 and slots_log2 in 6..26, got b {b}, slots_log2 {slots_log2}")
+    buf = torch.empty(words, dtype=torch.int64, device=device)
+    state = {"words": buf, "stats": buf[:4 * b].view(b, 4), "table": buf[4 * b:].view(b, 1 << slots_log2, VOXEL_MAP_RECORD),
+             "b": b, "slots_log2": slots_log2}
+    return voxel_map_clear(state)
+
+
+def _voxel_map_check(state, voxel=None):
+    b, slots_log2 = int(state["b"]), int(state["slots_log2"])
+    if state["words"].numel() != lib.m4d_voxel_map_state_words(b, slots_log2):
+        raise ValueError(f"state: not a voxel_map_state of {b} samples with 2^{slots_log2} slots")
+    if voxel is not None and not (float(voxel) > 0 and float(voxel) < float("inf")):
+        raise ValueError(f"voxel must be a finite edge length > 0, got {voxel}")
+    return b, slots_log2
+
+
+def voxel_map_integrate(vertices, counts, voxel, stamp, state):
+    """The compacted vertices of one step into the maps (m4d_voxel_map_integrate): ``vertices`` [b,cap,16] uint8 and ``counts``
+    [b] int32 as ``depth_cloud`` left them on the device, ``voxel`` the edge length in metres, ``stamp`` >= 1 the step's number
+    (the frames a voxel was seen in are counted by distinct stamps).  One launch, nothing synchronises."""
+    b, slots_log2 = _voxel_map_check(state, voxel)
+    if vertices.dim() != 3 or vertices.shape[0] != b or vertices.shape[2] != 16 or tuple(counts.shape) != (b,):
+        raise ValueError(f"expected vertices [{b},cap,16] and counts [{b}], got {tuple(vertices.shape)} and {tuple(counts.shape)}")
+    if int(stamp) < 1:
+        raise ValueError(f"stamp must be >= 1, got {stamp}")
+    check(lib.m4d_voxel_map_integrate(dptr(vertices, "vertices", torch.uint8), dptr(counts, "counts", torch.int32), b,
+                                      vertices.shape[1], float(voxel), int(stamp), dptr(state["words"], "state", torch.int64),
+                                      slots_log2, stream_ptr()), "m4d_voxel_map_integrate")
+    return state
+
+
+def voxel_map_extract(state, s, min_frames, voxel):
+    """The map of sample ``s`` (m4d_voxel_map_extract): (keys [n] int64 ascending, vertices [n,16] uint8, stats) -- one vertex
+    per voxel that at least ``min_frames`` frames observed, sorted by key on the device (``torch.sort`` + a gather); ``stats``:
+    the sample's {observations, dropped_range, dropped_full, occupied} as Python integers.  Waits for the device once, to
+    read the count and the statistics.  Once per trajectory: not a hot path."""
+    b, slots_log2 = _voxel_map_check(state, voxel)
+    s, min_frames = int(s), int(min_frames)
+    if not 0 <= s < b or min_frames < 1:
+        raise ValueError(f"need s in 0..{b - 1} and min_frames >= 1, got s {s}, min_frames {min_frames}")
+    dev, cap = state["words"].device, 1 << slots_log2
+    if "keys_out" not in state:                                 # every slot may qualify: sized once, kept with the state
+        state["keys_out"] = torch.empty(cap, dtype=torch.int64, device=dev)
+        state["vertices_out"] = torch.empty((cap, 16), dtype=torch.uint8, device=dev)
+        state["count"] = torch.empty(1, dtype=torch.int64, device=dev)
+    state["count"].zero_()
+    check(lib.m4d_voxel_map_extract(dptr(state["words"], "state", torch.int64), b, slots_log2, s, min_frames, float(voxel),
+                                    dptr(state["keys_out"], "keys_out", torch.int64),
+                                    dptr(state["vertices_out"], "vertices_out", torch.uint8), cap,
+                                    dptr(state["count"], "count", torch.int64), stream_ptr()), "m4d_voxel_map_extract")
+    host = torch.cat([state["count"], state["stats"][s]]).cpu().tolist()          # the one wait
+    n = host[0]
+    keys, order = torch.sort(state["keys_out"][:n])             # keys stay below 2^63: int64 order is the unsigned order
+    return keys, state["vertices_out"][:n][order], dict(zip(VOXEL_MAP_STATS, host[1:]))
+
+
+def voxel_map_clear(state, mask=None):
+    """Empties the maps of the samples with ``mask[s]`` set (uint8 / bool [b] device tensor; None: all of them) and zeroes
+    their statistics (m4d_voxel_map_clear).  One launch."""
+    b, slots_log2 = _voxel_map_check(state)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (b,):
+            raise ValueError(f"mask: expected a uint8 / bool [{b}] device tensor")
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    check(lib.m4d_voxel_map_clear(dptr(state["words"], "state", torch.int64), dptr(mask, "mask", torch.uint8), b, slots_log2,
+                                  stream_ptr()), "m4d_voxel_map_clear")
+    return state
+
+
+SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                    # the `kind` argument of m4d_summary_images
 SUMMARY_MAX_MAPS = 16
 
 

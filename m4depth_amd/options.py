@@ -107,6 +107,18 @@ def build_parser():
                         "difference (default 1.0 0.01: MVSNet's fusion thresholds, untuned for this network)")
     p.add_argument("--save_conf", action="store_true", default=argparse.SUPPRESS,
                    help="--cloud_views: also write <frame>_conf.png, 8-bit grey = confirming frames * 255 // K")
+    # like the multi-view options above: absent from the namespace until given
+    p.add_argument("--save_map", type=float, default=argparse.SUPPRESS, metavar="VOXEL",
+                   help="--save_dir: also write DIR/s<slot>_t<trajectory>/map.ply, ONE fused map per trajectory -- the vertices "
+                        "of its clouds (as --cloud_stride, --save_range and --cloud_views make them, with or without "
+                        "--save_cloud) merged on the GPU into one vertex per occupied voxel of VOXEL metres: mean position, "
+                        "mean colour, alpha = frames that saw it.  --cloud_views is the recommended companion: without it "
+                        "every depth-edge pixel lands in the map")
+    p.add_argument("--map_min_frames", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="--save_map: a voxel is written only if at least N frames of the trajectory put a point in it (default 2)")
+    p.add_argument("--map_slots_log2", type=int, default=argparse.SUPPRESS, metavar="L",
+                   help="--save_map: 2^L hash-table slots per sample, 16..26 (default 21: 168 MB per sample; a map stops "
+                        "taking new voxels at 3/4 of them, and the closing line of the run counts what was dropped)")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--loss", default="supervised", choices=["supervised", "photometric"],
                    help="train: supervised = the reference's log-depth L1 against ground truth; photometric = the reprojection "
@@ -276,21 +288,40 @@ def check_save_args(parser, args):
     from .export import PANELS
     others = [f for f in ("save_format", "save_panels", "save_range", "save_err_max") if getattr(args, f) is not None]
     others += [f for f in ("save_cloud",) if args.save_cloud]
+    # the voxel map: absent from the namespace until given; it runs on the clouds' vertices, so the clouds' options serve it too
+    for f in ("save_map", "map_min_frames", "map_slots_log2"):
+        setattr(args, f, getattr(args, f, None))
+    map_others = [f for f in ("map_min_frames", "map_slots_log2") if getattr(args, f) is not None]
+    if map_others and args.save_map is None:
+        parser.error("--%s needs --save_map" % map_others[0])
+    if args.save_map is not None:
+        others.append("save_map")
+        if not (0 < args.save_map < float("inf")):
+            parser.error("--save_map VOXEL needs a finite edge length > 0")
+        if args.cloud_frame == "camera":
+            parser.error("--save_map needs --cloud_frame world: a map merges the frames of a trajectory in one frame")
+        if args.map_min_frames is not None and args.map_min_frames < 1:
+            parser.error("--map_min_frames must be >= 1")
+        if args.map_slots_log2 is not None and not 16 <= args.map_slots_log2 <= 26:
+            parser.error("--map_slots_log2 must be in 16..26")
+        args.map_min_frames = 2 if args.map_min_frames is None else args.map_min_frames
+        args.map_slots_log2 = 21 if args.map_slots_log2 is None else args.map_slots_log2
+    geometry = args.save_cloud or args.save_map is not None
     cloud_others = [f for f in ("cloud_stride", "cloud_frame") if getattr(args, f) is not None]
-    if args.save_dir is not None and cloud_others and not args.save_cloud:
+    if args.save_dir is not None and cloud_others and not geometry:
         parser.error("--%s needs --save_cloud" % cloud_others[0])
     others += cloud_others
     if args.cloud_stride is not None and args.cloud_stride < 1:
         parser.error("--cloud_stride must be >= 1")
     args.cloud_stride = 2 if args.cloud_stride is None else args.cloud_stride
     args.cloud_frame = args.cloud_frame or "world"
-    # the multi-view check runs on the clouds' pose chain: every option of it needs --save_cloud (and so --save_dir)
+    # the multi-view check runs on the clouds' pose chain: every option of it needs --save_cloud or --save_map (and so --save_dir)
     for f in ("cloud_views", "cloud_min_views", "cloud_tol"):
         setattr(args, f, getattr(args, f, None))
     args.save_conf = bool(getattr(args, "save_conf", False))
     view_others = [f for f in ("cloud_views", "cloud_min_views", "cloud_tol") if getattr(args, f) is not None]
     view_others += [f for f in ("save_conf",) if args.save_conf]
-    if view_others and not args.save_cloud:
+    if view_others and not geometry:
         parser.error("--%s needs --save_cloud" % view_others[0])
     if args.cloud_views is not None and not 0 <= args.cloud_views <= 8:
         parser.error("--cloud_views must be 0 (off) or 1..8")
