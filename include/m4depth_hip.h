@@ -1048,6 +1048,80 @@ int m4d_voxel_map_clear(void* state, const unsigned char* mask, int b, int log2_
 /* unsigned 64-bit words of the state, b (4 + 10 * 2^L); -1 for a geometry the entries refuse. */
 long long m4d_voxel_map_state_words(int b, int log2_slots);
 
+/* ---- TSDF surface meshes (main.py --save_dir --save_mesh VOXEL): one triangle mesh per trajectory (csrc/m4d_tsdf.hip) ---- */
+
+/* Truncated-signed-distance fusion (Curless & Levoy 1996, KinectFusion) on a hashed voxel grid (Niessner et al. 2013) of the
+ * depth maps of a trajectory, and a naive-surface-nets extraction: one vertex per sign-changing cell, one quad per sign-changing
+ * grid edge.  Inputs as m4d_depth_cloud takes them: depth [b,h,w,1] / rgb [b,h,w,3] float32 at a batch stride in ELEMENTS,
+ * cam_f, cam_c [b,2], pose [b,7] float64 camera-to-world (qw qx qy qz tx ty tz, used as stored; required).  voxel = the float32
+ * edge length widened to double, K = trunc (2..8), T = (float) ((double) K * voxel) the truncation distance.  R = R(q) as
+ * get_rot_mat writes it, in float64 (m4d_depth_cloud's expressions).  One IEEE rounding per operation throughout.
+ *
+ * State: one buffer of m4d_tsdf_state_words(b, L) unsigned 64-bit words, 8-byte aligned, structure of arrays:
+ *   words [4 s, 4 s + 4)                        : the statistics of sample s -- occupied, dropped_range, dropped_full, updates;
+ *   words 4 b + s 2^L + slot                    : keys[s][slot], the voxel map's key ((ix + 2^20) << 42) | ((iy + 2^20) << 21) |
+ *                                                 (iz + 2^20); the empty slot is all ones;
+ *   bytes 8 (4 b + b 2^L) + 24 (s 2^L + slot)   : recs[s][slot] -- float32 S (the sum of the truncated signed distances in units
+ *                                                 of T), then uint32 n, sr, sg, sb, nc.  An empty record is all zero.
+ * 32 bytes per slot: 134 MB per sample at L = 22.  The table is the voxel map's: linear probing from the top L bits of
+ * key * 0x9E3779B97F4A7C15, at most 128 trips, no empty slot claimed once `occupied` has reached 3/4 of the slots.
+ * A sample whose pose holds a non-finite number is skipped by both per-frame launches: nothing of it is read or written.
+ *
+ * m4d_tsdf_allocate: one launch, one thread per pixel (every pixel: no stride).  A pixel with d finite and near <= d <= far:
+ *   ax = ((col + 0.5f) - cx) / fx,  ay = ((row + 0.5f) - cy) / fy                      (float32, then widened)
+ *   for k = -2K .. 2K:  z = (double) d + (double) k * (voxel * 0.5);  only z > 0;   X = ax * z, Y = ay * z
+ *     Pw[i] = ((R[i][0] X + R[i][1] Y) + R[i][2] z) + t[i];   cell[i] = floor(Pw[i] / voxel)
+ *     a cell outside [-2^20, 2^20) (or not finite): dropped_range += 1.  Otherwise the key is claimed: agent-scope load and
+ *     compare-and-swap; a claim writes the key only and adds 1 to occupied.  A sample whose probe runs out, or that meets an
+ *     empty slot at the 3/4 mark, adds 1 to dropped_full (only "zero or not" is contract for that counter).
+ *   A thread does not probe again for the key it has just found (consecutive samples of a ray share voxels): the SET of keys is
+ *   the same, and it is the same for every schedule while the table stays below the mark.
+ *
+ * m4d_tsdf_integrate: one launch after allocate, every slot of every sample has one thread; a record is touched by its owner only, so S does
+ *   not depend on the schedule.  Per non-empty slot with cell i:
+ *   D[j] = ((double) i[j] + 0.5) * voxel - t[j];   X[j] = (R[0][j] D[0] + R[1][j] D[1]) + R[2][j] D[2];   z = X[2] > 0 required
+ *   u = (fx X[0]) / z + cx,  v = (fy X[1]) / z + cy   (f, c widened);  0 <= u < w and 0 <= v < h required (false for NaN)
+ *   d = depth[(int) floor(v)][(int) floor(u)], finite and near <= d <= far required;   sdf = (float) ((double) d - z)
+ *   sdf < -T: nothing.  Otherwise S = S + fminf(sdf, T) / T, n += 1, and when sdf <= T also sr, sg, sb += the pixel's colour
+ *   under m4d_depth_export's rgb rule and nc += 1.  updates += the records updated (one atomic add per workgroup, which walks its slots in a loop).
+ *
+ * m4d_tsdf_extract_vertices: sample s, one thread per slot; the state is only read.  The slot's voxel k is the min corner of the
+ *   cell whose corners are the voxel centres k + {0,1}^3, corner c = dx | dy << 1 | dz << 2.  The cell is valid when all eight
+ *   exist (read-only probe, the insertion's sequence, ending at an empty slot) with n >= min_frames.  D_c = S / (float) n;
+ *   inside = D_c < 0.  A valid cell with both signs emits (key, 16-byte vertex):
+ *   edges in the order axis x, y, z and, within axis a, the corners c without bit a ascending, edge (c, c | 1 << a); for every
+ *   edge with inside(c) != inside(c | 1 << a):  t = D_a / (D_a - D_b);  sum[a] += t,  sum[j != a] += (float) bit j of c;
+ *   local[j] = sum[j] / (float) edges;   p[j] = (float) ((((double) i[j] + 0.5) + (double) local[j]) * voxel)     (float32 sums)
+ *   r = (2 SUM sr + SUM nc) / (2 SUM nc) over the eight corners in integer arithmetic (0 when SUM nc = 0; likewise g, b),
+ *   a = min(255, min n).  count: one unsigned 64-bit device word the caller zeroes; records beyond out_cap are counted only.
+ *
+ * m4d_tsdf_extract_faces: the same launch shape.  Per voxel k with n >= min_frames and axis a (0 x, 1 y, 2 z; b = (a+1) % 3,
+ *   c = (a+2) % 3): when k + e_a exists with n >= min_frames and inside(k) != inside(k + e_a), one quad of five 64-bit words:
+ *   word 0 = a | (inside(k) ? 0 : 4);  words 1..4 = the cell keys k, k - e_b, k - e_b - e_c, k - e_c when inside(k), and in
+ *   the reverse order otherwise (the owner key k is word 1 or word 4; the face's normal points from inside to outside).
+ *   Nothing is emitted when k[a] is the largest index or k[b] or k[c] the smallest.  Whether the four cells have vertices is
+ *   the host's business.  count / out_cap (in quads) as above.
+ *
+ * m4d_tsdf_clear: one launch; the samples with mask[s] != 0 (mask NULL: all) get empty keys, zero records and zero statistics.
+ *
+ * Each returns 1 without a launch for: a NULL pointer (other than mask), b outside 1..65535, L outside 6..26, h or w < 1,
+ * h*w > 2^24, far <= near (NaN included), voxel not > 0 or not finite, trunc outside 2..8, a stride smaller than an image, s
+ * outside 0..b-1, min_frames < 1, out_cap < 1, a float pointer off 4 bytes, pose / state / keys_out / quads_out / count off 8,
+ * vertices_out off 16.  Plain launches (capturable).  Additive entry points: ABI 6 unchanged. */
+int m4d_tsdf_allocate(const float* depth, long long depth_stride, const float* cam_f, const float* cam_c, const double* pose,
+                      int b, int h, int w, float near, float far, float voxel, int trunc, void* state, int log2_slots,
+                      void* stream);
+int m4d_tsdf_integrate(const float* depth, long long depth_stride, const float* rgb, long long rgb_stride, const float* cam_f,
+                       const float* cam_c, const double* pose, int b, int h, int w, float near, float far, float voxel, int trunc,
+                       void* state, int log2_slots, void* stream);
+int m4d_tsdf_extract_vertices(const void* state, int b, int log2_slots, int s, int min_frames, float voxel, void* keys_out,
+                              void* vertices_out, long long out_cap, void* count, void* stream);
+int m4d_tsdf_extract_faces(const void* state, int b, int log2_slots, int s, int min_frames, void* quads_out, long long out_cap,
+                           void* count, void* stream);
+int m4d_tsdf_clear(void* state, const unsigned char* mask, int b, int log2_slots, void* stream);
+/* unsigned 64-bit words of the state, b (4 + 4 * 2^L); -1 for a geometry the entries refuse. */
+long long m4d_tsdf_state_words(int b, int log2_slots);
+
 /* ---- training summaries (main.py --mode=train --log_dir): float32 maps -> the uint8 images of a TensorBoard event -------- */
 
 /* Up to 16 float32 maps of different sizes -> uint8 images, in one launch.  src, stride, h, w, c, kind and out_offset are

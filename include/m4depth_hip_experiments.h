@@ -27,6 +27,12 @@ void m4d_wino6_set_half_tile_max_workgroups(int max_wg);
 int m4d_voxel_map_integrate_uncombined(const void* vertices, const int* counts, int b, int cap, float voxel, long long stamp,
                                        void* state, int log2_slots, void* stream);
 
+/* m4d_tsdf_allocate (include/m4depth_hip.h) without the per-thread skip of a key that equals the previous one: every sample of
+ * every ray probes the table.  Same arguments, same key set; what tools/bench_tsdf_mesh.py measures the product kernel against. */
+int m4d_tsdf_allocate_plain(const float* depth, long long depth_stride, const float* cam_f, const float* cam_c, const double* pose,
+                            int b, int h, int w, float near, float far, float voxel, int trunc, void* state, int log2_slots,
+                            void* stream);
+
 /* ---- launch tape (csrc/m4d_tape.hip): a recorded sequence of this library's kernel launches, replayed as PLAIN STREAM
  * LAUNCHES from one host loop -- the host-side cost of a hipGraph replay without its effect on concurrent small kernels
  * (DESIGN_HISTORY.md).  Between m4d_tape_begin()

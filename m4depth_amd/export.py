@@ -18,6 +18,11 @@ device); the depth PNG and the panels keep showing the raw estimate.
 With ``save_map=VOXEL`` the vertices of every step are also merged, on the device, into one voxel map per sample
 (``network_ops.voxel_map_integrate``: a hash table of integer sums); when a sample's trajectory ends the map is extracted,
 written as ``map.ply`` into the trajectory's directory by a worker thread (``write_map_ply``) and the table cleared.
+
+With ``save_mesh=VOXEL`` the estimate of every step is also fused, on the device, into one truncated signed distance field per
+sample (``network_ops.tsdf_integrate``: a hashed voxel grid, two launches); when a sample's trajectory ends the surface is
+extracted by naive surface nets (``network_ops.tsdf_extract``), written as ``mesh.ply`` into the trajectory's directory by a
+worker thread (``write_mesh_ply``) and the volume cleared.
 """
 from __future__ import annotations
 
@@ -168,6 +173,66 @@ def read_map_ply(path):
     return xyz, rgba, info
 
 
+_MESH_FIELDS = ("voxel", "trunc", "min_frames", "occupied", "dropped_range", "dropped_full", "updates", "quads_dropped")
+PLY_FACE = np.dtype([("n", "u1"), ("vertex_indices", "<i4", (3,))])        # 13 bytes: a triangle of `property list uchar int`
+_PLY_FACE_PROPERTY = "property list uchar int vertex_indices"
+
+
+def write_mesh_ply(path, vertices, triangles, voxel, trunc, min_frames, stats):
+    """The TSDF surface of a trajectory as a binary little-endian PLY mesh (MeshLab, CloudCompare and Open3D open it):
+    ``vertices`` [n,16] uint8 and ``triangles`` [m,3] int32 as ``network_ops.tsdf_extract`` returns them -- the clouds' vertex
+    properties (float x, y, z, uchar red, green, blue and alpha = the fewest frames that updated one of the cell's eight voxels,
+    capped at 255), then ``element face`` with ``property list uchar int vertex_indices``, every face a triangle wound so that
+    its normal points from the inside of the surface to the outside (towards the cameras that saw it).  World frame: the pose
+    comment is the identity.  ``comment tsdf_mesh`` holds the edge length, the truncation in voxels, ``min_frames`` and
+    ``stats`` (occupied, dropped_range, dropped_full, updates, quads_dropped) as name value pairs."""
+    body = np.ascontiguousarray(vertices).view(np.uint8).reshape(-1, 16)
+    tri = np.ascontiguousarray(triangles, dtype="<i4").reshape(-1, 3)
+    if len(tri) and (tri.min() < 0 or tri.max() >= len(body)):
+        raise ValueError(f"{path}: a triangle names a vertex outside 0..{len(body) - 1}")
+    faces = np.zeros(len(tri), PLY_FACE)
+    faces["n"] = 3
+    faces["vertex_indices"] = tri
+    info = dict(stats, voxel="%.9g" % np.float32(voxel), trunc=int(trunc), min_frames=int(min_frames))
+    header = ["ply", "format binary_little_endian 1.0", "comment pose 1 0 0 0 0 0 0",
+              "comment tsdf_mesh " + " ".join("%s %s" % (k, info[k]) for k in _MESH_FIELDS),
+              "element vertex %d" % len(body)] + _PLY_PROPERTIES + ["element face %d" % len(faces), _PLY_FACE_PROPERTY,
+                                                                    "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(body.data)
+        fh.write(faces.tobytes())
+
+
+def read_mesh_ply(path):
+    """A ``mesh.ply`` of ``PredictionWriter(save_mesh=...)``: (xyz float32 [n,3], rgba uint8 [n,4], triangles int32 [m,3], info)
+    with ``info`` the ``comment tsdf_mesh`` line as a dict -- voxel (float) and trunc, min_frames, occupied, dropped_range,
+    dropped_full, updates, quads_dropped (int)."""
+    with open(path, "rb") as fh:
+        lines = []
+        while not lines or lines[-1] != "end_header":
+            line = fh.readline()
+            if not line or len(lines) > 64:
+                raise ValueError(f"{path}: no PLY header")
+            lines.append(line.decode("ascii").rstrip("\r\n"))
+        body = fh.read()
+    info = [l.split()[2:] for l in lines if l.startswith("comment tsdf_mesh ")]
+    elements = [l.split()[1:] for l in lines if l.startswith("element ")]
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"] or lines.count("comment pose 1 0 0 0 0 0 0") != 1 \
+            or len(info) != 1 or tuple(info[0][0::2]) != _MESH_FIELDS or [e[0] for e in elements] != ["vertex", "face"] \
+            or [l for l in lines if l.startswith("property ")] != _PLY_PROPERTIES + [_PLY_FACE_PROPERTY]:
+        raise ValueError(f"{path}: not a TSDF mesh of PredictionWriter")
+    n, m = int(elements[0][1]), int(elements[1][1])
+    if len(body) != 16 * n + PLY_FACE.itemsize * m:
+        raise ValueError(f"{path}: {n} vertices and {m} faces in the header, {len(body)} bytes in the body")
+    raw = np.frombuffer(body[:16 * n], np.uint8).reshape(n, 16)
+    faces = np.frombuffer(body[16 * n:], PLY_FACE)
+    if m and ((faces["n"] != 3).any() or faces["vertex_indices"].min() < 0 or faces["vertex_indices"].max() >= n):
+        raise ValueError(f"{path}: a face that is no triangle of the file's vertices")
+    info = {k: (float(v) if k == "voxel" else int(v)) for k, v in zip(info[0][0::2], info[0][1::2])}
+    return raw[:, :12].copy().view(np.float32), raw[:, 12:].copy(), faces["vertex_indices"].astype(np.int32), info
+
+
 def read_conf_png(path, views):
     """A ``<name>_conf.png`` of ``PredictionWriter(save_conf=True)`` as the counts it was made of: uint8 [h,w], the number of
     earlier frames (0..``views``) that confirmed the pixel; the file holds ``count * 255 // views``."""
@@ -186,7 +251,7 @@ def read_conf_png(path, views):
 
 
 class _Slot:
-    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False, cloud_host=True):
+    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False, cloud_host=True, geometry=False):
         self.depth_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
         self.depth_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
         self.panels_d = self.panels_h = None
@@ -201,6 +266,7 @@ class _Slot:
                 self.cloud_h = torch.empty((b, cloud_cap, 16), dtype=torch.uint8).pin_memory()
                 self.counts_h = torch.empty(b, dtype=torch.int32).pin_memory()
                 self.pose_h = torch.empty((b, 7), dtype=torch.float64).pin_memory()
+        if cloud_cap or geometry:                          # (a writer of meshes alone has no vertex buffer)
             self.reset_d = torch.empty(b, dtype=torch.uint8, device=dev)
             self.reset_h = torch.empty(b, dtype=torch.uint8).pin_memory()
         self.conf_d = self.conf_h = None
@@ -246,11 +312,24 @@ class PredictionWriter:
     (a device mask raises ValueError) and names with one directory per trajectory (``FrameNamer``'s).  Without ``cloud`` the
     cloud launches still run, their buffers stay on the device and no ``_cloud.ply`` is written.  ``maps``, ``map_voxels``,
     ``map_dropped_range`` and ``map_dropped_full`` sum over the maps handed to the workers: a ``map_dropped_full`` > 0 says
-    that ``map_slots_log2`` is too small for the scene."""
+    that ``map_slots_log2`` is too small for the scene.
+
+    ``save_mesh=VOXEL`` (metres; independent of ``cloud`` and ``save_map``) also writes ``<directory of the trajectory's
+    frames>/mesh.ply``: the trajectory's estimates fused into a truncated signed distance field on a hashed voxel grid and
+    extracted as a triangle mesh by naive surface nets (include/m4depth_hip.h, ``write_mesh_ply``).  Every submit runs
+    ``network_ops.tsdf_integrate`` -- two launches -- on what the clouds see: the ``cloud_views``-filtered copy of the estimate
+    when that option is on, limited to [near, far], at EVERY pixel (``cloud_step`` does not apply: a stride wider than a voxel
+    would leave holes).  ``mesh_trunc`` is the truncation distance in voxels (2..8), a voxel takes part in the extraction only if
+    at least ``mesh_min_frames`` frames updated it, and each sample owns a table of 2^``mesh_slots_log2`` slots of 32 bytes (134 MB
+    at the default 22).  Trajectories end, and their tables are cleared, exactly where the maps' do, under the same needs (world
+    frame, host-side reset flags, one directory per trajectory).  With ``save_mesh`` alone the pose chain, the views check and
+    the two mesh launches run; ``depth_cloud`` does not.  ``meshes``, ``mesh_vertices``, ``mesh_triangles``,
+    ``mesh_dropped_range``, ``mesh_dropped_full`` and ``mesh_quads_dropped`` sum over the meshes handed to the workers."""
 
     def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
                  encode=True, cloud=False, cloud_step=2, cloud_frame="world", cloud_views=0, cloud_min_views=None,
-                 cloud_tol=(1.0, 0.01), save_conf=False, save_map=None, map_min_frames=2, map_slots_log2=21):
+                 cloud_tol=(1.0, 0.01), save_conf=False, save_map=None, map_min_frames=2, map_slots_log2=21, save_mesh=None,
+                 mesh_trunc=4, mesh_min_frames=2, mesh_slots_log2=22):
         if fmt not in FORMATS:
             raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
         panels = tuple(panels)
@@ -274,8 +353,21 @@ class PredictionWriter:
             raise ValueError("save_map needs cloud_frame='world': a map merges the frames of a trajectory in one frame")
         if save_map is not None and (int(map_min_frames) < 1 or not 6 <= int(map_slots_log2) <= 26):
             raise ValueError(f"need map_min_frames >= 1 and map_slots_log2 in 6..26, got {map_min_frames}, {map_slots_log2}")
-        if cloud_views and not (cloud or save_map is not None):
-            raise ValueError("cloud_views needs cloud=True: the check runs on the clouds' pose chain")
+        save_mesh = None if save_mesh is None else float(np.float32(save_mesh))
+        mesh_trunc = 4 if mesh_trunc is None else mesh_trunc
+        mesh_min_frames = 2 if mesh_min_frames is None else mesh_min_frames
+        mesh_slots_log2 = 22 if mesh_slots_log2 is None else mesh_slots_log2
+        if save_mesh is not None and not (0 < save_mesh < float("inf")):
+            raise ValueError(f"save_mesh: the voxel edge must be a finite length > 0, got {save_mesh}")
+        if save_mesh is not None and cloud_frame != "world":
+            raise ValueError("save_mesh needs cloud_frame='world': a mesh fuses the frames of a trajectory in one frame")
+        if save_mesh is not None and (not nops.TSDF_TRUNC[0] <= int(mesh_trunc) <= nops.TSDF_TRUNC[1] or int(mesh_min_frames) < 1
+                                      or not 6 <= int(mesh_slots_log2) <= 26):
+            raise ValueError(f"need mesh_trunc in {nops.TSDF_TRUNC[0]}..{nops.TSDF_TRUNC[1]}, mesh_min_frames >= 1 and "
+                             f"mesh_slots_log2 in 6..26, got {mesh_trunc}, {mesh_min_frames}, {mesh_slots_log2}")
+        if cloud_views and not (cloud or save_map is not None or save_mesh is not None):
+            raise ValueError("cloud_views needs cloud=True: the check runs on the clouds' pose chain (save_map or save_mesh "
+                             "run on it as well)")
         if save_conf and not cloud_views:
             raise ValueError("save_conf needs cloud_views >= 1")
         if cloud_min_views is not None and not cloud_views:
@@ -293,7 +385,14 @@ class PredictionWriter:
         self.cloud_kept = self.cloud_cap = 0               # vertices written / vertices the clouds could hold, finished frames
         self._pose = None                                  # [b,7] float64 device state of the cloud: camera-to-world poses
         self.save_map, self.map_min_frames, self.map_slots_log2 = save_map, int(map_min_frames), int(map_slots_log2)
-        self._geometry3d = self.cloud or save_map is not None      # the pose chain and the cloud launches run
+        self.save_mesh, self.mesh_trunc = save_mesh, int(mesh_trunc)
+        self.mesh_min_frames, self.mesh_slots_log2 = int(mesh_min_frames), int(mesh_slots_log2)
+        self._vertices3d = self.cloud or save_map is not None      # the cloud launches run
+        self._geometry3d = self._vertices3d or save_mesh is not None   # the pose chain (and the views check) runs
+        self._mesh = None                                  # network_ops.tsdf_state, allocated with the slots
+        self._mesh_dirs = None                             # per sample: the directory of its open trajectory
+        self.meshes = self.mesh_vertices = self.mesh_triangles = 0
+        self.mesh_dropped_range = self.mesh_dropped_full = self.mesh_quads_dropped = 0
         self._map = None                                   # network_ops.voxel_map_state, allocated with the slots
         self._map_dirs = None                              # per sample: the directory of its open trajectory
         self._step = 0                                     # submits so far: the stamp of a step's vertices
@@ -327,9 +426,11 @@ class PredictionWriter:
     def _allocate(self, est):
         b, h, w = est.shape[:3]
         self._geometry = (b, h, w)
-        cap = nops.cloud_capacity(h, w, self.cloud_step) if self._geometry3d else 0
-        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf, self.cloud)
+        cap = nops.cloud_capacity(h, w, self.cloud_step) if self._vertices3d else 0
+        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf, self.cloud, self._geometry3d)
                        for _ in range(self.n_slots)]
+        if self.save_mesh is not None:
+            self._mesh = nops.tsdf_state(b, self.mesh_slots_log2, est.device)
         if self.save_map is not None:
             self._map = nops.voxel_map_state(b, self.map_slots_log2, est.device)
         if any(p != "rgb" for p in self.panels):
@@ -364,17 +465,50 @@ class PredictionWriter:
                 if self._error is None:
                     self._error = e
 
+    def _finish_mesh(self, s):
+        """The mesh of sample ``s``'s open trajectory to a worker thread; the caller clears the volume on the same stream."""
+        keys, vertices, triangles, stats = nops.tsdf_extract(self._mesh, s, self.mesh_min_frames, self.save_mesh)
+        v_host, t_host = torch.empty(vertices.shape, dtype=torch.uint8), torch.empty(triangles.shape, dtype=torch.int32)
+        if len(keys):                                      # (an empty mesh is written too)
+            v_host = v_host.pin_memory()
+            v_host.copy_(vertices, non_blocking=True)
+        if len(triangles):
+            t_host = t_host.pin_memory()
+            t_host.copy_(triangles, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        self.meshes += 1
+        self.mesh_vertices += len(keys)
+        self.mesh_triangles += len(triangles)
+        self.mesh_dropped_range += stats["dropped_range"]
+        self.mesh_dropped_full += stats["dropped_full"]
+        self.mesh_quads_dropped += stats["quads_dropped"]
+        self._pool.submit(self._work_mesh, os.path.join(self._mesh_dirs[s], "mesh.ply"), v_host, t_host, event, stats)
+
+    def _work_mesh(self, rel_path, v_host, t_host, event, stats):
+        try:
+            event.synchronize()
+            if self.encode:
+                path = os.path.join(self.out_dir, rel_path)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                write_mesh_ply(path, v_host.numpy(), t_host.numpy(), self.save_mesh, self.mesh_trunc, self.mesh_min_frames, stats)
+        except BaseException as e:
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+
     def _submit_cloud(self, slot, est, rgb, rot, trans, camera, reset, names):
         """The cloud of one step into ``slot``, on the current stream: pose update, compaction, copies; with ``save_map`` the
         maps of the trajectories that ended, then the step's vertices into the maps."""
         if rgb is None or rot is None or trans is None or camera is None:
             raise ValueError("a writer with cloud=True or save_map needs rgb, rot, trans and camera at every submit")
-        if self.save_map is not None:
+        if self.save_map is not None or self.save_mesh is not None:
+            what = "save_map" if self.save_map is not None else "save_mesh"
             if torch.is_tensor(reset) and reset.is_cuda:
-                raise ValueError("save_map needs host-side reset flags: which trajectory ended is decided on the host")
+                raise ValueError(f"{what} needs host-side reset flags: which trajectory ended is decided on the host")
             dirs = [os.path.dirname(n) for n in names]
             if len(set(dirs)) != len(dirs):
-                raise ValueError(f"save_map needs names with one directory per sample and trajectory, got {list(names)}")
+                raise ValueError(f"{what} needs names with one directory per sample and trajectory, got {list(names)}")
         first = self._pose is None
         if first:
             self._pose = torch.empty((est.shape[0], 7), dtype=torch.float64, device=est.device)
@@ -398,6 +532,10 @@ class PredictionWriter:
                     for s in np.nonzero(reset)[0]:         # the trajectories that ended with the previous frame
                         self._finish_map(int(s))
                     nops.voxel_map_clear(self._map, mask)
+                if self.save_mesh is not None and reset.any():
+                    for s in np.nonzero(reset)[0]:
+                        self._finish_mesh(int(s))
+                    nops.tsdf_clear(self._mesh, mask)
         nops.pose_accumulate(rot, trans, self._pose, reset=mask, force_all=first)
         if self.cloud_views:                               # the clouds see the filtered copy; PNG and panels the estimate
             b, h, w = est.shape[:3]
@@ -412,6 +550,12 @@ class PredictionWriter:
                                       n_views=slot.conf_d if self.save_conf else self._views_n, depth_f=self._views_depth)
             if self.save_conf:
                 slot.conf_h.copy_(slot.conf_d, non_blocking=True)
+        if self.save_mesh is not None:                     # the mesh sees what the clouds see, at every pixel
+            nops.tsdf_integrate(est, rgb, camera["f"], camera["c"], self._pose, self.save_mesh, self.mesh_trunc, self._mesh,
+                                near=self.near, far=self.far)
+            self._mesh_dirs = dirs
+        if not self._vertices3d:
+            return
         nops.depth_cloud(est, rgb, camera["f"], camera["c"], step=self.cloud_step, near=self.near, far=self.far,
                          pose=self._pose if self.cloud_frame == "world" else None, vertices=slot.cloud_d, counts=slot.counts_d)
         if self.save_map is not None:
@@ -504,6 +648,10 @@ class PredictionWriter:
                 for s in range(len(self._map_dirs)):
                     self._finish_map(s)
                 self._map_dirs = None
+            if self._mesh_dirs is not None:
+                for s in range(len(self._mesh_dirs)):
+                    self._finish_mesh(s)
+                self._mesh_dirs = None
         except BaseException as e:
             with self._lock:
                 if self._error is None:

@@ -14,7 +14,8 @@ is sharded (m4depth_amd.dist) and the metric accumulators are all-gathered over 
 ``--mode=predict --save_dir DIR`` writes every frame's estimate as a 16-bit depth PNG in a dataset's own encoding (and, with
 ``--save_panels``, a colour panel PNG) through ``m4depth_amd.export.PredictionWriter`` instead of collecting predictions.npy;
 ``--save_cloud`` adds a coloured point cloud per frame (binary PLY), compacted on the GPU, in the frame of the trajectory's first
-camera; ``--save_map VOXEL`` adds one fused voxel map per trajectory (``map.ply``), merged on the GPU from the clouds' vertices.
+camera; ``--save_map VOXEL`` adds one fused voxel map per trajectory (``map.ply``), merged on the GPU from the clouds' vertices;
+``--save_mesh VOXEL`` adds one triangle mesh per trajectory (``mesh.ply``), a TSDF fused and extracted on the GPU.
 ``--mode=train --log_dir DIR`` writes the training summaries (loss, RMSE_log, the reference's summary images) as a TensorBoard
 event file through ``m4depth_amd.summaries.TrainSummaryWriter``.
 ``--eval_streams B`` runs a dataset's streaming evaluation (no ``--db_seq_len``) with B whole trajectories side by side
@@ -680,7 +681,8 @@ def predict(args, model, batches, rank, dev):
                                   cloud_step=args.cloud_stride, cloud_frame=args.cloud_frame, cloud_views=args.cloud_views,
                                   cloud_min_views=args.cloud_min_views, cloud_tol=args.cloud_tol, save_conf=args.save_conf,
                                   save_map=args.save_map, map_min_frames=args.map_min_frames,
-                                  map_slots_log2=args.map_slots_log2)
+                                  map_slots_log2=args.map_slots_log2, save_mesh=args.save_mesh, mesh_trunc=args.mesh_trunc,
+                                  mesh_min_frames=args.mesh_min_frames, mesh_slots_log2=args.mesh_slots_log2)
         want_gt = any(p in ("gt", "err") for p in writer.panels)
     preds = []
     for data in batches:
@@ -711,8 +713,8 @@ def predict(args, model, batches, rank, dev):
                 namer = FrameNamer(est.shape[0])
                 t_save = time.perf_counter()
             cloud = {}
-            geometry = writer.cloud or writer.save_map is not None
-            if geometry:                                       # the cloud launches follow the forward / the replay on its stream
+            geometry = writer.cloud or writer.save_map is not None or writer.save_mesh is not None
+            if geometry:                                      # the cloud launches follow the forward / the replay on its stream
                 cloud = dict(rot=frame["rot"], trans=frame["trans"], camera=frame["camera"], reset=frame["new_traj"])
             writer.submit(est, namer(frame["new_traj"]), gt=frame.get("depth") if want_gt else None,
                           rgb=frame["RGB_im"] if "rgb" in writer.panels or geometry else None, **cloud)
@@ -732,6 +734,10 @@ def predict(args, model, batches, rank, dev):
               + (f", {writer.maps} voxel maps at {writer.save_map:g} m: {writer.map_voxels} voxels written, "
                  f"{writer.map_dropped_range} vertices dropped out of range, {writer.map_dropped_full} dropped by full tables"
                  + (" (raise --map_slots_log2)" if writer.map_dropped_full else "") if writer.save_map is not None else "")
+              + (f", {writer.meshes} meshes at {writer.save_mesh:g} m: {writer.mesh_vertices} vertices, "
+                 f"{writer.mesh_triangles} triangles, {writer.mesh_dropped_range} samples dropped out of range, "
+                 f"{writer.mesh_dropped_full} dropped by full tables"
+                 + (" (raise --mesh_slots_log2)" if writer.mesh_dropped_full else "") if writer.save_mesh is not None else "")
               + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
 
 

@@ -801,7 +801,150 @@ def voxel_map_clear(state, mask=None):
     return state
 
 
-SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                    # the `kind` argument of m4d_summary_images
+TSDF_STATS = ("occupied", "dropped_range", "dropped_full", "updates")   # the statistics words of m4d_tsdf_*
+TSDF_TRUNC = (2, 8)                                             # the truncation distance in voxels m4d_tsdf_* accept
+
+
+def tsdf_state(b, slots_log2, device):
+    """The state of ``b`` TSDF volumes with 2^``slots_log2`` slots each (include/m4depth_hip.h), cleared: {"words": the int64
+    buffer the library works on, "stats": its [b,4] head, "keys": its [b, 2^L] keys, "recs": its [b, 2^L, 6] int32 records (S is
+    float32: view column 0), "b", "slots_log2"}.  Keys and counters are unsigned on the device; torch shows them signed."""
+    b, slots_log2 = int(b), int(slots_log2)
+    words = int(lib.m4d_tsdf_state_words(b, slots_log2))
+    if words < 0:
+        raise ValueError(f"tsdf_state: need b in 1..65535 and slots_log2 in 6..26, got b {b}, slots_log2 {slots_log2}")
+    return tsdf_clear(tsdf_state_views(torch.empty(words, dtype=torch.int64, device=device), b, slots_log2))
+
+
+def tsdf_state_views(buf, b, slots_log2):
+    """The dict of ``tsdf_state`` over an int64 buffer of m4d_tsdf_state_words(b, slots_log2) words, as it is (not cleared)."""
+    slots = 1 << slots_log2
+    return {"words": buf, "stats": buf[:4 * b].view(b, 4), "keys": buf[4 * b:4 * b + b * slots].view(b, slots),
+            "recs": buf[4 * b + b * slots:].view(torch.int32).view(b, slots, 6), "b": b, "slots_log2": slots_log2}
+
+
+def _tsdf_check(state, voxel=None):
+    b, slots_log2 = int(state["b"]), int(state["slots_log2"])
+    if state["words"].numel() != lib.m4d_tsdf_state_words(b, slots_log2):
+        raise ValueError(f"state: not a tsdf_state of {b} samples with 2^{slots_log2} slots")
+    if voxel is not None and not (float(voxel) > 0 and float(voxel) < float("inf")):
+        raise ValueError(f"voxel must be a finite edge length > 0, got {voxel}")
+    return b, slots_log2
+
+
+def tsdf_integrate(depth, rgb, cam_f, cam_c, pose, voxel, trunc, state, near=1.0, far=80.0):
+    """One frame batch into the TSDF volumes: m4d_tsdf_allocate (every pixel's ray over the truncation band claims its voxels),
+    then m4d_tsdf_integrate (every allocated voxel the frame sees takes its truncated signed distance and colour).  ``depth``
+    [b,h,w,1], ``rgb`` [b,h,w,3]: float32 device tensors with dense images at a batch stride; ``cam_f`` / ``cam_c`` [b,2];
+    ``pose`` [b,7] float64 as ``pose_accumulate`` keeps it; ``voxel`` the edge in metres, ``trunc`` the truncation distance in
+    voxels (2..8).  Two launches, nothing synchronises."""
+    b, slots_log2 = _tsdf_check(state, voxel)
+    trunc = int(trunc)
+    if not TSDF_TRUNC[0] <= trunc <= TSDF_TRUNC[1]:
+        raise ValueError(f"trunc must be in {TSDF_TRUNC[0]}..{TSDF_TRUNC[1]} voxels, got {trunc}")
+    if depth.dim() != 4 or depth.shape[3] != 1 or depth.shape[0] != b:
+        raise ValueError(f"depth: expected [{b},h,w,1], got {tuple(depth.shape)}")
+    h, w = depth.shape[1:3]
+    if not float(far) > float(near):
+        raise ValueError(f"need near < far, got {near}, {far}")
+    if tuple(rgb.shape) != (b, h, w, 3):
+        raise ValueError(f"rgb {tuple(rgb.shape)} does not belong to depth {tuple(depth.shape)}")
+    if tuple(cam_f.shape) != (b, 2) or tuple(cam_c.shape) != (b, 2):
+        raise ValueError(f"cam_f / cam_c: expected [{b},2], got {tuple(cam_f.shape)} and {tuple(cam_c.shape)}")
+    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (b, 7):
+        raise ValueError(f"pose: expected a [{b},7] float64 device tensor")
+    ds, rs = _batch_stride(depth, "depth"), _batch_stride(rgb, "rgb")
+    f, c = dptr(as_f32(cam_f, "cam_f"), "cam_f"), dptr(as_f32(cam_c, "cam_c"), "cam_c")
+    words = dptr(state["words"], "state", torch.int64)
+    check(lib.m4d_tsdf_allocate(ctypes.c_void_p(depth.data_ptr()), ds, f, c, dptr(pose, "pose", torch.float64), b, h, w,
+                                float(near), float(far), float(voxel), trunc, words, slots_log2, stream_ptr()), "m4d_tsdf_allocate")
+    check(lib.m4d_tsdf_integrate(ctypes.c_void_p(depth.data_ptr()), ds, ctypes.c_void_p(rgb.data_ptr()), rs, f, c,
+                                 dptr(pose, "pose", torch.float64), b, h, w, float(near), float(far), float(voxel), trunc, words,
+                                 slots_log2, stream_ptr()), "m4d_tsdf_integrate")
+    return state
+
+
+def tsdf_extract_raw(state, s, min_frames, voxel, vertex_cap, quad_cap, out=None):
+    """The two extraction launches of sample ``s``: (keys [vertex_cap] int64, vertices [vertex_cap,16] uint8, quads [quad_cap,5]
+    int64, counts [2] int64 = records found by each launch -- beyond a capacity they are counted, not written), in the order
+    the waves arrived.  ``out``: these four as destinations (counts zeroed by the caller); fresh buffers otherwise."""
+    b, slots_log2 = _tsdf_check(state, voxel)
+    s, min_frames = int(s), int(min_frames)
+    if not 0 <= s < b or min_frames < 1:
+        raise ValueError(f"need s in 0..{b - 1} and min_frames >= 1, got s {s}, min_frames {min_frames}")
+    dev = state["words"].device
+    vertex_cap, quad_cap = max(int(vertex_cap), 1), max(int(quad_cap), 1)
+    if out is None:
+        out = (torch.empty(vertex_cap, dtype=torch.int64, device=dev), torch.empty((vertex_cap, 16), dtype=torch.uint8, device=dev),
+               torch.empty((quad_cap, 5), dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.int64, device=dev))
+    keys, vertices, quads, counts = out
+    if tuple(keys.shape) != (vertex_cap,) or tuple(vertices.shape) != (vertex_cap, 16) or tuple(quads.shape) != (quad_cap, 5) \
+            or tuple(counts.shape) != (2,):
+        raise ValueError(f"out: expected keys [{vertex_cap}], vertices [{vertex_cap},16], quads [{quad_cap},5] and counts [2]")
+    words = dptr(state["words"], "state", torch.int64)
+    check(lib.m4d_tsdf_extract_vertices(words, b, slots_log2, s, min_frames, float(voxel), dptr(keys, "keys_out", torch.int64),
+                                        dptr(vertices, "vertices_out", torch.uint8), vertex_cap,
+                                        dptr(counts[0:1], "count", torch.int64), stream_ptr()), "m4d_tsdf_extract_vertices")
+    check(lib.m4d_tsdf_extract_faces(words, b, slots_log2, s, min_frames, dptr(quads, "quads_out", torch.int64), quad_cap,
+                                     dptr(counts[1:2], "count", torch.int64), stream_ptr()), "m4d_tsdf_extract_faces")
+    return keys, vertices, quads, counts
+
+
+def tsdf_extract(state, s, min_frames, voxel):
+    """The surface of sample ``s`` by naive surface nets: (keys [n] int64 ascending, vertices [n,16] uint8, triangles [2q,3] int32,
+    stats) -- one vertex per sign-changing cell whose eight voxels at least ``min_frames`` frames updated, one quad per
+    sign-changing grid edge, ordered by (owner key, axis) and split along its (0,2) diagonal; ``stats``: the sample's {occupied,
+    dropped_range, dropped_full, updates} and ``quads_dropped``, the quads that named a cell without a vertex (the rim of an open
+    surface).  The outputs are sized from ``occupied`` (vertices <= occupied, quads <= 3 occupied), which is read with one wait; the
+    launches' own counts are read with a second one.  Sorting (``torch.sort``) and the key -> index mapping
+    (``torch.searchsorted``) run on the device.  Once per trajectory: not a hot path."""
+    _tsdf_check(state, voxel)
+    if not 0 <= int(s) < int(state["b"]):
+        raise ValueError(f"need s in 0..{int(state['b']) - 1}, got {s}")
+    stats = dict(zip(TSDF_STATS, state["stats"][int(s)].cpu().tolist()))      # the wait of the trajectory
+    slots = 1 << int(state["slots_log2"])
+    occupied = min(stats["occupied"], slots)
+    keys, vertices, quads, counts = tsdf_extract_raw(state, s, min_frames, voxel, occupied, 3 * occupied)
+    n_v, n_q = (min(n, cap) for n, cap in zip(counts.cpu().tolist(), (keys.shape[0], quads.shape[0])))
+    keys, vertices, triangles, stats["quads_dropped"] = tsdf_order(keys[:n_v], vertices[:n_v], quads[:n_q])
+    return keys, vertices, triangles, stats
+
+
+def tsdf_order(keys, vertices, quads):
+    """What the extraction launches found, in arrival order, as a mesh: (keys ascending, vertices in that order, triangles [2q,3]
+    int32, quads dropped for naming a cell without a vertex).  Device tensors in, device tensors out."""
+    n_v, n_q = keys.shape[0], quads.shape[0]
+    keys, order = torch.sort(keys)                              # keys stay below 2^63: int64 order is the unsigned order
+    vertices = vertices[order]
+    flags, ring = quads[:, 0], quads[:, 1:]
+    owner = torch.where(flags >= 4, ring[:, 3], ring[:, 0])
+    first = torch.sort(flags & 3, stable=True)[1]               # by axis, then stably by owner: (owner key, axis)
+    order = first[torch.sort(owner[first], stable=True)[1]]
+    ring = ring[order]
+    if n_v:
+        at = torch.searchsorted(keys, ring.contiguous()).clamp_(max=n_v - 1)
+        have = (keys[at] == ring).all(dim=1)
+    else:
+        at, have = torch.zeros_like(ring), torch.zeros(ring.shape[0], dtype=torch.bool, device=ring.device)
+    q = at[have]
+    triangles = torch.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], dim=1).reshape(-1, 3).to(torch.int32)
+    return keys, vertices, triangles, int(n_q - q.shape[0])
+
+
+def tsdf_clear(state, mask=None):
+    """Empties the volumes of the samples with ``mask[s]`` set (uint8 / bool [b] device tensor; None: all of them) and zeroes
+    their statistics (m4d_tsdf_clear).  One launch."""
+    b, slots_log2 = _tsdf_check(state)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (b,):
+            raise ValueError(f"mask: expected a uint8 / bool [{b}] device tensor")
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    check(lib.m4d_tsdf_clear(dptr(state["words"], "state", torch.int64), dptr(mask, "mask", torch.uint8), b, slots_log2,
+                             stream_ptr()), "m4d_tsdf_clear")
+    return state
+
+
+SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                   # the `kind` argument of m4d_summary_images
 SUMMARY_MAX_MAPS = 16
 
 

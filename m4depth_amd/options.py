@@ -119,6 +119,20 @@ def build_parser():
     p.add_argument("--map_slots_log2", type=int, default=argparse.SUPPRESS, metavar="L",
                    help="--save_map: 2^L hash-table slots per sample, 16..26 (default 21: 168 MB per sample; a map stops "
                         "taking new voxels at 3/4 of them, and the closing line of the run counts what was dropped)")
+    # like the map's: absent from the namespace until given
+    p.add_argument("--save_mesh", type=float, default=argparse.SUPPRESS, metavar="VOXEL",
+                   help="--save_dir: also write DIR/s<slot>_t<trajectory>/mesh.ply, ONE triangle mesh per trajectory -- the "
+                        "estimates (as --save_range and --cloud_views make them; --cloud_stride does not apply, every pixel "
+                        "counts) fused on the GPU into a truncated signed distance field on a hashed grid of VOXEL metres and "
+                        "extracted by naive surface nets.  Independent of --save_cloud and --save_map.  --cloud_views is the "
+                        "recommended companion.  VOXEL, --mesh_trunc and --mesh_min_frames are untuned")
+    p.add_argument("--mesh_trunc", type=int, default=argparse.SUPPRESS, metavar="K",
+                   help="--save_mesh: the truncation distance in voxels, 2..8 (default 4)")
+    p.add_argument("--mesh_min_frames", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="--save_mesh: a voxel takes part in the surface only if at least N frames updated it (default 2)")
+    p.add_argument("--mesh_slots_log2", type=int, default=argparse.SUPPRESS, metavar="L",
+                   help="--save_mesh: 2^L hash-table slots per sample, 16..26 (default 22: 134 MB per sample; a volume stops "
+                        "taking new voxels at 3/4 of them, and the closing line of the run counts what was dropped)")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--loss", default="supervised", choices=["supervised", "photometric"],
                    help="train: supervised = the reference's log-depth L1 against ground truth; photometric = the reprojection "
@@ -306,7 +320,28 @@ def check_save_args(parser, args):
             parser.error("--map_slots_log2 must be in 16..26")
         args.map_min_frames = 2 if args.map_min_frames is None else args.map_min_frames
         args.map_slots_log2 = 21 if args.map_slots_log2 is None else args.map_slots_log2
-    geometry = args.save_cloud or args.save_map is not None
+    # the TSDF mesh: the same pattern; it reads the estimate itself, so of the clouds' options only --cloud_frame concerns it
+    for f in ("save_mesh", "mesh_trunc", "mesh_min_frames", "mesh_slots_log2"):
+        setattr(args, f, getattr(args, f, None))
+    mesh_others = [f for f in ("mesh_trunc", "mesh_min_frames", "mesh_slots_log2") if getattr(args, f) is not None]
+    if mesh_others and args.save_mesh is None:
+        parser.error("--%s needs --save_mesh" % mesh_others[0])
+    if args.save_mesh is not None:
+        others.append("save_mesh")
+        if not (0 < args.save_mesh < float("inf")):
+            parser.error("--save_mesh VOXEL needs a finite edge length > 0")
+        if args.cloud_frame == "camera":
+            parser.error("--save_mesh needs --cloud_frame world: a mesh fuses the frames of a trajectory in one frame")
+        if args.mesh_trunc is not None and not 2 <= args.mesh_trunc <= 8:
+            parser.error("--mesh_trunc must be in 2..8")
+        if args.mesh_min_frames is not None and args.mesh_min_frames < 1:
+            parser.error("--mesh_min_frames must be >= 1")
+        if args.mesh_slots_log2 is not None and not 16 <= args.mesh_slots_log2 <= 26:
+            parser.error("--mesh_slots_log2 must be in 16..26")
+        args.mesh_trunc = 4 if args.mesh_trunc is None else args.mesh_trunc
+        args.mesh_min_frames = 2 if args.mesh_min_frames is None else args.mesh_min_frames
+        args.mesh_slots_log2 = 22 if args.mesh_slots_log2 is None else args.mesh_slots_log2
+    geometry = args.save_cloud or args.save_map is not None or args.save_mesh is not None
     cloud_others = [f for f in ("cloud_stride", "cloud_frame") if getattr(args, f) is not None]
     if args.save_dir is not None and cloud_others and not geometry:
         parser.error("--%s needs --save_cloud" % cloud_others[0])
