@@ -97,15 +97,12 @@ cloud_write_kernel(CloudArgs a, const int* __restrict__ workspace, uint4* __rest
   float z = d;
   if (a.pose) {                                               // Rw X + tw in float64, one rounding to float32
     const double* p = a.pose + s * 7;
-    const double qw = p[0], qx = p[1], qy = p[2], qz = p[3];
-    const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;
-    const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
-    const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
-    const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+    double r[9];
+    m4d_rot64(p, r);
     const double X = x, Y = y, Z = z;
-    x = (float)((((1.0 - (tyy + tzz)) * X + (txy - twz) * Y) + (txz + twy) * Z) + p[4]);
-    y = (float)((((txy + twz) * X + (1.0 - (txx + tzz)) * Y) + (tyz - twx) * Z) + p[5]);
-    z = (float)((((txz - twy) * X + (tyz + twx) * Y) + (1.0 - (txx + tyy)) * Z) + p[6]);
+    x = (float)(((r[0] * X + r[1] * Y) + r[2] * Z) + p[4]);
+    y = (float)(((r[3] * X + r[4] * Y) + r[5] * Z) + p[5]);
+    z = (float)(((r[6] * X + r[7] * Y) + r[8] * Z) + p[6]);
   }
   const float* c = a.rgb + s * a.rgb_stride + ((long long)row * a.w + col) * 3;
   const unsigned rgba = cloud_byte(c[0]) | (cloud_byte(c[1]) << 8) | (cloud_byte(c[2]) << 16) | 0xFF000000u;
@@ -129,14 +126,11 @@ pose_accumulate_kernel(const unsigned char* __restrict__ reset, int force_all, c
   w /= n; x /= n; y /= n; z /= n;
   const double pw = p[0], px = p[1], py = p[2], pz = p[3];
   const double t0 = trans[s * 3], t1 = trans[s * 3 + 1], t2 = trans[s * 3 + 2];
-  // tw <- R(p) t + tw, R as get_rot_mat writes it
-  const double tx = 2.0 * px, ty = 2.0 * py, tz = 2.0 * pz;
-  const double twx = tx * pw, twy = ty * pw, twz = tz * pw;
-  const double txx = tx * px, txy = ty * px, txz = tz * px;
-  const double tyy = ty * py, tyz = tz * py, tzz = tz * pz;
-  p[4] = (((1.0 - (tyy + tzz)) * t0 + (txy - twz) * t1) + (txz + twy) * t2) + p[4];
-  p[5] = (((txy + twz) * t0 + (1.0 - (txx + tzz)) * t1) + (tyz - twx) * t2) + p[5];
-  p[6] = (((txz - twy) * t0 + (tyz + twx) * t1) + (1.0 - (txx + tyy)) * t2) + p[6];
+  double r[9];                                                // tw <- R(p) t + tw
+  m4d_rot64(p, r);
+  p[4] = ((r[0] * t0 + r[1] * t1) + r[2] * t2) + p[4];
+  p[5] = ((r[3] * t0 + r[4] * t1) + r[5] * t2) + p[5];
+  p[6] = ((r[6] * t0 + r[7] * t1) + r[8] * t2) + p[6];
   // Rw <- Rw R: the Hamilton product p q, renormalised
   double rw = ((pw * w - px * x) - py * y) - pz * z;
   double rx = ((pw * x + px * w) + py * z) - pz * y;

@@ -203,6 +203,20 @@ __device__ __forceinline__ M4dMotion m4d_load_motion(const float* __restrict__ r
   return m;
 }
 
+// R(q) of a float64 pose (qw qx qy qz tx ty tz), row-major, as get_rot_mat writes it: the one statement of these expressions
+// for the kernels that work in float64 (m4d_cloud.hip, m4d_confidence.hip, m4d_tsdf.hip).  The products that follow keep their
+// own operand order in each kernel.
+__device__ __forceinline__ void m4d_rot64(const double* __restrict__ p, double r[9]) {
+  const double qw = p[0], qx = p[1], qy = p[2], qz = p[3];
+  const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;
+  const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
+  const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
+  const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+  r[0] = 1.0 - (tyy + tzz); r[1] = txy - twz;          r[2] = txz + twy;
+  r[3] = txy + twz;          r[4] = 1.0 - (txx + tzz); r[5] = tyz - twx;
+  r[6] = txz - twy;          r[7] = tyz + twx;          r[8] = 1.0 - (txx + tyy);
+}
+
 // The per-pixel factors shared by parallax2depth / depth2parallax / DSCV
 // (utils/depth_operations.py:146-162, 174-190, 239-261).
 struct M4dPixel {

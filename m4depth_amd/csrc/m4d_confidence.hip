@@ -28,18 +28,6 @@ struct ViewsArgs {
   unsigned char* n_views; float* depth_f;
 };
 
-// R(q) as get_rot_mat writes it, float64
-__device__ __forceinline__ void views_rot(const double* __restrict__ p, double r[9]) {
-  const double qw = p[0], qx = p[1], qy = p[2], qz = p[3];
-  const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;
-  const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
-  const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
-  const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-  r[0] = 1.0 - (tyy + tzz); r[1] = txy - twz;          r[2] = txz + twy;
-  r[3] = txy + twz;          r[4] = 1.0 - (txx + tzz); r[5] = tyz - twx;
-  r[6] = txz - twy;          r[7] = tyz + twx;          r[8] = 1.0 - (txx + tyy);
-}
-
 template <bool kVec>
 __global__ void __launch_bounds__(kThreads)
 depth_views_kernel(ViewsArgs a) {
@@ -53,8 +41,8 @@ depth_views_kernel(ViewsArgs a) {
     const double* pk = a.ring_pose + ((long long)slot * a.b + s) * 7;
     const double* pc = a.pose + s * 7;
     double rk[9], rc[9];
-    views_rot(pk, rk);
-    views_rot(pc, rc);
+    m4d_rot64(pk, rk);
+    m4d_rot64(pc, rc);
     double* t = s_t[threadIdx.x];
 #pragma unroll
     for (int i = 0; i < 3; ++i)

@@ -2,63 +2,34 @@
 // (Curless & Levoy 1996; Niessner et al. 2013) and a naive-surface-nets extraction, on the device
 // (include/m4depth_hip.h: m4d_tsdf_allocate, m4d_tsdf_integrate, m4d_tsdf_extract_vertices, m4d_tsdf_extract_faces, m4d_tsdf_clear).
 //
-// State: per sample four statistics words, then -- structure of arrays -- the keys of an open-addressing table (linear probing,
-// the voxel map's key packing, hash, probe bound and 3/4 rule) and the 24-byte records behind them.  The per-frame pass over the
-// table streams the keys only and touches the records of the voxels the frame sees.
+// State: per sample four statistics words, then -- structure of arrays -- the keys of a hashed voxel grid (m4d_voxel_hash.h, the
+// voxel map's table) and the 24-byte records behind them.  The per-frame pass over the table streams the keys only and touches
+// the records of the voxels the frame sees.
 //   allocate : one thread per pixel walks its ray over the truncation band and claims the keys (agent-scope load + compare-and-
 //              swap); a claim writes the key only.  The SET of keys does not depend on the schedule.
 //   integrate: every slot has one thread; the owner of a record is the only thread that touches it, so the float32 sum S is the
 //              same for every schedule.  The only atomic is one add per workgroup on the `updates` statistic.
 //   extract  : one thread per slot looks its neighbours up with a read-only probe; records leave through a wave ballot and one
 //              atomic add per wave on a count word.  The host orders them.
-// No loop depends on what the table holds (kProbe trips at most), nothing waits for another thread.
-#include "m4d_common.h"
+#include "m4d_voxel_hash.h"
 #include "../../include/m4depth_hip.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int kChunk = 256;
 constexpr int kStats = 4;                                     // occupied, dropped_range, dropped_full, updates
 constexpr int kRecWords = 3;                                  // 24 bytes: float S, uint32 n, sr, sg, sb, nc
-constexpr int kProbe = 128;
-constexpr u64 kEmpty = ~0ull;
-constexpr int kHalf = 1 << 20;
-constexpr unsigned kCellMax = (1u << 21) - 1u;                // the largest biased cell index
 constexpr long long kMaxPixels = 1LL << 24;
 constexpr unsigned kIntegrateBlocks = 1024;                  // workgroups per sample of the integrate pass, at most
 
-#define TS_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define TS_ADD(p, v) __hip_atomic_fetch_add((p), (u64)(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
 struct TsdfRec { float S; unsigned n, sr, sg, sb, nc; };
 static_assert(sizeof(TsdfRec) == 24, "record layout");
-
-__device__ __forceinline__ u64 ts_slot_of(u64 key, int log2_slots) {
-  return (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots);
-}
 
 __device__ __forceinline__ u64* ts_keys(u64* state, int b, int s, int log2_slots) {
   return state + (long long)b * kStats + ((long long)s << log2_slots);
 }
 __device__ __forceinline__ TsdfRec* ts_recs(u64* state, int b, int s, int log2_slots) {
   return (TsdfRec*)(state + (long long)b * kStats + ((long long)b << log2_slots)) + ((long long)s << log2_slots);
-}
-
-// R(q) as get_rot_mat writes it, float64 (m4d_depth_cloud's expressions)
-struct Rot { double r[3][3]; };
-__device__ __forceinline__ Rot ts_rot(const double* p) {
-  const double qw = p[0], qx = p[1], qy = p[2], qz = p[3];
-  const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;
-  const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
-  const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
-  const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-  Rot m;
-  m.r[0][0] = 1.0 - (tyy + tzz); m.r[0][1] = txy - twz; m.r[0][2] = txz + twy;
-  m.r[1][0] = txy + twz; m.r[1][1] = 1.0 - (txx + tzz); m.r[1][2] = tyz - twx;
-  m.r[2][0] = txz - twy; m.r[2][1] = tyz + twx; m.r[2][2] = 1.0 - (txx + tyy);
-  return m;
 }
 
 __device__ __forceinline__ bool ts_pose_finite(const double* p) {
@@ -68,12 +39,7 @@ __device__ __forceinline__ bool ts_pose_finite(const double* p) {
   return ok;
 }
 
-__device__ __forceinline__ bool ts_cell(double x, double voxel, unsigned& cell) {
-  const double fl = floor(x / voxel);
-  if (!(fl >= -(double)kHalf && fl < (double)kHalf)) return false;
-  cell = (unsigned)((int)fl + kHalf);
-  return true;
-}
+__device__ __forceinline__ bool ts_cell(double x, double voxel, unsigned& cell) { return vh_cell_of(floor(x / voxel), cell); }
 
 __device__ __forceinline__ unsigned ts_byte(float v) {        // m4d_depth_export's rgb rule; fmaxf(NaN, 0) = 0
   return (unsigned)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f);
@@ -105,44 +71,25 @@ tsdf_allocate_kernel(FrameArgs a, u64* __restrict__ state, int b, int log2_slots
   const int row = (int)(px / a.w), col = (int)(px % a.w);
   const float fx = a.cam_f[s * 2], fy = a.cam_f[s * 2 + 1], cx = a.cam_c[s * 2], cy = a.cam_c[s * 2 + 1];
   const double ax = (double)((((float)col + 0.5f) - cx) / fx), ay = (double)((((float)row + 0.5f) - cy) / fy);
-  const Rot m = ts_rot(p);
+  double r[9];
+  m4d_rot64(p, r);
   const double voxel = (double)a.voxel, hv = voxel * 0.5;
   u64* stats = state + (long long)s * kStats;
   u64* keys = ts_keys(state, b, s, log2_slots);
-  const u64 slots = 1ull << log2_slots, limit = slots - (slots >> 2);
   u64 last = kEmpty;
   unsigned n_range = 0, n_full = 0;
   for (int k = -2 * a.trunc; active && k <= 2 * a.trunc; ++k) {
     const double z = (double)d + (double)k * hv;
     if (!(z > 0.0)) continue;
     const double X = ax * z, Y = ay * z;
-    const double wx = ((m.r[0][0] * X + m.r[0][1] * Y) + m.r[0][2] * z) + p[4];
-    const double wy = ((m.r[1][0] * X + m.r[1][1] * Y) + m.r[1][2] * z) + p[5];
-    const double wz = ((m.r[2][0] * X + m.r[2][1] * Y) + m.r[2][2] * z) + p[6];
+    const double wx = ((r[0] * X + r[1] * Y) + r[2] * z) + p[4];
+    const double wy = ((r[3] * X + r[4] * Y) + r[5] * z) + p[5];
+    const double wz = ((r[6] * X + r[7] * Y) + r[8] * z) + p[6];
     unsigned ix, iy, iz;
     if (!(ts_cell(wx, voxel, ix) && ts_cell(wy, voxel, iy) && ts_cell(wz, voxel, iz))) { ++n_range; continue; }
-    const u64 key = ((u64)ix << 42) | ((u64)iy << 21) | (u64)iz;
+    const u64 key = vh_pack(ix, iy, iz);
     if (kSkip && key == last) continue;
-    u64 slot = ts_slot_of(key, log2_slots);
-    bool found = false;
-    for (int i = 0; i < kProbe; ++i) {
-      u64* q = keys + slot;
-      u64 cur = TS_LOAD(q);
-      if (cur == kEmpty) {
-        if (TS_LOAD(stats + 0) >= limit) break;               // three quarters full: empty slots are no longer claimed
-        u64 expected = kEmpty;
-        if (__hip_atomic_compare_exchange_strong(q, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT)) {
-          TS_ADD(stats + 0, 1);
-          cur = key;
-        } else {
-          cur = expected;
-        }
-      }
-      if (cur == key) { found = true; break; }
-      slot = (slot + 1) & (slots - 1);
-    }
-    if (found) last = key; else ++n_full;
+    if (vh_claim<1>(keys, key, log2_slots, stats + 0)) last = key; else ++n_full;
   }
   // the drop counters of a workgroup leave as one add each (a full table drops every sample of every ray)
 #pragma unroll
@@ -153,8 +100,8 @@ tsdf_allocate_kernel(FrameArgs a, u64* __restrict__ state, int b, int log2_slots
     unsigned range = 0, full = 0;
 #pragma unroll
     for (int i = 0; i < kChunk / 64; ++i) { range += s_range[i]; full += s_full[i]; }
-    if (range) TS_ADD(stats + 1, range);
-    if (full) TS_ADD(stats + 2, full);
+    if (range) VH_ADD(stats + 1, range);
+    if (full) VH_ADD(stats + 2, full);
   }
 }
 
@@ -167,7 +114,8 @@ tsdf_integrate_kernel(FrameArgs a, u64* __restrict__ state, int b, int log2_slot
   const int s = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double* p = a.pose + s * 7;
   if (!ts_pose_finite(p)) return;                              // the whole workgroup: s is its sample
-  const Rot m = ts_rot(p);
+  double r[9];
+  m4d_rot64(p, r);
   const double voxel = (double)a.voxel;
   const float T = (float)((double)a.trunc * voxel);
   const double fx = (double)a.cam_f[s * 2], fy = (double)a.cam_f[s * 2 + 1];
@@ -180,12 +128,12 @@ tsdf_integrate_kernel(FrameArgs a, u64* __restrict__ state, int b, int log2_slot
   for (long long slot = (long long)blockIdx.x * kChunk + threadIdx.x; slot < slots; slot += stride) {
     const u64 key = keys[slot];
     if (key == kEmpty) continue;
-    const double D0 = ((double)((int)(key >> 42) - kHalf) + 0.5) * voxel - t0;
-    const double D1 = ((double)((int)((key >> 21) & 0x1FFFFFull) - kHalf) + 0.5) * voxel - t1;
-    const double D2 = ((double)((int)(key & 0x1FFFFFull) - kHalf) + 0.5) * voxel - t2;
-    const double X0 = (m.r[0][0] * D0 + m.r[1][0] * D1) + m.r[2][0] * D2;
-    const double X1 = (m.r[0][1] * D0 + m.r[1][1] * D1) + m.r[2][1] * D2;
-    const double z = (m.r[0][2] * D0 + m.r[1][2] * D1) + m.r[2][2] * D2;
+    const double D0 = ((double)vh_cell(key, 0) + 0.5) * voxel - t0;
+    const double D1 = ((double)vh_cell(key, 1) + 0.5) * voxel - t1;
+    const double D2 = ((double)vh_cell(key, 2) + 0.5) * voxel - t2;
+    const double X0 = (r[0] * D0 + r[3] * D1) + r[6] * D2;                      // R^T (centre - t)
+    const double X1 = (r[1] * D0 + r[4] * D1) + r[7] * D2;
+    const double z = (r[2] * D0 + r[5] * D1) + r[8] * D2;
     if (!(z > 0.0)) continue;
     const double u = (fx * X0) / z + cx, v = (fy * X1) / z + cy;
     if (!(u >= 0.0 && u < (double)a.w && v >= 0.0 && v < (double)a.h)) continue;      // NaN fails
@@ -213,34 +161,8 @@ tsdf_integrate_kernel(FrameArgs a, u64* __restrict__ state, int b, int log2_slot
     unsigned all = 0;
 #pragma unroll
     for (int i = 0; i < kChunk / 64; ++i) all += s_upd[i];
-    if (all) TS_ADD(state + (long long)s * kStats + 3, all);
+    if (all) VH_ADD(state + (long long)s * kStats + 3, all);
   }
-}
-
-// the slot of `key` in the table, or -1: the insertion's probe sequence, read-only; it ends at an empty slot
-__device__ __forceinline__ long long ts_find(const u64* __restrict__ keys, u64 key, int log2_slots) {
-  const u64 slots = 1ull << log2_slots;
-  u64 slot = ts_slot_of(key, log2_slots);
-  for (int i = 0; i < kProbe; ++i) {
-    const u64 cur = keys[slot];
-    if (cur == key) return (long long)slot;
-    if (cur == kEmpty) return -1;
-    slot = (slot + 1) & (slots - 1);
-  }
-  return -1;
-}
-
-// wave ballot + one atomic add per wave: the place of this lane's record, or -1 when it has none
-__device__ __forceinline__ long long ts_place(bool keep, u64* count) {
-  const int lane = threadIdx.x & 63;
-  const u64 mask = __ballot(keep);
-  if (!mask) return -1;
-  const int first = __builtin_ctzll(mask);
-  const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-  u64 base = 0;
-  if (lane == first) base = TS_ADD(count, __popcll(mask));
-  base = __shfl(base, first, 64);
-  return keep ? (long long)base + rank : -1;
 }
 
 __global__ void __launch_bounds__(kChunk)
@@ -256,7 +178,7 @@ tsdf_vertices_kernel(const u64* __restrict__ keys, const TsdfRec* __restrict__ r
   if (slot < (1ll << log2_slots)) {
     key = keys[slot];
     if (key != kEmpty) {
-      const unsigned cx = (unsigned)(key >> 42), cy = (unsigned)((key >> 21) & 0x1FFFFFull), cz = (unsigned)(key & 0x1FFFFFull);
+      const unsigned cx = vh_biased(key, 0), cy = vh_biased(key, 1), cz = vh_biased(key, 2);
       bool valid = cx < kCellMax && cy < kCellMax && cz < kCellMax;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
@@ -264,8 +186,8 @@ tsdf_vertices_kernel(const u64* __restrict__ keys, const TsdfRec* __restrict__ r
         if (!valid) continue;
         long long at = slot;
         if (c) {
-          const u64 other = ((u64)(cx + (c & 1)) << 42) | ((u64)(cy + ((c >> 1) & 1)) << 21) | (u64)(cz + ((c >> 2) & 1));
-          at = ts_find(keys, other, log2_slots);
+          const u64 other = vh_pack(cx + (c & 1), cy + ((c >> 1) & 1), cz + ((c >> 2) & 1));
+          at = vh_find(keys, other, log2_slots);
         }
         if (at < 0) { valid = false; continue; }
         const TsdfRec r = recs[at];
@@ -282,7 +204,7 @@ tsdf_vertices_kernel(const u64* __restrict__ keys, const TsdfRec* __restrict__ r
       }
     }
   }
-  const long long at = ts_place(keep, count);
+  const long long at = vh_place(keep, count);
   if (at < 0 || at >= out_cap) return;
   float sum[3] = {0.0f, 0.0f, 0.0f};
   int crossings = 0;
@@ -303,9 +225,8 @@ tsdf_vertices_kernel(const u64* __restrict__ keys, const TsdfRec* __restrict__ r
   float pos[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const int cell = (int)((key >> (42 - 21 * i)) & 0x1FFFFFull) - kHalf;
     const float local = sum[i] / (float)crossings;
-    pos[i] = (float)((((double)cell + 0.5) + (double)local) * voxel);
+    pos[i] = (float)((((double)vh_cell(key, i) + 0.5) + (double)local) * voxel);
   }
   unsigned r = 0, g = 0, bl = 0;
   if (nc) { r = (unsigned)((2 * sr + nc) / (2 * nc)); g = (unsigned)((2 * sg + nc) / (2 * nc)); bl = (unsigned)((2 * sb + nc) / (2 * nc)); }
@@ -328,7 +249,7 @@ tsdf_faces_kernel(const u64* __restrict__ keys, const TsdfRec* __restrict__ recs
       const TsdfRec r = recs[slot];
       valid = r.n >= min_frames && r.n > 0u;
       if (valid) in_k = r.S / (float)r.n < 0.0f;
-      cell[0] = (unsigned)(key >> 42); cell[1] = (unsigned)((key >> 21) & 0x1FFFFFull); cell[2] = (unsigned)(key & 0x1FFFFFull);
+      cell[0] = vh_biased(key, 0); cell[1] = vh_biased(key, 1); cell[2] = vh_biased(key, 2);
     }
   }
 #pragma unroll
@@ -337,13 +258,13 @@ tsdf_faces_kernel(const u64* __restrict__ keys, const TsdfRec* __restrict__ recs
     const u64 ea = 1ull << (42 - 21 * a), eb = 1ull << (42 - 21 * bx), ec = 1ull << (42 - 21 * cx);
     bool emit = false;
     if (valid && cell[a] < kCellMax && cell[bx] >= 1u && cell[cx] >= 1u) {
-      const long long at = ts_find(keys, key + ea, log2_slots);
+      const long long at = vh_find(keys, key + ea, log2_slots);
       if (at >= 0) {
         const TsdfRec r = recs[at];
         if (r.n >= min_frames && r.n > 0u) emit = (r.S / (float)r.n < 0.0f) != in_k;
       }
     }
-    const long long at = ts_place(emit, count);
+    const long long at = vh_place(emit, count);
     if (at < 0 || at >= out_cap) continue;
     u64* q = quads_out + at * 5;
     const u64 c0 = key, c1 = key - eb, c2 = key - eb - ec, c3 = key - ec;
@@ -368,13 +289,11 @@ tsdf_clear_kernel(u64* __restrict__ state, const unsigned char* __restrict__ mas
   if (blockIdx.x == 0 && threadIdx.x < kStats) state[(long long)s * kStats + threadIdx.x] = 0ull;
 }
 
-inline bool ts_geometry(int b, int log2_slots) { return b >= 1 && b <= 65535 && log2_slots >= 6 && log2_slots <= 26; }
-
 inline int ts_frame_args(const float* depth, long long depth_stride, const float* rgb, long long rgb_stride, const float* cam_f,
                          const float* cam_c, const double* pose, int b, int h, int w, float near, float far, float voxel,
                          int trunc, const void* state, int log2_slots, bool want_rgb, FrameArgs& a) {
   M4D_CHECK_ARG(depth && cam_f && cam_c && pose && state && (rgb || !want_rgb));
-  M4D_CHECK_ARG(ts_geometry(b, log2_slots) && h >= 1 && w >= 1 && (long long)h * w <= kMaxPixels);
+  M4D_CHECK_ARG(vh_geometry(b, log2_slots) && h >= 1 && w >= 1 && (long long)h * w <= kMaxPixels);
   M4D_CHECK_ARG(far > near && voxel > 0.0f && voxel < __builtin_inff() && trunc >= 2 && trunc <= 8);
   M4D_CHECK_ARG(depth_stride >= (long long)h * w && (!want_rgb || rgb_stride >= 3LL * h * w));
   M4D_CHECK_ARG(((((uintptr_t)depth) | ((uintptr_t)rgb) | ((uintptr_t)cam_f) | ((uintptr_t)cam_c)) & 3u) == 0);
@@ -394,12 +313,10 @@ int ts_allocate(const float* depth, long long depth_stride, const float* cam_f, 
   return M4D_LAUNCH_RESULT();
 }
 
-inline unsigned ts_slot_blocks(int log2_slots) { return (unsigned)(((1ll << log2_slots) + kChunk - 1) / kChunk); }
-
 }  // namespace
 
 extern "C" long long m4d_tsdf_state_words(int b, int log2_slots) {
-  return ts_geometry(b, log2_slots) ? (long long)b * (kStats + ((long long)(1 + kRecWords) << log2_slots)) : -1;
+  return vh_geometry(b, log2_slots) ? (long long)b * (kStats + ((long long)(1 + kRecWords) << log2_slots)) : -1;
 }
 
 extern "C" int m4d_tsdf_allocate(const float* depth, long long depth_stride, const float* cam_f, const float* cam_c,
@@ -423,7 +340,7 @@ extern "C" int m4d_tsdf_integrate(const float* depth, long long depth_stride, co
   FrameArgs a;
   if (int e = ts_frame_args(depth, depth_stride, rgb, rgb_stride, cam_f, cam_c, pose, b, h, w, near, far, voxel, trunc, state,
                             log2_slots, true, a)) return e;
-  const unsigned blocks = ts_slot_blocks(log2_slots);
+  const unsigned blocks = vh_slot_blocks(log2_slots, kChunk);
   m4d_launch(tsdf_integrate_kernel, dim3(blocks > kIntegrateBlocks ? kIntegrateBlocks : blocks, (unsigned)b), dim3(kChunk), 0,
              (hipStream_t)stream, a, (u64*)state, b, log2_slots);
   return M4D_LAUNCH_RESULT();
@@ -432,33 +349,33 @@ extern "C" int m4d_tsdf_integrate(const float* depth, long long depth_stride, co
 extern "C" int m4d_tsdf_extract_vertices(const void* state, int b, int log2_slots, int s, int min_frames, float voxel,
                                          void* keys_out, void* vertices_out, long long out_cap, void* count, void* stream) {
   M4D_CHECK_ARG(state && keys_out && vertices_out && count);
-  M4D_CHECK_ARG(ts_geometry(b, log2_slots) && s >= 0 && s < b && min_frames >= 1 && out_cap >= 1);
+  M4D_CHECK_ARG(vh_geometry(b, log2_slots) && s >= 0 && s < b && min_frames >= 1 && out_cap >= 1);
   M4D_CHECK_ARG(voxel > 0.0f && voxel < __builtin_inff());
   M4D_CHECK_ARG(((((uintptr_t)state) | ((uintptr_t)keys_out) | ((uintptr_t)count)) & 7u) == 0 &&
                 (((uintptr_t)vertices_out) & 15u) == 0);
   const u64* base = (const u64*)state + (long long)b * kStats;
   const u64* keys = base + ((long long)s << log2_slots);
   const TsdfRec* recs = (const TsdfRec*)(base + ((long long)b << log2_slots)) + ((long long)s << log2_slots);
-  m4d_launch(tsdf_vertices_kernel, dim3(ts_slot_blocks(log2_slots)), dim3(kChunk), 0, (hipStream_t)stream, keys, recs, log2_slots,
-             (unsigned)min_frames, voxel, (u64*)keys_out, (uint4*)vertices_out, out_cap, (u64*)count);
+  m4d_launch(tsdf_vertices_kernel, dim3(vh_slot_blocks(log2_slots, kChunk)), dim3(kChunk), 0, (hipStream_t)stream, keys, recs,
+             log2_slots, (unsigned)min_frames, voxel, (u64*)keys_out, (uint4*)vertices_out, out_cap, (u64*)count);
   return M4D_LAUNCH_RESULT();
 }
 
 extern "C" int m4d_tsdf_extract_faces(const void* state, int b, int log2_slots, int s, int min_frames, void* quads_out,
                                       long long out_cap, void* count, void* stream) {
   M4D_CHECK_ARG(state && quads_out && count);
-  M4D_CHECK_ARG(ts_geometry(b, log2_slots) && s >= 0 && s < b && min_frames >= 1 && out_cap >= 1);
+  M4D_CHECK_ARG(vh_geometry(b, log2_slots) && s >= 0 && s < b && min_frames >= 1 && out_cap >= 1);
   M4D_CHECK_ARG(((((uintptr_t)state) | ((uintptr_t)quads_out) | ((uintptr_t)count)) & 7u) == 0);
   const u64* base = (const u64*)state + (long long)b * kStats;
   const u64* keys = base + ((long long)s << log2_slots);
   const TsdfRec* recs = (const TsdfRec*)(base + ((long long)b << log2_slots)) + ((long long)s << log2_slots);
-  m4d_launch(tsdf_faces_kernel, dim3(ts_slot_blocks(log2_slots)), dim3(kChunk), 0, (hipStream_t)stream, keys, recs, log2_slots,
-             (unsigned)min_frames, (u64*)quads_out, out_cap, (u64*)count);
+  m4d_launch(tsdf_faces_kernel, dim3(vh_slot_blocks(log2_slots, kChunk)), dim3(kChunk), 0, (hipStream_t)stream, keys, recs,
+             log2_slots, (unsigned)min_frames, (u64*)quads_out, out_cap, (u64*)count);
   return M4D_LAUNCH_RESULT();
 }
 
 extern "C" int m4d_tsdf_clear(void* state, const unsigned char* mask, int b, int log2_slots, void* stream) {
-  M4D_CHECK_ARG(state && ts_geometry(b, log2_slots) && (((uintptr_t)state) & 7u) == 0);
+  M4D_CHECK_ARG(state && vh_geometry(b, log2_slots) && (((uintptr_t)state) & 7u) == 0);
   const long long per_sample = ((1ll << log2_slots) + kChunk - 1) / kChunk;
   const dim3 grid((unsigned)(per_sample > 2048 ? 2048 : per_sample), (unsigned)b);
   m4d_launch(tsdf_clear_kernel, grid, dim3(kChunk), 0, (hipStream_t)stream, (u64*)state, mask, b, log2_slots);

@@ -1,9 +1,8 @@
 // Voxel maps: the per-frame point clouds of a trajectory merged into one vertex per occupied voxel, on the device
 // (include/m4depth_hip.h: m4d_voxel_map_integrate, m4d_voxel_map_extract, m4d_voxel_map_clear).
 //
-// State: one open-addressing hash table per sample, linear probing, records of kRec = 10 unsigned 64-bit words (key, n, sx, sy,
-// sz, sr, sg, sb, last_stamp, frames) behind four statistics words per sample.  Keys are read and claimed with agent-scope
-// atomics only (the table of a sample is touched by workgroups on every XCD); every accumulator is an integer, so the sums do
+// State: one hashed voxel grid per sample (m4d_voxel_hash.h), records of kRec = 10 unsigned 64-bit words (key, n, sx, sy, sz,
+// sr, sg, sb, last_stamp, frames) behind four statistics words per sample.  Every accumulator is an integer, so the sums do
 // not depend on the order in which threads arrive and the table's CONTENT is the same for every schedule -- only the slot a key
 // lives in may differ, and the extraction's order is made the key order on the host.
 //
@@ -11,36 +10,22 @@
 // contributions of every run of consecutive lanes with one key (a segmented shuffle reduction on two packed words), and only
 // the head lane of a run probes the table and issues the atomics: 9 atomics per run instead of per vertex.  Integer sums: the
 // bits cannot change.  kCombine = false is the one-vertex-one-probe form it was measured against.
-// No loop depends on what the table holds: the probe loop runs kProbe trips at most, nothing waits for another thread.
-#include "m4d_common.h"
+#include "m4d_voxel_hash.h"
 #include "../../include/m4depth_hip.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kChunk = 256;                                   // vertices per workgroup = threads per workgroup
 constexpr int kWaves = kChunk / 64;
 constexpr int kRec = 10;                                      // words of a table record
 constexpr int kStats = 4;                                     // observations, dropped_range, dropped_full, occupied
-constexpr int kProbe = 128;                                   // probe trips of one insertion: the constant bound
-constexpr u64 kEmpty = ~0ull;
-constexpr int kHalf = 1 << 20;                                // voxel indices live in [-2^20, 2^20)
 constexpr long long kMaxCap = 1LL << 24;                      // m4d_depth_cloud's bound on the vertices of a sample
-
-#define VM_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define VM_ADD(p, v) __hip_atomic_fetch_add((p), (u64)(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-__device__ __forceinline__ u64 vm_slot_of(u64 key, int log2_slots) {       // Fibonacci hashing: the top bits of key * 2^64 / phi
-  return (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots);
-}
 
 // one coordinate -> voxel index + 2^20 and the offset bin 0..255; false = out of range
 __device__ __forceinline__ bool vm_axis(float x, double voxel, unsigned& cell, unsigned& off) {
   const double g = (double)x / voxel;
   const double fl = floor(g);
-  if (!(fl >= -(double)kHalf && fl < (double)kHalf)) return false;
-  cell = (unsigned)((int)fl + kHalf);
+  if (!vh_cell_of(fl, cell)) return false;
   const int o = (int)floor((g - fl) * 256.0);                 // g - fl rounds to 1.0 for a tiny negative g: bin 255
   off = (unsigned)(o > 255 ? 255 : o);
   return true;
@@ -67,7 +52,7 @@ voxel_integrate_kernel(const uint4* __restrict__ vertices, const int* __restrict
     ok = isfinite(x) && isfinite(y) && isfinite(z) && vm_axis(x, voxel, cx, ox) && vm_axis(y, voxel, cy, oy) &&
          vm_axis(z, voxel, cz, oz);
     if (ok) {
-      key = ((u64)cx << 42) | ((u64)cy << 21) | (u64)cz;
+      key = vh_pack(cx, cy, cz);
       pa = (u64)ox | ((u64)oy << 16) | ((u64)oz << 32) | (1ull << 48);
       pb = (u64)(v.w & 0xFFu) | ((u64)((v.w >> 8) & 0xFFu) << 16) | ((u64)((v.w >> 16) & 0xFFu) << 32);
     }
@@ -93,40 +78,21 @@ voxel_integrate_kernel(const uint4* __restrict__ vertices, const int* __restrict
 
   u64* stats = state + (long long)s * kStats;
   if (head) {
-    const u64 slots = 1ull << log2_slots, limit = slots - (slots >> 2);
     u64* table = state + (long long)b * kStats + ((long long)s << log2_slots) * kRec;
-    u64 slot = vm_slot_of(key, log2_slots);
-    u64* rec = nullptr;
-    for (int i = 0; i < kProbe; ++i) {
-      u64* p = table + slot * kRec;
-      u64 cur = VM_LOAD(p);
-      if (cur == kEmpty) {
-        if (VM_LOAD(stats + 3) >= limit) break;               // three quarters full: empty slots are no longer claimed
-        u64 expected = kEmpty;
-        if (__hip_atomic_compare_exchange_strong(p, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT)) {
-          VM_ADD(stats + 3, 1);
-          cur = key;
-        } else {
-          cur = expected;                                     // somebody else's claim: maybe of this very key
-        }
-      }
-      if (cur == key) { rec = p; break; }
-      slot = (slot + 1) & (slots - 1);
-    }
+    u64* rec = vh_claim<kRec>(table, key, log2_slots, stats + 3);
     const u64 n = pa >> 48;
     if (rec) {
-      VM_ADD(rec + 1, n);
-      VM_ADD(rec + 2, pa & 0xFFFFu);
-      VM_ADD(rec + 3, (pa >> 16) & 0xFFFFu);
-      VM_ADD(rec + 4, (pa >> 32) & 0xFFFFu);
-      VM_ADD(rec + 5, pb & 0xFFFFu);
-      VM_ADD(rec + 6, (pb >> 16) & 0xFFFFu);
-      VM_ADD(rec + 7, (pb >> 32) & 0xFFFFu);
+      VH_ADD(rec + 1, n);
+      VH_ADD(rec + 2, pa & 0xFFFFu);
+      VH_ADD(rec + 3, (pa >> 16) & 0xFFFFu);
+      VH_ADD(rec + 4, (pa >> 32) & 0xFFFFu);
+      VH_ADD(rec + 5, pb & 0xFFFFu);
+      VH_ADD(rec + 6, (pb >> 16) & 0xFFFFu);
+      VH_ADD(rec + 7, (pb >> 32) & 0xFFFFu);
       const u64 old = __hip_atomic_fetch_max(rec + 8, stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (old < stamp) VM_ADD(rec + 9, 1);
+      if (old < stamp) VH_ADD(rec + 9, 1);
     } else {
-      VM_ADD(stats + 2, n);                                   // the probe ran out, or the table is full
+      VH_ADD(stats + 2, n);                                   // the probe ran out, or the table is full
     }
   }
 
@@ -135,8 +101,8 @@ voxel_integrate_kernel(const uint4* __restrict__ vertices, const int* __restrict
     unsigned obs = 0, range = 0;
 #pragma unroll
     for (int i = 0; i < kWaves; ++i) { obs += s_obs[i]; range += s_range[i]; }
-    if (obs) VM_ADD(stats + 0, obs);
-    if (range) VM_ADD(stats + 1, range);
+    if (obs) VH_ADD(stats + 0, obs);
+    if (range) VH_ADD(stats + 1, range);
   }
 }
 
@@ -146,7 +112,6 @@ voxel_extract_kernel(const u64* __restrict__ table, int log2_slots, u64 min_fram
                      u64* __restrict__ keys_out, uint4* __restrict__ vertices_out, long long out_cap,
                      u64* __restrict__ count) {
   const long long slot = (long long)blockIdx.x * kChunk + threadIdx.x;
-  const int lane = threadIdx.x & 63;
   const u64* rec = table + slot * kRec;
   bool keep = false;
   u64 key = kEmpty;
@@ -154,22 +119,14 @@ voxel_extract_kernel(const u64* __restrict__ table, int log2_slots, u64 min_fram
     key = rec[0];
     keep = key != kEmpty && rec[1] > 0 && rec[9] >= min_frames;
   }
-  const u64 mask = __ballot(keep);
-  if (!mask) return;
-  const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-  u64 base = 0;
-  if (lane == __builtin_ctzll(mask)) base = VM_ADD(count, __popcll(mask));
-  base = __shfl(base, __builtin_ctzll(mask), 64);
-  if (!keep) return;
-  const long long at = (long long)base + rank;
-  if (at >= out_cap) return;                                  // the count still says how many there were
+  const long long at = vh_place(keep, count);
+  if (at < 0 || at >= out_cap) return;                        // the count still says how many there were
   const u64 n = rec[1];
   const double voxel = (double)voxel_f, dn = (double)n;
   float p[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const int cell = (int)((key >> (42 - 21 * a)) & 0x1FFFFFull) - kHalf;
-    p[a] = (float)(((double)cell + ((double)rec[2 + a] / dn + 0.5) / 256.0) * voxel);
+    p[a] = (float)(((double)vh_cell(key, a) + ((double)rec[2 + a] / dn + 0.5) / 256.0) * voxel);
   }
   const unsigned r = (unsigned)((2 * rec[5] + n) / (2 * n)), g = (unsigned)((2 * rec[6] + n) / (2 * n)),
                  bl = (unsigned)((2 * rec[7] + n) / (2 * n));
@@ -192,13 +149,11 @@ voxel_clear_kernel(u64* __restrict__ state, const unsigned char* __restrict__ ma
   if (blockIdx.x == 0 && threadIdx.x < kStats) state[(long long)s * kStats + threadIdx.x] = 0ull;
 }
 
-inline bool vm_geometry(int b, int log2_slots) { return b >= 1 && b <= 65535 && log2_slots >= 6 && log2_slots <= 26; }
-
 template <bool kCombine>
 int vm_integrate(const void* vertices, const int* counts, int b, int cap, float voxel, long long stamp, void* state,
                  int log2_slots, void* stream) {
   M4D_CHECK_ARG(vertices && counts && state);
-  M4D_CHECK_ARG(vm_geometry(b, log2_slots) && cap >= 1 && cap <= kMaxCap);
+  M4D_CHECK_ARG(vh_geometry(b, log2_slots) && cap >= 1 && cap <= kMaxCap);
   M4D_CHECK_ARG(voxel > 0.0f && voxel < __builtin_inff() && stamp >= 1);
   M4D_CHECK_ARG((((uintptr_t)vertices) & 15u) == 0 && (((uintptr_t)counts) & 3u) == 0 && (((uintptr_t)state) & 7u) == 0);
   const dim3 grid((unsigned)((cap + kChunk - 1) / kChunk), (unsigned)b);
@@ -210,7 +165,7 @@ int vm_integrate(const void* vertices, const int* counts, int b, int cap, float 
 }  // namespace
 
 extern "C" long long m4d_voxel_map_state_words(int b, int log2_slots) {
-  return vm_geometry(b, log2_slots) ? (long long)b * (kStats + ((long long)kRec << log2_slots)) : -1;
+  return vh_geometry(b, log2_slots) ? (long long)b * (kStats + ((long long)kRec << log2_slots)) : -1;
 }
 
 extern "C" int m4d_voxel_map_integrate(const void* vertices, const int* counts, int b, int cap, float voxel, long long stamp,
@@ -229,19 +184,18 @@ extern "C" int m4d_voxel_map_integrate_uncombined(const void* vertices, const in
 extern "C" int m4d_voxel_map_extract(const void* state, int b, int log2_slots, int s, int min_frames, float voxel,
                                      void* keys_out, void* vertices_out, long long out_cap, void* count, void* stream) {
   M4D_CHECK_ARG(state && keys_out && vertices_out && count);
-  M4D_CHECK_ARG(vm_geometry(b, log2_slots) && s >= 0 && s < b && min_frames >= 1 && out_cap >= 1);
+  M4D_CHECK_ARG(vh_geometry(b, log2_slots) && s >= 0 && s < b && min_frames >= 1 && out_cap >= 1);
   M4D_CHECK_ARG(voxel > 0.0f && voxel < __builtin_inff());
   M4D_CHECK_ARG(((((uintptr_t)state) | ((uintptr_t)keys_out) | ((uintptr_t)count)) & 7u) == 0 &&
                 (((uintptr_t)vertices_out) & 15u) == 0);
   const u64* table = (const u64*)state + (long long)b * kStats + ((long long)s << log2_slots) * kRec;
-  const unsigned blocks = (unsigned)(((1ll << log2_slots) + kChunk - 1) / kChunk);
-  m4d_launch(voxel_extract_kernel, dim3(blocks), dim3(kChunk), 0, (hipStream_t)stream, table, log2_slots, (u64)min_frames, voxel,
-             (u64*)keys_out, (uint4*)vertices_out, out_cap, (u64*)count);
+  m4d_launch(voxel_extract_kernel, dim3(vh_slot_blocks(log2_slots, kChunk)), dim3(kChunk), 0, (hipStream_t)stream, table,
+             log2_slots, (u64)min_frames, voxel, (u64*)keys_out, (uint4*)vertices_out, out_cap, (u64*)count);
   return M4D_LAUNCH_RESULT();
 }
 
 extern "C" int m4d_voxel_map_clear(void* state, const unsigned char* mask, int b, int log2_slots, void* stream) {
-  M4D_CHECK_ARG(state && vm_geometry(b, log2_slots) && (((uintptr_t)state) & 7u) == 0);
+  M4D_CHECK_ARG(state && vh_geometry(b, log2_slots) && (((uintptr_t)state) & 7u) == 0);
   const long long per_sample = ((1ll << log2_slots) * kRec + kChunk - 1) / kChunk;
   const dim3 grid((unsigned)(per_sample > 2048 ? 2048 : per_sample), (unsigned)b);
   m4d_launch(voxel_clear_kernel, grid, dim3(kChunk), 0, (hipStream_t)stream, (u64*)state, mask, b, log2_slots);

@@ -277,6 +277,34 @@ class _Slot:
         self.pending = 0
 
 
+class _TrajectoryProduct:
+    """One per-trajectory product of the writer (the voxel map, the TSDF mesh): its device state, the directory of every
+    sample's open trajectory, and the callables that are all the two differ in -- ``new_state(b, device)``;
+    ``extract(state, s)`` -> (device arrays, stats, {counter of the writer: what this trajectory adds}); ``clear(state, mask)``;
+    ``write(path, *host arrays, stats)``."""
+
+    def __init__(self, file_name, new_state, extract, clear, write):
+        self.file_name, self.new_state, self.extract, self.clear, self.write = file_name, new_state, extract, clear, write
+        self.state = None                                  # allocated with the slots
+        self.dirs = None                                   # set by the first step that went into the state
+
+
+def _trajectory_options(flag, voxel, cloud_frame, reason, ints):
+    """The option group of a trajectory product: ``voxel`` (None: off) as a float32 length and its companions ``ints`` = (name,
+    value, default, lowest, highest or None) as integers (None: the default); the companions are checked only with the flag."""
+    voxel = None if voxel is None else float(np.float32(voxel))
+    ints = [(name, default if v is None else v, lo, hi) for name, v, default, lo, hi in ints]
+    if voxel is not None:
+        if not (0 < voxel < float("inf")):
+            raise ValueError(f"{flag}: the voxel edge must be a finite length > 0, got {voxel}")
+        if cloud_frame != "world":
+            raise ValueError(f"{flag} needs cloud_frame='world': {reason}")
+        if any(int(v) < lo or (hi is not None and int(v) > hi) for _, v, lo, hi in ints):
+            need = [f"{name} >= {lo}" if hi is None else f"{name} in {lo}..{hi}" for name, _, lo, hi in ints]
+            raise ValueError(f"need {', '.join(need[:-1])} and {need[-1]}, got {', '.join(str(v) for _, v, _, _ in ints)}")
+    return (voxel, *(int(v) for _, v, _, _ in ints))
+
+
 class PredictionWriter:
     """Writes ``<out_dir>/<name>_depth.png`` (16-bit greyscale, ``fmt``) and, with ``panels``, ``<name>_panels.png`` (RGB) for
     every sample handed to ``submit``.  A ring of ``slots`` device + pinned host buffer pairs; ``submit`` launches the export
@@ -344,27 +372,13 @@ class PredictionWriter:
         cloud_views = int(cloud_views)
         if not 0 <= cloud_views <= nops.VIEWS_MAX:
             raise ValueError(f"cloud_views must be 0 (off) or 1..{nops.VIEWS_MAX}, got {cloud_views}")
-        save_map = None if save_map is None else float(np.float32(save_map))
-        map_min_frames = 2 if map_min_frames is None else map_min_frames           # None: the default, as for cloud_min_views
-        map_slots_log2 = 21 if map_slots_log2 is None else map_slots_log2
-        if save_map is not None and not (0 < save_map < float("inf")):
-            raise ValueError(f"save_map: the voxel edge must be a finite length > 0, got {save_map}")
-        if save_map is not None and cloud_frame != "world":
-            raise ValueError("save_map needs cloud_frame='world': a map merges the frames of a trajectory in one frame")
-        if save_map is not None and (int(map_min_frames) < 1 or not 6 <= int(map_slots_log2) <= 26):
-            raise ValueError(f"need map_min_frames >= 1 and map_slots_log2 in 6..26, got {map_min_frames}, {map_slots_log2}")
-        save_mesh = None if save_mesh is None else float(np.float32(save_mesh))
-        mesh_trunc = 4 if mesh_trunc is None else mesh_trunc
-        mesh_min_frames = 2 if mesh_min_frames is None else mesh_min_frames
-        mesh_slots_log2 = 22 if mesh_slots_log2 is None else mesh_slots_log2
-        if save_mesh is not None and not (0 < save_mesh < float("inf")):
-            raise ValueError(f"save_mesh: the voxel edge must be a finite length > 0, got {save_mesh}")
-        if save_mesh is not None and cloud_frame != "world":
-            raise ValueError("save_mesh needs cloud_frame='world': a mesh fuses the frames of a trajectory in one frame")
-        if save_mesh is not None and (not nops.TSDF_TRUNC[0] <= int(mesh_trunc) <= nops.TSDF_TRUNC[1] or int(mesh_min_frames) < 1
-                                      or not 6 <= int(mesh_slots_log2) <= 26):
-            raise ValueError(f"need mesh_trunc in {nops.TSDF_TRUNC[0]}..{nops.TSDF_TRUNC[1]}, mesh_min_frames >= 1 and "
-                             f"mesh_slots_log2 in 6..26, got {mesh_trunc}, {mesh_min_frames}, {mesh_slots_log2}")
+        save_map, map_min_frames, map_slots_log2 = _trajectory_options(
+            "save_map", save_map, cloud_frame, "a map merges the frames of a trajectory in one frame",
+            (("map_min_frames", map_min_frames, 2, 1, None), ("map_slots_log2", map_slots_log2, 21, 6, 26)))
+        save_mesh, mesh_trunc, mesh_min_frames, mesh_slots_log2 = _trajectory_options(
+            "save_mesh", save_mesh, cloud_frame, "a mesh fuses the frames of a trajectory in one frame",
+            (("mesh_trunc", mesh_trunc, 4, *nops.TSDF_TRUNC), ("mesh_min_frames", mesh_min_frames, 2, 1, None),
+             ("mesh_slots_log2", mesh_slots_log2, 22, 6, 26)))
         if cloud_views and not (cloud or save_map is not None or save_mesh is not None):
             raise ValueError("cloud_views needs cloud=True: the check runs on the clouds' pose chain (save_map or save_mesh "
                              "run on it as well)")
@@ -384,19 +398,23 @@ class PredictionWriter:
         self._views_n = self._views_depth = None           # [b,h,w] counts (without save_conf) and the filtered copy
         self.cloud_kept = self.cloud_cap = 0               # vertices written / vertices the clouds could hold, finished frames
         self._pose = None                                  # [b,7] float64 device state of the cloud: camera-to-world poses
-        self.save_map, self.map_min_frames, self.map_slots_log2 = save_map, int(map_min_frames), int(map_slots_log2)
-        self.save_mesh, self.mesh_trunc = save_mesh, int(mesh_trunc)
-        self.mesh_min_frames, self.mesh_slots_log2 = int(mesh_min_frames), int(mesh_slots_log2)
+        self.save_map, self.map_min_frames, self.map_slots_log2 = save_map, map_min_frames, map_slots_log2
+        self.save_mesh, self.mesh_trunc = save_mesh, mesh_trunc
+        self.mesh_min_frames, self.mesh_slots_log2 = mesh_min_frames, mesh_slots_log2
         self._vertices3d = self.cloud or save_map is not None      # the cloud launches run
         self._geometry3d = self._vertices3d or save_mesh is not None   # the pose chain (and the views check) runs
-        self._mesh = None                                  # network_ops.tsdf_state, allocated with the slots
-        self._mesh_dirs = None                             # per sample: the directory of its open trajectory
+        self._map = self._mesh = None                      # the trajectory products that are on
+        if save_map is not None:
+            self._map = _TrajectoryProduct("map.ply", lambda b, dev: nops.voxel_map_state(b, map_slots_log2, dev),
+                                           self._extract_map, nops.voxel_map_clear, self._write_map)
+        if save_mesh is not None:
+            self._mesh = _TrajectoryProduct("mesh.ply", lambda b, dev: nops.tsdf_state(b, mesh_slots_log2, dev),
+                                            self._extract_mesh, nops.tsdf_clear, self._write_mesh)
+        self._products = [p for p in (self._map, self._mesh) if p is not None]     # in the order they finish and clear
+        self.maps = self.map_voxels = self.map_dropped_range = self.map_dropped_full = 0
         self.meshes = self.mesh_vertices = self.mesh_triangles = 0
         self.mesh_dropped_range = self.mesh_dropped_full = self.mesh_quads_dropped = 0
-        self._map = None                                   # network_ops.voxel_map_state, allocated with the slots
-        self._map_dirs = None                              # per sample: the directory of its open trajectory
         self._step = 0                                     # submits so far: the stamp of a step's vertices
-        self.maps = self.map_voxels = self.map_dropped_range = self.map_dropped_full = 0
         self.out_dir, self.fmt, self.panels = str(out_dir), fmt, panels
         self.near, self.far, self.err_max = float(near), float(far), float(err_max)
         self.n_slots, self.compress_level, self.encode = int(slots), int(compress_level), bool(encode)
@@ -429,73 +447,59 @@ class PredictionWriter:
         cap = nops.cloud_capacity(h, w, self.cloud_step) if self._vertices3d else 0
         self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf, self.cloud, self._geometry3d)
                        for _ in range(self.n_slots)]
-        if self.save_mesh is not None:
-            self._mesh = nops.tsdf_state(b, self.mesh_slots_log2, est.device)
-        if self.save_map is not None:
-            self._map = nops.voxel_map_state(b, self.map_slots_log2, est.device)
+        for product in self._products[::-1]:
+            product.state = product.new_state(b, est.device)
         if any(p != "rgb" for p in self.panels):
             self._lut = torch.from_numpy(default_lut()).to(est.device)
         for i in range(self.n_slots):
             self._free.put(i)
 
-    def _finish_map(self, s):
-        """The map of sample ``s``'s open trajectory to a worker thread; the caller clears the table on the same stream."""
-        keys, vertices, stats = nops.voxel_map_extract(self._map, s, self.map_min_frames, self.save_map)   # the one wait
-        host = torch.empty(vertices.shape, dtype=torch.uint8)
-        if len(keys):                                      # (an empty map is written too: a trajectory nothing survived of)
-            host = host.pin_memory()
-            host.copy_(vertices, non_blocking=True)
+    def _extract_map(self, state, s):
+        keys, vertices, stats = nops.voxel_map_extract(state, s, self.map_min_frames, self.save_map)   # the one wait
+        return (vertices,), stats, {"maps": 1, "map_voxels": len(keys), "map_dropped_range": stats["dropped_range"],
+                                    "map_dropped_full": stats["dropped_full"]}
+
+    def _write_map(self, path, vertices, stats):
+        write_map_ply(path, vertices, self.save_map, self.map_min_frames, stats)
+
+    def _extract_mesh(self, state, s):
+        keys, vertices, triangles, stats = nops.tsdf_extract(state, s, self.mesh_min_frames, self.save_mesh)
+        return (vertices, triangles), stats, {"meshes": 1, "mesh_vertices": len(keys), "mesh_triangles": len(triangles),
+                                              "mesh_dropped_range": stats["dropped_range"],
+                                              "mesh_dropped_full": stats["dropped_full"],
+                                              "mesh_quads_dropped": stats["quads_dropped"]}
+
+    def _write_mesh(self, path, vertices, triangles, stats):
+        write_mesh_ply(path, vertices, triangles, self.save_mesh, self.mesh_trunc, self.mesh_min_frames, stats)
+
+    def _finish(self, product, s):
+        """``product`` of sample ``s``'s open trajectory to a worker thread; the caller clears the state on the same stream."""
+        arrays, stats, counters = product.extract(product.state, s)
+        hosts = [torch.empty(a.shape, dtype=a.dtype) for a in arrays]
+        for i, a in enumerate(arrays):
+            if len(a):                                     # (an empty map or mesh is written too: nothing survived)
+                hosts[i] = hosts[i].pin_memory()
+                hosts[i].copy_(a, non_blocking=True)
         event = torch.cuda.Event()
         event.record()
-        self.maps += 1
-        self.map_voxels += len(keys)
-        self.map_dropped_range += stats["dropped_range"]
-        self.map_dropped_full += stats["dropped_full"]
-        self._pool.submit(self._work_map, os.path.join(self._map_dirs[s], "map.ply"), host, event, stats)
+        for name, n in counters.items():
+            setattr(self, name, getattr(self, name) + n)
+        self._pool.submit(self._work_product, product, os.path.join(product.dirs[s], product.file_name), hosts, event, stats)
 
-    def _work_map(self, rel_path, host, event, stats):
+    def _keep_error(self, e):
+        with self._lock:
+            if self._error is None:
+                self._error = e
+
+    def _work_product(self, product, rel_path, hosts, event, stats):
         try:
             event.synchronize()
             if self.encode:
                 path = os.path.join(self.out_dir, rel_path)
                 os.makedirs(os.path.dirname(path), exist_ok=True)
-                write_map_ply(path, host.numpy(), self.save_map, self.map_min_frames, stats)
+                product.write(path, *(h.numpy() for h in hosts), stats)
         except BaseException as e:
-            with self._lock:
-                if self._error is None:
-                    self._error = e
-
-    def _finish_mesh(self, s):
-        """The mesh of sample ``s``'s open trajectory to a worker thread; the caller clears the volume on the same stream."""
-        keys, vertices, triangles, stats = nops.tsdf_extract(self._mesh, s, self.mesh_min_frames, self.save_mesh)
-        v_host, t_host = torch.empty(vertices.shape, dtype=torch.uint8), torch.empty(triangles.shape, dtype=torch.int32)
-        if len(keys):                                      # (an empty mesh is written too)
-            v_host = v_host.pin_memory()
-            v_host.copy_(vertices, non_blocking=True)
-        if len(triangles):
-            t_host = t_host.pin_memory()
-            t_host.copy_(triangles, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record()
-        self.meshes += 1
-        self.mesh_vertices += len(keys)
-        self.mesh_triangles += len(triangles)
-        self.mesh_dropped_range += stats["dropped_range"]
-        self.mesh_dropped_full += stats["dropped_full"]
-        self.mesh_quads_dropped += stats["quads_dropped"]
-        self._pool.submit(self._work_mesh, os.path.join(self._mesh_dirs[s], "mesh.ply"), v_host, t_host, event, stats)
-
-    def _work_mesh(self, rel_path, v_host, t_host, event, stats):
-        try:
-            event.synchronize()
-            if self.encode:
-                path = os.path.join(self.out_dir, rel_path)
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                write_mesh_ply(path, v_host.numpy(), t_host.numpy(), self.save_mesh, self.mesh_trunc, self.mesh_min_frames, stats)
-        except BaseException as e:
-            with self._lock:
-                if self._error is None:
-                    self._error = e
+            self._keep_error(e)
 
     def _submit_cloud(self, slot, est, rgb, rot, trans, camera, reset, names):
         """The cloud of one step into ``slot``, on the current stream: pose update, compaction, copies; with ``save_map`` the
@@ -528,14 +532,10 @@ class PredictionWriter:
                 slot.reset_h.numpy()[:] = reset
                 slot.reset_d.copy_(slot.reset_h, non_blocking=True)
                 mask = slot.reset_d
-                if self.save_map is not None and reset.any():
+                for product in self._products if reset.any() else ():
                     for s in np.nonzero(reset)[0]:         # the trajectories that ended with the previous frame
-                        self._finish_map(int(s))
-                    nops.voxel_map_clear(self._map, mask)
-                if self.save_mesh is not None and reset.any():
-                    for s in np.nonzero(reset)[0]:
-                        self._finish_mesh(int(s))
-                    nops.tsdf_clear(self._mesh, mask)
+                        self._finish(product, int(s))
+                    product.clear(product.state, mask)
         nops.pose_accumulate(rot, trans, self._pose, reset=mask, force_all=first)
         if self.cloud_views:                               # the clouds see the filtered copy; PNG and panels the estimate
             b, h, w = est.shape[:3]
@@ -551,16 +551,16 @@ class PredictionWriter:
             if self.save_conf:
                 slot.conf_h.copy_(slot.conf_d, non_blocking=True)
         if self.save_mesh is not None:                     # the mesh sees what the clouds see, at every pixel
-            nops.tsdf_integrate(est, rgb, camera["f"], camera["c"], self._pose, self.save_mesh, self.mesh_trunc, self._mesh,
-                                near=self.near, far=self.far)
-            self._mesh_dirs = dirs
+            nops.tsdf_integrate(est, rgb, camera["f"], camera["c"], self._pose, self.save_mesh, self.mesh_trunc,
+                                self._mesh.state, near=self.near, far=self.far)
+            self._mesh.dirs = dirs
         if not self._vertices3d:
             return
         nops.depth_cloud(est, rgb, camera["f"], camera["c"], step=self.cloud_step, near=self.near, far=self.far,
                          pose=self._pose if self.cloud_frame == "world" else None, vertices=slot.cloud_d, counts=slot.counts_d)
         if self.save_map is not None:
-            nops.voxel_map_integrate(slot.cloud_d, slot.counts_d, self.save_map, self._step, self._map)
-            self._map_dirs = dirs
+            nops.voxel_map_integrate(slot.cloud_d, slot.counts_d, self.save_map, self._step, self._map.state)
+            self._map.dirs = dirs
         if self.cloud:
             slot.cloud_h.copy_(slot.cloud_d, non_blocking=True)
             slot.counts_h.copy_(slot.counts_d, non_blocking=True)
@@ -628,9 +628,7 @@ class PredictionWriter:
                         arr = (arr.astype(np.uint16) * 255 // self.cloud_views).astype(np.uint8)
                     Image.fromarray(arr).save(path, format="PNG", compress_level=self.compress_level)
         except BaseException as e:                         # kept for close(); the slot is freed all the same
-            with self._lock:
-                if self._error is None:
-                    self._error = e
+            self._keep_error(e)
         finally:
             with self._lock:
                 slot.pending -= 1
@@ -644,18 +642,13 @@ class PredictionWriter:
             return
         self._closed = True
         try:
-            if self._map_dirs is not None:                 # the open trajectories end here
-                for s in range(len(self._map_dirs)):
-                    self._finish_map(s)
-                self._map_dirs = None
-            if self._mesh_dirs is not None:
-                for s in range(len(self._mesh_dirs)):
-                    self._finish_mesh(s)
-                self._mesh_dirs = None
+            for product in self._products:                 # the open trajectories end here
+                if product.dirs is not None:
+                    for s in range(len(product.dirs)):
+                        self._finish(product, s)
+                    product.dirs = None
         except BaseException as e:
-            with self._lock:
-                if self._error is None:
-                    self._error = e
+            self._keep_error(e)
         if self._slots is not None:
             for _ in range(self.n_slots):
                 self._free.get()

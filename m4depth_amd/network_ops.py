@@ -451,12 +451,27 @@ def consistency_per_sample(est, est_prev, cur, prev, rot, trans, f, c, reset, ac
 POSE_ALIGN_STATE = 64        # doubles per sample at the head of the pose-alignment workspace (include/m4depth_hip.h)
 
 
+def _mask(m, name, b, optional=False):
+    """A per-sample device mask as the library reads it: uint8 [b] (a bool mask reinterpreted), or None where it is optional."""
+    if m is None and optional:
+        return None
+    if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != (b,):
+        raise ValueError(f"{name}: expected a uint8 / bool [{b}] device tensor")
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
 def _masks(reset, active, b):
-    for name, m in (("reset", reset), ("active", active)):
-        if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != (b,):
-            raise ValueError(f"{name}: expected a uint8 / bool [{b}] device tensor")
-    return (reset.view(torch.uint8) if reset.dtype == torch.bool else reset,
-            active.view(torch.uint8) if active.dtype == torch.bool else active)
+    return _mask(reset, "reset", b), _mask(active, "active", b)
+
+
+def _check_pose7(pose, b):
+    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (b, 7):
+        raise ValueError(f"pose: expected a [{b},7] float64 device tensor")
+
+
+def _check_camera(cam_f, cam_c, b):
+    if tuple(cam_f.shape) != (b, 2) or tuple(cam_c.shape) != (b, 2):
+        raise ValueError(f"cam_f / cam_c: expected [{b},2], got {tuple(cam_f.shape)} and {tuple(cam_c.shape)}")
 
 
 def _pose(rot, trans):
@@ -594,10 +609,7 @@ def pose_accumulate(rot, trans, pose, reset=None, force_all=False):
         raise ValueError("rot: small-angle rotations [b,3] cannot be accumulated into a pose; quaternions [b,4] only")
     if tuple(rot.shape) != (b, 4) or tuple(trans.shape) != (b, 3):
         raise ValueError(f"expected rot [{b},4] and trans [{b},3], got {tuple(rot.shape)} and {tuple(trans.shape)}")
-    if reset is not None:
-        if not isinstance(reset, torch.Tensor) or reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (b,):
-            raise ValueError(f"reset: expected a uint8 / bool [{b}] device tensor")
-        reset = reset.view(torch.uint8) if reset.dtype == torch.bool else reset
+    reset = _mask(reset, "reset", b, optional=True)
     check(lib.m4d_pose_accumulate(dptr(reset, "reset", torch.uint8), int(bool(force_all)), dptr(as_f32(rot, "rot"), "rot"),
                                   dptr(as_f32(trans, "trans"), "trans"), b, dptr(pose, "pose", torch.float64), stream_ptr()),
           "m4d_pose_accumulate")
@@ -627,10 +639,9 @@ def depth_cloud(depth, rgb, cam_f, cam_c, step=2, near=1.0, far=80.0, pose=None,
         raise ValueError(f"need near < far, got {near}, {far}")
     if tuple(rgb.shape) != (b, h, w, 3):
         raise ValueError(f"rgb {tuple(rgb.shape)} does not belong to depth {tuple(depth.shape)}")
-    if tuple(cam_f.shape) != (b, 2) or tuple(cam_c.shape) != (b, 2):
-        raise ValueError(f"cam_f / cam_c: expected [{b},2], got {tuple(cam_f.shape)} and {tuple(cam_c.shape)}")
-    if pose is not None and (not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (b, 7)):
-        raise ValueError(f"pose: expected a [{b},7] float64 device tensor")
+    _check_camera(cam_f, cam_c, b)
+    if pose is not None:
+        _check_pose7(pose, b)
     ds, rs = _batch_stride(depth, "depth"), _batch_stride(rgb, "rgb")
     cap = cloud_capacity(h, w, step)
     dev = depth.device
@@ -687,18 +698,13 @@ def depth_views(depth, cam_f, cam_c, pose, state, reset=None, force_all=False, t
         raise ValueError(f"min_views must be in 1..{views}, got {min_views}")
     if not (float(tol_px) > 0 and float(tol_rel) > 0):
         raise ValueError(f"need tol_px > 0 and tol_rel > 0, got {tol_px}, {tol_rel}")
-    if tuple(cam_f.shape) != (b, 2) or tuple(cam_c.shape) != (b, 2):
-        raise ValueError(f"cam_f / cam_c: expected [{b},2], got {tuple(cam_f.shape)} and {tuple(cam_c.shape)}")
-    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (b, 7):
-        raise ValueError(f"pose: expected a [{b},7] float64 device tensor")
+    _check_camera(cam_f, cam_c, b)
+    _check_pose7(pose, b)
     ring_depth, ring_pose, (age_in, age_out) = state["ring_depth"], state["ring_pose"], state["age"]
     if tuple(ring_depth.shape) != (views + 1, b, h, w) or tuple(ring_pose.shape) != (views + 1, b, 7) \
             or tuple(age_in.shape) != (b,) or tuple(age_out.shape) != (b,) or not 0 <= int(state["head"]) <= views:
         raise ValueError(f"state: not a depth_views_state of {(b, h, w)} with {views} views")
-    if reset is not None:
-        if not isinstance(reset, torch.Tensor) or reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (b,):
-            raise ValueError(f"reset: expected a uint8 / bool [{b}] device tensor")
-        reset = reset.view(torch.uint8) if reset.dtype == torch.bool else reset
+    reset = _mask(reset, "reset", b, optional=True)
     ds = _batch_stride(depth, "depth")
     dev = depth.device
     if n_views is None:
@@ -739,13 +745,25 @@ def voxel_map_state(b, slots_log2, device):
     return voxel_map_clear(state)
 
 
-def _voxel_map_check(state, voxel=None):
+def _hashed_check(state, noun, state_words, voxel=None):
+    """(b, slots_log2) of a ``voxel_map_state`` / ``tsdf_state`` (``noun``: which; ``state_words``: the library's size of one)."""
     b, slots_log2 = int(state["b"]), int(state["slots_log2"])
-    if state["words"].numel() != lib.m4d_voxel_map_state_words(b, slots_log2):
-        raise ValueError(f"state: not a voxel_map_state of {b} samples with 2^{slots_log2} slots")
+    if state["words"].numel() != state_words(b, slots_log2):
+        raise ValueError(f"state: not a {noun} of {b} samples with 2^{slots_log2} slots")
     if voxel is not None and not (float(voxel) > 0 and float(voxel) < float("inf")):
         raise ValueError(f"voxel must be a finite edge length > 0, got {voxel}")
     return b, slots_log2
+
+
+def _hashed_clear(state, mask, check_state, clear, entry):
+    b, slots_log2 = check_state(state)
+    mask = _mask(mask, "mask", b, optional=True)
+    check(clear(dptr(state["words"], "state", torch.int64), dptr(mask, "mask", torch.uint8), b, slots_log2, stream_ptr()), entry)
+    return state
+
+
+def _voxel_map_check(state, voxel=None):
+    return _hashed_check(state, "voxel_map_state", lib.m4d_voxel_map_state_words, voxel)
 
 
 def voxel_map_integrate(vertices, counts, voxel, stamp, state):
@@ -791,14 +809,7 @@ def voxel_map_extract(state, s, min_frames, voxel):
 def voxel_map_clear(state, mask=None):
     """Empties the maps of the samples with ``mask[s]`` set (uint8 / bool [b] device tensor; None: all of them) and zeroes
     their statistics (m4d_voxel_map_clear).  One launch."""
-    b, slots_log2 = _voxel_map_check(state)
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (b,):
-            raise ValueError(f"mask: expected a uint8 / bool [{b}] device tensor")
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    check(lib.m4d_voxel_map_clear(dptr(state["words"], "state", torch.int64), dptr(mask, "mask", torch.uint8), b, slots_log2,
-                                  stream_ptr()), "m4d_voxel_map_clear")
-    return state
+    return _hashed_clear(state, mask, _voxel_map_check, lib.m4d_voxel_map_clear, "m4d_voxel_map_clear")
 
 
 TSDF_STATS = ("occupied", "dropped_range", "dropped_full", "updates")   # the statistics words of m4d_tsdf_*
@@ -824,12 +835,7 @@ def tsdf_state_views(buf, b, slots_log2):
 
 
 def _tsdf_check(state, voxel=None):
-    b, slots_log2 = int(state["b"]), int(state["slots_log2"])
-    if state["words"].numel() != lib.m4d_tsdf_state_words(b, slots_log2):
-        raise ValueError(f"state: not a tsdf_state of {b} samples with 2^{slots_log2} slots")
-    if voxel is not None and not (float(voxel) > 0 and float(voxel) < float("inf")):
-        raise ValueError(f"voxel must be a finite edge length > 0, got {voxel}")
-    return b, slots_log2
+    return _hashed_check(state, "tsdf_state", lib.m4d_tsdf_state_words, voxel)
 
 
 def tsdf_integrate(depth, rgb, cam_f, cam_c, pose, voxel, trunc, state, near=1.0, far=80.0):
@@ -849,10 +855,8 @@ def tsdf_integrate(depth, rgb, cam_f, cam_c, pose, voxel, trunc, state, near=1.0
         raise ValueError(f"need near < far, got {near}, {far}")
     if tuple(rgb.shape) != (b, h, w, 3):
         raise ValueError(f"rgb {tuple(rgb.shape)} does not belong to depth {tuple(depth.shape)}")
-    if tuple(cam_f.shape) != (b, 2) or tuple(cam_c.shape) != (b, 2):
-        raise ValueError(f"cam_f / cam_c: expected [{b},2], got {tuple(cam_f.shape)} and {tuple(cam_c.shape)}")
-    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (b, 7):
-        raise ValueError(f"pose: expected a [{b},7] float64 device tensor")
+    _check_camera(cam_f, cam_c, b)
+    _check_pose7(pose, b)
     ds, rs = _batch_stride(depth, "depth"), _batch_stride(rgb, "rgb")
     f, c = dptr(as_f32(cam_f, "cam_f"), "cam_f"), dptr(as_f32(cam_c, "cam_c"), "cam_c")
     words = dptr(state["words"], "state", torch.int64)
@@ -934,14 +938,7 @@ def tsdf_order(keys, vertices, quads):
 def tsdf_clear(state, mask=None):
     """Empties the volumes of the samples with ``mask[s]`` set (uint8 / bool [b] device tensor; None: all of them) and zeroes
     their statistics (m4d_tsdf_clear).  One launch."""
-    b, slots_log2 = _tsdf_check(state)
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (b,):
-            raise ValueError(f"mask: expected a uint8 / bool [{b}] device tensor")
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    check(lib.m4d_tsdf_clear(dptr(state["words"], "state", torch.int64), dptr(mask, "mask", torch.uint8), b, slots_log2,
-                             stream_ptr()), "m4d_tsdf_clear")
-    return state
+    return _hashed_clear(state, mask, _tsdf_check, lib.m4d_tsdf_clear, "m4d_tsdf_clear")
 
 
 SUMMARY_KINDS = {"unit": 0, "log_depth": 1}                   # the `kind` argument of m4d_summary_images

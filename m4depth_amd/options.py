@@ -297,50 +297,46 @@ def check_recording_args(parser, args):
         parser.error("--rec_max_gap must be > 0")
 
 
+# the per-trajectory products of --save_dir: flag, its companions (option, default, lowest, highest or None) and why the camera
+# frame is refused.  The voxel map runs on the clouds' vertices, so the clouds' options serve it too; the TSDF mesh reads the
+# estimate itself, so of the clouds' options only --cloud_frame concerns it
+_TRAJECTORY_PRODUCTS = (
+    ("save_map", (("map_min_frames", 2, 1, None), ("map_slots_log2", 21, 16, 26)),
+     "a map merges the frames of a trajectory in one frame"),
+    ("save_mesh", (("mesh_trunc", 4, 2, 8), ("mesh_min_frames", 2, 1, None), ("mesh_slots_log2", 22, 16, 26)),
+     "a mesh fuses the frames of a trajectory in one frame"))
+
+
+def _check_trajectory_product(parser, args, flag, companions, reason):
+    """The refusals and defaults of one of them (its options are absent from the namespace until given); whether it is on."""
+    for f in (flag,) + tuple(c[0] for c in companions):
+        setattr(args, f, getattr(args, f, None))
+    voxel = getattr(args, flag)
+    given = [c[0] for c in companions if getattr(args, c[0]) is not None]
+    if given and voxel is None:
+        parser.error("--%s needs --%s" % (given[0], flag))
+    if voxel is None:
+        return False
+    if not (0 < voxel < float("inf")):
+        parser.error("--%s VOXEL needs a finite edge length > 0" % flag)
+    if args.cloud_frame == "camera":
+        parser.error("--%s needs --cloud_frame world: %s" % (flag, reason))
+    for f, default, lo, hi in companions:
+        v = getattr(args, f)
+        if v is not None and (v < lo or (hi is not None and v > hi)):
+            parser.error("--%s must be %s" % (f, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi)))
+        setattr(args, f, default if v is None else v)
+    return True
+
+
 def check_save_args(parser, args):
     """Refusals of the ``--save_*`` options; fills in their defaults and parses ``--save_panels`` into a tuple."""
     from .export import PANELS
     others = [f for f in ("save_format", "save_panels", "save_range", "save_err_max") if getattr(args, f) is not None]
     others += [f for f in ("save_cloud",) if args.save_cloud]
-    # the voxel map: absent from the namespace until given; it runs on the clouds' vertices, so the clouds' options serve it too
-    for f in ("save_map", "map_min_frames", "map_slots_log2"):
-        setattr(args, f, getattr(args, f, None))
-    map_others = [f for f in ("map_min_frames", "map_slots_log2") if getattr(args, f) is not None]
-    if map_others and args.save_map is None:
-        parser.error("--%s needs --save_map" % map_others[0])
-    if args.save_map is not None:
-        others.append("save_map")
-        if not (0 < args.save_map < float("inf")):
-            parser.error("--save_map VOXEL needs a finite edge length > 0")
-        if args.cloud_frame == "camera":
-            parser.error("--save_map needs --cloud_frame world: a map merges the frames of a trajectory in one frame")
-        if args.map_min_frames is not None and args.map_min_frames < 1:
-            parser.error("--map_min_frames must be >= 1")
-        if args.map_slots_log2 is not None and not 16 <= args.map_slots_log2 <= 26:
-            parser.error("--map_slots_log2 must be in 16..26")
-        args.map_min_frames = 2 if args.map_min_frames is None else args.map_min_frames
-        args.map_slots_log2 = 21 if args.map_slots_log2 is None else args.map_slots_log2
-    # the TSDF mesh: the same pattern; it reads the estimate itself, so of the clouds' options only --cloud_frame concerns it
-    for f in ("save_mesh", "mesh_trunc", "mesh_min_frames", "mesh_slots_log2"):
-        setattr(args, f, getattr(args, f, None))
-    mesh_others = [f for f in ("mesh_trunc", "mesh_min_frames", "mesh_slots_log2") if getattr(args, f) is not None]
-    if mesh_others and args.save_mesh is None:
-        parser.error("--%s needs --save_mesh" % mesh_others[0])
-    if args.save_mesh is not None:
-        others.append("save_mesh")
-        if not (0 < args.save_mesh < float("inf")):
-            parser.error("--save_mesh VOXEL needs a finite edge length > 0")
-        if args.cloud_frame == "camera":
-            parser.error("--save_mesh needs --cloud_frame world: a mesh fuses the frames of a trajectory in one frame")
-        if args.mesh_trunc is not None and not 2 <= args.mesh_trunc <= 8:
-            parser.error("--mesh_trunc must be in 2..8")
-        if args.mesh_min_frames is not None and args.mesh_min_frames < 1:
-            parser.error("--mesh_min_frames must be >= 1")
-        if args.mesh_slots_log2 is not None and not 16 <= args.mesh_slots_log2 <= 26:
-            parser.error("--mesh_slots_log2 must be in 16..26")
-        args.mesh_trunc = 4 if args.mesh_trunc is None else args.mesh_trunc
-        args.mesh_min_frames = 2 if args.mesh_min_frames is None else args.mesh_min_frames
-        args.mesh_slots_log2 = 22 if args.mesh_slots_log2 is None else args.mesh_slots_log2
+    for product in _TRAJECTORY_PRODUCTS:
+        if _check_trajectory_product(parser, args, *product):
+            others.append(product[0])
     geometry = args.save_cloud or args.save_map is not None or args.save_mesh is not None
     cloud_others = [f for f in ("cloud_stride", "cloud_frame") if getattr(args, f) is not None]
     if args.save_dir is not None and cloud_others and not geometry:

@@ -6,20 +6,11 @@ view tested the pixel and the two residuals the kernel compares.  Also the synth
 seen from cameras that move and turn a little more every frame."""
 import numpy as np
 
+from pose_ref import rot
+
 F = np.float32
 D = np.float64
 QNAN_BITS = np.uint32(0x7FC00000)
-
-
-def rot(q):
-    """get_rot_mat's formula in float64: q [4] -> 3 x 3 nested tuple."""
-    w, x, y, z = (D(v) for v in q)
-    tx, ty, tz = D(2.0) * x, D(2.0) * y, D(2.0) * z
-    twx, twy, twz = tx * w, ty * w, tz * w
-    txx, txy, txz = tx * x, ty * x, tz * x
-    tyy, tyz, tzz = ty * y, tz * y, tz * z
-    return ((D(1.0) - (tyy + tzz), txy - twz, txz + twy), (txy + twz, D(1.0) - (txx + tzz), tyz - twx),
-            (txz - twy, tyz + twx, D(1.0) - (txx + tyy)))
 
 
 def relative(pose_k, pose_c):

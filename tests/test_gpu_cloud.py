@@ -2,10 +2,10 @@
 a numpy restatement of the formulas in include/m4depth_hip.h.
 
 Camera-frame vertices are + - * / on float32, one rounding per operation, and the compaction is a pure reordering: counts and
-bytes are compared exactly.  World-frame vertices are evaluated in float64 and rounded once: the float64 evaluation's own error
-(a dozen roundings of 1.1e-16 relative on coordinates of tens of metres) is far below half a float32 ulp (6e-8 relative), so the
-device and numpy can differ only in which way a value next to a rounding boundary goes: 1 float32 ulp.  The pose chain is the
-same float64 arithmetic on both sides apart from the last bit of sqrt: 1e-12 absolute over 200 steps."""
+bytes are compared exactly.  World-frame vertices are + - * on float64 in the kernel's operand order (tests/pose_ref.py) and one
+rounding to float32: the kernel's own bytes are compared exactly too.  The pose chain adds float64 sqrt and /, which IEEE 754
+rounds correctly on both sides: every state of the 200 steps is compared bit for bit.  (The writer and driver tests, whose
+poses travel through files, keep the one-ulp / 1e-12 bounds they had.)"""
 import csv
 import json
 import os
@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from helpers import F, npy, make_fake_dataset
+from pose_ref import rot as rot_matrix, apply_pose
 
 pytestmark = pytest.mark.gpu
 
@@ -23,24 +24,6 @@ GUARD = 64                                                                      
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------
-def rot_matrix(q):
-    """get_rot_mat's formula in float64; q [4] -> rows (r0, r1, r2)."""
-    w, x, y, z = (np.float64(v) for v in q)
-    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
-    twx, twy, twz = tx * w, ty * w, tz * w
-    txx, txy, txz = tx * x, ty * x, tz * x
-    tyy, tyz, tzz = ty * y, tz * y, tz * z
-    return ((1.0 - (tyy + tzz), txy - twz, txz + twy), (txy + twz, 1.0 - (txx + tzz), tyz - twx),
-            (txz - twy, tyz + twx, 1.0 - (txx + tyy)))
-
-
-def apply_pose(pose, x, y, z):
-    """R(q) X + t in float64 (rows summed left to right, then t)."""
-    r = rot_matrix(pose[:4])
-    X, Y, Z = (np.asarray(v, np.float64) for v in (x, y, z))
-    return [((r[i][0] * X + r[i][1] * Y) + r[i][2] * Z) + np.float64(pose[4 + i]) for i in range(3)]
-
-
 def pose_step(pose, rot, trans, reset):
     """m4d_pose_accumulate of one sample: pose [7] float64, rot [4] / trans [3] float32."""
     if reset:
@@ -176,18 +159,17 @@ def test_world_frame_within_one_ulp_of_float64(dev, step):
     depth, rgb, f, c, pose = CASE
     got, counts, cap = _run(dev, step, pose, strided=False)
     colours = rgb_bytes(rgb)
-    worst = 0
     for s in range(B):
         xyz, rgba = cloud_of(depth[s], colours[s], f[s], c[s], step, NEAR, FAR, pose=pose[s])
         n = len(xyz)
         assert counts[s] == n
         got_xyz = got[s, :n, :12].copy().view(F)
         assert np.array_equal(got[s, :n, 12:], rgba), f"sample {s}: colours or order differ"
-        ok = within_one_ulp(got_xyz, xyz)
-        worst = max(worst, int((got_xyz != xyz).sum()))
-        assert ok.all(), f"sample {s}: {(~ok).sum()} coordinates off by more than 1 ulp; first at {np.argwhere(~ok)[0]}"
+        bad = np.argwhere(got_xyz.view(np.uint32) != xyz.view(np.uint32))
+        print(f"step {step} sample {s}: {len(bad)} of {3 * n} coordinates differ from numpy; "
+              f"{int((~within_one_ulp(got_xyz, xyz)).sum())} by more than one ulp")
+        assert len(bad) == 0, f"sample {s}: {len(bad)} coordinates differ in their bits; first at {bad[0]}"
         assert (got[s, n:] == SENTINEL).all()
-    print(f"step {step}: at most {worst} coordinates of a sample differ from numpy by one ulp")
 
 
 def test_cloud_replays_from_a_captured_graph(dev):
@@ -249,9 +231,12 @@ def test_pose_chain_follows_float64_numpy(dev):
         pose = np.stack([pose_step(pose[s], rot[k, s], trans[k, s], reset[k, s] or k in force) for s in range(b)])
         want[k] = pose
     err = np.abs(got - want).max()
+    differ = np.argwhere(got.view(np.uint64) != want.view(np.uint64))
     norm = np.abs(np.linalg.norm(got[..., :4], axis=-1) - 1.0).max()
-    print(f"pose chain: max |device - numpy| {err:.3e}, max |norm - 1| {norm:.3e}, |t| up to {np.abs(want[..., 4:]).max():.1f}")
+    print(f"pose chain: max |device - numpy| {err:.3e}, {len(differ)} of {got.size} values differ in their bits, "
+          f"max |norm - 1| {norm:.3e}, |t| up to {np.abs(want[..., 4:]).max():.1f}")
     assert np.isfinite(got).all() and err <= 1e-12
+    assert len(differ) == 0, f"first difference at (step, sample, word) {differ[0]}"
     assert norm <= 1e-15
     identity = np.array([1, 0, 0, 0, 0, 0, 0], np.float64)
     for k, s in list(zip(*np.nonzero(reset))) + [(120, s) for s in range(b)]:

@@ -16,6 +16,7 @@ import torch
 
 import depth_views_ref as R
 from helpers import F, npy, cameras_np, make_fake_dataset
+from pose_ref import apply_pose
 
 pytestmark = pytest.mark.gpu
 
@@ -350,12 +351,6 @@ def rgb_bytes(v):
     v = np.asarray(v, F)
     v = np.where(np.isnan(v), F(0.0), v)
     return np.rint(np.minimum(np.maximum(v, F(0.0)), F(1.0)) * F(255.0)).astype(np.uint8)
-
-
-def apply_pose(pose, x, y, z):
-    r = R.rot(pose[:4])
-    X, Y, Z = (np.asarray(v, np.float64) for v in (x, y, z))
-    return [((r[i][0] * X + r[i][1] * Y) + r[i][2] * Z) + np.float64(pose[4 + i]) for i in range(3)]
 
 
 def cloud_of(depth, colours, f, c, step, near, far, pose=None):

@@ -5,18 +5,11 @@ fits its table equals this one bit for bit.  ``exact=True`` is the float64 varia
 on: every float32 quantity of the header (the pixel factors, sdf, T, S, D, the crossing sums, the vertex) stays float64."""
 import numpy as np
 
-HALF = 1 << 20
+from pose_ref import rot
+from voxel_map_ref import HALF, EMPTY, pack, unpack             # the voxel map's keys: csrc/m4d_voxel_hash.h
+
 CELL_MAX = (1 << 21) - 1
-EMPTY = (1 << 64) - 1
 F32, F64 = np.float32, np.float64
-
-
-def pack(ix, iy, iz):
-    return ((int(ix) + HALF) << 42) | ((int(iy) + HALF) << 21) | (int(iz) + HALF)
-
-
-def unpack(key):
-    return tuple(((int(key) >> sh) & 0x1FFFFF) - HALF for sh in (42, 21, 0))
 
 
 def _biased(keys):
@@ -28,20 +21,6 @@ def _biased(keys):
 def _pack_biased(cells):
     c = np.asarray(cells, np.int64).astype(np.uint64)
     return (c[..., 0] << np.uint64(42)) | (c[..., 1] << np.uint64(21)) | c[..., 2]
-
-
-def rot(pose):
-    """R(q) as get_rot_mat writes it, float64, with m4d_depth_cloud's expressions: a 3 x 3 list of scalars."""
-    qw, qx, qy, qz = (F64(v) for v in pose[:4])
-    two = F64(2.0)
-    tx, ty, tz = two * qx, two * qy, two * qz
-    twx, twy, twz = tx * qw, ty * qw, tz * qw
-    txx, txy, txz = tx * qx, ty * qx, tz * qx
-    tyy, tyz, tzz = ty * qy, tz * qy, tz * qz
-    one = F64(1.0)
-    return [[one - (tyy + tzz), txy - twz, txz + twy],
-            [txy + twz, one - (txx + tzz), tyz - twx],
-            [txz - twy, tyz + twx, one - (txx + tyy)]]
 
 
 def rgb_bytes(rgb):

@@ -17,7 +17,7 @@ def axis(x, voxel):
 
 
 def pack(ix, iy, iz):
-    return ((ix + HALF) << 42) | ((iy + HALF) << 21) | (iz + HALF)
+    return ((int(ix) + HALF) << 42) | ((int(iy) + HALF) << 21) | (int(iz) + HALF)
 
 
 def unpack(key):
