@@ -1122,6 +1122,52 @@ int m4d_tsdf_clear(void* state, const unsigned char* mask, int b, int log2_slots
 /* unsigned 64-bit words of the state, b (4 + 4 * 2^L); -1 for a geometry the entries refuse. */
 long long m4d_tsdf_state_words(int b, int log2_slots);
 
+/* ---- fused depth per frame (main.py --fused VOXEL, --save_fused): the TSDF volume rendered into a camera (csrc/m4d_tsdf.hip) ---- */
+
+/* m4d_tsdf_raycast: the second half of KinectFusion -- every pixel's ray is marched through the field of the state above and
+ * the z-depth (the network's convention) of the first front-face zero crossing is written.  One launch, one thread per pixel; the
+ * state is only read: the launch runs after m4d_tsdf_integrate on the same stream.  state / b / log2_slots, cam_f, cam_c [b,2],
+ * pose [b,7] float64, voxel, K = trunc as above; depth_out [b,h,w,1] float32, guide and fill likewise (or NULL), each at its
+ * batch stride in ELEMENTS.  One IEEE rounding per operation, float64 where m4d_tsdf_allocate uses it and in its operand order,
+ * so that the two agree on the voxel a point falls in.
+ *   Per sample s: a pose that holds a non-finite number makes every pixel a miss.  R = R(q), t = pose[4..6]; voxel widened to
+ *   double, hv = voxel * 0.5.
+ *   Per pixel (row, col): ax = ((col + 0.5f) - cx) / fx,  ay = ((row + 0.5f) - cy) / fy             (float32, then widened)
+ *   March range: z_lo = (double) near, z_hi = (double) far.  With guide != NULL and g = guide[s * guide_stride + px] finite,
+ *   near <= g <= far:  Wd = ((double) window * (double) K) * voxel,  z_lo = fmax(near, (double) g - Wd),
+ *   z_hi = fmin(far, (double) g + Wd); any other guide pixel marches the whole range.
+ *   Positions: z_i = z_lo + (double) i * hv for i = 0 .. n_max = (long long) floor((z_hi - z_lo) / hv).
+ *   Sample i: X = ax * z_i, Y = ay * z_i;  Pw[j] = ((R[j][0] X + R[j][1] Y) + R[j][2] z_i) + t[j];  cell[j] = floor(Pw[j] / voxel).
+ *     KNOWN when the three cells lie in [-2^20, 2^20), the key is found (read-only probe, the insertion's sequence, ending at
+ *     an empty slot) and its record has n >= min_frames and n > 0; then D = S / (float) n.  UNKNOWN otherwise.
+ *   March, state (i, mode, run, prev), from i = 0, coarse, no prev, while i <= n_max:
+ *     coarse, unknown: i += 2K (one truncation distance in z).
+ *     coarse, known  : i = (i == 0 ? 0 : i - 2K + 1), the position just after the last unknown coarse one; mode = fine, run = 0,
+ *                      no prev; position i is sampled again.
+ *     fine, unknown  : no prev, run += 1; when run == 2K: mode = coarse, i += 2K; else i += 1.
+ *     fine, known    : run = 0.  With a prev (of position i - 1), prev >= 0 and D < 0: the HIT,
+ *                      z* = z_{i-1} + hv * (double) (prev / (prev - D))      (the quotient float32, then widened).
+ *                      Otherwise prev = D, i += 1.
+ *   The first positive-to-negative crossing between two consecutive known samples wins; negative-to-positive crossings (back
+ *   faces) and crossings across an unknown sample are none.  After a back-up the fine walk reaches the known coarse position
+ *   before run can reach 2K, so a position is sampled at most once per mode: 2 (n_max + 1) trips at most.
+ *   Output: depth_out[s * out_stride + px] = (float) z* on a hit; on a miss fill[s * fill_stride + px] when fill != NULL, else
+ *   the quiet NaN 0x7FC00000.  depth_out may be fill itself when the two strides are equal (a pixel is read before it is written,
+ *   by its own thread); any other overlap of depth_out with fill or guide is undefined.
+ *   hits: NULL, or b unsigned 64-bit words; the launch ADDS the hits of sample s to hits[s] (one integer atomic add per
+ *   workgroup: the value is order-free).  The caller zeroes the words.
+ * A thread does not probe for a key that the previous sample of its ray had; a wave is an 8x8 pixel tile.  Neither changes a bit.
+ * Returns 1 without a launch for: a NULL state, cam_f, cam_c, pose or depth_out, b outside 1..65535, L outside 6..26, h or
+ * w < 1, h*w > 2^24, far <= near or near <= 0 (NaN included), voxel not > 0 or not finite, trunc outside 2..8, min_frames < 1,
+ * window < 1 with a guide, ((double) far - (double) near) / ((double) voxel * 0.5) > 2^20 (the march's constant bound), a stride
+ * smaller than an image, a float pointer off 4 bytes, state / pose / hits off 8.  Plain launch (capturable).  Additive entry
+ * point: ABI 6 unchanged. */
+int m4d_tsdf_raycast(const void* state, int b, int log2_slots, const float* cam_f, const float* cam_c, const double* pose,
+                     int h, int w, float near, float far, float voxel, int trunc, int min_frames,
+                     const float* guide, long long guide_stride, int window,
+                     const float* fill, long long fill_stride,
+                     float* depth_out, long long out_stride, void* hits, void* stream);
+
 /* ---- training summaries (main.py --mode=train --log_dir): float32 maps -> the uint8 images of a TensorBoard event -------- */
 
 /* Up to 16 float32 maps of different sizes -> uint8 images, in one launch.  src, stride, h, w, c, kind and out_offset are

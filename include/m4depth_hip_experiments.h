@@ -33,6 +33,15 @@ int m4d_tsdf_allocate_plain(const float* depth, long long depth_stride, const fl
                             int b, int h, int w, float near, float far, float voxel, int trunc, void* state, int log2_slots,
                             void* stream);
 
+/* m4d_tsdf_raycast (include/m4depth_hip.h) in the forms its two choices were measured against: variant bit 0 = a wave is an 8x8
+ * pixel tile (clear: 64 consecutive pixels of the raster), bit 1 = no probe for a key the previous sample of the ray had (clear:
+ * every sample probes).  0 is the plain kernel, 3 the product's; anything else is refused.  The other arguments and every bit of
+ * the result are m4d_tsdf_raycast's; what tools/bench_tsdf_raycast.py measures the product kernel against. */
+int m4d_tsdf_raycast_plain(int variant, const void* state, int b, int log2_slots, const float* cam_f, const float* cam_c,
+                           const double* pose, int h, int w, float near, float far, float voxel, int trunc, int min_frames,
+                           const float* guide, long long guide_stride, int window, const float* fill, long long fill_stride,
+                           float* depth_out, long long out_stride, void* hits, void* stream);
+
 /* ---- launch tape (csrc/m4d_tape.hip): a recorded sequence of this library's kernel launches, replayed as PLAIN STREAM
  * LAUNCHES from one host loop -- the host-side cost of a hipGraph replay without its effect on concurrent small kernels
  * (DESIGN_HISTORY.md).  Between m4d_tape_begin()

@@ -11,6 +11,8 @@
 //              same for every schedule.  The only atomic is one add per workgroup on the `updates` statistic.
 //   extract  : one thread per slot looks its neighbours up with a read-only probe; records leave through a wave ballot and one
 //              atomic add per wave on a count word.  The host orders them.
+//   raycast  : one thread per pixel marches its ray through the field, coarse to fine, with the read-only probe, and writes the
+//              depth of the first front-face zero crossing (m4d_tsdf_raycast): the volume rendered back into a frame.
 #include "m4d_voxel_hash.h"
 #include "../../include/m4depth_hip.h"
 
@@ -289,6 +291,151 @@ tsdf_clear_kernel(u64* __restrict__ state, const unsigned char* __restrict__ mas
   if (blockIdx.x == 0 && threadIdx.x < kStats) state[(long long)s * kStats + threadIdx.x] = 0ull;
 }
 
+struct RayArgs {
+  const float* cam_f; const float* cam_c; const double* pose;
+  const float* guide; long long guide_stride;
+  const float* fill; long long fill_stride;
+  float* out; long long out_stride;
+  u64* hits;
+  int h, w, trunc, window;
+  unsigned min_frames;
+  float near, far, voxel;
+};
+
+// One thread per pixel marches its ray through the volume: the state is only read.  Per sample of the ray: three float64
+// divisions for the cell, one dependent 8-byte key load per probe trip, then the first 8 bytes (S, n) of the 24-byte record.
+// kTile : a wave is an 8x8 pixel tile (a workgroup 16x16) instead of 64 consecutive pixels of the raster: neighbouring rays end at
+//         similar depths, so the trip counts of a wave agree more.
+// kReuse: a sample whose key equals the previous sample's takes that sample's answer without a probe (half-voxel steps share
+//         voxels, and the fine walk starts on the coarse sample it backed up from).
+template <bool kTile, bool kReuse>
+__global__ void __launch_bounds__(kChunk)
+tsdf_raycast_kernel(RayArgs a, const u64* __restrict__ state, int b, int log2_slots) {
+  __shared__ unsigned s_hits[kChunk / 64];
+  const int s = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int row, col;
+  if (kTile) {
+    const int tiles_x = (a.w + 15) >> 4;
+    row = (int)(blockIdx.x / tiles_x) * 16 + (wave >> 1) * 8 + (lane >> 3);
+    col = (int)(blockIdx.x % tiles_x) * 16 + (wave & 1) * 8 + (lane & 7);
+  } else {
+    const long long at = (long long)blockIdx.x * kChunk + threadIdx.x;
+    row = (int)(at / a.w); col = (int)(at % a.w);
+  }
+  const bool active = row < a.h && col < a.w;
+  const long long px = (long long)row * a.w + col;
+  const float miss = active && a.fill ? a.fill[s * a.fill_stride + px] : __uint_as_float(0x7FC00000u);
+  const double* p = a.pose + s * 7;
+  if (!ts_pose_finite(p)) {                                    // the whole workgroup: s is its sample
+    if (active) a.out[s * a.out_stride + px] = miss;
+    return;
+  }
+  bool hit = false;
+  float result = miss;
+  if (active) {
+    const float fx = a.cam_f[s * 2], fy = a.cam_f[s * 2 + 1], cx = a.cam_c[s * 2], cy = a.cam_c[s * 2 + 1];
+    const double ax = (double)((((float)col + 0.5f) - cx) / fx), ay = (double)((((float)row + 0.5f) - cy) / fy);
+    double r[9];
+    m4d_rot64(p, r);
+    const double voxel = (double)a.voxel, hv = voxel * 0.5;
+    const int K2 = 2 * a.trunc;
+    double z_lo = (double)a.near, z_hi = (double)a.far;
+    if (a.guide) {
+      const float g = a.guide[s * a.guide_stride + px];
+      if (isfinite(g) && g >= a.near && g <= a.far) {
+        const double Wd = ((double)a.window * (double)a.trunc) * voxel;
+        z_lo = fmax((double)a.near, (double)g - Wd);
+        z_hi = fmin((double)a.far, (double)g + Wd);
+      }
+    }
+    const long long n_max = (long long)floor((z_hi - z_lo) / hv);
+    const u64* keys = state + (long long)b * kStats + ((long long)s << log2_slots);
+    const TsdfRec* recs = (const TsdfRec*)(state + (long long)b * kStats + ((long long)b << log2_slots)) + ((long long)s << log2_slots);
+    long long i = 0;
+    int run = 0;
+    bool fine = false, have_prev = false, last_known = false;
+    float prev = 0.0f, last_D = 0.0f;
+    u64 last = kEmpty;
+    for (long long trip = 0; trip < 2 * (n_max + 1) && i <= n_max; ++trip) {   // every position: once coarse, once fine, at most
+      const double z = z_lo + (double)i * hv;
+      const double X = ax * z, Y = ay * z;
+      const double wx = ((r[0] * X + r[1] * Y) + r[2] * z) + p[4];
+      const double wy = ((r[3] * X + r[4] * Y) + r[5] * z) + p[5];
+      const double wz = ((r[6] * X + r[7] * Y) + r[8] * z) + p[6];
+      unsigned ix, iy, iz;
+      bool known = false;
+      float D = 0.0f;
+      if (ts_cell(wx, voxel, ix) && ts_cell(wy, voxel, iy) && ts_cell(wz, voxel, iz)) {
+        const u64 key = vh_pack(ix, iy, iz);
+        if (kReuse && key == last) {
+          known = last_known; D = last_D;
+        } else {
+          const long long at = vh_find(keys, key, log2_slots);
+          if (at >= 0) {
+            const uint2 sn = *(const uint2*)(recs + at);       // S and n: the first 8 of the record's 24 bytes
+            if (sn.y >= a.min_frames && sn.y > 0u) { known = true; D = __uint_as_float(sn.x) / (float)sn.y; }
+          }
+          last = key; last_known = known; last_D = D;
+        }
+      }
+      if (!fine) {
+        if (!known) { i += K2; continue; }
+        i = i == 0 ? 0 : i - K2 + 1;                           // just after the last unknown coarse position
+        fine = true; run = 0; have_prev = false;
+        continue;
+      }
+      if (!known) {
+        have_prev = false;
+        if (++run == K2) { fine = false; i += K2; } else { i += 1; }
+        continue;
+      }
+      run = 0;
+      if (have_prev && prev >= 0.0f && D < 0.0f) {
+        const double z_prev = z_lo + (double)(i - 1) * hv;
+        result = (float)(z_prev + hv * (double)(prev / (prev - D)));
+        hit = true;
+        break;
+      }
+      prev = D; have_prev = true; i += 1;
+    }
+    a.out[s * a.out_stride + px] = result;
+  }
+  if (!a.hits) return;                                         // uniform
+  unsigned n_hit = hit ? 1u : 0u;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n_hit += __shfl_down(n_hit, off, 64);
+  if (lane == 0) s_hits[wave] = n_hit;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned all = 0;
+#pragma unroll
+    for (int i = 0; i < kChunk / 64; ++i) all += s_hits[i];
+    if (all) VH_ADD(a.hits + s, all);
+  }
+}
+
+template <bool kTile, bool kReuse>
+int ts_raycast(const void* state, int b, int log2_slots, const float* cam_f, const float* cam_c, const double* pose, int h, int w,
+               float near, float far, float voxel, int trunc, int min_frames, const float* guide, long long guide_stride,
+               int window, const float* fill, long long fill_stride, float* depth_out, long long out_stride, void* hits,
+               void* stream) {
+  M4D_CHECK_ARG(state && cam_f && cam_c && pose && depth_out);
+  M4D_CHECK_ARG(vh_geometry(b, log2_slots) && h >= 1 && w >= 1 && (long long)h * w <= kMaxPixels);
+  M4D_CHECK_ARG(far > near && near > 0.0f && voxel > 0.0f && voxel < __builtin_inff() && trunc >= 2 && trunc <= 8);
+  M4D_CHECK_ARG(min_frames >= 1 && (!guide || window >= 1));
+  M4D_CHECK_ARG(((double)far - (double)near) / ((double)voxel * 0.5) <= 1048576.0);      // the march's constant bound
+  const long long image = (long long)h * w;
+  M4D_CHECK_ARG(out_stride >= image && (!guide || guide_stride >= image) && (!fill || fill_stride >= image));
+  M4D_CHECK_ARG(((((uintptr_t)cam_f) | ((uintptr_t)cam_c) | ((uintptr_t)guide) | ((uintptr_t)fill) | ((uintptr_t)depth_out)) & 3u) == 0);
+  M4D_CHECK_ARG(((((uintptr_t)state) | ((uintptr_t)pose) | ((uintptr_t)hits)) & 7u) == 0);
+  const RayArgs a = {cam_f, cam_c, pose, guide, guide_stride, fill, fill_stride, depth_out, out_stride, (u64*)hits,
+                     h, w, trunc, guide ? window : 0, (unsigned)min_frames, near, far, voxel};
+  const long long groups = kTile ? (long long)((w + 15) / 16) * ((h + 15) / 16) : (image + kChunk - 1) / kChunk;
+  m4d_launch(tsdf_raycast_kernel<kTile, kReuse>, dim3((unsigned)groups, (unsigned)b), dim3(kChunk), 0, (hipStream_t)stream, a,
+             (const u64*)state, b, log2_slots);
+  return M4D_LAUNCH_RESULT();
+}
+
 inline int ts_frame_args(const float* depth, long long depth_stride, const float* rgb, long long rgb_stride, const float* cam_f,
                          const float* cam_c, const double* pose, int b, int h, int w, float near, float far, float voxel,
                          int trunc, const void* state, int log2_slots, bool want_rgb, FrameArgs& a) {
@@ -381,3 +528,33 @@ extern "C" int m4d_tsdf_clear(void* state, const unsigned char* mask, int b, int
   m4d_launch(tsdf_clear_kernel, grid, dim3(kChunk), 0, (hipStream_t)stream, (u64*)state, mask, b, log2_slots);
   return M4D_LAUNCH_RESULT();
 }
+
+// the product form: 8x8 pixel tiles per wave, no probe for a key the previous sample had (tools/bench_tsdf_raycast.py)
+extern "C" int m4d_tsdf_raycast(const void* state, int b, int log2_slots, const float* cam_f, const float* cam_c,
+                                const double* pose, int h, int w, float near, float far, float voxel, int trunc, int min_frames,
+                                const float* guide, long long guide_stride, int window, const float* fill, long long fill_stride,
+                                float* depth_out, long long out_stride, void* hits, void* stream) {
+  return ts_raycast<true, true>(state, b, log2_slots, cam_f, cam_c, pose, h, w, near, far, voxel, trunc, min_frames, guide,
+                                guide_stride, window, fill, fill_stride, depth_out, out_stride, hits, stream);
+}
+
+#if M4D_EXPERIMENTS
+// the forms the two choices were measured against; variant bit 0 = 8x8 tiles, bit 1 = key reuse (0 = the plain kernel)
+extern "C" int m4d_tsdf_raycast_plain(int variant, const void* state, int b, int log2_slots, const float* cam_f,
+                                      const float* cam_c, const double* pose, int h, int w, float near, float far, float voxel,
+                                      int trunc, int min_frames, const float* guide, long long guide_stride, int window,
+                                      const float* fill, long long fill_stride, float* depth_out, long long out_stride,
+                                      void* hits, void* stream) {
+#define TS_RAYCAST_FORM(tile, reuse)                                                                                         \
+  ts_raycast<tile, reuse>(state, b, log2_slots, cam_f, cam_c, pose, h, w, near, far, voxel, trunc, min_frames, guide,        \
+                          guide_stride, window, fill, fill_stride, depth_out, out_stride, hits, stream)
+  switch (variant) {
+    case 0: return TS_RAYCAST_FORM(false, false);
+    case 1: return TS_RAYCAST_FORM(true, false);
+    case 2: return TS_RAYCAST_FORM(false, true);
+    case 3: return TS_RAYCAST_FORM(true, true);
+  }
+#undef TS_RAYCAST_FORM
+  return (int)hipErrorInvalidValue;
+}
+#endif

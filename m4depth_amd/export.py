@@ -22,7 +22,8 @@ written as ``map.ply`` into the trajectory's directory by a worker thread (``wri
 With ``save_mesh=VOXEL`` the estimate of every step is also fused, on the device, into one truncated signed distance field per
 sample (``network_ops.tsdf_integrate``: a hashed voxel grid, two launches); when a sample's trajectory ends the surface is
 extracted by naive surface nets (``network_ops.tsdf_extract``), written as ``mesh.ply`` into the trajectory's directory by a
-worker thread (``write_mesh_ply``) and the volume cleared.
+worker thread (``write_mesh_ply``) and the volume cleared.  ``save_fused=True`` also renders that volume into every frame's
+camera (``network_ops.tsdf_raycast``, one launch) and writes the fused depth map as ``<frame>_fused.png``.
 """
 from __future__ import annotations
 
@@ -251,7 +252,7 @@ def read_conf_png(path, views):
 
 
 class _Slot:
-    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False, cloud_host=True, geometry=False):
+    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False, cloud_host=True, geometry=False, fused=False):
         self.depth_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
         self.depth_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
         self.panels_d = self.panels_h = None
@@ -273,6 +274,13 @@ class _Slot:
         if conf:
             self.conf_d = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
             self.conf_h = torch.empty((b, h, w), dtype=torch.uint8).pin_memory()
+        self.fused_h = None
+        if fused:                                          # the rendered volume: float32, its 16-bit form and the pixels rendered
+            self.fused_f = torch.empty((b, h, w, 1), dtype=torch.float32, device=dev)
+            self.fused_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
+            self.fused_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
+            self.hits_d = torch.empty(b, dtype=torch.int64, device=dev)
+            self.hits_h = torch.empty(b, dtype=torch.int64).pin_memory()
         self.event = torch.cuda.Event()
         self.pending = 0
 
@@ -352,12 +360,20 @@ class PredictionWriter:
     at the default 22).  Trajectories end, and their tables are cleared, exactly where the maps' do, under the same needs (world
     frame, host-side reset flags, one directory per trajectory).  With ``save_mesh`` alone the pose chain, the views check and
     the two mesh launches run; ``depth_cloud`` does not.  ``meshes``, ``mesh_vertices``, ``mesh_triangles``,
-    ``mesh_dropped_range``, ``mesh_dropped_full`` and ``mesh_quads_dropped`` sum over the meshes handed to the workers."""
+    ``mesh_dropped_range``, ``mesh_dropped_full`` and ``mesh_quads_dropped`` sum over the meshes handed to the workers.
+
+    ``save_fused=True`` (needs ``save_mesh``) also writes ``<name>_fused.png``: the mesh's volume, right after the frame went
+    into it, rendered into the frame's camera by ``network_ops.tsdf_raycast`` over [near, far] (``fused_window=W``: only W
+    truncation distances around the raw estimate) and encoded like the estimate (``fmt``); a pixel without a surface is what the
+    format makes of a non-finite estimate (0 in kitti16, 0x7C00 in midair16).  One more launch pair and one more 16-bit image
+    across PCIe per submit.  Under ``cloud_views`` the volume holds the filtered estimates, so the rendered map fills pixels the
+    filter dropped wherever earlier frames put a surface.  ``fused_pixels`` / ``fused_cap`` sum the pixels rendered and the
+    pixels there are, over the frames the workers have finished."""
 
     def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
                  encode=True, cloud=False, cloud_step=2, cloud_frame="world", cloud_views=0, cloud_min_views=None,
                  cloud_tol=(1.0, 0.01), save_conf=False, save_map=None, map_min_frames=2, map_slots_log2=21, save_mesh=None,
-                 mesh_trunc=4, mesh_min_frames=2, mesh_slots_log2=22):
+                 mesh_trunc=4, mesh_min_frames=2, mesh_slots_log2=22, save_fused=False, fused_window=None):
         if fmt not in FORMATS:
             raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
         panels = tuple(panels)
@@ -379,6 +395,12 @@ class PredictionWriter:
             "save_mesh", save_mesh, cloud_frame, "a mesh fuses the frames of a trajectory in one frame",
             (("mesh_trunc", mesh_trunc, 4, *nops.TSDF_TRUNC), ("mesh_min_frames", mesh_min_frames, 2, 1, None),
              ("mesh_slots_log2", mesh_slots_log2, 22, 6, 26)))
+        if save_fused and save_mesh is None:
+            raise ValueError("save_fused needs save_mesh: it renders the mesh's volume")
+        if fused_window is not None and (not save_fused or int(fused_window) < 1):
+            raise ValueError(f"fused_window needs save_fused and a width >= 1 truncation distances, got {fused_window}")
+        self.save_fused, self.fused_window = bool(save_fused), None if fused_window is None else int(fused_window)
+        self.fused_pixels = self.fused_cap = 0             # pixels rendered / pixels there are, finished frames
         if cloud_views and not (cloud or save_map is not None or save_mesh is not None):
             raise ValueError("cloud_views needs cloud=True: the check runs on the clouds' pose chain (save_map or save_mesh "
                              "run on it as well)")
@@ -445,7 +467,8 @@ class PredictionWriter:
         b, h, w = est.shape[:3]
         self._geometry = (b, h, w)
         cap = nops.cloud_capacity(h, w, self.cloud_step) if self._vertices3d else 0
-        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf, self.cloud, self._geometry3d)
+        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf, self.cloud, self._geometry3d,
+                             self.save_fused)
                        for _ in range(self.n_slots)]
         for product in self._products[::-1]:
             product.state = product.new_state(b, est.device)
@@ -537,6 +560,7 @@ class PredictionWriter:
                         self._finish(product, int(s))
                     product.clear(product.state, mask)
         nops.pose_accumulate(rot, trans, self._pose, reset=mask, force_all=first)
+        raw = est
         if self.cloud_views:                               # the clouds see the filtered copy; PNG and panels the estimate
             b, h, w = est.shape[:3]
             if self._views is None:
@@ -554,6 +578,15 @@ class PredictionWriter:
             nops.tsdf_integrate(est, rgb, camera["f"], camera["c"], self._pose, self.save_mesh, self.mesh_trunc,
                                 self._mesh.state, near=self.near, far=self.far)
             self._mesh.dirs = dirs
+        if self.save_fused:                                # the volume as it is now, seen from this frame
+            slot.hits_d.zero_()
+            nops.tsdf_raycast(self._mesh.state, camera["f"], camera["c"], self._pose, est.shape[1], est.shape[2], self.save_mesh,
+                              self.mesh_trunc, self.mesh_min_frames, near=self.near, far=self.far,
+                              guide=raw if self.fused_window else None, window=self.fused_window, out=slot.fused_f,
+                              hits=slot.hits_d)
+            nops.depth_export(slot.fused_f, self.fmt, depth16=slot.fused_d)
+            slot.fused_h.copy_(slot.fused_d, non_blocking=True)
+            slot.hits_h.copy_(slot.hits_d, non_blocking=True)
         if not self._vertices3d:
             return
         nops.depth_cloud(est, rgb, camera["f"], camera["c"], step=self.cloud_step, near=self.near, far=self.far,
@@ -601,6 +634,8 @@ class PredictionWriter:
                 jobs.append((name + "_cloud.ply", None, s))
             if self.save_conf:
                 jobs.append((name + "_conf.png", slot.conf_h, s))
+            if self.save_fused:
+                jobs.append((name + "_fused.png", slot.fused_h, s))
         slot.pending = len(jobs)
         self.frames += len(names)
         for job in jobs:
@@ -614,6 +649,10 @@ class PredictionWriter:
                 with self._lock:
                     self.cloud_kept += int(slot.counts_h[s])
                     self.cloud_cap += slot.cloud_h.shape[1]
+            if host is not None and host is slot.fused_h:  # counts the host already has: the share rendered
+                with self._lock:
+                    self.fused_pixels += int(slot.hits_h[s])
+                    self.fused_cap += host.shape[1] * host.shape[2]
             if self.encode:
                 path = os.path.join(self.out_dir, rel_path)
                 os.makedirs(os.path.dirname(path), exist_ok=True)

@@ -536,7 +536,11 @@ def eval_streams(args, model, dev):
     files without a depth column) they are skipped.  ``--refine_pose`` puts ``pose_refine.PoseRefiner`` in front of every step
     (eager launches, also before a graph replay, which copies the frame's motion into its static inputs): the network and the
     scorer get the refined motion, its rows go to an [n_steps,B,8] log and, after the last step, to
-    ``pose-refine-frames-<dataset>.txt``.  Returns (whether the seven were computed, the six consistency means or None)."""
+    ``pose-refine-frames-<dataset>.txt``.  ``--fused VOXEL`` puts ``fusion.FusedDepth`` behind every step (eager launches on the
+    frame the network saw): the fused depth is scored by a second per-sample metric launch into an [n_steps,B,7] log of its own,
+    the pixels rendered go to an [n_steps,B] log, and after the last step ``perfs-fused-<dataset>.txt`` and
+    ``fused-frames-<dataset>.txt`` are written; ``perfs-<dataset>.txt`` is what it is without the flag.
+    Returns (whether the seven were computed, the six consistency means or None)."""
     from . import network_ops as nops
     from . import stream_eval as SE
     has_gt = records_have_depth(args) if args.consistency else True    # without --consistency the loader refuses or the step fails
@@ -557,6 +561,14 @@ def eval_streams(args, model, dev):
         from . import pose_refine as PR
         refiner = PR.from_args(args, copy_estimate=args.graph)
         p_rows = torch.empty((n_steps, B, len(PR.COLUMNS)), dtype=torch.float32, device=dev)
+    fuser = None
+    if getattr(args, "fused", None) is not None:                   # four launches and a second metric pair behind every step
+        from . import fusion as FU
+        fuser = FU.from_args(args)
+        rows_f = torch.empty((n_steps, B, 7), dtype=torch.float32, device=dev)
+        counted_f = torch.empty((n_steps, B), dtype=torch.uint8, device=dev)
+        hits = torch.zeros((n_steps, B), dtype=torch.int64, device=dev)           # the launches add: zeroed once, here
+        fused = None
     active = (sched.cells[..., 0] >= 0).sum(axis=1)                # the schedule's, known on the host without a device read
     runner, t0 = None, None
     for step, batch in enumerate(ds):
@@ -580,8 +592,17 @@ def eval_streams(args, model, dev):
                                           counted=counted[step])
         if scorer is not None:
             scorer.step(frame, est, batch["reset"], batch["active"], c_rows[step], c_counted[step])
+        if fuser is not None:                                      # the motion is the refined one under --refine_pose
+            if fused is None:
+                fused = torch.empty_like(est)
+            fuser.step(est, frame["RGB_im"], frame["rot"], frame["trans"], frame["camera"], batch["reset"], out=fused,
+                       hits=hits[step])
+            nops.depth_metrics_per_sample(batch["depth"], fused, batch["new_traj"], batch["active"], 80., rows=rows_f[step],
+                                          counted=counted_f[step])
     if has_gt:
         rows_h, counted_h = rows.cpu().numpy(), counted.cpu().numpy()
+    if fuser is not None:
+        rows_f_h, hits_h, volumes = rows_f.cpu().numpy(), hits.cpu().numpy(), fuser.stats()
     if scorer is not None:
         c_rows_h, c_counted_h = c_rows.cpu().numpy(), c_counted.cpu().numpy()
     if refiner is not None:
@@ -590,7 +611,8 @@ def eval_streams(args, model, dev):
         dt = time.perf_counter() - t0
         n = int(active[1:].sum())
         print(f"eval_streams {B} slots ({args.eval_streams_policy}, {'graph' if args.graph else 'eager'}"
-              f"{', consistency' if scorer is not None else ''}{', refine_pose' if refiner is not None else ''}): {n / dt:.1f} "
+              f"{', consistency' if scorer is not None else ''}{', refine_pose' if refiner is not None else ''}"
+              f"{', fused' if fuser is not None else ''}): {n / dt:.1f} "
               f"sample-frames/s over {n} active sample-frames of {n_steps - 1} steps (the first step excluded)")
     if has_gt:
         total, count = SE.fold(rows_h, counted_h, sched.cells)
@@ -613,6 +635,21 @@ def eval_streams(args, model, dev):
         PR.write_frames(PR.frames_path(args.ckpt_dir, args.dataset), frames)
         applied = sum(1 for _, _, row in frames if row[6] != 0)
         print(f"wrote {PR.frames_path(args.ckpt_dir, args.dataset)} ({applied} of {len(frames)} frames refined)")
+    if fuser is not None:
+        total_f, count_f = SE.fold(rows_f_h, counted_h, sched.cells)
+        means_f = SE.fold_result(total_f, count_f)
+        h, w = fused.shape[1:3]
+        frames = SE.fold_fused(rows_h, rows_f_h, hits_h, counted_h, sched.cells, h * w)
+        os.makedirs(args.ckpt_dir, exist_ok=True)
+        FU.write_perfs(FU.perfs_path(args.ckpt_dir, args.dataset), means_f)
+        FU.write_frames(FU.frames_path(args.ckpt_dir, args.dataset), frames)
+        dropped = sum(v["dropped_full"] for v in volumes)
+        cover = float(np.mean([row[0] for _, _, row in frames])) if frames else 0.0
+        print(f"fused depth at {fuser.voxel:g} m (K {fuser.trunc}, min_frames {fuser.min_frames}, "
+              f"{'whole range' if fuser.window is None else 'window %d' % fuser.window}): mean coverage {cover:.4f} over "
+              f"{len(frames)} counted frames, AbsRel raw {SE.fold_result(total, count)[0]:.6f} fused {means_f[0]:.6f}, "
+              f"{dropped} samples dropped by full tables" + (" (raise --fused_slots_log2)" if dropped else ""))
+        print(f"wrote {FU.perfs_path(args.ckpt_dir, args.dataset)} and {FU.frames_path(args.ckpt_dir, args.dataset)}")
     return has_gt, means
 
 
@@ -682,7 +719,9 @@ def predict(args, model, batches, rank, dev):
                                   cloud_min_views=args.cloud_min_views, cloud_tol=args.cloud_tol, save_conf=args.save_conf,
                                   save_map=args.save_map, map_min_frames=args.map_min_frames,
                                   map_slots_log2=args.map_slots_log2, save_mesh=args.save_mesh, mesh_trunc=args.mesh_trunc,
-                                  mesh_min_frames=args.mesh_min_frames, mesh_slots_log2=args.mesh_slots_log2)
+                                  mesh_min_frames=args.mesh_min_frames, mesh_slots_log2=args.mesh_slots_log2,
+                                  save_fused=getattr(args, "save_fused", False),
+                                  fused_window=getattr(args, "fused_window", None))
         want_gt = any(p in ("gt", "err") for p in writer.panels)
     preds = []
     for data in batches:
@@ -738,6 +777,8 @@ def predict(args, model, batches, rank, dev):
                  f"{writer.mesh_triangles} triangles, {writer.mesh_dropped_range} samples dropped out of range, "
                  f"{writer.mesh_dropped_full} dropped by full tables"
                  + (" (raise --mesh_slots_log2)" if writer.mesh_dropped_full else "") if writer.save_mesh is not None else "")
+              + (f", fused depth rendered on {100.0 * writer.fused_pixels / max(writer.fused_cap, 1):.1f} % of the pixels"
+                 if writer.save_fused else "")
               + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
 
 

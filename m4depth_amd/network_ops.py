@@ -868,6 +868,60 @@ def tsdf_integrate(depth, rgb, cam_f, cam_c, pose, voxel, trunc, state, near=1.0
     return state
 
 
+def tsdf_raycast(state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near=1.0, far=80.0, guide=None, window=None,
+                 fill=None, out=None, hits=None):
+    """The TSDF volumes rendered into the cameras ``pose`` (m4d_tsdf_raycast): returns depth [b,h,w,1] float32, the z-depth of
+    the first front-face zero crossing of the field along every pixel's ray over [near, far], marched coarse to fine in half
+    voxels.  ``state`` as ``tsdf_integrate`` left it (only read); ``cam_f`` / ``cam_c`` [b,2]; ``pose`` [b,7] float64; ``voxel``,
+    ``trunc`` the volume's; a voxel counts once ``min_frames`` frames updated it.  ``guide`` [b,h,w,1] with ``window`` (>= 1; both
+    or neither): a pixel with a finite guide depth in [near, far] marches only ``window`` truncation distances around it.
+    ``fill`` [b,h,w,1]: what a pixel without a surface gets (None: NaN).  ``guide``, ``fill`` and ``out`` are float32 device
+    tensors with dense images at a batch stride; ``out`` (the destination, the caller's) may be ``fill`` itself.  ``hits``: int64
+    [b] the launch adds every sample's rendered pixels to (the caller zeroes it; a row of a log is fine).  One launch, nothing
+    synchronises."""
+    b, slots_log2 = _tsdf_check(state, voxel)
+    trunc, min_frames, h, w = int(trunc), int(min_frames), int(h), int(w)
+    if not TSDF_TRUNC[0] <= trunc <= TSDF_TRUNC[1]:
+        raise ValueError(f"trunc must be in {TSDF_TRUNC[0]}..{TSDF_TRUNC[1]} voxels, got {trunc}")
+    if min_frames < 1:
+        raise ValueError(f"min_frames must be >= 1, got {min_frames}")
+    if h < 1 or w < 1 or h * w > 1 << 24:
+        raise ValueError(f"need h, w >= 1 and h*w <= 2^24, got {h}x{w}")
+    near, far = float(near), float(far)
+    if not (far > near and near > 0):
+        raise ValueError(f"need 0 < near < far, got {near}, {far}")
+    f32 = lambda v: ctypes.c_float(v).value                    # noqa: E731  (the library's float arguments)
+    if (f32(far) - f32(near)) / (f32(voxel) * 0.5) > 1 << 20:
+        raise ValueError(f"[{near}, {far}] holds more than 2^20 half voxels of {voxel}: the march's bound")
+    if (guide is None) != (window is None):
+        raise ValueError("guide and window come together or not at all")
+    if window is not None and int(window) < 1:
+        raise ValueError(f"window must be >= 1 truncation distances, got {window}")
+    _check_camera(cam_f, cam_c, b)
+    _check_pose7(pose, b)
+    if hits is not None and (not isinstance(hits, torch.Tensor) or tuple(hits.shape) != (b,)):
+        raise ValueError(f"hits: expected an int64 [{b}] device tensor")
+    if out is None:
+        out = torch.empty((b, h, w, 1), dtype=torch.float32, device=state["words"].device)
+    strides = {}
+    for name, t in (("guide", guide), ("fill", fill), ("out", out)):
+        if t is None:
+            strides[name] = 0
+            continue
+        strides[name] = _batch_stride(t, name)
+        if tuple(t.shape) != (b, h, w, 1):
+            raise ValueError(f"{name}: expected [{b},{h},{w},1], got {tuple(t.shape)}")
+    if fill is not None and fill.data_ptr() == out.data_ptr() and strides["fill"] != strides["out"]:
+        raise ValueError("out may be fill itself only at the same batch stride")
+    ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())          # noqa: E731  (views: checked above)
+    check(lib.m4d_tsdf_raycast(dptr(state["words"], "state", torch.int64), b, slots_log2, dptr(as_f32(cam_f, "cam_f"), "cam_f"),
+                               dptr(as_f32(cam_c, "cam_c"), "cam_c"), dptr(pose, "pose", torch.float64), h, w, near, far,
+                               float(voxel), trunc, min_frames, ptr(guide), strides["guide"], 0 if window is None else int(window),
+                               ptr(fill), strides["fill"], ptr(out), strides["out"], dptr(hits, "hits", torch.int64),
+                               stream_ptr()), "m4d_tsdf_raycast")
+    return out
+
+
 def tsdf_extract_raw(state, s, min_frames, voxel, vertex_cap, quad_cap, out=None):
     """The two extraction launches of sample ``s``: (keys [vertex_cap] int64, vertices [vertex_cap,16] uint8, quads [quad_cap,5]
     int64, counts [2] int64 = records found by each launch -- beyond a capacity they are counted, not written), in the order

@@ -133,6 +133,26 @@ def build_parser():
     p.add_argument("--mesh_slots_log2", type=int, default=argparse.SUPPRESS, metavar="L",
                    help="--save_mesh: 2^L hash-table slots per sample, 16..26 (default 22: 134 MB per sample; a volume stops "
                         "taking new voxels at 3/4 of them, and the closing line of the run counts what was dropped)")
+    # like the mesh's: absent from the namespace until given
+    p.add_argument("--fused", type=float, default=argparse.SUPPRESS, metavar="VOXEL",
+                   help="--eval_streams: also score the FUSED depth of every frame -- the estimates of the trajectory so far fused "
+                        "on the GPU into a truncated signed distance field on a hashed grid of VOXEL metres (as --save_mesh does) "
+                        "and rendered back into the frame by ray marching over 1..80 m; where the volume has no surface the raw "
+                        "estimate stays.  Writes perfs-fused-<dataset>.txt (the seven metrics of the fused depth, next to the "
+                        "unchanged perfs-<dataset>.txt) and fused-frames-<dataset>.txt.  Needs ground truth")
+    p.add_argument("--fused_trunc", type=int, default=argparse.SUPPRESS, metavar="K",
+                   help="--fused: the truncation distance in voxels, 2..8 (default 4)")
+    p.add_argument("--fused_min_frames", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="--fused: a voxel is rendered only if at least N frames updated it (default 2)")
+    p.add_argument("--fused_slots_log2", type=int, default=argparse.SUPPRESS, metavar="L",
+                   help="--fused: 2^L hash-table slots per sample, 16..26 (default 22: 134 MB per sample; the closing line counts "
+                        "what a full table dropped)")
+    p.add_argument("--fused_window", type=int, default=argparse.SUPPRESS, metavar="W",
+                   help="--fused / --save_fused: march only W >= 1 truncation distances around the raw estimate of each pixel "
+                        "instead of the whole range (several times fewer probes; a surface further from the estimate is missed)")
+    p.add_argument("--save_fused", action="store_true", default=argparse.SUPPRESS,
+                   help="--save_mesh: also write <frame>_fused.png, the mesh's volume rendered into the frame (--save_format; "
+                        "a pixel without a surface is written as a non-finite estimate is: 0 in kitti16, 0x7C00 in midair16)")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--loss", default="supervised", choices=["supervised", "photometric"],
                    help="train: supervised = the reference's log-depth L1 against ground truth; photometric = the reprojection "
@@ -431,6 +451,43 @@ def check_refine_args(parser, args):
             parser.error("--refine_pose_strides: --height and --width must be multiples of the largest stride, at least 3 of them")
 
 
+# --fused VOXEL renders the volume --save_mesh builds: its companions are the mesh's, under its own prefix, so that the defaults
+# and bounds of the two cannot drift; --fused_window (no default: absent = the whole range) also serves --save_fused
+_MESH_COMPANIONS = dict((p[0], p[1]) for p in _TRAJECTORY_PRODUCTS)["save_mesh"]
+_FUSED_COMPANIONS = tuple(("fused_" + name[len("mesh_"):], default, lo, hi) for name, default, lo, hi in _MESH_COMPANIONS)
+
+
+def check_fused_args(parser, args):
+    """Refusals of ``--fused`` / ``--save_fused`` and their options (absent from the namespace until given); fills in the defaults.
+    Runs after ``check_save_args``."""
+    for f in ("fused", "fused_window") + tuple(c[0] for c in _FUSED_COMPANIONS):
+        setattr(args, f, getattr(args, f, None))
+    args.save_fused = bool(getattr(args, "save_fused", False))
+    given = [c[0] for c in _FUSED_COMPANIONS if getattr(args, c[0]) is not None]
+    if given and args.fused is None:
+        parser.error("--%s needs --fused" % given[0])
+    if args.fused_window is not None and args.fused is None and not args.save_fused:
+        parser.error("--fused_window needs --fused or --save_fused")
+    if args.fused_window is not None and args.fused_window < 1:
+        parser.error("--fused_window must be >= 1")
+    if args.save_fused and args.save_mesh is None:
+        parser.error("--save_fused needs --save_mesh: it renders the mesh's volume")
+    if args.fused is None:
+        return
+    if not (args.eval_streams and args.mode == "eval"):
+        parser.error("--fused needs --eval_streams B (with or without --graph) in --mode=eval: it fuses whole trajectories, frame "
+                     "by frame")
+    if not (0 < args.fused < float("inf")):
+        parser.error("--fused VOXEL needs a finite edge length > 0")
+    for f, default, lo, hi in _FUSED_COMPANIONS:
+        v = getattr(args, f)
+        if v is not None and (v < lo or (hi is not None and v > hi)):
+            parser.error("--%s must be %s" % (f, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi)))
+        setattr(args, f, default if v is None else v)
+    if args.consistency and args.records_path is not None and not records_have_depth(args):
+        parser.error("--fused scores against ground truth: the records of --records_path name no ground-truth map")
+
+
 def check_args(parser, args, world=None):
     """Every refusal of ``m4depth_amd.main``, in the order they win."""
     check_stream_args(parser, args)
@@ -439,3 +496,4 @@ def check_args(parser, args, world=None):
     check_train_args(parser, args, world)
     check_recording_args(parser, args)
     check_save_args(parser, args)
+    check_fused_args(parser, args)

@@ -138,6 +138,30 @@ def fold_consistency(rows, counted, cells, traj_order=None):
     return total, count, frames
 
 
+def fold_fused(rows, rows_f, hits, counted, cells, pixels, traj_order=None):
+    """The per-frame rows of ``main.py --fused`` from the raw and the fused 7-column logs (``rows``, ``rows_f`` [n_steps,B,7]) and
+    the [n_steps,B] log of rendered pixels, in the same sequential walk (trajectory in ``traj_order``, default ascending = csv
+    order; frame in order): the counted (trajectory, frame, float32 [coverage = hits / pixels, AbsRel raw, AbsRel fused])
+    triples -- the frames the seven metrics count."""
+    rows, rows_f = np.asarray(rows, np.float32), np.asarray(rows_f, np.float32)
+    hits, counted, cells = np.asarray(hits), np.asarray(counted), np.asarray(cells)
+    if rows.shape != rows_f.shape or rows.shape[:2] != cells.shape[:2] or rows.shape[2:] != (7,) \
+            or counted.shape != cells.shape[:2] or hits.shape != cells.shape[:2]:
+        raise ValueError(f"fold: rows {rows.shape} / {rows_f.shape}, hits {hits.shape}, counted {counted.shape} and cells "
+                         f"{cells.shape} disagree")
+    st, sl = np.nonzero(cells[..., 0] >= 0)
+    tr, fr = cells[st, sl, 0], cells[st, sl, 1]
+    if traj_order is None:
+        rank = tr
+    else:
+        pos = {int(t): i for i, t in enumerate(traj_order)}
+        rank = np.array([pos[int(t)] for t in tr], np.int64)
+    walk = np.lexsort((fr, rank))                    # trajectory, then frame
+    return [(int(tr[k]), int(fr[k]), np.array([np.float32(hits[st[k], sl[k]]) / np.float32(pixels), rows[st[k], sl[k], 0],
+                                               rows_f[st[k], sl[k], 0]], np.float32))
+            for k in walk if counted[st[k], sl[k]]]
+
+
 def fold_pose_refine(rows, cells, traj_order=None):
     """The per-frame rows of ``pose_refine.PoseRefiner`` (``pose_refine.COLUMNS``) from its [n_steps,B,8] log, in the same
     sequential walk (trajectory in ``traj_order``, default ascending = csv order; frame in order): the (trajectory, frame, row)
