@@ -6,24 +6,10 @@ batch (``network_ops.depth_export``) writes the estimate in a dataset's own 16-b
 ``PredictionWriter`` moves them through a ring of pinned buffers, and host threads do the PNG compression: the predict loop
 never waits for the host unless every slot of the ring is in flight, and host memory is ``slots`` frames however long the run.
 
-With ``cloud=True`` the writer also keeps one camera-to-world pose per sample on the device (``network_ops.pose_accumulate``),
-turns every estimate into a dense list of coloured vertices (``network_ops.depth_cloud``) and writes it as a binary PLY file
-beside the PNGs; the host never redoes the camera model or the pose chain, and never reads a vertex count before the slot's
-event has passed.
-
-With ``cloud_views=K`` a cloud keeps only the pixels that up to K earlier frames of the sample's trajectory confirm
-(``network_ops.depth_views``: a forward-backward reprojection check against a ring of the last K estimates and poses on the
-device); the depth PNG and the panels keep showing the raw estimate.
-
-With ``save_map=VOXEL`` the vertices of every step are also merged, on the device, into one voxel map per sample
-(``network_ops.voxel_map_integrate``: a hash table of integer sums); when a sample's trajectory ends the map is extracted,
-written as ``map.ply`` into the trajectory's directory by a worker thread (``write_map_ply``) and the table cleared.
-
-With ``save_mesh=VOXEL`` the estimate of every step is also fused, on the device, into one truncated signed distance field per
-sample (``network_ops.tsdf_integrate``: a hashed voxel grid, two launches); when a sample's trajectory ends the surface is
-extracted by naive surface nets (``network_ops.tsdf_extract``), written as ``mesh.ply`` into the trajectory's directory by a
-worker thread (``write_mesh_ply``) and the volume cleared.  ``save_fused=True`` also renders that volume into every frame's
-camera (``network_ops.tsdf_raycast``, one launch) and writes the fused depth map as ``<frame>_fused.png``.
+The 3-D outputs -- a point cloud per frame, one voxel map and one TSDF mesh per trajectory, the mesh's volume rendered into every
+frame -- come from one ``fusion.TrajectoryChain``, which owns their device state and issues every launch on it; the writer
+copies what it made through the same ring and hands what a finished trajectory leaves to the same threads.  The host never
+redoes the camera model or the pose chain, and never reads a vertex count before the slot's event has passed.
 """
 from __future__ import annotations
 
@@ -36,6 +22,7 @@ import numpy as np
 import torch
 
 from . import network_ops as nops
+from .fusion import TrajectoryChain
 
 FORMATS = ("kitti16", "midair16")
 PANELS = ("rgb", "est", "gt", "err")
@@ -252,65 +239,38 @@ def read_conf_png(path, views):
 
 
 class _Slot:
-    def __init__(self, b, h, w, n_panels, dev, cloud_cap=0, conf=False, cloud_host=True, geometry=False, fused=False):
-        self.depth_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
-        self.depth_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
-        self.panels_d = self.panels_h = None
-        if n_panels:
-            self.panels_d = torch.empty((b, n_panels * h, w, 3), dtype=torch.uint8, device=dev)
-            self.panels_h = torch.empty((b, n_panels * h, w, 3), dtype=torch.uint8).pin_memory()
-        self.cloud_d = None
-        if cloud_cap:
-            self.cloud_d = torch.empty((b, cloud_cap, 16), dtype=torch.uint8, device=dev)
+    """What one submit of ``writer`` copies to the host: the device buffers its launches fill and their pinned twins."""
+
+    def __init__(self, writer, b, h, w, dev):
+        def pair(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=dev), torch.empty(shape, dtype=dtype).pin_memory()
+
+        self.depth_d, self.depth_h = pair((b, h, w), torch.int16)
+        self.panels_d = self.panels_h = self.cloud_d = self.conf_d = self.conf_h = self.fused_h = None
+        if writer.panels:
+            self.panels_d, self.panels_h = pair((b, len(writer.panels) * h, w, 3), torch.uint8)
+        if writer.cloud:
+            self.cloud_d, self.cloud_h = pair((b, nops.cloud_capacity(h, w, writer.cloud_step), 16), torch.uint8)
+            self.counts_d, self.counts_h = pair(b, torch.int32)
+            self.pose_h = torch.empty((b, 7), dtype=torch.float64).pin_memory()
+        elif writer.save_map is not None:                  # a writer of maps alone keeps the vertices on the device
+            self.cloud_d = torch.empty((b, nops.cloud_capacity(h, w, writer.cloud_step), 16), dtype=torch.uint8, device=dev)
             self.counts_d = torch.empty(b, dtype=torch.int32, device=dev)
-            if cloud_host:                                 # a writer of maps alone keeps the vertices on the device
-                self.cloud_h = torch.empty((b, cloud_cap, 16), dtype=torch.uint8).pin_memory()
-                self.counts_h = torch.empty(b, dtype=torch.int32).pin_memory()
-                self.pose_h = torch.empty((b, 7), dtype=torch.float64).pin_memory()
-        if cloud_cap or geometry:                          # (a writer of meshes alone has no vertex buffer)
-            self.reset_d = torch.empty(b, dtype=torch.uint8, device=dev)
-            self.reset_h = torch.empty(b, dtype=torch.uint8).pin_memory()
-        self.conf_d = self.conf_h = None
-        if conf:
-            self.conf_d = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
-            self.conf_h = torch.empty((b, h, w), dtype=torch.uint8).pin_memory()
-        self.fused_h = None
-        if fused:                                          # the rendered volume: float32, its 16-bit form and the pixels rendered
+        if writer.needs_geometry:
+            self.reset_d, self.reset_h = pair(b, torch.uint8)
+        if writer.save_conf:
+            self.conf_d, self.conf_h = pair((b, h, w), torch.uint8)
+        if writer.save_fused:                              # the rendered volume: float32, its 16-bit form and the pixels rendered
             self.fused_f = torch.empty((b, h, w, 1), dtype=torch.float32, device=dev)
-            self.fused_d = torch.empty((b, h, w), dtype=torch.int16, device=dev)
-            self.fused_h = torch.empty((b, h, w), dtype=torch.int16).pin_memory()
-            self.hits_d = torch.empty(b, dtype=torch.int64, device=dev)
-            self.hits_h = torch.empty(b, dtype=torch.int64).pin_memory()
+            self.fused_d, self.fused_h = pair((b, h, w), torch.int16)
+            self.hits_d, self.hits_h = pair(b, torch.int64)
         self.event = torch.cuda.Event()
         self.pending = 0
 
 
-class _TrajectoryProduct:
-    """One per-trajectory product of the writer (the voxel map, the TSDF mesh): its device state, the directory of every
-    sample's open trajectory, and the callables that are all the two differ in -- ``new_state(b, device)``;
-    ``extract(state, s)`` -> (device arrays, stats, {counter of the writer: what this trajectory adds}); ``clear(state, mask)``;
-    ``write(path, *host arrays, stats)``."""
-
-    def __init__(self, file_name, new_state, extract, clear, write):
-        self.file_name, self.new_state, self.extract, self.clear, self.write = file_name, new_state, extract, clear, write
-        self.state = None                                  # allocated with the slots
-        self.dirs = None                                   # set by the first step that went into the state
-
-
-def _trajectory_options(flag, voxel, cloud_frame, reason, ints):
-    """The option group of a trajectory product: ``voxel`` (None: off) as a float32 length and its companions ``ints`` = (name,
-    value, default, lowest, highest or None) as integers (None: the default); the companions are checked only with the flag."""
-    voxel = None if voxel is None else float(np.float32(voxel))
-    ints = [(name, default if v is None else v, lo, hi) for name, v, default, lo, hi in ints]
-    if voxel is not None:
-        if not (0 < voxel < float("inf")):
-            raise ValueError(f"{flag}: the voxel edge must be a finite length > 0, got {voxel}")
-        if cloud_frame != "world":
-            raise ValueError(f"{flag} needs cloud_frame='world': {reason}")
-        if any(int(v) < lo or (hi is not None and int(v) > hi) for _, v, lo, hi in ints):
-            need = [f"{name} >= {lo}" if hi is None else f"{name} in {lo}..{hi}" for name, _, lo, hi in ints]
-            raise ValueError(f"need {', '.join(need[:-1])} and {need[-1]}, got {', '.join(str(v) for _, v, _, _ in ints)}")
-    return (voxel, *(int(v) for _, v, _, _ in ints))
+# what the chain's options are called here, for its ValueError texts
+_CHAIN_NAMES = {"views": "cloud_views", "min_views": "cloud_min_views", "tol": "cloud_tol", "map_voxel": "save_map", "voxel": "save_mesh",
+                "trunc": "mesh_trunc", "min_frames": "mesh_min_frames", "slots_log2": "mesh_slots_log2", "window": "fused_window"}
 
 
 class PredictionWriter:
@@ -322,58 +282,30 @@ class PredictionWriter:
     ``encode=False`` does everything but the file encoding (for measuring the loop without the PNG encoder).  All submits
     must come from one stream and have one geometry.
 
-    ``cloud=True`` also writes ``<name>_cloud.ply``: every ``cloud_step``-th pixel of every ``cloud_step``-th row whose
-    estimate is finite and within [near, far], as float x, y, z + uchar red, green, blue, alpha, in the frame of the
-    trajectory's first camera (``cloud_frame="world"``) or of the frame's own camera (``"camera"``); the frame's
-    camera-to-world pose is in the header either way (``read_cloud_ply``).  Each slot then also owns a [b,cap,16] byte vertex
-    buffer with its pinned twin, the counts and a pinned copy of the poses; the whole ``cap`` region crosses PCIe every step
-    (the count is only known on the device), the worker writes the first ``counts[s]`` vertices.
+    Everything else comes from ``chain``, a ``fusion.TrajectoryChain`` over [near, far] whose docstring has the options
+    (``cloud_views`` / ``cloud_min_views`` / ``cloud_tol``: its views check; ``save_mesh`` / ``mesh_*`` / ``fused_window``: its
+    volume; ``save_map`` / ``map_*``: its map); ``submit`` then needs the frame's motion (``needs_geometry``).  PNG and panels
+    show the raw estimate; clouds, maps and meshes see the filtered one where the views check is on.
 
-    ``cloud_views=K`` (1..8; needs ``cloud``) filters the clouds: a pixel gives a vertex only if at least ``cloud_min_views``
-    (default min(2, K)) of the up to K earlier frames of its trajectory confirm it within ``cloud_tol`` = (pixels, relative
-    depth) -- ``network_ops.depth_views``, one more launch per submit, at full resolution whatever ``cloud_step`` is.  The
-    writer then owns the ring of the last K + 1 estimates and poses, (K+1) b h w floats.  The rule is strict: the first
-    ``cloud_min_views`` frames of every trajectory give clouds without vertices.  ``save_conf=True`` also writes
-    ``<name>_conf.png``: 8-bit grey, ``confirming views * 255 // K`` (``read_conf_png``).  ``cloud_kept`` / ``cloud_cap`` sum the
-    vertices written and the vertices a cloud could hold at most, over the frames the workers have finished.
+    ``cloud=True``: ``<name>_cloud.ply`` (``read_cloud_ply``), every ``cloud_step``-th pixel of every ``cloud_step``-th row in the
+    frame of the trajectory's first camera (``cloud_frame="world"``) or of the frame's own (``"camera"``).  A cloud's whole
+    capacity crosses PCIe every step (the count is only known on the device); the worker writes the first ``counts[s]``
+    vertices.  ``save_conf=True`` (needs ``cloud_views=K``): ``<name>_conf.png``, 8-bit grey, ``confirming views * 255 // K``.
+    ``save_fused=True`` (needs ``save_mesh``): ``<name>_fused.png``, the volume right after the frame went in, rendered into the
+    frame's camera and encoded like the estimate.  ``cloud_kept`` / ``cloud_cap`` and ``fused_pixels`` / ``fused_cap``: vertices
+    written / a cloud's capacity and pixels rendered / pixels there are, over the frames the workers have finished.
 
-    ``save_map=VOXEL`` (metres; with or without ``cloud``) also writes ``<directory of the trajectory's frames>/map.ply``: the
-    vertices of the trajectory's clouds merged into one vertex per occupied voxel (include/m4depth_hip.h, ``write_map_ply``).
-    After ``depth_cloud`` of every submit ``network_ops.voxel_map_integrate`` adds the step's compacted vertices -- made with
-    ``cloud_step``, [near, far] and the ``cloud_views`` filter, as they lie in the slot's device buffer -- to the sample's hash
-    table of 2^``map_slots_log2`` slots (168 MB per sample at the default 21), stamped with the writer's step counter.  A
-    sample whose host-side ``reset`` flag is set has its map extracted (voxels at least ``map_min_frames`` frames saw), handed
-    to a worker thread and cleared before the new frame goes in, and ``close()`` does that for every open trajectory: the loop
-    waits for the device once per finished trajectory, never per frame.  The map needs the world frame, host-side reset flags
-    (a device mask raises ValueError) and names with one directory per trajectory (``FrameNamer``'s).  Without ``cloud`` the
-    cloud launches still run, their buffers stay on the device and no ``_cloud.ply`` is written.  ``maps``, ``map_voxels``,
-    ``map_dropped_range`` and ``map_dropped_full`` sum over the maps handed to the workers: a ``map_dropped_full`` > 0 says
-    that ``map_slots_log2`` is too small for the scene.
-
-    ``save_mesh=VOXEL`` (metres; independent of ``cloud`` and ``save_map``) also writes ``<directory of the trajectory's
-    frames>/mesh.ply``: the trajectory's estimates fused into a truncated signed distance field on a hashed voxel grid and
-    extracted as a triangle mesh by naive surface nets (include/m4depth_hip.h, ``write_mesh_ply``).  Every submit runs
-    ``network_ops.tsdf_integrate`` -- two launches -- on what the clouds see: the ``cloud_views``-filtered copy of the estimate
-    when that option is on, limited to [near, far], at EVERY pixel (``cloud_step`` does not apply: a stride wider than a voxel
-    would leave holes).  ``mesh_trunc`` is the truncation distance in voxels (2..8), a voxel takes part in the extraction only if
-    at least ``mesh_min_frames`` frames updated it, and each sample owns a table of 2^``mesh_slots_log2`` slots of 32 bytes (134 MB
-    at the default 22).  Trajectories end, and their tables are cleared, exactly where the maps' do, under the same needs (world
-    frame, host-side reset flags, one directory per trajectory).  With ``save_mesh`` alone the pose chain, the views check and
-    the two mesh launches run; ``depth_cloud`` does not.  ``meshes``, ``mesh_vertices``, ``mesh_triangles``,
-    ``mesh_dropped_range``, ``mesh_dropped_full`` and ``mesh_quads_dropped`` sum over the meshes handed to the workers.
-
-    ``save_fused=True`` (needs ``save_mesh``) also writes ``<name>_fused.png``: the mesh's volume, right after the frame went
-    into it, rendered into the frame's camera by ``network_ops.tsdf_raycast`` over [near, far] (``fused_window=W``: only W
-    truncation distances around the raw estimate) and encoded like the estimate (``fmt``); a pixel without a surface is what the
-    format makes of a non-finite estimate (0 in kitti16, 0x7C00 in midair16).  One more launch pair and one more 16-bit image
-    across PCIe per submit.  Under ``cloud_views`` the volume holds the filtered estimates, so the rendered map fills pixels the
-    filter dropped wherever earlier frames put a surface.  ``fused_pixels`` / ``fused_cap`` sum the pixels rendered and the
-    pixels there are, over the frames the workers have finished."""
+    ``save_map=VOXEL`` / ``save_mesh=VOXEL``: ``map.ply`` / ``mesh.ply`` in the directory of a trajectory's frames, from the step's
+    cloud vertices (kept on the device without ``cloud``) and from the estimate at EVERY pixel.  A sample whose host-side
+    ``reset`` flag is set has them extracted, handed to a worker thread and cleared before the new frame goes in; ``close()``
+    does that for every open trajectory: the loop waits for the device once per finished trajectory, never per frame.  Both
+    need the world frame, host-side reset flags and names with one directory per trajectory (``FrameNamer``'s).  ``maps`` /
+    ``map_*`` and ``meshes`` / ``mesh_*`` sum over what went to the workers: a ``*_dropped_full`` > 0 asks for more slots."""
 
     def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
                  encode=True, cloud=False, cloud_step=2, cloud_frame="world", cloud_views=0, cloud_min_views=None,
-                 cloud_tol=(1.0, 0.01), save_conf=False, save_map=None, map_min_frames=2, map_slots_log2=21, save_mesh=None,
-                 mesh_trunc=4, mesh_min_frames=2, mesh_slots_log2=22, save_fused=False, fused_window=None):
+                 cloud_tol=(1.0, 0.01), save_conf=False, save_map=None, map_min_frames=None, map_slots_log2=None, save_mesh=None,
+                 mesh_trunc=None, mesh_min_frames=None, mesh_slots_log2=None, save_fused=False, fused_window=None):
         if fmt not in FORMATS:
             raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
         panels = tuple(panels)
@@ -385,58 +317,34 @@ class PredictionWriter:
             raise ValueError("slots and threads must be >= 1")
         if int(cloud_step) < 1 or cloud_frame not in CLOUD_FRAMES:
             raise ValueError(f"cloud_step must be >= 1 and cloud_frame one of {CLOUD_FRAMES}, got {cloud_step}, {cloud_frame!r}")
-        cloud_views = int(cloud_views)
-        if not 0 <= cloud_views <= nops.VIEWS_MAX:
-            raise ValueError(f"cloud_views must be 0 (off) or 1..{nops.VIEWS_MAX}, got {cloud_views}")
-        save_map, map_min_frames, map_slots_log2 = _trajectory_options(
-            "save_map", save_map, cloud_frame, "a map merges the frames of a trajectory in one frame",
-            (("map_min_frames", map_min_frames, 2, 1, None), ("map_slots_log2", map_slots_log2, 21, 6, 26)))
-        save_mesh, mesh_trunc, mesh_min_frames, mesh_slots_log2 = _trajectory_options(
-            "save_mesh", save_mesh, cloud_frame, "a mesh fuses the frames of a trajectory in one frame",
-            (("mesh_trunc", mesh_trunc, 4, *nops.TSDF_TRUNC), ("mesh_min_frames", mesh_min_frames, 2, 1, None),
-             ("mesh_slots_log2", mesh_slots_log2, 22, 6, 26)))
         if save_fused and save_mesh is None:
             raise ValueError("save_fused needs save_mesh: it renders the mesh's volume")
         if fused_window is not None and (not save_fused or int(fused_window) < 1):
             raise ValueError(f"fused_window needs save_fused and a width >= 1 truncation distances, got {fused_window}")
-        self.save_fused, self.fused_window = bool(save_fused), None if fused_window is None else int(fused_window)
-        self.fused_pixels = self.fused_cap = 0             # pixels rendered / pixels there are, finished frames
-        if cloud_views and not (cloud or save_map is not None or save_mesh is not None):
+        self.chain = chain = TrajectoryChain(
+            save_mesh, mesh_trunc, mesh_min_frames, mesh_slots_log2, near, far, window=fused_window, views=cloud_views,
+            min_views=cloud_min_views, tol=cloud_tol, map_voxel=save_map, map_min_frames=map_min_frames,
+            map_slots_log2=map_slots_log2, names=_CHAIN_NAMES)
+        for flag, voxel, verb in (("save_map", chain.map_voxel, "map merges"), ("save_mesh", chain.voxel, "mesh fuses")):
+            if voxel is not None and cloud_frame != "world":
+                raise ValueError(f"{flag} needs cloud_frame='world': a {verb} the frames of a trajectory in one frame")
+        if chain.views and not (cloud or chain.map_voxel is not None or chain.voxel is not None):
             raise ValueError("cloud_views needs cloud=True: the check runs on the clouds' pose chain (save_map or save_mesh "
                              "run on it as well)")
-        if save_conf and not cloud_views:
+        if save_conf and not chain.views:
             raise ValueError("save_conf needs cloud_views >= 1")
-        if cloud_min_views is not None and not cloud_views:
-            raise ValueError("cloud_min_views needs cloud_views >= 1")
-        cloud_min_views = min(2, cloud_views) if cloud_min_views is None else int(cloud_min_views)
-        if cloud_views and not 1 <= cloud_min_views <= cloud_views:
-            raise ValueError(f"cloud_min_views must be in 1..{cloud_views}, got {cloud_min_views}")
-        cloud_tol = tuple(float(v) for v in cloud_tol)
-        if len(cloud_tol) != 2 or not (cloud_tol[0] > 0 and cloud_tol[1] > 0):
-            raise ValueError(f"cloud_tol: expected (pixels > 0, relative depth > 0), got {cloud_tol}")
-        self.cloud, self.cloud_step, self.cloud_frame = bool(cloud), int(cloud_step), cloud_frame
-        self.cloud_views, self.cloud_min_views, self.cloud_tol, self.save_conf = cloud_views, cloud_min_views, cloud_tol, bool(save_conf)
-        self._views = None                                 # depth_views' ring and ages, next to the pose chain
-        self._views_n = self._views_depth = None           # [b,h,w] counts (without save_conf) and the filtered copy
-        self.cloud_kept = self.cloud_cap = 0               # vertices written / vertices the clouds could hold, finished frames
-        self._pose = None                                  # [b,7] float64 device state of the cloud: camera-to-world poses
-        self.save_map, self.map_min_frames, self.map_slots_log2 = save_map, map_min_frames, map_slots_log2
-        self.save_mesh, self.mesh_trunc = save_mesh, mesh_trunc
-        self.mesh_min_frames, self.mesh_slots_log2 = mesh_min_frames, mesh_slots_log2
-        self._vertices3d = self.cloud or save_map is not None      # the cloud launches run
-        self._geometry3d = self._vertices3d or save_mesh is not None   # the pose chain (and the views check) runs
-        self._map = self._mesh = None                      # the trajectory products that are on
-        if save_map is not None:
-            self._map = _TrajectoryProduct("map.ply", lambda b, dev: nops.voxel_map_state(b, map_slots_log2, dev),
-                                           self._extract_map, nops.voxel_map_clear, self._write_map)
-        if save_mesh is not None:
-            self._mesh = _TrajectoryProduct("mesh.ply", lambda b, dev: nops.tsdf_state(b, mesh_slots_log2, dev),
-                                            self._extract_mesh, nops.tsdf_clear, self._write_mesh)
-        self._products = [p for p in (self._map, self._mesh) if p is not None]     # in the order they finish and clear
+        self.cloud, self.cloud_step, self.cloud_frame, self.save_conf = bool(cloud), int(cloud_step), cloud_frame, bool(save_conf)
+        self.cloud_views, self.cloud_min_views, self.cloud_tol = chain.views, chain.min_views, chain.tol
+        self.save_map, self.map_min_frames, self.map_slots_log2 = chain.map_voxel, chain.map_min_frames, chain.map_slots_log2
+        self.save_mesh, self.mesh_trunc, self.mesh_min_frames = chain.voxel, chain.trunc, chain.min_frames
+        self.mesh_slots_log2 = chain.slots_log2
+        self.save_fused, self.fused_window = bool(save_fused), chain.window
+        self.fused_pixels = self.fused_cap = self.cloud_kept = self.cloud_cap = 0          # over the finished frames
+        self._per_trajectory = self.save_map is not None or self.save_mesh is not None     # map.ply / mesh.ply are written
+        self._dirs = None                                  # the directory of every sample's open trajectory, once a step went in
         self.maps = self.map_voxels = self.map_dropped_range = self.map_dropped_full = 0
         self.meshes = self.mesh_vertices = self.mesh_triangles = 0
         self.mesh_dropped_range = self.mesh_dropped_full = self.mesh_quads_dropped = 0
-        self._step = 0                                     # submits so far: the stamp of a step's vertices
         self.out_dir, self.fmt, self.panels = str(out_dir), fmt, panels
         self.near, self.far, self.err_max = float(near), float(far), float(err_max)
         self.n_slots, self.compress_level, self.encode = int(slots), int(compress_level), bool(encode)
@@ -449,6 +357,9 @@ class PredictionWriter:
         self._lock = threading.Lock()
         self._error = None
         self._closed = False
+
+    needs_geometry = property(lambda self: self.cloud or self._per_trajectory,
+                              doc="Whether the chain runs: ``submit`` then needs ``rgb``, ``rot``, ``trans``, ``camera`` and ``reset``.")
 
     def __enter__(self):
         return self
@@ -466,38 +377,35 @@ class PredictionWriter:
     def _allocate(self, est):
         b, h, w = est.shape[:3]
         self._geometry = (b, h, w)
-        cap = nops.cloud_capacity(h, w, self.cloud_step) if self._vertices3d else 0
-        self._slots = [_Slot(b, h, w, len(self.panels), est.device, cap, self.save_conf, self.cloud, self._geometry3d,
-                             self.save_fused)
-                       for _ in range(self.n_slots)]
-        for product in self._products[::-1]:
-            product.state = product.new_state(b, est.device)
+        self._slots = [_Slot(self, b, h, w, est.device) for _ in range(self.n_slots)]
         if any(p != "rgb" for p in self.panels):
             self._lut = torch.from_numpy(default_lut()).to(est.device)
         for i in range(self.n_slots):
             self._free.put(i)
 
-    def _extract_map(self, state, s):
-        keys, vertices, stats = nops.voxel_map_extract(state, s, self.map_min_frames, self.save_map)   # the one wait
-        return (vertices,), stats, {"maps": 1, "map_voxels": len(keys), "map_dropped_range": stats["dropped_range"],
-                                    "map_dropped_full": stats["dropped_full"]}
+    def _finish(self, s):
+        """The map and the mesh of sample ``s``'s open trajectory to worker threads (one wait each); the caller clears the
+        state on the same stream."""
+        if self.save_map is not None:
+            keys, vertices, stats = self.chain.extract_map(s)
+            self.maps += 1
+            self.map_voxels += len(keys)
+            self.map_dropped_range += stats["dropped_range"]
+            self.map_dropped_full += stats["dropped_full"]
+            self._hand_over(s, "map.ply", write_map_ply, (vertices,), (self.save_map, self.map_min_frames, stats))
+        if self.save_mesh is not None:
+            keys, vertices, triangles, stats = self.chain.extract_volume(s)
+            self.meshes += 1
+            self.mesh_vertices += len(keys)
+            self.mesh_triangles += len(triangles)
+            self.mesh_dropped_range += stats["dropped_range"]
+            self.mesh_dropped_full += stats["dropped_full"]
+            self.mesh_quads_dropped += stats["quads_dropped"]
+            self._hand_over(s, "mesh.ply", write_mesh_ply, (vertices, triangles),
+                            (self.save_mesh, self.mesh_trunc, self.mesh_min_frames, stats))
 
-    def _write_map(self, path, vertices, stats):
-        write_map_ply(path, vertices, self.save_map, self.map_min_frames, stats)
-
-    def _extract_mesh(self, state, s):
-        keys, vertices, triangles, stats = nops.tsdf_extract(state, s, self.mesh_min_frames, self.save_mesh)
-        return (vertices, triangles), stats, {"meshes": 1, "mesh_vertices": len(keys), "mesh_triangles": len(triangles),
-                                              "mesh_dropped_range": stats["dropped_range"],
-                                              "mesh_dropped_full": stats["dropped_full"],
-                                              "mesh_quads_dropped": stats["quads_dropped"]}
-
-    def _write_mesh(self, path, vertices, triangles, stats):
-        write_mesh_ply(path, vertices, triangles, self.save_mesh, self.mesh_trunc, self.mesh_min_frames, stats)
-
-    def _finish(self, product, s):
-        """``product`` of sample ``s``'s open trajectory to a worker thread; the caller clears the state on the same stream."""
-        arrays, stats, counters = product.extract(product.state, s)
+    def _hand_over(self, s, file_name, write, arrays, rest):
+        """``write(path, *arrays on the host, *rest)`` in a worker thread, once the copies of ``arrays`` have passed."""
         hosts = [torch.empty(a.shape, dtype=a.dtype) for a in arrays]
         for i, a in enumerate(arrays):
             if len(a):                                     # (an empty map or mesh is written too: nothing survived)
@@ -505,105 +413,87 @@ class PredictionWriter:
                 hosts[i].copy_(a, non_blocking=True)
         event = torch.cuda.Event()
         event.record()
-        for name, n in counters.items():
-            setattr(self, name, getattr(self, name) + n)
-        self._pool.submit(self._work_product, product, os.path.join(product.dirs[s], product.file_name), hosts, event, stats)
+        self._pool.submit(self._work_product, os.path.join(self._dirs[s], file_name), write, hosts, event, rest)
 
     def _keep_error(self, e):
         with self._lock:
             if self._error is None:
                 self._error = e
 
-    def _work_product(self, product, rel_path, hosts, event, stats):
+    def _work_product(self, rel_path, write, hosts, event, rest):
         try:
             event.synchronize()
             if self.encode:
                 path = os.path.join(self.out_dir, rel_path)
                 os.makedirs(os.path.dirname(path), exist_ok=True)
-                product.write(path, *(h.numpy() for h in hosts), stats)
+                write(path, *(h.numpy() for h in hosts), *rest)
         except BaseException as e:
             self._keep_error(e)
 
+    def _mask(self, slot, reset, first):
+        """``reset`` of a submit as (the step's device mask or None, the samples whose trajectory ended with the previous frame).
+        The first step resets everybody, so its flags change nothing: host flags are checked and then not even uploaded; a
+        device mask costs nothing to pass on and so still gets ``pose_accumulate``'s dtype and shape check."""
+        if reset is None:
+            return None, ()
+        on_device = torch.is_tensor(reset) and reset.is_cuda
+        if not on_device:                                  # host flags (the frame's new_traj)
+            reset = np.asarray(reset.numpy() if torch.is_tensor(reset) else reset, dtype=bool).reshape(-1)
+        n = reset.numel() if on_device else len(reset)
+        if n != slot.reset_h.shape[0]:
+            raise ValueError(f"reset has {n} samples, the writer {slot.reset_h.shape[0]}")
+        if on_device or first:
+            return (reset if on_device else None), ()
+        slot.reset_h.numpy()[:] = reset                    # through the slot's pinned bytes
+        slot.reset_d.copy_(slot.reset_h, non_blocking=True)
+        return slot.reset_d, np.nonzero(reset)[0].tolist()
+
     def _submit_cloud(self, slot, est, rgb, rot, trans, camera, reset, names):
-        """The cloud of one step into ``slot``, on the current stream: pose update, compaction, copies; with ``save_map`` the
-        maps of the trajectories that ended, then the step's vertices into the maps."""
+        """The chain's step into ``slot``, on the current stream: what ended goes to the workers, then the launches in the
+        chain's order, each followed by the copies of what it made."""
+        chain = self.chain
         if rgb is None or rot is None or trans is None or camera is None:
             raise ValueError("a writer with cloud=True or save_map needs rgb, rot, trans and camera at every submit")
-        if self.save_map is not None or self.save_mesh is not None:
+        if self._per_trajectory:
             what = "save_map" if self.save_map is not None else "save_mesh"
             if torch.is_tensor(reset) and reset.is_cuda:
                 raise ValueError(f"{what} needs host-side reset flags: which trajectory ended is decided on the host")
             dirs = [os.path.dirname(n) for n in names]
             if len(set(dirs)) != len(dirs):
                 raise ValueError(f"{what} needs names with one directory per sample and trajectory, got {list(names)}")
-        first = self._pose is None
-        if first:
-            self._pose = torch.empty((est.shape[0], 7), dtype=torch.float64, device=est.device)
-        # the first submit resets everybody (force_all), so its flags change nothing: host flags are checked and then not even
-        # uploaded, a device mask costs nothing to pass on and so still gets pose_accumulate's dtype and shape check
-        mask = None
-        if reset is not None:                              # checked at every submit, used from the second on
-            on_device = torch.is_tensor(reset) and reset.is_cuda
-            if not on_device:                              # host flags (the frame's new_traj)
-                reset = np.asarray(reset.numpy() if torch.is_tensor(reset) else reset, dtype=bool).reshape(-1)
-            n = reset.numel() if on_device else len(reset)
-            if n != slot.reset_h.shape[0]:
-                raise ValueError(f"reset has {n} samples, the writer {slot.reset_h.shape[0]}")
-            if on_device:
-                mask = reset                               # dtype and shape: pose_accumulate's check
-            elif not first:                                # through the slot's pinned bytes
-                slot.reset_h.numpy()[:] = reset
-                slot.reset_d.copy_(slot.reset_h, non_blocking=True)
-                mask = slot.reset_d
-                for product in self._products if reset.any() else ():
-                    for s in np.nonzero(reset)[0]:         # the trajectories that ended with the previous frame
-                        self._finish(product, int(s))
-                    product.clear(product.state, mask)
-        nops.pose_accumulate(rot, trans, self._pose, reset=mask, force_all=first)
-        raw = est
-        if self.cloud_views:                               # the clouds see the filtered copy; PNG and panels the estimate
-            b, h, w = est.shape[:3]
-            if self._views is None:
-                self._views = nops.depth_views_state(b, h, w, self.cloud_views, est.device)
-                self._views_depth = torch.empty((b, h, w, 1), dtype=torch.float32, device=est.device)
-                if not self.save_conf:
-                    self._views_n = torch.empty((b, h, w), dtype=torch.uint8, device=est.device)
-            # est may be a buffer the next graph replay overwrites: the ring copy happens in this launch, on this stream
-            _, est = nops.depth_views(est, camera["f"], camera["c"], self._pose, self._views, reset=mask, force_all=first,
-                                      tol_px=self.cloud_tol[0], tol_rel=self.cloud_tol[1], min_views=self.cloud_min_views,
-                                      n_views=slot.conf_d if self.save_conf else self._views_n, depth_f=self._views_depth)
+        mask, ended = self._mask(slot, reset, first=chain.pose is None)
+        for s in ended:
+            self._finish(s)
+        chain.advance(rot, trans, mask, clear=bool(ended))  # the clear launches only where a trajectory ended
+        seen = est                                         # what clouds, maps and meshes see; PNG, panels and guide the estimate
+        if chain.views:
+            seen = chain.filter(est, camera, counts=slot.conf_d)
             if self.save_conf:
                 slot.conf_h.copy_(slot.conf_d, non_blocking=True)
-        if self.save_mesh is not None:                     # the mesh sees what the clouds see, at every pixel
-            nops.tsdf_integrate(est, rgb, camera["f"], camera["c"], self._pose, self.save_mesh, self.mesh_trunc,
-                                self._mesh.state, near=self.near, far=self.far)
-            self._mesh.dirs = dirs
-        if self.save_fused:                                # the volume as it is now, seen from this frame
+        if self.save_mesh is not None:
+            chain.fuse(seen, rgb, camera)
+        if self.save_fused:
             slot.hits_d.zero_()
-            nops.tsdf_raycast(self._mesh.state, camera["f"], camera["c"], self._pose, est.shape[1], est.shape[2], self.save_mesh,
-                              self.mesh_trunc, self.mesh_min_frames, near=self.near, far=self.far,
-                              guide=raw if self.fused_window else None, window=self.fused_window, out=slot.fused_f,
-                              hits=slot.hits_d)
+            chain.render(est, camera, out=slot.fused_f, hits=slot.hits_d)
             nops.depth_export(slot.fused_f, self.fmt, depth16=slot.fused_d)
             slot.fused_h.copy_(slot.fused_d, non_blocking=True)
             slot.hits_h.copy_(slot.hits_d, non_blocking=True)
-        if not self._vertices3d:
-            return
-        nops.depth_cloud(est, rgb, camera["f"], camera["c"], step=self.cloud_step, near=self.near, far=self.far,
-                         pose=self._pose if self.cloud_frame == "world" else None, vertices=slot.cloud_d, counts=slot.counts_d)
-        if self.save_map is not None:
-            nops.voxel_map_integrate(slot.cloud_d, slot.counts_d, self.save_map, self._step, self._map.state)
-            self._map.dirs = dirs
-        if self.cloud:
-            slot.cloud_h.copy_(slot.cloud_d, non_blocking=True)
-            slot.counts_h.copy_(slot.counts_d, non_blocking=True)
-            slot.pose_h.copy_(self._pose, non_blocking=True)
+        if slot.cloud_d is not None:
+            chain.compact(seen, rgb, camera, self.cloud_step, self.cloud_frame == "world", slot.cloud_d, slot.counts_d)
+            if self.save_map is not None:
+                chain.merge(slot.cloud_d, slot.counts_d)
+            if self.cloud:
+                slot.cloud_h.copy_(slot.cloud_d, non_blocking=True)
+                slot.counts_h.copy_(slot.counts_d, non_blocking=True)
+                slot.pose_h.copy_(chain.pose, non_blocking=True)
+        if self._per_trajectory:
+            self._dirs = dirs
 
     def submit(self, est, names, gt=None, rgb=None, rot=None, trans=None, camera=None, reset=None):
         """``est`` [b,h,w,1] (+ ``gt`` / ``rgb`` as the panels need) of one step; ``names``: b relative paths without suffix.
-        With ``cloud``: ``rgb``, the frame's motion ``rot`` [b,4] / ``trans`` [b,3], ``camera`` {f, c} [b,2] and ``reset`` --
-        which samples start a trajectory with this frame (host flags or a uint8 [b] device mask, None = nobody); the first
-        submit resets every sample."""
+        With ``needs_geometry``: ``rgb``, the frame's motion ``rot`` [b,4] / ``trans`` [b,3], ``camera`` {f, c} [b,2] and
+        ``reset`` -- which samples start a trajectory with this frame (host flags or a uint8 [b] device mask, None = nobody);
+        the first submit resets every sample."""
         if self._closed:
             raise RuntimeError("PredictionWriter.submit after close()")
         if self._slots is None:
@@ -618,24 +508,15 @@ class PredictionWriter:
             slot.depth_h.copy_(slot.depth_d, non_blocking=True)
             if slot.panels_d is not None:
                 slot.panels_h.copy_(slot.panels_d, non_blocking=True)
-            self._step += 1
-            if self._geometry3d:
+            if self.needs_geometry:
                 self._submit_cloud(slot, est, rgb, rot, trans, camera, reset, names)
             slot.event.record()
         except BaseException:
             self._free.put(index)
             raise
-        jobs = []
-        for s, name in enumerate(names):
-            jobs.append((name + "_depth.png", slot.depth_h, s))
-            if slot.panels_h is not None:
-                jobs.append((name + "_panels.png", slot.panels_h, s))
-            if self.cloud:
-                jobs.append((name + "_cloud.ply", None, s))
-            if self.save_conf:
-                jobs.append((name + "_conf.png", slot.conf_h, s))
-            if self.save_fused:
-                jobs.append((name + "_fused.png", slot.fused_h, s))
+        files = (("_depth.png", slot.depth_h, True), ("_panels.png", slot.panels_h, bool(self.panels)), ("_cloud.ply", None, self.cloud),
+                 ("_conf.png", slot.conf_h, self.save_conf), ("_fused.png", slot.fused_h, self.save_fused))   # suffix, pinned copy, on
+        jobs = [(name + suffix, host, s) for s, name in enumerate(names) for suffix, host, on in files if on]
         slot.pending = len(jobs)
         self.frames += len(names)
         for job in jobs:
@@ -681,11 +562,9 @@ class PredictionWriter:
             return
         self._closed = True
         try:
-            for product in self._products:                 # the open trajectories end here
-                if product.dirs is not None:
-                    for s in range(len(product.dirs)):
-                        self._finish(product, s)
-                    product.dirs = None
+            for s in range(len(self._dirs or ())):         # the open trajectories end here
+                self._finish(s)
+            self._dirs = None
         except BaseException as e:
             self._keep_error(e)
         if self._slots is not None:
@@ -694,3 +573,26 @@ class PredictionWriter:
         self._pool.shutdown(wait=True)
         if self._error is not None:
             raise self._error
+
+    def summary(self):
+        """What was written, as the fragments of the driver's closing line (complete after ``close()``)."""
+        said = [self.fmt]
+        if self.panels:
+            said.append("panels " + ",".join(self.panels))
+        if self.cloud:
+            said.append(f"clouds at stride {self.cloud_step}")
+        if self.cloud_views and self.cloud:
+            said.append(f"{self.cloud_views}-view check kept {self.cloud_kept} of {self.cloud_cap} cloud pixels "
+                        f"({100.0 * self.cloud_kept / max(self.cloud_cap, 1):.1f} %)")
+        if self.save_map is not None:
+            said.append(f"{self.maps} voxel maps at {self.save_map:g} m: {self.map_voxels} voxels written, "
+                        f"{self.map_dropped_range} vertices dropped out of range, {self.map_dropped_full} dropped by full tables"
+                        + (" (raise --map_slots_log2)" if self.map_dropped_full else ""))
+        if self.save_mesh is not None:
+            said.append(f"{self.meshes} meshes at {self.save_mesh:g} m: {self.mesh_vertices} vertices, "
+                        f"{self.mesh_triangles} triangles, {self.mesh_dropped_range} samples dropped out of range, "
+                        f"{self.mesh_dropped_full} dropped by full tables"
+                        + (" (raise --mesh_slots_log2)" if self.mesh_dropped_full else ""))
+        if self.save_fused:
+            said.append(f"fused depth rendered on {100.0 * self.fused_pixels / max(self.fused_cap, 1):.1f} % of the pixels")
+        return said

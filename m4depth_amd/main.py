@@ -752,11 +752,10 @@ def predict(args, model, batches, rank, dev):
                 namer = FrameNamer(est.shape[0])
                 t_save = time.perf_counter()
             cloud = {}
-            geometry = writer.cloud or writer.save_map is not None or writer.save_mesh is not None
-            if geometry:                                      # the cloud launches follow the forward / the replay on its stream
+            if writer.needs_geometry:                         # the chain's launches follow the forward / the replay on its stream
                 cloud = dict(rot=frame["rot"], trans=frame["trans"], camera=frame["camera"], reset=frame["new_traj"])
             writer.submit(est, namer(frame["new_traj"]), gt=frame.get("depth") if want_gt else None,
-                          rgb=frame["RGB_im"] if "rgb" in writer.panels or geometry else None, **cloud)
+                          rgb=frame["RGB_im"] if "rgb" in writer.panels or writer.needs_geometry else None, **cloud)
     if writer is None:
         if rank == 0:
             os.makedirs(args.ckpt_dir, exist_ok=True)
@@ -765,21 +764,8 @@ def predict(args, model, batches, rank, dev):
     writer.close()
     if namer is not None:
         dt = time.perf_counter() - t_save
-        print(f"predict: wrote {writer.frames} frames ({args.save_format}"
-              + (", panels " + ",".join(writer.panels) if writer.panels else "")
-              + (f", clouds at stride {writer.cloud_step}" if writer.cloud else "")
-              + (f", {writer.cloud_views}-view check kept {writer.cloud_kept} of {writer.cloud_cap} cloud pixels "
-                 f"({100.0 * writer.cloud_kept / max(writer.cloud_cap, 1):.1f} %)" if writer.cloud_views and writer.cloud else "")
-              + (f", {writer.maps} voxel maps at {writer.save_map:g} m: {writer.map_voxels} voxels written, "
-                 f"{writer.map_dropped_range} vertices dropped out of range, {writer.map_dropped_full} dropped by full tables"
-                 + (" (raise --map_slots_log2)" if writer.map_dropped_full else "") if writer.save_map is not None else "")
-              + (f", {writer.meshes} meshes at {writer.save_mesh:g} m: {writer.mesh_vertices} vertices, "
-                 f"{writer.mesh_triangles} triangles, {writer.mesh_dropped_range} samples dropped out of range, "
-                 f"{writer.mesh_dropped_full} dropped by full tables"
-                 + (" (raise --mesh_slots_log2)" if writer.mesh_dropped_full else "") if writer.save_mesh is not None else "")
-              + (f", fused depth rendered on {100.0 * writer.fused_pixels / max(writer.fused_cap, 1):.1f} % of the pixels"
-                 if writer.save_fused else "")
-              + f") to {args.save_dir}: {writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
+        print(f"predict: wrote {writer.frames} frames ({', '.join(writer.summary())}) to {args.save_dir}: "
+              f"{writer.frames / dt:.1f} frames/s, the first forward excluded from the clock")
 
 
 def main(argv=None):

@@ -6,6 +6,7 @@ from __future__ import annotations
 import argparse
 import os
 
+from .fusion import MAP_COMPANIONS, VOLUME_COMPANIONS
 from .network import M4depthAblationParameters
 
 
@@ -317,14 +318,29 @@ def check_recording_args(parser, args):
         parser.error("--rec_max_gap must be > 0")
 
 
+CLI_SLOTS_LOG2_MIN = 16      # the command line's floor for every --*_slots_log2; the Python API takes smaller tables
+
+
+def _cli_companions(prefix, companions):                # the chain's table (fusion.py) under the options' prefix, with that floor
+    return tuple((prefix + name, default, max(lo, CLI_SLOTS_LOG2_MIN) if name == "slots_log2" else lo, hi)
+                 for name, default, lo, hi in companions)
+
+
 # the per-trajectory products of --save_dir: flag, its companions (option, default, lowest, highest or None) and why the camera
 # frame is refused.  The voxel map runs on the clouds' vertices, so the clouds' options serve it too; the TSDF mesh reads the
 # estimate itself, so of the clouds' options only --cloud_frame concerns it
 _TRAJECTORY_PRODUCTS = (
-    ("save_map", (("map_min_frames", 2, 1, None), ("map_slots_log2", 21, 16, 26)),
-     "a map merges the frames of a trajectory in one frame"),
-    ("save_mesh", (("mesh_trunc", 4, 2, 8), ("mesh_min_frames", 2, 1, None), ("mesh_slots_log2", 22, 16, 26)),
-     "a mesh fuses the frames of a trajectory in one frame"))
+    ("save_map", _cli_companions("map_", MAP_COMPANIONS), "a map merges the frames of a trajectory in one frame"),
+    ("save_mesh", _cli_companions("mesh_", VOLUME_COMPANIONS), "a mesh fuses the frames of a trajectory in one frame"))
+
+
+def _check_companions(parser, args, companions):
+    """The ranges of the companions that were given, and the defaults of the others."""
+    for f, default, lo, hi in companions:
+        v = getattr(args, f)
+        if v is not None and (v < lo or (hi is not None and v > hi)):
+            parser.error("--%s must be %s" % (f, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi)))
+        setattr(args, f, default if v is None else v)
 
 
 def _check_trajectory_product(parser, args, flag, companions, reason):
@@ -341,11 +357,7 @@ def _check_trajectory_product(parser, args, flag, companions, reason):
         parser.error("--%s VOXEL needs a finite edge length > 0" % flag)
     if args.cloud_frame == "camera":
         parser.error("--%s needs --cloud_frame world: %s" % (flag, reason))
-    for f, default, lo, hi in companions:
-        v = getattr(args, f)
-        if v is not None and (v < lo or (hi is not None and v > hi)):
-            parser.error("--%s must be %s" % (f, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi)))
-        setattr(args, f, default if v is None else v)
+    _check_companions(parser, args, companions)
     return True
 
 
@@ -451,10 +463,9 @@ def check_refine_args(parser, args):
             parser.error("--refine_pose_strides: --height and --width must be multiples of the largest stride, at least 3 of them")
 
 
-# --fused VOXEL renders the volume --save_mesh builds: its companions are the mesh's, under its own prefix, so that the defaults
-# and bounds of the two cannot drift; --fused_window (no default: absent = the whole range) also serves --save_fused
-_MESH_COMPANIONS = dict((p[0], p[1]) for p in _TRAJECTORY_PRODUCTS)["save_mesh"]
-_FUSED_COMPANIONS = tuple(("fused_" + name[len("mesh_"):], default, lo, hi) for name, default, lo, hi in _MESH_COMPANIONS)
+# --fused VOXEL renders the volume --save_mesh builds: its companions are the same table under its own prefix;
+# --fused_window (no default: absent = the whole range) also serves --save_fused
+_FUSED_COMPANIONS = _cli_companions("fused_", VOLUME_COMPANIONS)
 
 
 def check_fused_args(parser, args):
@@ -479,11 +490,7 @@ def check_fused_args(parser, args):
                      "by frame")
     if not (0 < args.fused < float("inf")):
         parser.error("--fused VOXEL needs a finite edge length > 0")
-    for f, default, lo, hi in _FUSED_COMPANIONS:
-        v = getattr(args, f)
-        if v is not None and (v < lo or (hi is not None and v > hi)):
-            parser.error("--%s must be %s" % (f, ">= %d" % lo if hi is None else "in %d..%d" % (lo, hi)))
-        setattr(args, f, default if v is None else v)
+    _check_companions(parser, args, _FUSED_COMPANIONS)
     if args.consistency and args.records_path is not None and not records_have_depth(args):
         parser.error("--fused scores against ground truth: the records of --records_path name no ground-truth map")
 
