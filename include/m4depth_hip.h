@@ -1168,6 +1168,54 @@ int m4d_tsdf_raycast(const void* state, int b, int log2_slots, const float* cam_
                      const float* fill, long long fill_stride,
                      float* depth_out, long long out_stride, void* hits, void* stream);
 
+/* m4d_tsdf_render: m4d_tsdf_raycast with a choice of how the field is sampled and, per pixel, the normal and the colour of the
+ * surface it hit.  The arguments of m4d_tsdf_raycast, interp (0 nearest voxel, 1 trilinear) and three optional outputs, each NULL
+ * or at a batch stride of its own in ELEMENTS: normal_out [b,h,w,3] float32 (unit, camera frame), colour_out [b,h,w,3] float32 in
+ * [0,1], view_out [b,h,w,3] uint8 (a shaded RGB8 picture).  depth_out is required.  One launch, one thread per pixel, a wave an 8x8
+ * pixel tile, the state only read.  One IEEE rounding per operation; lerp(a, b, t) = a + t * (b - a) in float32 (a subtraction, a
+ * product, a sum).  Corner c = dx | dy << 1 | dz << 2 of a base cell B is the voxel B + (dx, dy, dz).
+ *   Positions, Pw, cell, KNOWN, the march and its state are m4d_tsdf_raycast's: unknown space is visited exactly as there.
+ *   Base cell and fractions of a point Pw:  g[j] = Pw[j] / voxel - 0.5 (float64; the quotient is the one cell[j] is the floor of),
+ *     B[j] = floor(g[j]),  fr[j] = (float) (g[j] - B[j]).  The nearest voxel cell is one of the eight corners.
+ *     Corner c is KNOWN when its three indices lie in [-2^20, 2^20) (no wrap: a corner at -2^20 - 1 or 2^20 is missing), its key
+ *     is found by the read-only probe and its record has n >= min_frames and n > 0; then v_c = S / (float) n.
+ *   tri(v) of eight values and fr, in this order (x, then y, then z):
+ *     x00 = lerp(v0, v1, fr[0]), x10 = lerp(v2, v3, fr[0]), x01 = lerp(v4, v5, fr[0]), x11 = lerp(v6, v7, fr[0]);
+ *     y0 = lerp(x00, x10, fr[1]), y1 = lerp(x01, x11, fr[1]);  tri = lerp(y0, y1, fr[2]).
+ *   Sampling.  interp = 0, and every coarse-mode sample: D is the nearest voxel's, as m4d_tsdf_raycast's.  interp = 1, a KNOWN
+ *     sample in fine mode: D = tri(v) at the sample's Pw when all eight corners are KNOWN, else the nearest voxel's value.  The hit
+ *     test and z* = z_{i-1} + hv * (double) (prev / (prev - D)) are unchanged.  With interp = 0 depth_out and hits are
+ *     m4d_tsdf_raycast's bit for bit.
+ *   At a hit (either interp; computed when an output needs it): P* = the ray's point at the float64 z* (X = ax * z*, Y = ay * z*,
+ *     Pw as above), with its base cell, fractions and corners.
+ *     normal: only when all eight corners are KNOWN.  The gradient of the interpolant, float32:
+ *       gx = lerp(lerp(v1 - v0, v3 - v2, fr[1]), lerp(v5 - v4, v7 - v6, fr[1]), fr[2])
+ *       gy = lerp(lerp(v2 - v0, v3 - v1, fr[0]), lerp(v6 - v4, v7 - v5, fr[0]), fr[2])
+ *       gz = lerp(lerp(v4 - v0, v5 - v1, fr[0]), lerp(v6 - v2, v7 - v3, fr[0]), fr[1])
+ *     widened; into the camera frame c[j] = (R[0][j] gx + R[1][j] gy) + R[2][j] gz; len = sqrt((c0 c0 + c1 c1) + c2 c2);
+ *     n[j] = (float) (c[j] / len).  The field grows towards free space, so n faces the camera on a front face.  len not > 0 (zero
+ *     or NaN) or a corner that is not KNOWN: the three floats are the quiet NaN 0x7FC00000.
+ *     colour: m_c[k] = ((float) s_k / (float) nc) / 255.0f of a record, s = sr, sg, sb.  All eight corners KNOWN with nc > 0:
+ *     tri(m[k]) per channel.  Otherwise the nearest voxel of P* (cell = floor(Pw / voxel), in range) when KNOWN with nc > 0: its
+ *     m[k].  Otherwise three quiet NaNs.
+ *     view: vl = sqrt((ax ax + ay ay) + 1.0), dot = ((n0 ax + n1 ay) + n2) / vl on the widened float32 normal,
+ *     shade = (float) (0.25 + 0.75 * fmax(0.0, -dot)), 1.0f where the normal is missing; byte k = m4d_depth_export's rgb rule of
+ *     (colour[k] * shade), a missing colour counting as 0.5f.
+ *   A miss (a sample with a non-finite pose included): depth_out as m4d_tsdf_raycast's (fill applies to depth_out only), normal_out
+ *     and colour_out three quiet NaNs, view_out 0, 0, 0.
+ * A thread probes the eight corners of a base cell together (the eight first-slot key loads, then the eight (S, n) loads; the
+ * sequential probe only for a corner whose first slot holds another key) and keeps them while B does not change; the 16 colour
+ * bytes of a record are read only at a hit.  Neither changes a bit.
+ * Returns 1 without a launch for what m4d_tsdf_raycast refuses, interp outside 0..1, a normal / colour / view stride smaller than
+ * 3 h w, normal_out / colour_out off 4 bytes.  Plain launch (capturable).  Additive entry point: ABI 6 unchanged. */
+int m4d_tsdf_render(const void* state, int b, int log2_slots, const float* cam_f, const float* cam_c, const double* pose,
+                    int h, int w, float near, float far, float voxel, int trunc, int min_frames,
+                    const float* guide, long long guide_stride, int window,
+                    const float* fill, long long fill_stride, int interp,
+                    float* depth_out, long long out_stride, float* normal_out, long long normal_stride,
+                    float* colour_out, long long colour_stride, uint8_t* view_out, long long view_stride,
+                    void* hits, void* stream);
+
 /* ---- training summaries (main.py --mode=train --log_dir): float32 maps -> the uint8 images of a TensorBoard event -------- */
 
 /* Up to 16 float32 maps of different sizes -> uint8 images, in one launch.  src, stride, h, w, c, kind and out_offset are

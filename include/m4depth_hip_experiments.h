@@ -42,6 +42,17 @@ int m4d_tsdf_raycast_plain(int variant, const void* state, int b, int log2_slots
                            const float* guide, long long guide_stride, int window, const float* fill, long long fill_stride,
                            float* depth_out, long long out_stride, void* hits, void* stream);
 
+/* m4d_tsdf_render (include/m4depth_hip.h) in the forms its two devices were measured against: variant bit 0 = the eight corners
+ * of a base cell are probed together (clear: eight read-only probes back to back), bit 1 = the corners are kept while the base
+ * cell does not change (clear: every fine sample probes).  0 is the plain kernel, 3 the product's; anything else is refused.
+ * The other arguments and every bit of the result are m4d_tsdf_render's (tools/bench_tsdf_raycast.py). */
+int m4d_tsdf_render_plain(int variant, const void* state, int b, int log2_slots, const float* cam_f, const float* cam_c,
+                          const double* pose, int h, int w, float near, float far, float voxel, int trunc, int min_frames,
+                          const float* guide, long long guide_stride, int window, const float* fill, long long fill_stride,
+                          int interp, float* depth_out, long long out_stride, float* normal_out, long long normal_stride,
+                          float* colour_out, long long colour_stride, uint8_t* view_out, long long view_stride,
+                          void* hits, void* stream);
+
 /* ---- launch tape (csrc/m4d_tape.hip): a recorded sequence of this library's kernel launches, replayed as PLAIN STREAM
  * LAUNCHES from one host loop -- the host-side cost of a hipGraph replay without its effect on concurrent small kernels
  * (DESIGN_HISTORY.md).  Between m4d_tape_begin()

@@ -247,6 +247,7 @@ class _Slot:
 
         self.depth_d, self.depth_h = pair((b, h, w), torch.int16)
         self.panels_d = self.panels_h = self.cloud_d = self.conf_d = self.conf_h = self.fused_h = None
+        self.view_d = self.view_h = None
         if writer.panels:
             self.panels_d, self.panels_h = pair((b, len(writer.panels) * h, w, 3), torch.uint8)
         if writer.cloud:
@@ -264,13 +265,16 @@ class _Slot:
             self.fused_f = torch.empty((b, h, w, 1), dtype=torch.float32, device=dev)
             self.fused_d, self.fused_h = pair((b, h, w), torch.int16)
             self.hits_d, self.hits_h = pair(b, torch.int64)
+        if writer.save_fused_view:                         # the same launch's RGB8 picture
+            self.view_d, self.view_h = pair((b, h, w, 3), torch.uint8)
         self.event = torch.cuda.Event()
         self.pending = 0
 
 
 # what the chain's options are called here, for its ValueError texts
 _CHAIN_NAMES = {"views": "cloud_views", "min_views": "cloud_min_views", "tol": "cloud_tol", "map_voxel": "save_map", "voxel": "save_mesh",
-                "trunc": "mesh_trunc", "min_frames": "mesh_min_frames", "slots_log2": "mesh_slots_log2", "window": "fused_window"}
+                "trunc": "mesh_trunc", "min_frames": "mesh_min_frames", "slots_log2": "mesh_slots_log2", "window": "fused_window",
+                "interp": "fused_interp"}
 
 
 class PredictionWriter:
@@ -292,7 +296,9 @@ class PredictionWriter:
     capacity crosses PCIe every step (the count is only known on the device); the worker writes the first ``counts[s]``
     vertices.  ``save_conf=True`` (needs ``cloud_views=K``): ``<name>_conf.png``, 8-bit grey, ``confirming views * 255 // K``.
     ``save_fused=True`` (needs ``save_mesh``): ``<name>_fused.png``, the volume right after the frame went in, rendered into the
-    frame's camera and encoded like the estimate.  ``cloud_kept`` / ``cloud_cap`` and ``fused_pixels`` / ``fused_cap``: vertices
+    frame's camera and encoded like the estimate; ``fused_interp``: "nearest" or "trilinear", how that rendering samples the
+    field; ``save_fused_view=True`` (needs ``save_fused``): ``<name>_fused_view.png``, RGB8, the rendered surface's colour under a
+    headlight (``network_ops.tsdf_render``'s ``view``).  ``cloud_kept`` / ``cloud_cap`` and ``fused_pixels`` / ``fused_cap``: vertices
     written / a cloud's capacity and pixels rendered / pixels there are, over the frames the workers have finished.
 
     ``save_map=VOXEL`` / ``save_mesh=VOXEL``: ``map.ply`` / ``mesh.ply`` in the directory of a trajectory's frames, from the step's
@@ -305,7 +311,8 @@ class PredictionWriter:
     def __init__(self, out_dir, fmt, panels=(), near=1.0, far=80.0, err_max=0.5, slots=4, threads=8, compress_level=1,
                  encode=True, cloud=False, cloud_step=2, cloud_frame="world", cloud_views=0, cloud_min_views=None,
                  cloud_tol=(1.0, 0.01), save_conf=False, save_map=None, map_min_frames=None, map_slots_log2=None, save_mesh=None,
-                 mesh_trunc=None, mesh_min_frames=None, mesh_slots_log2=None, save_fused=False, fused_window=None):
+                 mesh_trunc=None, mesh_min_frames=None, mesh_slots_log2=None, save_fused=False, fused_window=None, fused_interp=None,
+                 save_fused_view=False):
         if fmt not in FORMATS:
             raise ValueError(f"fmt: expected one of {FORMATS}, got {fmt!r}")
         panels = tuple(panels)
@@ -321,10 +328,14 @@ class PredictionWriter:
             raise ValueError("save_fused needs save_mesh: it renders the mesh's volume")
         if fused_window is not None and (not save_fused or int(fused_window) < 1):
             raise ValueError(f"fused_window needs save_fused and a width >= 1 truncation distances, got {fused_window}")
+        if fused_interp is not None and not save_fused:
+            raise ValueError(f"fused_interp needs save_fused, got {fused_interp!r}")
+        if save_fused_view and not save_fused:
+            raise ValueError("save_fused_view needs save_fused: it is the same rendering's picture")
         self.chain = chain = TrajectoryChain(
             save_mesh, mesh_trunc, mesh_min_frames, mesh_slots_log2, near, far, window=fused_window, views=cloud_views,
             min_views=cloud_min_views, tol=cloud_tol, map_voxel=save_map, map_min_frames=map_min_frames,
-            map_slots_log2=map_slots_log2, names=_CHAIN_NAMES)
+            map_slots_log2=map_slots_log2, names=_CHAIN_NAMES, interp="nearest" if fused_interp is None else fused_interp)
         for flag, voxel, verb in (("save_map", chain.map_voxel, "map merges"), ("save_mesh", chain.voxel, "mesh fuses")):
             if voxel is not None and cloud_frame != "world":
                 raise ValueError(f"{flag} needs cloud_frame='world': a {verb} the frames of a trajectory in one frame")
@@ -339,6 +350,7 @@ class PredictionWriter:
         self.save_mesh, self.mesh_trunc, self.mesh_min_frames = chain.voxel, chain.trunc, chain.min_frames
         self.mesh_slots_log2 = chain.slots_log2
         self.save_fused, self.fused_window = bool(save_fused), chain.window
+        self.fused_interp, self.save_fused_view = chain.interp, bool(save_fused_view)
         self.fused_pixels = self.fused_cap = self.cloud_kept = self.cloud_cap = 0          # over the finished frames
         self._per_trajectory = self.save_map is not None or self.save_mesh is not None     # map.ply / mesh.ply are written
         self._dirs = None                                  # the directory of every sample's open trajectory, once a step went in
@@ -474,9 +486,11 @@ class PredictionWriter:
             chain.fuse(seen, rgb, camera)
         if self.save_fused:
             slot.hits_d.zero_()
-            chain.render(est, camera, out=slot.fused_f, hits=slot.hits_d)
+            chain.render(est, camera, out=slot.fused_f, hits=slot.hits_d, view=slot.view_d)
             nops.depth_export(slot.fused_f, self.fmt, depth16=slot.fused_d)
             slot.fused_h.copy_(slot.fused_d, non_blocking=True)
+            if slot.view_d is not None:
+                slot.view_h.copy_(slot.view_d, non_blocking=True)
             slot.hits_h.copy_(slot.hits_d, non_blocking=True)
         if slot.cloud_d is not None:
             chain.compact(seen, rgb, camera, self.cloud_step, self.cloud_frame == "world", slot.cloud_d, slot.counts_d)
@@ -515,7 +529,8 @@ class PredictionWriter:
             self._free.put(index)
             raise
         files = (("_depth.png", slot.depth_h, True), ("_panels.png", slot.panels_h, bool(self.panels)), ("_cloud.ply", None, self.cloud),
-                 ("_conf.png", slot.conf_h, self.save_conf), ("_fused.png", slot.fused_h, self.save_fused))   # suffix, pinned copy, on
+                 ("_conf.png", slot.conf_h, self.save_conf), ("_fused.png", slot.fused_h, self.save_fused),
+                 ("_fused_view.png", slot.view_h, self.save_fused_view))                         # suffix, pinned copy, on
         jobs = [(name + suffix, host, s) for s, name in enumerate(names) for suffix, host, on in files if on]
         slot.pending = len(jobs)
         self.frames += len(names)
@@ -594,5 +609,7 @@ class PredictionWriter:
                         f"{self.mesh_dropped_full} dropped by full tables"
                         + (" (raise --mesh_slots_log2)" if self.mesh_dropped_full else ""))
         if self.save_fused:
-            said.append(f"fused depth rendered on {100.0 * self.fused_pixels / max(self.fused_cap, 1):.1f} % of the pixels")
+            said.append(f"fused depth rendered on {100.0 * self.fused_pixels / max(self.fused_cap, 1):.1f} % of the pixels"
+                        + ("" if self.fused_interp == "nearest" else f" ({self.fused_interp} sampling)")
+                        + (", with views" if self.save_fused_view else ""))
         return said

@@ -28,7 +28,8 @@ class TrajectoryChain:
     Always ``pose``, the [b,7] float64 camera-to-world poses, and the range [``near``, ``far``] every reader of an estimate
     keeps to.  ``voxel=VOXEL`` (metres): ``state``, a TSDF volume per sample on a hashed grid of 2^``slots_log2`` slots (32 bytes
     each: 134 MB at 22), ``trunc`` the truncation distance in voxels; a voxel is rendered or meshed once ``min_frames`` frames
-    updated it; ``window=W`` marches only W truncation distances around a pixel's raw estimate (None: the whole range).
+    updated it; ``window=W`` marches only W truncation distances around a pixel's raw estimate (None: the whole range);
+    ``interp``: how ``render`` samples the field, "nearest" or "trilinear" (``network_ops.tsdf_render``).
     ``views=K`` (1..8): the multi-view check, a ring of the last K + 1 estimates and poses ((K+1) b h w floats) and the filtered
     copy -- a pixel survives if at least ``min_views`` (default min(2, K)) of the up to K earlier frames of its trajectory
     confirm it within ``tol`` = (pixels, relative depth).  ``map_voxel=VOXEL``: ``map_state``, a voxel map per sample, a hash
@@ -40,7 +41,8 @@ class TrajectoryChain:
     consumer wants: each is one ``network_ops`` call on the current stream.  Only ``extract_*`` and ``stats`` synchronise."""
 
     def __init__(self, voxel=None, trunc=None, min_frames=None, slots_log2=None, near=NEAR, far=FAR, window=None, views=0,
-                 min_views=None, tol=(1.0, 0.01), map_voxel=None, map_min_frames=None, map_slots_log2=None, names=None):
+                 min_views=None, tol=(1.0, 0.01), map_voxel=None, map_min_frames=None, map_slots_log2=None, names=None,
+                 interp="nearest"):
         def name(k):                                       # what the caller calls the keyword ``k``
             return (names or {}).get(k, k)
 
@@ -66,6 +68,9 @@ class TrajectoryChain:
         if window is not None and int(window) < 1:
             raise ValueError(f"{name('window')} must be >= 1 truncation distances (None: the whole range), got {window}")
         self.window = None if window is None else int(window)
+        if interp not in nops.TSDF_INTERP:
+            raise ValueError(f"{name('interp')} must be one of {', '.join(nops.TSDF_INTERP)}, got {interp!r}")
+        self.interp = interp
         self.pose = self.state = self.map_state = None
         self.stamp = 0                                     # advances so far: the stamp of a step's vertices in the map
         self._views = self._filtered = self._counts = None  # depth_views' ring and ages, the filtered copy, the [b,h,w] counts
@@ -124,12 +129,17 @@ class TrajectoryChain:
         nops.tsdf_integrate(est, rgb, camera["f"], camera["c"], self.pose, self.voxel, self.trunc, self.state, near=self.near,
                             far=self.far)
 
-    def render(self, raw, camera, fill=False, out=None, hits=None):
+    def render(self, raw, camera, fill=False, out=None, hits=None, normal=None, colour=None, view=None):
         """The volumes as they are, seen from the frame: [b,h,w,1] (``out`` when given).  ``raw``: the RAW estimate, the guide
-        of a windowed march and, with ``fill``, what a pixel without a surface keeps; ``hits``: as ``tsdf_raycast``'s."""
-        return nops.tsdf_raycast(self.state, camera["f"], camera["c"], self.pose, raw.shape[1], raw.shape[2], self.voxel, self.trunc,
-                                 self.min_frames, near=self.near, far=self.far, guide=raw if self.window else None,
-                                 window=self.window, fill=raw if fill else None, out=out, hits=hits)
+        of a windowed march and, with ``fill``, what a pixel without a surface keeps; ``hits``: as ``tsdf_raycast``'s;
+        ``normal`` / ``colour`` / ``view``: ``tsdf_render``'s optional destinations.  The nearest rule with none of them is
+        ``tsdf_raycast``'s launch."""
+        args = (self.state, camera["f"], camera["c"], self.pose, raw.shape[1], raw.shape[2], self.voxel, self.trunc, self.min_frames)
+        kw = dict(near=self.near, far=self.far, guide=raw if self.window else None, window=self.window,
+                  fill=raw if fill else None, out=out, hits=hits)
+        if self.interp == "nearest" and normal is None and colour is None and view is None:
+            return nops.tsdf_raycast(*args, **kw)
+        return nops.tsdf_render(*args, interp=self.interp, normal=normal, colour=colour, view=view, **kw)
 
     def compact(self, est, rgb, camera, step, world, vertices, counts):
         """``est`` as ``depth_cloud``'s ``vertices`` / ``counts``, in the trajectory's frame (``world``) or the camera's."""
@@ -156,15 +166,15 @@ class TrajectoryChain:
 
 
 class FusedDepth(TrajectoryChain):
-    """A chain with a volume (``voxel`` and its companions, ``near`` / ``far``, ``window``: the chain's leading keywords), no
+    """A chain with a volume (``voxel`` and its companions, ``near`` / ``far``, ``window``, ``interp``: the chain's keywords), no
     views check and no map, stepped by a consumer that has the reset flags on the device only."""
 
-    def step(self, est, rgb, rot, trans, camera, reset, out=None, hits=None, views_est=None):
+    def step(self, est, rgb, rot, trans, camera, reset, out=None, hits=None, views_est=None, normal=None, colour=None, view=None):
         """One frame batch, on the current stream: returns fused [b,h,w,1] (``out`` when given).  ``est`` [b,h,w,1] the
         estimate, ``rgb`` [b,h,w,3], ``rot`` [b,4] / ``trans`` [b,3] the frame's motion as the network got it, ``camera`` {f, c}
         [b,2], ``reset``: the DEVICE mask of ``advance`` (never read by the host; the first step resets everybody).  ``hits``:
         int64 [b], zeroed by the caller, takes the pixels rendered per sample.  ``views_est``: what is fused instead of ``est``
-        (a filtered copy); the guide and the fill stay the raw estimate."""
+        (a filtered copy); the guide and the fill stay the raw estimate.  ``normal`` / ``colour`` / ``view``: ``render``'s."""
         if est.dim() != 4 or est.shape[3] != 1:
             raise ValueError(f"est: expected [b,h,w,1], got {tuple(est.shape)}")
         if not (torch.is_tensor(reset) and reset.is_cuda):
@@ -173,12 +183,12 @@ class FusedDepth(TrajectoryChain):
             raise ValueError(f"est has {est.shape[0]} samples, the volumes {int(self.state['b'])}")
         self.advance(rot, trans, reset, clear=True)
         self.fuse(est if views_est is None else views_est, rgb, camera)
-        return self.render(est, camera, fill=True, out=out, hits=hits)
+        return self.render(est, camera, fill=True, out=out, hits=hits, normal=normal, colour=colour, view=view)
 
 
 def from_args(args):
     return FusedDepth(args.fused, trunc=args.fused_trunc, min_frames=args.fused_min_frames, slots_log2=args.fused_slots_log2,
-                      window=args.fused_window)
+                      window=args.fused_window, interp=args.fused_interp)
 
 
 def perfs_path(ckpt_dir, dataset):

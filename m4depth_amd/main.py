@@ -646,7 +646,8 @@ def eval_streams(args, model, dev):
         dropped = sum(v["dropped_full"] for v in volumes)
         cover = float(np.mean([row[0] for _, _, row in frames])) if frames else 0.0
         print(f"fused depth at {fuser.voxel:g} m (K {fuser.trunc}, min_frames {fuser.min_frames}, "
-              f"{'whole range' if fuser.window is None else 'window %d' % fuser.window}): mean coverage {cover:.4f} over "
+              f"{'whole range' if fuser.window is None else 'window %d' % fuser.window}"
+              f"{'' if fuser.interp == 'nearest' else ', %s sampling' % fuser.interp}): mean coverage {cover:.4f} over "
               f"{len(frames)} counted frames, AbsRel raw {SE.fold_result(total, count)[0]:.6f} fused {means_f[0]:.6f}, "
               f"{dropped} samples dropped by full tables" + (" (raise --fused_slots_log2)" if dropped else ""))
         print(f"wrote {FU.perfs_path(args.ckpt_dir, args.dataset)} and {FU.frames_path(args.ckpt_dir, args.dataset)}")
@@ -721,7 +722,9 @@ def predict(args, model, batches, rank, dev):
                                   map_slots_log2=args.map_slots_log2, save_mesh=args.save_mesh, mesh_trunc=args.mesh_trunc,
                                   mesh_min_frames=args.mesh_min_frames, mesh_slots_log2=args.mesh_slots_log2,
                                   save_fused=getattr(args, "save_fused", False),
-                                  fused_window=getattr(args, "fused_window", None))
+                                  fused_window=getattr(args, "fused_window", None),
+                                  fused_interp=getattr(args, "fused_interp", None) if getattr(args, "save_fused", False) else None,
+                                  save_fused_view=getattr(args, "save_fused_view", False))
         want_gt = any(p in ("gt", "err") for p in writer.panels)
     preds = []
     for data in batches:

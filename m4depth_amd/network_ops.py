@@ -868,17 +868,8 @@ def tsdf_integrate(depth, rgb, cam_f, cam_c, pose, voxel, trunc, state, near=1.0
     return state
 
 
-def tsdf_raycast(state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near=1.0, far=80.0, guide=None, window=None,
-                 fill=None, out=None, hits=None):
-    """The TSDF volumes rendered into the cameras ``pose`` (m4d_tsdf_raycast): returns depth [b,h,w,1] float32, the z-depth of
-    the first front-face zero crossing of the field along every pixel's ray over [near, far], marched coarse to fine in half
-    voxels.  ``state`` as ``tsdf_integrate`` left it (only read); ``cam_f`` / ``cam_c`` [b,2]; ``pose`` [b,7] float64; ``voxel``,
-    ``trunc`` the volume's; a voxel counts once ``min_frames`` frames updated it.  ``guide`` [b,h,w,1] with ``window`` (>= 1; both
-    or neither): a pixel with a finite guide depth in [near, far] marches only ``window`` truncation distances around it.
-    ``fill`` [b,h,w,1]: what a pixel without a surface gets (None: NaN).  ``guide``, ``fill`` and ``out`` are float32 device
-    tensors with dense images at a batch stride; ``out`` (the destination, the caller's) may be ``fill`` itself.  ``hits``: int64
-    [b] the launch adds every sample's rendered pixels to (the caller zeroes it; a row of a log is fine).  One launch, nothing
-    synchronises."""
+def _tsdf_ray_args(state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near, far, guide, window, fill, out, hits):
+    """What ``tsdf_raycast`` and ``tsdf_render`` check alike: (b, slots_log2, trunc, min_frames, h, w, near, far, out, strides)."""
     b, slots_log2 = _tsdf_check(state, voxel)
     trunc, min_frames, h, w = int(trunc), int(min_frames), int(h), int(w)
     if not TSDF_TRUNC[0] <= trunc <= TSDF_TRUNC[1]:
@@ -913,12 +904,68 @@ def tsdf_raycast(state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near
             raise ValueError(f"{name}: expected [{b},{h},{w},1], got {tuple(t.shape)}")
     if fill is not None and fill.data_ptr() == out.data_ptr() and strides["fill"] != strides["out"]:
         raise ValueError("out may be fill itself only at the same batch stride")
+    return b, slots_log2, trunc, min_frames, h, w, near, far, out, strides
+
+
+def tsdf_raycast(state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near=1.0, far=80.0, guide=None, window=None,
+                 fill=None, out=None, hits=None):
+    """The TSDF volumes rendered into the cameras ``pose`` (m4d_tsdf_raycast): returns depth [b,h,w,1] float32, the z-depth of
+    the first front-face zero crossing of the field along every pixel's ray over [near, far], marched coarse to fine in half
+    voxels.  ``state`` as ``tsdf_integrate`` left it (only read); ``cam_f`` / ``cam_c`` [b,2]; ``pose`` [b,7] float64; ``voxel``,
+    ``trunc`` the volume's; a voxel counts once ``min_frames`` frames updated it.  ``guide`` [b,h,w,1] with ``window`` (>= 1; both
+    or neither): a pixel with a finite guide depth in [near, far] marches only ``window`` truncation distances around it.
+    ``fill`` [b,h,w,1]: what a pixel without a surface gets (None: NaN).  ``guide``, ``fill`` and ``out`` are float32 device
+    tensors with dense images at a batch stride; ``out`` (the destination, the caller's) may be ``fill`` itself.  ``hits``: int64
+    [b] the launch adds every sample's rendered pixels to (the caller zeroes it; a row of a log is fine).  One launch, nothing
+    synchronises."""
+    b, slots_log2, trunc, min_frames, h, w, near, far, out, strides = _tsdf_ray_args(
+        state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near, far, guide, window, fill, out, hits)
     ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())          # noqa: E731  (views: checked above)
     check(lib.m4d_tsdf_raycast(dptr(state["words"], "state", torch.int64), b, slots_log2, dptr(as_f32(cam_f, "cam_f"), "cam_f"),
                                dptr(as_f32(cam_c, "cam_c"), "cam_c"), dptr(pose, "pose", torch.float64), h, w, near, far,
                                float(voxel), trunc, min_frames, ptr(guide), strides["guide"], 0 if window is None else int(window),
                                ptr(fill), strides["fill"], ptr(out), strides["out"], dptr(hits, "hits", torch.int64),
                                stream_ptr()), "m4d_tsdf_raycast")
+    return out
+
+
+TSDF_INTERP = {"nearest": 0, "trilinear": 1}                    # how m4d_tsdf_render samples the field
+
+
+def tsdf_render(state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near=1.0, far=80.0, guide=None, window=None,
+                fill=None, interp="nearest", out=None, normal=None, colour=None, view=None, hits=None):
+    """``tsdf_raycast`` with a choice of the sample and the surface's looks (m4d_tsdf_render): returns depth [b,h,w,1] float32.
+    ``interp``: "nearest" (the depth and the hits are ``tsdf_raycast``'s bit for bit) or "trilinear" (a fine-mode sample blends
+    the eight voxels around it when all are known: no half-voxel staircase).  Optional destinations, written for every pixel:
+    ``normal`` [b,h,w,3] float32, the unit gradient of the interpolant at the hit in the camera frame, towards the camera (NaN at
+    a miss or next to an unknown voxel); ``colour`` [b,h,w,3] float32 in [0,1], the blended mean colour (NaN at a miss);
+    ``view`` [b,h,w,3] uint8, the colour under a headlight (0 at a miss).  ``fill`` applies to the depth only.  Every tensor is
+    a device tensor with dense images at a batch stride.  The other arguments are ``tsdf_raycast``'s.  One launch, nothing
+    synchronises."""
+    if interp not in TSDF_INTERP:
+        raise ValueError(f"interp must be one of {', '.join(TSDF_INTERP)}, got {interp!r}")
+    b, slots_log2, trunc, min_frames, h, w, near, far, out, strides = _tsdf_ray_args(
+        state, cam_f, cam_c, pose, h, w, voxel, trunc, min_frames, near, far, guide, window, fill, out, hits)
+    for name, t in (("normal", normal), ("colour", colour), ("view", view)):
+        if t is None:
+            strides[name] = 0
+        elif name == "view":
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+                raise TypeError("view: expected a uint8 device tensor")
+            if t.dim() < 2 or not t[0].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < t[0].numel()):
+                raise ValueError(f"view: expected [b, ...] with dense images at a batch stride, got strides {t.stride()}")
+            strides[name] = t.stride(0) if t.shape[0] > 1 else t[0].numel()
+        else:
+            strides[name] = _batch_stride(t, name)
+        if t is not None and tuple(t.shape) != (b, h, w, 3):
+            raise ValueError(f"{name}: expected [{b},{h},{w},3], got {tuple(t.shape)}")
+    ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())          # noqa: E731  (views: checked above)
+    check(lib.m4d_tsdf_render(dptr(state["words"], "state", torch.int64), b, slots_log2, dptr(as_f32(cam_f, "cam_f"), "cam_f"),
+                              dptr(as_f32(cam_c, "cam_c"), "cam_c"), dptr(pose, "pose", torch.float64), h, w, near, far,
+                              float(voxel), trunc, min_frames, ptr(guide), strides["guide"], 0 if window is None else int(window),
+                              ptr(fill), strides["fill"], TSDF_INTERP[interp], ptr(out), strides["out"], ptr(normal),
+                              strides["normal"], ptr(colour), strides["colour"], ptr(view), strides["view"],
+                              dptr(hits, "hits", torch.int64), stream_ptr()), "m4d_tsdf_render")
     return out
 
 

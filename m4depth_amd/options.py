@@ -151,9 +151,16 @@ def build_parser():
     p.add_argument("--fused_window", type=int, default=argparse.SUPPRESS, metavar="W",
                    help="--fused / --save_fused: march only W >= 1 truncation distances around the raw estimate of each pixel "
                         "instead of the whole range (several times fewer probes; a surface further from the estimate is missed)")
+    p.add_argument("--fused_interp", choices=["nearest", "trilinear"], default=argparse.SUPPRESS,
+                   help="--fused / --save_fused: how the march samples the field (default nearest: the value of the voxel a "
+                        "sample falls in; trilinear: the blend of the eight voxels around it where all are known -- no half-voxel "
+                        "staircase in the rendered depth, eight table probes per sample instead of one)")
     p.add_argument("--save_fused", action="store_true", default=argparse.SUPPRESS,
                    help="--save_mesh: also write <frame>_fused.png, the mesh's volume rendered into the frame (--save_format; "
                         "a pixel without a surface is written as a non-finite estimate is: 0 in kitti16, 0x7C00 in midair16)")
+    p.add_argument("--save_fused_view", action="store_true", default=argparse.SUPPRESS,
+                   help="--save_fused: also write <frame>_fused_view.png, an RGB8 picture of the rendered surface -- the volume's "
+                        "colour under a headlight along the interpolated field's normal; black where there is no surface")
     p.add_argument("--learning_rate", type=float, default=1e-4, help="Adam step size (main.py:88)")
     p.add_argument("--loss", default="supervised", choices=["supervised", "photometric"],
                    help="train: supervised = the reference's log-depth L1 against ground truth; photometric = the reprojection "
@@ -464,7 +471,7 @@ def check_refine_args(parser, args):
 
 
 # --fused VOXEL renders the volume --save_mesh builds: its companions are the same table under its own prefix;
-# --fused_window (no default: absent = the whole range) also serves --save_fused
+# --fused_window (no default: absent = the whole range) and --fused_interp (absent = nearest) also serve --save_fused
 _FUSED_COMPANIONS = _cli_companions("fused_", VOLUME_COMPANIONS)
 
 
@@ -474,9 +481,15 @@ def check_fused_args(parser, args):
     for f in ("fused", "fused_window") + tuple(c[0] for c in _FUSED_COMPANIONS):
         setattr(args, f, getattr(args, f, None))
     args.save_fused = bool(getattr(args, "save_fused", False))
+    args.save_fused_view = bool(getattr(args, "save_fused_view", False))
     given = [c[0] for c in _FUSED_COMPANIONS if getattr(args, c[0]) is not None]
     if given and args.fused is None:
         parser.error("--%s needs --fused" % given[0])
+    if hasattr(args, "fused_interp") and args.fused is None and not args.save_fused:
+        parser.error("--fused_interp needs --fused or --save_fused")
+    args.fused_interp = getattr(args, "fused_interp", "nearest")
+    if args.save_fused_view and not args.save_fused:
+        parser.error("--save_fused_view needs --save_fused: it is the same rendering's picture")
     if args.fused_window is not None and args.fused is None and not args.save_fused:
         parser.error("--fused_window needs --fused or --save_fused")
     if args.fused_window is not None and args.fused_window < 1:

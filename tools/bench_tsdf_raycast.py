@@ -4,7 +4,14 @@ waves, no key reuse); the predict loop (--stream --graph --save_dir --save_cloud
 and main.py --eval_streams 8 --graph with and without --fused 0.05.
 
     M4D_LIB_FLAVOUR=experiments python tools/bench_tsdf_raycast.py [--out profiles/tsdf_raycast.txt] [--rounds 9] [--calls 100]
-                                                                   [--window 0.3] [--no_driver] [--no_eval]
+                                                                   [--window 0.3] [--no_driver] [--no_eval] [--render]
+                                                                   [--parent_lib SO]
+
+--render adds m4d_tsdf_render to the same rounds (profiles/tsdf_render.txt): nearest and trilinear sampling beside
+m4d_tsdf_raycast, each without and with the normal, colour and view outputs, and the forms the trilinear march's two devices were
+measured against (m4d_tsdf_render_plain: the eight corners probed one by one, no corners kept).  --parent_lib SO times the
+m4d_tsdf_raycast of another build of the library -- the parent commit's -- in the same rounds, and prints the ratio next to the
+spread of the rounds.
 
 Method and scene: those of tools/bench_tsdf_mesh.py -- ``calls`` launches of ONE variant at fixed arguments captured into a
 hipGraph, a timed window = as many replays as fill ``window`` seconds between two device events after a warm-up replay, the
@@ -37,6 +44,9 @@ SIZE, SLOTS_LOG2, PRIMED, TRUNC, MIN_FRAMES = 384, 22, 5, 4, 2
 BATCHES, VOXELS = (1, 8), (0.05, 0.2)
 PLAIN_FORMS = ((0, "row-major waves, every sample probes (plain)"), (1, "8x8 tiles, every sample probes"),
                (2, "row-major waves, key reuse"))
+RENDER_NAMES = ("nearest", "trilinear")
+RENDER_FORMS = ((0, "corners one by one, every sample probes (plain)"), (1, "corners together, every sample probes"),
+                (2, "corners one by one, kept while the base cell stays"))
 
 
 def main(argv=None):
@@ -45,10 +55,16 @@ def main(argv=None):
     from m4depth_amd import network_ops as nops
     from m4depth_amd._lib import lib, check, stream_ptr, build_info, has_experiments
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tsdf_raycast.txt"))
+    ap.add_argument("--out", default=None, help="default profiles/tsdf_raycast.txt, with --render profiles/tsdf_render.txt")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--calls", type=int, default=100, help="launches per captured graph")
     ap.add_argument("--window", type=float, default=0.3, help="seconds per timed window")
+    ap.add_argument("--render", action="store_true",
+                    help="also time m4d_tsdf_render: nearest and trilinear sampling, with and without its three optional outputs, and "
+                         "(experiments build) the forms its two devices were measured against")
+    ap.add_argument("--parent_lib", default=None, metavar="SO",
+                    help="another build of the library (the parent commit's libm4depth_hip.so): its m4d_tsdf_raycast is timed in the "
+                         "same rounds")
     ap.add_argument("--no_driver", action="store_true", help="skip the predict loops")
     ap.add_argument("--no_eval", action="store_true", help="skip the --eval_streams children")
     ap.add_argument("--driver_rounds", type=int, default=3)
@@ -58,9 +74,16 @@ def main(argv=None):
     ap.add_argument("--eval_len", type=int, nargs=2, default=(30, 60))
     ap.add_argument("--eval_limit", type=int, default=240, help="time limit of one --eval_streams child, seconds")
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "tsdf_render.txt" if args.render else "tsdf_raycast.txt")
     if not torch.cuda.is_available():
         raise SystemExit("bench_tsdf_raycast needs a GPU")
     dev = torch.device("cuda:0")
+    parent = None
+    if args.parent_lib:
+        from m4depth_amd._lib import SIGNATURES
+        parent = ctypes.CDLL(os.path.abspath(args.parent_lib))
+        parent.m4d_tsdf_raycast.restype, parent.m4d_tsdf_raycast.argtypes = SIGNATURES["m4d_tsdf_raycast"][:2]
     side = torch.cuda.Stream(device=dev)
     windows = []
 
@@ -108,6 +131,8 @@ def main(argv=None):
         depths, pose_d = [t(maps[k]) for k in range(PRIMED + 1)], [t(poses[k]) for k in range(PRIMED + 1)]
         depth, pose = depths[PRIMED], pose_d[PRIMED]
         out = torch.empty((b, SIZE, SIZE, 1), dtype=torch.float32, device=dev)
+        extra = (torch.empty((b, SIZE, SIZE, 3), device=dev), torch.empty((b, SIZE, SIZE, 3), device=dev),
+                 torch.empty((b, SIZE, SIZE, 3), dtype=torch.uint8, device=dev))       # normal, colour, view
         variants, notes = {}, {}
         for voxel in VOXELS:
             state = nops.tsdf_state(b, SLOTS_LOG2, dev)
@@ -147,15 +172,54 @@ def main(argv=None):
                                                          1.0, 80.0, voxel, TRUNC, MIN_FRAMES, *tail, stream_ptr()),
                               "m4d_tsdf_raycast_plain")
                     variants[f"  {what} v{voxel}, {label}"] = graph_of(plain)
+                if parent is not None:
+                    def before(voxel=voxel, state=state, pose=pose, cam_f=cam_f, cam_c=cam_c, b=b, tail=tail):
+                        check(parent.m4d_tsdf_raycast(p(state["words"]), b, SLOTS_LOG2, p(cam_f), p(cam_c), p(pose), SIZE, SIZE, 1.0, 80.0,
+                                                      voxel, TRUNC, MIN_FRAMES, *tail, stream_ptr()), "m4d_tsdf_raycast (--parent_lib)")
+                    variants[f"  m4d_tsdf_raycast of --parent_lib v{voxel}, {label}"] = graph_of(before)
+                if not args.render:
+                    continue
+                # m4d_tsdf_render: both samplings without and with the three optional outputs, then the forms its two devices
+                # were measured against (trilinear, no optional output)
+                for interp, outputs in ((0, False), (1, False), (0, True), (1, True)):
+                    looks = [x for t3, s3 in zip(extra, (3 * px,) * 3) for x in ((p(t3), s3) if outputs else (None, 0))]
+
+                    def render(voxel=voxel, state=state, pose=pose, cam_f=cam_f, cam_c=cam_c, b=b, tail=tail, interp=interp, looks=looks):
+                        check(lib.m4d_tsdf_render(p(state["words"]), b, SLOTS_LOG2, p(cam_f), p(cam_c), p(pose), SIZE, SIZE, 1.0, 80.0, voxel,
+                                                  TRUNC, MIN_FRAMES, *tail[:5], interp, *tail[5:7], *looks, tail[7], stream_ptr()),
+                              "m4d_tsdf_render")
+                    name = f"m4d_tsdf_render {RENDER_NAMES[interp]}{' + normal, colour, view' if outputs else ''} v{voxel}, {label}"
+                    variants[name] = graph_of(render)
+                    if interp and not outputs:
+                        hits.zero_()
+                        nops.tsdf_render(state, cam_f, cam_c, pose, SIZE, SIZE, voxel, TRUNC, MIN_FRAMES, guide=depth if window else None,
+                                         window=window, interp="trilinear", out=out, hits=hits)
+                        torch.cuda.synchronize()
+                        notes[name] = f"{100 * float(hits.sum()) / (b * px):.1f} % of the pixels rendered; corners together, kept"
+                for variant, what in (RENDER_FORMS if has_experiments else ()):
+                    def plain_render(variant=variant, voxel=voxel, state=state, pose=pose, cam_f=cam_f, cam_c=cam_c, b=b, tail=tail):
+                        check(lib.m4d_tsdf_render_plain(variant, p(state["words"]), b, SLOTS_LOG2, p(cam_f), p(cam_c), p(pose), SIZE, SIZE,
+                                                        1.0, 80.0, voxel, TRUNC, MIN_FRAMES, *tail[:5], 1, *tail[5:7], None, 0, None, 0,
+                                                        None, 0, tail[7], stream_ptr()), "m4d_tsdf_render_plain")
+                    variants[f"  trilinear, {what} v{voxel}, {label}"] = graph_of(plain_render)
         times = {name: [] for name in variants}
         names = list(variants)
         for k in range(args.rounds):
             for name in (names if k % 2 == 0 else names[::-1]):
                 times[name].append(timed(variants[name]))
+            print(f"batch {b}: round {k + 1} of {args.rounds}, {len(names)} variants", flush=True)
         lines.append(f"batch {b}, {SIZE}x{SIZE}, K = {TRUNC}, min_frames {MIN_FRAMES}, 2^{SLOTS_LOG2} slots per sample")
+        width = max(66, max(len(name) for name in names))
         for name in names:
-            lines.append(f"  {name:66s} {stats(times[name])}  per frame {np.median(times[name]) / b:8.2f} us"
+            lines.append(f"  {name:{width}s} {stats(times[name])}  per frame {np.median(times[name]) / b:8.2f} us"
                          + (f"   ({notes[name]})" if name in notes else ""))
+        for name in names:                                     # this build's raycast against --parent_lib's, and the spread of its rounds
+            other = "  m4d_tsdf_raycast of --parent_lib" + name[len("m4d_tsdf_raycast"):]
+            if name.startswith("m4d_tsdf_raycast v") and other in times:
+                mine, theirs = np.array(times[name]), np.array(times[other])
+                lines.append(f"  {name}: this build / --parent_lib = {np.median(mine) / np.median(theirs):.4f}; rounds of this build "
+                             f"{mine.min() / np.median(mine):.4f} .. {mine.max() / np.median(mine):.4f} of their median, of the other "
+                             f"{theirs.min() / np.median(theirs):.4f} .. {theirs.max() / np.median(theirs):.4f}")
         lines.append("")
         del variants, state
         torch.cuda.empty_cache()
